@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """Benchmarks of the path-tracing hot path on MI355X, one JSON line on stdout (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cbox|mesh|autodiff|cbox4k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cbox|mesh|autodiff|cbox4k] [--full] [--dump-outputs DIR]
 
 `--gpus N > 1` without a torch.distributed environment starts the N ranks itself (a `torch.distributed.run` child,
 before anything touches the GPU); under `python -m torch.distributed.run ... bench.py --gpus N` the ranks are used as given.
+
+A plain run sets up the configuration, runs W untimed and K timed steps and prints the line of that configuration.  `--full`
+adds what takes runs of its own: the CPU baselines (`cpu_baseline`, `vs_cpu`), the same-run parity against the oracle
+(`parity`) and, with the default `--config cbox`, the other configurations (`other_configs`).  `--dump-outputs DIR` writes what
+the timed path computed in its last step (the film a caller of the render receives; autodiff: the image and the optimised
+parameter) to DIR/<name>.npy in float32, at most 64 MB in all (a larger array is replaced by a fixed, seeded sample of its
+pixels, <name>.npy, with their flat indices in <name>_index.npy).
 
 Configurations (BASELINE.json `configs`):
   cbox      [1] synthetic Cornell box, RGB, 1024x1024 @ 256 spp per GPU -- the headline line.  N > 1: the film is cut into
@@ -15,8 +22,8 @@ Configurations (BASELINE.json `configs`):
   autodiff  [3] one inverse-rendering iteration (primal + derivative render + adjoint + Adam) on the Cornell box, the setup of
             docs/examples/10_inverse_rendering/invert_cbox.py; metric = ms per iteration.
   cbox4k    [4] 4096x4096 @ 4096 spp Cornell box, film tile-partitioned over the N ranks (strong scaling: the work is fixed).
-With the default `--config cbox` the line also carries the other configurations under "other_configs" (mesh and autodiff at
-N = 1, cbox4k at every N), each with its own small fixed step count, so that every BASELINE config has a driver-visible number.
+With `--full` and the default `--config cbox` the line also carries the other configurations under "other_configs" (mesh and
+autodiff at N = 1, cbox4k at every N), each with its own small fixed step count, so that every BASELINE config has a number.
 
 A step is one complete render (every sample traced to termination, film splatted, N > 1: films reduced).
 """
@@ -52,6 +59,26 @@ def _oracle():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_binding as ob
     return ob
+
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """`arrays` (name -> tensor, channels last) as dirname/<name>.npy in float32.  An array above its share of DUMP_BYTES is
+    replaced by a fixed, seeded sample of its pixels, (k, channels), and their ascending flat indices go to <name>_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 4096          # room for the .npy headers
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a.detach().cpu().numpy(), dtype=np.float32)
+        if a.nbytes > share:
+            px = a.reshape(-1, a.shape[-1] if a.ndim > 1 else 1)
+            k = share // (4 * px.shape[1] + 8)
+            idx = np.sort(np.random.default_rng(0).choice(px.shape[0], k, replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = px[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -222,8 +249,9 @@ def timed_renders(R, integ, scene, sensor, partition, steps, warmup):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-def run_cbox(args, R, strong=False):
-    """configs[1] (weak scaling, 1024^2 @ 256 spp per GPU) or, strong=True, configs[4] (4096^2 @ 4096 spp over the N ranks)."""
+def run_cbox(args, R, strong=False, dump=None):
+    """configs[1] (weak scaling, 1024^2 @ 256 spp per GPU) or, strong=True, configs[4] (4096^2 @ 4096 spp over the N ranks).
+    dump: directory for the film of the last timed step (rank 0: the reduced film)."""
     from mitsuba2_amd import render, scenes, dist as mdist
     n = R.world
     if strong:
@@ -247,6 +275,8 @@ def run_cbox(args, R, strong=False):
     red_ms = R.gather(reduce_s / steps * 1e3)
     if R.rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, {"film_rgba": sensor.film().bitmap(), "film_xyzaw": sensor.film().bitmap(raw=True)})
     # roofline of the dominant kernel on rank 0 -- the one that advances every in-flight path by one segment: k_shade<PathState,
     # false, true, true> (closest hit + shading + in-kernel shadow ring, the default schedule for LDS-resident scenes) or k_bounce
     # with --pipeline 1: algorithmic bytes per launch / average launch time.  Per segment the kernel reads one 88-B path record and
@@ -304,12 +334,12 @@ def run_cbox(args, R, strong=False):
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "alg_bytes_per_launch": alg_bytes / launches, **valu},
     }
-    if n == 1 and not strong and not args.no_cpu_baseline:
+    if args.full and n == 1 and not strong and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(sd, lambda spp: scenes.cornell_box_sensor(width, height, spp), "cbox", seconds=args.cpu_seconds)
         out["vs_cpu"] = {"gpu_over_scalar": out["value"] / out["cpu_baseline"]["scalar"]}
         if "packet" in out["cpu_baseline"]:
             out["vs_cpu"]["gpu_over_packet"] = out["value"] / out["cpu_baseline"]["packet"]
-    if n == 1 and not strong and not args.no_parity:
+    if args.full and n == 1 and not strong and not args.no_parity:
         out["parity"] = same_run_parity(render, scenes, scene, sd, R.device)
     return out
 
@@ -317,7 +347,7 @@ def run_cbox(args, R, strong=False):
 SAMPLE_RECORD_BYTES = 24       # per finished camera sample: 16 B (X, Y, Z, alpha) + 8 B film position
 
 
-def run_mesh(args, R, matpreview=False):
+def run_mesh(args, R, matpreview=False, dump=None):
     """configs[2]: ~250 k-triangle matpreview-style mesh, spectral variant, 1920x1080 @ 1024 spp on one GPU (2 passes).  Roofline of
     the BVH traversal kernel k_trace<false,false>: 48 B per closest-hit ray + the geometry once per launch, over the
     average launch duration measured with HIP events on the stream of each launch.  Two material sets on the same geometry, camera and
@@ -335,6 +365,8 @@ def run_mesh(args, R, matpreview=False):
     sensor = render.make_sensor(scenes.bumpy_sphere_sensor(w, h, spp))
     integ = render.PathIntegrator(profile=True)
     dt, acc, _, _ = timed_renders(R, integ, scene, sensor, None, steps, warmup)
+    if dump:
+        dump_outputs(dump, {"film_rgba": sensor.film().bitmap(), "film_xyzaw": sensor.film().bitmap(raw=True)})
     launches = max(acc["trace_closest_launches"], 1)
     geometry = 32 * info["bvh_nodes"] + 48 * info["primitives"]
     alg_bytes = 48 * acc["closest_hit_rays"] + geometry * launches
@@ -384,11 +416,11 @@ def run_mesh(args, R, matpreview=False):
                      "offline_counters": pmc_extra,
                      "bound_in_practice": "VALU issue for half-empty waves (lane utilisation 0.48) and the latency of dependent node fetches; the 17.7 MB of geometry are served by L2 and the Infinity Cache, HBM carries the ray / hit streams only"},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         path = render.srgb_coeff_path() if variant == "spectral" else None
         out["cpu_baseline"] = cpu_baseline(sd, lambda s: scenes.bumpy_sphere_sensor(w, h, s), "mesh %s%s" % ("matpreview " if matpreview else "", variant),
                                            spectral_path=path, seconds=args.cpu_seconds, max_spp=4 if matpreview else 8)
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         # same kernels, a 96x64 @ 64 spp render of the same scene against the oracle with the same per-sample seeds
         ob = _oracle()
         p = scenes.bumpy_sphere_sensor(96, 64, 64)
@@ -401,7 +433,7 @@ def run_mesh(args, R, matpreview=False):
     return out
 
 
-def run_autodiff(args, R):
+def run_autodiff(args, R, dump=None):
     """configs[3]: the loop of docs/examples/10_inverse_rendering/invert_cbox.py (diff_render.rst:11-28: path max_depth=3, box
     filter; spp=1, unbiased=True, write_bitmap commented out) in two variants: recovering the red wall's constant reflectance
     ('red.reflectance.value', the reference's example) and -- BASELINE config 4 as worded, "optimise diffuse-albedo texture" -- the
@@ -437,6 +469,7 @@ def run_autodiff(args, R):
                 img = autodiff.render(scene, optimizer=opt, unbiased=unbiased, spp=1)
                 (((img - image_ref) ** 2).sum() / img.numel()).backward()
                 opt.step()
+                return img
 
             before = float(((ref - params[key].detach()) ** 2).mean().item())
             for _ in range(5):
@@ -444,11 +477,12 @@ def run_autodiff(args, R):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(iters):
-                iteration()
+                img = iteration()
             torch.cuda.synchronize()
             ms = (time.perf_counter() - t0) * 1e3 / iters
             result["unbiased" if unbiased else "biased"] = {"ms_per_iteration": ms, "param_mse_at_start": before,
-                                                            "param_mse_after_run": float(((ref - params[key].detach()) ** 2).mean().item())}
+                                                            "param_mse_after_run": float(((ref - params[key].detach()) ** 2).mean().item()),
+                                                            "outputs": {"image": img.detach(), "param": params[key].detach().clone()}}
         params[key] = start(ref)
         params.update()
         opt = autodiff.Adam(params, lr=lr)
@@ -469,6 +503,8 @@ def run_autodiff(args, R):
 
     sd, scene = build(None)
     result, fwd, adj, image_ref = optimise(scene, "red.reflectance.value", lambda ref: torch.full_like(ref, 0.9), 0.2)
+    if dump:        # the timed headline: the last unbiased iteration's image and the reflectance after its Adam step
+        dump_outputs(dump, result["unbiased"]["outputs"])
     # texture variant: a smooth 256 x 256 albedo pattern is the target, a uniform grey the starting point
     yy, xx = np.meshgrid(np.linspace(0, 1, 256, dtype=np.float32), np.linspace(0, 1, 256, dtype=np.float32), indexing="ij")
     tex = np.stack([0.5 + 0.35 * np.sin(9 * xx) * np.cos(7 * yy), 0.45 + 0.3 * np.cos(5 * xx + 3 * yy), 0.4 + 0.3 * np.sin(11 * yy)], -1).astype(np.float32)
@@ -509,7 +545,7 @@ def run_autodiff(args, R):
                          "alg_bytes_per_launch": adj_bytes_t, "atomic_bytes_per_launch_upper_bound": int(48 * seg_per_sample * n_samples),
                          "note": "48 B of float atomics per textured path vertex, counted for every vertex (%.2f per sample): an upper bound" % seg_per_sample}},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         ob = _oracle()
         S = ob.OracleScene(sd)
         d = ob.make_desc(p, analytic=True, film_rgb=True)
@@ -557,7 +593,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="cbox", choices=["cbox", "mesh", "mesh_matpreview", "autodiff", "cbox4k", "launcher-selftest"])
-    ap.add_argument("--only", action="store_true", help="--config cbox without the other configurations")
+    ap.add_argument("--full", action="store_true", help="also the CPU baselines, the same-run parity and (--config cbox) the other configurations")
+    ap.add_argument("--only", action="store_true", help="with --full: the cbox line without the other configurations")
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--spp", type=int, default=256)
@@ -575,6 +612,7 @@ def main():
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, the real path) or gloo (rehearsal of N ranks on fewer GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be positive")
@@ -588,14 +626,14 @@ def main():
         R.barrier()
         out = {"n_gpus": R.world, "backend": args.backend, "ranks": R.gather(R.rank), "sum": R.sum([R.rank + 1])[0], "max": R.max(R.rank)}
     elif args.config in ("mesh", "mesh_matpreview"):
-        out = run_mesh(args, R, matpreview=args.config == "mesh_matpreview")
+        out = run_mesh(args, R, matpreview=args.config == "mesh_matpreview", dump=args.dump_outputs)
     elif args.config == "autodiff":
-        out = run_autodiff(args, R)
+        out = run_autodiff(args, R, dump=args.dump_outputs)
     elif args.config == "cbox4k":
-        out = run_cbox(args, R, strong=True)
+        out = run_cbox(args, R, strong=True, dump=args.dump_outputs)
     else:
-        out = run_cbox(args, R)
-        if not args.only:
+        out = run_cbox(args, R, dump=args.dump_outputs)
+        if args.full and not args.only:
             others = {}
             if R.world == 1:
                 others["mesh"] = run_mesh(args, R)
