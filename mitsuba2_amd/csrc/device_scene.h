@@ -17,6 +17,7 @@
 #include "device_math.h"
 #include "device_bsdf.h"
 #include "device_envmap.h"
+#include "flat_worklist.h"
 
 namespace mtsamd {
 
@@ -124,7 +125,20 @@ struct LdsView {
     const DevBsdf *bsdfs;
     const DevEmitter *emitters;
     const float *pmf, *cdf;
+    uint32_t *wl;              // flat scenes: kWlWords per wave of the workgroup (work lists of traverse_flat_worklist)
 };
+
+// Work lists of the flat-scene queries (traverse_flat_worklist): per wave 64 closest-hit keys (any hit: 64 flags) and up to
+// kWlItems items; more items than that (or than MTS_FLAT_WL_ROUNDS rounds of the active lanes) take the plain loop.
+// 5 rounds is what the headline's 4 workgroups per CU leave room for (4 x 4.6 KB beside the scene and the shadow rings).
+#ifndef MTS_FLAT_WORKLIST
+#define MTS_FLAT_WORKLIST 1
+#endif
+#ifndef MTS_FLAT_WL_ROUNDS
+#define MTS_FLAT_WL_ROUNDS 5
+#endif
+constexpr uint32_t kWlItems = 64u * MTS_FLAT_WL_ROUNDS;
+constexpr uint32_t kWlWords = 128u + kWlItems / 2u;
 
 inline uint32_t flat_shape_count(const SceneView &sv) { return sv.n_shapes; }
 
@@ -157,6 +171,8 @@ MTS_DEV LdsView lds_stage(const SceneView &sv, float4 *smem) {
         float *fw = reinterpret_cast<float *>(w);
         for (uint32_t i = threadIdx.x; i < sv.n_prims; i += blockDim.x) { fw[i] = sv.area_pmf[i]; fw[sv.n_prims + i] = sv.area_cdf[i]; }
         l.pmf = fw; l.cdf = fw + sv.n_prims;
+        const uint32_t wl_off = (uint32_t) (reinterpret_cast<uint32_t *>(fw + 2u * sv.n_prims) - reinterpret_cast<uint32_t *>(smem));
+        l.wl = MTS_FLAT_WORKLIST ? reinterpret_cast<uint32_t *>(smem) + ((wl_off + 1u) & ~1u) : nullptr;     // 8-byte aligned (64-bit keys)
     } else {
         float4 *n = smem;
         float4 *t = n + 4u * sv.lds_nodes;
@@ -171,7 +187,8 @@ MTS_DEV LdsView lds_stage(const SceneView &sv, float4 *smem) {
 inline size_t lds_bytes(const SceneView &sv, uint32_t block) {
     if (sv.flat)
         return (size_t) 64 * sv.n_prims + (size_t) 80 * (sv.n_pairs + 1) + (size_t) 32 * sv.n_clusters + sizeof(DevShape) * sv.n_shapes + sizeof(DevBsdf) * sv.n_bsdfs +
-               sizeof(DevEmitter) * sv.n_emitters + (size_t) 8 * sv.n_prims;
+               sizeof(DevEmitter) * sv.n_emitters + (size_t) 8 * sv.n_prims +
+               (MTS_FLAT_WORKLIST ? 4u + (size_t) 4 * kWlWords * (block / 64u) : 0u);
     return (size_t) 64 * sv.lds_nodes + (size_t) 48 * sv.lds_slots + sizeof(StackEntry) * sv.stack_depth * block;
 }
 
@@ -681,10 +698,10 @@ MTS_DEV v2f rcp_nr2(v2f x) {
     return vfma(e, r, r);
 }
 
-// Barycentrics of primitive `prim` for the ray (o, d), by the very operations of the packed loops below on that element (the packed
+// Barycentrics (and the returned t) of primitive `prim` for the ray (o, d), by the very operations of the packed loops below on that element (the packed
 // instructions are element-wise IEEE operations, so the bits are the same).  With MTS_FLAT_LATE_UV the closest-hit loops carry only
 // (t, primitive) through their 36 tests -- two conditional moves per triangle less -- and the winner's (u, v) are formed once here.
-MTS_DEV void flat_hit_uv(const LdsView &lds, f3 o, f3 d, uint32_t prim, float &u, float &v) {
+MTS_DEV float flat_hit_uv(const LdsView &lds, f3 o, f3 d, uint32_t prim, float &u, float &v) {
     const float4 *rec = lds.pairs + 5u * (prim >> 1);
     const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
     const bool hi = (prim & 1u) != 0u;
@@ -700,10 +717,39 @@ MTS_DEV void flat_hit_uv(const LdsView &lds, f3 o, f3 d, uint32_t prim, float &u
     u = fmaf(tz, pvz, fmaf(ty, pvy, tx * pvx)) * r;
     const float qx = fmaf(ty, e1.z, -(tz * e1.y)), qy = fmaf(tz, e1.x, -(tx * e1.z)), qz = fmaf(tx, e1.y, -(ty * e1.x));
     v = fmaf(d.z, qz, fmaf(d.y, qy, d.x * qx)) * r;
+    return fmaf(e2.z, qz, fmaf(e2.y, qy, e2.x * qx)) * r;       // t, as the loops compute it
 }
 #ifndef MTS_FLAT_LATE_UV
 #define MTS_FLAT_LATE_UV 1
 #endif
+
+// The packed Moeller-Trumbore test of one primitive pair (record q0..q4: A = x elements, B = y elements) against the ray (o, d):
+// per element exactly Mesh::ray_intersect_triangle (mesh.h:195-221).  Every flat-scene query runs this one body; acceptance (closed
+// intervals, tie rule) is the caller's, through tri_accept.
+struct PairUvt { v2f u, v, uv, t; };
+MTS_DEV PairUvt pair_test(const float4 &q0, const float4 &q1, const float4 &q2, const float4 &q3, const float4 &q4,
+                          v2f ox, v2f oy, v2f oz, v2f dx, v2f dy, v2f dz) {
+    const v2f p0x = { q0.x, q0.y }, p0y = { q0.z, q0.w }, p0z = { q1.x, q1.y };
+    const v2f e1x = { q1.z, q1.w }, e1y = { q2.x, q2.y }, e1z = { q2.z, q2.w };
+    const v2f e2x = { q3.x, q3.y }, e2y = { q3.z, q3.w }, e2z = { q4.x, q4.y };
+    // pvec = cross(d, e2)
+    const v2f pvx = vfma(dy, e2z, -(dz * e2y)), pvy = vfma(dz, e2x, -(dx * e2z)), pvz = vfma(dx, e2y, -(dy * e2x));
+    const v2f det = vfma(e1z, pvz, vfma(e1y, pvy, e1x * pvx));
+    const v2f inv = rcp_nr2(det);
+    const v2f tx = ox - p0x, ty = oy - p0y, tz = oz - p0z;
+    PairUvt r;
+    r.u = vfma(tz, pvz, vfma(ty, pvy, tx * pvx)) * inv;
+    // qvec = cross(tvec, e1)
+    const v2f qx = vfma(ty, e1z, -(tz * e1y)), qy = vfma(tz, e1x, -(tx * e1z)), qz = vfma(tx, e1y, -(ty * e1x));
+    r.v = vfma(dz, qz, vfma(dy, qy, dx * qx)) * inv;
+    r.t = vfma(e2z, qz, vfma(e2y, qy, e2x * qx)) * inv;
+    r.uv = r.u + r.v;
+    return r;
+}
+// u <= 1 is implied by v >= 0 && u + v <= 1 (rounded addition is monotone); NaNs fail u >= 0 or u + v <= 1
+MTS_DEV bool tri_accept(float u, float v, float uv, float t, float mint, float tmax) {
+    return (u >= 0.0f) && (v >= 0.0f) && (uv <= 1.0f) && (t >= mint) && (t <= tmax);
+}
 
 // Flat scenes: a wave-uniform loop over every primitive, two per iteration on the packed-fp32 pipe
 // (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32), operands broadcast from LDS (no stack, no divergence).
@@ -735,32 +781,18 @@ MTS_DEV bool traverse_flat(const SceneView &sv, const LdsView &lds, f3 o, f3 d, 
         const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
         rec += 5;
 #endif
-        const v2f p0x = { q0.x, q0.y }, p0y = { q0.z, q0.w }, p0z = { q1.x, q1.y };
-        const v2f e1x = { q1.z, q1.w }, e1y = { q2.x, q2.y }, e1z = { q2.z, q2.w };
-        const v2f e2x = { q3.x, q3.y }, e2y = { q3.z, q3.w }, e2z = { q4.x, q4.y };
-        // pvec = cross(d, e2)
-        const v2f pvx = vfma(dy, e2z, -(dz * e2y)), pvy = vfma(dz, e2x, -(dx * e2z)), pvz = vfma(dx, e2y, -(dy * e2x));
-        const v2f det = vfma(e1z, pvz, vfma(e1y, pvy, e1x * pvx));
-        const v2f inv = rcp_nr2(det);
-        const v2f tx = ox - p0x, ty = oy - p0y, tz = oz - p0z;
-        const v2f u = vfma(tz, pvz, vfma(ty, pvy, tx * pvx)) * inv;
-        // qvec = cross(tvec, e1)
-        const v2f qx = vfma(ty, e1z, -(tz * e1y)), qy = vfma(tz, e1x, -(tx * e1z)), qz = vfma(tx, e1y, -(ty * e1x));
-        const v2f v = vfma(dz, qz, vfma(dy, qy, dx * qx)) * inv;
-        const v2f t = vfma(e2z, qz, vfma(e2y, qy, e2x * qx)) * inv;
-        const v2f uv = u + v;
-        // u <= 1 is implied by v >= 0 && u + v <= 1 (rounded addition is monotone); NaNs fail u >= 0 or u + v <= 1
+        const PairUvt r = pair_test(q0, q1, q2, q3, q4, ox, oy, oz, dx, dy, dz);
         if (ANY) {
-            bool ok_a = (u.x >= 0.0f) && (v.x >= 0.0f) && (uv.x <= 1.0f) && (t.x >= mint) && (t.x <= maxt);
-            bool ok_b = (u.y >= 0.0f) && (v.y >= 0.0f) && (uv.y <= 1.0f) && (t.y >= mint) && (t.y <= maxt);
+            const bool ok_a = tri_accept(r.u.x, r.v.x, r.uv.x, r.t.x, mint, maxt);
+            const bool ok_b = tri_accept(r.u.y, r.v.y, r.uv.y, r.t.y, mint, maxt);
             any = any || ok_a || ok_b;
         } else {
-            bool ok_a = (u.x >= 0.0f) && (v.x >= 0.0f) && (uv.x <= 1.0f) && (t.x >= mint) && (t.x <= best);
-            best = ok_a ? t.x : best; best_prim = ok_a ? 2u * k : best_prim;
-            if (!MTS_FLAT_LATE_UV) { bu = ok_a ? u.x : bu; bv = ok_a ? v.x : bv; }
-            bool ok_b = (u.y >= 0.0f) && (v.y >= 0.0f) && (uv.y <= 1.0f) && (t.y >= mint) && (t.y <= best);
-            best = ok_b ? t.y : best; best_prim = ok_b ? 2u * k + 1u : best_prim;
-            if (!MTS_FLAT_LATE_UV) { bu = ok_b ? u.y : bu; bv = ok_b ? v.y : bv; }
+            const bool ok_a = tri_accept(r.u.x, r.v.x, r.uv.x, r.t.x, mint, best);
+            best = ok_a ? r.t.x : best; best_prim = ok_a ? 2u * k : best_prim;
+            if (!MTS_FLAT_LATE_UV) { bu = ok_a ? r.u.x : bu; bv = ok_a ? r.v.x : bv; }
+            const bool ok_b = tri_accept(r.u.y, r.v.y, r.uv.y, r.t.y, mint, best);
+            best = ok_b ? r.t.y : best; best_prim = ok_b ? 2u * k + 1u : best_prim;
+            if (!MTS_FLAT_LATE_UV) { bu = ok_b ? r.u.y : bu; bv = ok_b ? r.v.y : bv; }
         }
     }
     if (ANY) return any;
@@ -782,9 +814,9 @@ MTS_DEV bool traverse_flat_clustered(const SceneView &sv, const LdsView &lds, f3
     float best = maxt, bu = 0.0f, bv = 0.0f;
     uint32_t best_prim = kNoPrim;
 #ifndef MTS_CULL_STATS
-#define MTS_CULL_STATS 0                                     // 1 (diagnostic builds): count the triangles really tested
+#define MTS_CULL_STATS 0       // diagnostic builds: count the triangles really tested by closest-hit (1) or any-hit (2) queries
 #endif
-    if (!MTS_CULL_STATS) tri_tests += sv.n_prims;            // nominal count, as the plain loop (the statistics do not depend on the schedule)
+    if (!(MTS_CULL_STATS & 1)) tri_tests += sv.n_prims;            // nominal count, as the plain loop (the statistics do not depend on the schedule)
     const v2f ox = splat(o.x), oy = splat(o.y), oz = splat(o.z), dx = splat(d.x), dy = splat(d.y), dz = splat(d.z);
     const f3 inv = mk3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
     const float4 *rec = lds.pairs;
@@ -799,28 +831,17 @@ MTS_DEV bool traverse_flat_clustered(const SceneView &sv, const LdsView &lds, f3
         const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), mint));
         const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), best));
         if (__ballot(tn <= tf) == 0ull) { rec += 5u * n; k += n; continue; }
-        if (MTS_CULL_STATS) tri_tests += 2u * n;
+        if (MTS_CULL_STATS & 1) tri_tests += 2u * n;
         for (uint32_t i = 0; i < n; ++i, ++k) {
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
             rec += 5;
-            const v2f p0x = { q0.x, q0.y }, p0y = { q0.z, q0.w }, p0z = { q1.x, q1.y };
-            const v2f e1x = { q1.z, q1.w }, e1y = { q2.x, q2.y }, e1z = { q2.z, q2.w };
-            const v2f e2x = { q3.x, q3.y }, e2y = { q3.z, q3.w }, e2z = { q4.x, q4.y };
-            const v2f pvx = vfma(dy, e2z, -(dz * e2y)), pvy = vfma(dz, e2x, -(dx * e2z)), pvz = vfma(dx, e2y, -(dy * e2x));
-            const v2f det = vfma(e1z, pvz, vfma(e1y, pvy, e1x * pvx));
-            const v2f ivd = rcp_nr2(det);
-            const v2f tx = ox - p0x, ty = oy - p0y, tz = oz - p0z;
-            const v2f u = vfma(tz, pvz, vfma(ty, pvy, tx * pvx)) * ivd;
-            const v2f qx = vfma(ty, e1z, -(tz * e1y)), qy = vfma(tz, e1x, -(tx * e1z)), qz = vfma(tx, e1y, -(ty * e1x));
-            const v2f v = vfma(dz, qz, vfma(dy, qy, dx * qx)) * ivd;
-            const v2f t = vfma(e2z, qz, vfma(e2y, qy, e2x * qx)) * ivd;
-            const v2f uv = u + v;
-            bool ok_a = (u.x >= 0.0f) && (v.x >= 0.0f) && (uv.x <= 1.0f) && (t.x >= mint) && (t.x <= best);
-            best = ok_a ? t.x : best; best_prim = ok_a ? 2u * k : best_prim;
-            if (!MTS_FLAT_LATE_UV) { bu = ok_a ? u.x : bu; bv = ok_a ? v.x : bv; }
-            bool ok_b = (u.y >= 0.0f) && (v.y >= 0.0f) && (uv.y <= 1.0f) && (t.y >= mint) && (t.y <= best);
-            best = ok_b ? t.y : best; best_prim = ok_b ? 2u * k + 1u : best_prim;
-            if (!MTS_FLAT_LATE_UV) { bu = ok_b ? u.y : bu; bv = ok_b ? v.y : bv; }
+            const PairUvt r = pair_test(q0, q1, q2, q3, q4, ox, oy, oz, dx, dy, dz);
+            const bool ok_a = tri_accept(r.u.x, r.v.x, r.uv.x, r.t.x, mint, best);
+            best = ok_a ? r.t.x : best; best_prim = ok_a ? 2u * k : best_prim;
+            if (!MTS_FLAT_LATE_UV) { bu = ok_a ? r.u.x : bu; bv = ok_a ? r.v.x : bv; }
+            const bool ok_b = tri_accept(r.u.y, r.v.y, r.uv.y, r.t.y, mint, best);
+            best = ok_b ? r.t.y : best; best_prim = ok_b ? 2u * k + 1u : best_prim;
+            if (!MTS_FLAT_LATE_UV) { bu = ok_b ? r.u.y : bu; bv = ok_b ? r.v.y : bv; }
         }
     }
     if (MTS_FLAT_LATE_UV && best_prim != kNoPrim) flat_hit_uv(lds, o, d, best_prim, bu, bv);
@@ -832,7 +853,7 @@ MTS_DEV bool traverse_flat_clustered(const SceneView &sv, const LdsView &lds, f3
 // active lane's segment reaches are skipped; a lane that has found an occluder no longer votes.
 MTS_DEV bool traverse_flat_clustered_any(const SceneView &sv, const LdsView &lds, f3 o, f3 d, float mint, float maxt, uint32_t &tri_tests) {
     bool any = false;
-    tri_tests += sv.n_prims;                                 // nominal count, as the plain loop
+    if (!(MTS_CULL_STATS & 2)) tri_tests += sv.n_prims;     // nominal count, as the plain loop
     const v2f ox = splat(o.x), oy = splat(o.y), oz = splat(o.z), dx = splat(d.x), dy = splat(d.y), dz = splat(d.z);
     const f3 inv = mk3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
     const float4 *rec = lds.pairs;
@@ -845,34 +866,122 @@ MTS_DEV bool traverse_flat_clustered_any(const SceneView &sv, const LdsView &lds
         const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), mint));
         const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), maxt));
         if (__ballot(!any && tn <= tf) == 0ull) { rec += 5u * n; continue; }
+        if (MTS_CULL_STATS & 2) tri_tests += 2u * n;
         for (uint32_t i = 0; i < n; ++i) {
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
             rec += 5;
-            const v2f p0x = { q0.x, q0.y }, p0y = { q0.z, q0.w }, p0z = { q1.x, q1.y };
-            const v2f e1x = { q1.z, q1.w }, e1y = { q2.x, q2.y }, e1z = { q2.z, q2.w };
-            const v2f e2x = { q3.x, q3.y }, e2y = { q3.z, q3.w }, e2z = { q4.x, q4.y };
-            const v2f pvx = vfma(dy, e2z, -(dz * e2y)), pvy = vfma(dz, e2x, -(dx * e2z)), pvz = vfma(dx, e2y, -(dy * e2x));
-            const v2f det = vfma(e1z, pvz, vfma(e1y, pvy, e1x * pvx));
-            const v2f ivd = rcp_nr2(det);
-            const v2f tx = ox - p0x, ty = oy - p0y, tz = oz - p0z;
-            const v2f u = vfma(tz, pvz, vfma(ty, pvy, tx * pvx)) * ivd;
-            const v2f qx = vfma(ty, e1z, -(tz * e1y)), qy = vfma(tz, e1x, -(tx * e1z)), qz = vfma(tx, e1y, -(ty * e1x));
-            const v2f v = vfma(dz, qz, vfma(dy, qy, dx * qx)) * ivd;
-            const v2f t = vfma(e2z, qz, vfma(e2y, qy, e2x * qx)) * ivd;
-            const v2f uv = u + v;
-            const bool ok_a = (u.x >= 0.0f) && (v.x >= 0.0f) && (uv.x <= 1.0f) && (t.x >= mint) && (t.x <= maxt);
-            const bool ok_b = (u.y >= 0.0f) && (v.y >= 0.0f) && (uv.y <= 1.0f) && (t.y >= mint) && (t.y <= maxt);
+            const PairUvt r = pair_test(q0, q1, q2, q3, q4, ox, oy, oz, dx, dy, dz);
+            const bool ok_a = tri_accept(r.u.x, r.v.x, r.uv.x, r.t.x, mint, maxt);
+            const bool ok_b = tri_accept(r.u.y, r.v.y, r.uv.y, r.t.y, mint, maxt);
             any = any || ok_a || ok_b;
         }
     }
     return any;
 }
 
-// `coherent` (wave-uniform): the active lanes carry the camera rays of one or two pixels -> cluster culling (flat scenes, closest hit)
+// Incoherent queries on a flat scene (secondary and shadow rays): some lane of a wave reaches nearly every cluster box, so the
+// wave-uniform loops test nearly every pair for every lane, while one ray reaches only a few boxes.  Here each active lane lists the
+// pairs of the clusters its segment [mint, maxt] reaches (the box test only culls, as in traverse_flat_clustered), and the
+// (ray, pair) items of all active lanes are dealt out over the active lanes: ceil(items / active) rounds of one pair test each
+// instead of n_pairs.  A round fetches the owner's ray by ds_bpermute and runs pair_test on it.
+//   closest hit: each accepted triangle offers the key (t, ~prim) (flat_worklist.h) to its owner's slot by an LDS 64-bit minimum; the
+//                minimum is what the sequential loop keeps, whatever the order of the items.  The winner's t, u, v are then formed by
+//                flat_hit_uv: the bits of the sequential loop, -0 included.
+//   any hit:     an accepted triangle sets its owner's flag; the query ends once every owner with items left is occluded.
+// Correct under any exec mask (the active lanes are counted by ballot / mbcnt).  More items than kWlItems or than
+// MTS_FLAT_WL_ROUNDS rounds: the plain loop.
+static_assert(kFlatMaxPrims <= 64u, "a pair mask is 32 bits");
+template <bool ANY>
+MTS_DEV bool traverse_flat_worklist(const SceneView &sv, const LdsView &lds, f3 o, f3 d, float mint, float maxt, Hit &hit, uint32_t &tri_tests) {
+    const uint64_t active = __ballot(1);
+    const uint32_t n_act = (uint32_t) __popcll(active), lane = lane_id(), rank = mask_rank(active);
+    // pairs whose cluster box the segment reaches
+    const f3 inv = mk3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
+    uint32_t pairs = 0u, first = 0u;
+    for (uint32_t c = 0; c < sv.n_clusters; ++c) {
+        const float4 lo = lds.clusters[2u * c], hi = lds.clusters[2u * c + 1u];
+        const uint32_t n = __float_as_uint(lo.w);
+        const float ax = (lo.x - o.x) * inv.x, bx = (hi.x - o.x) * inv.x;
+        const float ay = (lo.y - o.y) * inv.y, by = (hi.y - o.y) * inv.y;
+        const float az = (lo.z - o.z) * inv.z, bz = (hi.z - o.z) * inv.z;
+        const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), mint));
+        const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), maxt));
+        const uint32_t bits = (uint32_t) ((1ull << n) - 1ull) << first;
+        pairs |= tn <= tf ? bits : 0u;
+        first += n;
+    }
+    // exclusive prefix of the item counts over the active lanes and their total, one ballot per bit of the count (<= 32)
+    const uint32_t cnt = (uint32_t) __popc(pairs);
+    uint32_t pos = 0u, total = 0u;
+#pragma unroll
+    for (uint32_t b = 0; b < 6u; ++b) {
+        const uint64_t m = __ballot((cnt >> b) & 1u);
+        pos += mask_rank(m) << b; total += (uint32_t) __popcll(m) << b;
+    }
+    if (total > kWlItems || total > MTS_FLAT_WL_ROUNDS * n_act) return traverse_flat<ANY>(sv, lds, o, d, mint, maxt, hit, tri_tests);
+    constexpr bool kRealCount = (MTS_CULL_STATS & (ANY ? 2 : 1)) != 0;
+    if (!kRealCount) tri_tests += sv.n_prims;               // nominal count, as the plain loop
+    uint32_t *ws = lds.wl + (threadIdx.x >> 6) * kWlWords;
+    unsigned long long *key = reinterpret_cast<unsigned long long *>(ws);
+    uint16_t *tbl = reinterpret_cast<uint16_t *>(ws + 128u);
+    if (ANY) ws[lane] = 0u;
+    else key[lane] = kWlNoKey;
+    wl_push_items(tbl, pos, pairs, lane);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (uint32_t j0 = 0u; j0 < total; j0 += n_act) {
+        // the lanes past the end of the list test the all-zero pair, which is never hit: the whole wave takes part in the permutes
+        const uint32_t j = j0 + rank;
+        const uint32_t item = j < total ? (uint32_t) tbl[j] : wl_item(lane, sv.n_pairs);
+        const uint32_t owner = wl_item_owner(item), pair = wl_item_pair(item);
+        const int addr = (int) (owner << 2);
+        const float rox = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(o.x)));
+        const float roy = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(o.y)));
+        const float roz = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(o.z)));
+        const float rdx = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(d.x)));
+        const float rdy = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(d.y)));
+        const float rdz = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(d.z)));
+        const float rmint = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(mint)));
+        const float rmaxt = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(maxt)));
+        const float4 *rec = lds.pairs + 5u * pair;
+        const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
+        const PairUvt r = pair_test(q0, q1, q2, q3, q4, splat(rox), splat(roy), splat(roz), splat(rdx), splat(rdy), splat(rdz));
+        const bool ok_a = tri_accept(r.u.x, r.v.x, r.uv.x, r.t.x, rmint, rmaxt);
+        const bool ok_b = tri_accept(r.u.y, r.v.y, r.uv.y, r.t.y, rmint, rmaxt);
+        if (kRealCount && j < total) tri_tests += 2u;
+        if (ANY) {
+            if (ok_a || ok_b) ws[owner] = 1u;
+        } else if (ok_a || ok_b) {
+            const uint64_t ka = ok_a ? wl_key(r.t.x, 2u * pair) : kWlNoKey, kb = ok_b ? wl_key(r.t.y, 2u * pair + 1u) : kWlNoKey;
+            atomicMin(&key[owner], (unsigned long long) (ka < kb ? ka : kb));
+        }
+        if (ANY) {      // done once no lane with items beyond this round is still unoccluded
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (__ballot(ws[lane] == 0u && pos + cnt > j0 + n_act) == 0ull) break;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (ANY) return ws[lane] != 0u;
+    const uint64_t k = key[lane];
+    hit.t = maxt; hit.prim = kNoPrim; hit.u = 0.0f; hit.v = 0.0f;
+    if (k == kWlNoKey) return false;
+    hit.prim = wl_key_prim(k);
+    hit.t = flat_hit_uv(lds, o, d, hit.prim, hit.u, hit.v);
+    return true;
+}
+
+// `coherent` (wave-uniform): the active lanes carry the camera rays of one or two pixels -> cluster culling (flat scenes, closest hit);
+// other flat-scene queries: per-(ray, pair) work lists
 template <bool FLAT, bool ANY>
 MTS_DEV bool traverse(const SceneView &sv, const LdsView &lds, f3 o, f3 d, float mint, float maxt, Hit &hit, uint32_t &tri_tests,
                       bool coherent = false) {
     if (FLAT && !ANY && MTS_FLAT_CULL && coherent && sv.n_clusters > 1u) return traverse_flat_clustered(sv, lds, o, d, mint, maxt, hit, tri_tests);
+    if (FLAT && MTS_FLAT_WORKLIST && sv.n_clusters > 1u && lds.wl) return traverse_flat_worklist<ANY>(sv, lds, o, d, mint, maxt, hit, tri_tests);
     if (FLAT) return traverse_flat<ANY>(sv, lds, o, d, mint, maxt, hit, tri_tests);
     return traverse_bvh<ANY>(sv, lds, o, d, mint, maxt, hit, tri_tests);
 }
