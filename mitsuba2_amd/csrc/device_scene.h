@@ -130,12 +130,12 @@ struct LdsView {
 
 // Work lists of the flat-scene queries (traverse_flat_worklist): per wave 64 closest-hit keys (any hit: 64 flags) and up to
 // kWlItems items; more items than that (or than MTS_FLAT_WL_ROUNDS rounds of the active lanes) take the plain loop.
-// 5 rounds is what the headline's 4 workgroups per CU leave room for (4 x 4.6 KB beside the scene and the shadow rings).
+// The headline's 4 workgroups per CU must keep room for the lists beside the scene and the shadow rings (static_assert in kernels.h).
 #ifndef MTS_FLAT_WORKLIST
 #define MTS_FLAT_WORKLIST 1
 #endif
 #ifndef MTS_FLAT_WL_ROUNDS
-#define MTS_FLAT_WL_ROUNDS 5
+#define MTS_FLAT_WL_ROUNDS 8
 #endif
 constexpr uint32_t kWlItems = 64u * MTS_FLAT_WL_ROUNDS;
 constexpr uint32_t kWlWords = 128u + kWlItems / 2u;
@@ -814,8 +814,8 @@ MTS_DEV bool traverse_flat_clustered(const SceneView &sv, const LdsView &lds, f3
     float best = maxt, bu = 0.0f, bv = 0.0f;
     uint32_t best_prim = kNoPrim;
 #ifndef MTS_CULL_STATS
-#define MTS_CULL_STATS 0       // diagnostic builds: count the triangles really tested by closest-hit (1) or any-hit (2) queries
-#endif
+#define MTS_CULL_STATS 0       // diagnostic builds: count the triangles really tested by closest-hit (1) or any-hit (2) queries;
+#endif                         // 4 / 8: work-list fallbacks / queries (traverse_flat_worklist)
     if (!(MTS_CULL_STATS & 1)) tri_tests += sv.n_prims;            // nominal count, as the plain loop (the statistics do not depend on the schedule)
     const v2f ox = splat(o.x), oy = splat(o.y), oz = splat(o.z), dx = splat(d.x), dy = splat(d.y), dz = splat(d.z);
     const f3 inv = mk3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
@@ -918,7 +918,11 @@ MTS_DEV bool traverse_flat_worklist(const SceneView &sv, const LdsView &lds, f3 
         const uint64_t m = __ballot((cnt >> b) & 1u);
         pos += mask_rank(m) << b; total += (uint32_t) __popcll(m) << b;
     }
-    if (total > kWlItems || total > MTS_FLAT_WL_ROUNDS * n_act) return traverse_flat<ANY>(sv, lds, o, d, mint, maxt, hit, tri_tests);
+    const bool fallback = total > kWlItems || total > MTS_FLAT_WL_ROUNDS * n_act;
+    // diagnostic builds (scripts/debug/cull_stats.py), on top of the nominal counts: the wave queries that take the plain loop (4) or all
+    // wave queries of this function (8), counted by the first active lane
+    if (MTS_CULL_STATS & 12) tri_tests += (rank == 0u && ((MTS_CULL_STATS & 8) || fallback)) ? 1u : 0u;
+    if (fallback) return traverse_flat<ANY>(sv, lds, o, d, mint, maxt, hit, tri_tests);
     constexpr bool kRealCount = (MTS_CULL_STATS & (ANY ? 2 : 1)) != 0;
     if (!kRealCount) tri_tests += sv.n_prims;               // nominal count, as the plain loop
     uint32_t *ws = lds.wl + (threadIdx.x >> 6) * kWlWords;

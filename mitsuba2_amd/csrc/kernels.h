@@ -148,6 +148,22 @@ struct RayStreams {
 };
 
 size_t bounce_lds_bytes(const SceneView &sv);
+// k_shade with the in-kernel shadow ring (split 3): per wave a ring of kShadowRing shadow rays.  An entry is o (+ mint), d (+ maxt) and
+// nee as three float4 (48 B); RGB paths keep the output slot in nee.w (always 0 there), spectral ones need all four wavelengths and
+// keep it in a word of its own (52 B).  Dynamic LDS of a launch: the scene (+ work lists), the four rings and, when a workgroup gathers
+// the paths of gather_w > 4 scheduling waves, their prefix sums (gather_w + 1 words).
+constexpr uint32_t kShadowRing = 128u;                       // >= 63 queued + 64 pushed
+constexpr uint32_t kShadeWaves = 4u;                         // waves per k_shade workgroup (kBlock / 64)
+inline size_t shadow_ring_bytes(bool spectral) { return (size_t) kShadowRing * (spectral ? 52u : 48u); }
+inline size_t shade_ring_offset(const SceneView &sv, uint32_t block) { return (lds_bytes(sv, block) + 15u) & ~(size_t) 15u; }
+inline size_t shade_ring_lds_bytes(const SceneView &sv, bool spectral, uint32_t gather_w) {
+    return shade_ring_offset(sv, 64u * kShadeWaves) + kShadeWaves * shadow_ring_bytes(spectral) + (gather_w > 4u ? 4u * ((size_t) gather_w + 1u) : 0u);
+}
+// The headline's k_shade runs 4 workgroups per CU (160 KiB of LDS): the fixed part -- rings, work lists, static LDS (<= 512 B) -- has
+// to leave room for a Cornell-box-sized scene (5.2 KB; 6 KiB here).  A larger MTS_FLAT_WL_ROUNDS fails here instead of silently
+// costing a workgroup per CU (tests/test_shade_lds_cpu.py checks the real Cornell box against the compiler's figures).
+static_assert(kShadeWaves * (48u * kShadowRing + 4u * kWlWords) + 4u + 512u + 6144u <= 160u * 1024u / 4u,
+              "work lists + shadow rings no longer fit 4 k_shade workgroups per CU");
 hipError_t launch_bounce(const RenderParams &p, hipStream_t s);
 hipError_t launch_split_stage(const RenderParams &p, int stage, hipStream_t s);
 uint32_t trace_lds_depth(const SceneView &sv);

@@ -19,6 +19,7 @@
 namespace mtsamd {
 
 constexpr int kBlock = 256;
+static_assert(kBlock == 64 * (int) kShadeWaves, "k_shade LDS sizing (kernels.h)");
 
 // ---------------------------------------------------------------------------------------------
 struct PathState {
@@ -992,8 +993,19 @@ template <> struct ShadeWaves<PathState, false> { static constexpr int kMin = MT
 // INLINE (flat scenes only): the shadow rays of consecutive 64-path chunks are collected in a per-wave LDS ring and resolved
 // 64 at a time inside this kernel -- the any-hit loop then always runs on full waves (only about two thirds of the paths cast
 // a shadow ray) -- and `nee` is added to the radiance the wave has already stored in its output segment.
-constexpr uint32_t kShadowRing = 128u;                       // >= 63 queued + 64 pushed
-template <typename State> struct ShadowRing { float4 *o, *d, *nee; uint32_t *slot; };
+// The ring of one wave (kernels.h, shadow_ring_bytes): rows o[kShadowRing], d[kShadowRing], nee[kShadowRing] (+ slot[kShadowRing]).
+template <typename State> struct ShadowRing {
+    static constexpr bool kSlotInNee = false;               // spectral: nee.w is the fourth wavelength
+    static constexpr uint32_t kFloat4 = kShadowRing * 13u / 4u;
+    float4 *o, *d, *nee; uint32_t *slot;
+};
+template <> struct ShadowRing<PathState> {
+    static constexpr bool kSlotInNee = true;                // RGB: nee.w is 0, the slot index takes its place
+    static constexpr uint32_t kFloat4 = kShadowRing * 3u;
+    float4 *o, *d, *nee; uint32_t *slot;
+};
+static_assert(ShadowRing<PathState>::kFloat4 * 16u == 48u * kShadowRing && ShadowRing<PathStateS>::kFloat4 * 16u == 52u * kShadowRing,
+              "ring sizes of shadow_ring_bytes()");
 
 template <typename State, bool GENERAL>
 MTS_DEV void drain_shadow_ring(const RenderParams &P, const LdsView &lds, const ShadowRing<State> &q, uint32_t head, uint32_t count,
@@ -1006,10 +1018,11 @@ MTS_DEV void drain_shadow_ring(const RenderParams &P, const LdsView &lds, const 
         const float4 o = q.o[k], d = q.d[k];
         Hit h;
         if (!traverse<true, true>(P.sv, lds, mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), o.w, d.w, h, c.tri_tests)) {
-            const size_t slot = base + q.slot[k];
-            float4 r = P.out.res[slot];
             const float4 e = q.nee[k];
-            r.x += e.x; r.y += e.y; r.z += e.z; r.w += e.w;      // RGB: w = eta + 0
+            const size_t slot = base + (ShadowRing<State>::kSlotInNee ? __float_as_uint(e.w) : q.slot[k]);
+            float4 r = P.out.res[slot];
+            r.x += e.x; r.y += e.y; r.z += e.z;
+            if (!ShadowRing<State>::kSlotInNee) r.w += e.w;      // RGB: w = eta, nee adds nothing to it
             P.out.res[slot] = r;
         }
     }
@@ -1037,12 +1050,14 @@ void k_shade(const RenderParams P) {
     // consecutive scheduling waves and leave the survivors at the front of the group -- hardware wave h fills the segments of the
     // waves h, h + 4, h + 8, ... of the group one after the other: the pool is compacted as it is advanced, and the number of
     // workgroups that stage the scene for a handful of paths shrinks with it.
-    const uint32_t gw = (FLAT && P.gather_w > 4u) ? P.gather_w : 4u;
+    const uint32_t gw = (INLINE && P.gather_w > 4u) ? P.gather_w : 4u;      // only the shadow-ring schedule gathers (api.cpp)
     const uint32_t hw = threadIdx.x >> 6;
     const uint32_t wave = gw > 4u ? P.wave_first + blockIdx.x * gw + hw : P.wave_first + ((blockIdx.x * kBlock + threadIdx.x) >> 6);
     const uint32_t wave_last = P.wave_last ? P.wave_last : P.n_waves;
     __shared__ uint32_t s_cnt[kBlock / 64u], s_surv[kBlock / 64u];
-    __shared__ uint32_t s_pre[FLAT ? 1025 : 1];      // gather: s_pre[k] = paths in the group's waves before the k-th
+    // gather: s_pre[k] = paths in the group's waves before the k-th, in dynamic LDS after the shadow rings (launch_bounce adds
+    // gather_w + 1 words to those launches only: the steady-state launches do not reserve it)
+    uint32_t *const s_pre = reinterpret_cast<uint32_t *>(smem + P.lds_queue_offset + kShadeWaves * ShadowRing<State>::kFloat4);
     if (FLAT && gw > 4u) {
         const uint32_t g0 = wave - hw;
         for (uint32_t k = threadIdx.x; k < gw; k += kBlock) s_pre[k + 1u] = (g0 + k < wave_last) ? P.count_in[g0 + k] : 0u;
@@ -1082,9 +1097,9 @@ void k_shade(const RenderParams P) {
     }
     ShadowRing<State> ring = {};
     if (INLINE) {
-        float4 *qb = smem + P.lds_queue_offset + (size_t) (threadIdx.x >> 6) * (kShadowRing * 13u / 4u);
+        float4 *qb = smem + P.lds_queue_offset + (size_t) (threadIdx.x >> 6) * ShadowRing<State>::kFloat4;
         ring.o = qb; ring.d = qb + kShadowRing; ring.nee = qb + 2u * kShadowRing;
-        ring.slot = reinterpret_cast<uint32_t *>(qb + 3u * kShadowRing);
+        ring.slot = ShadowRing<State>::kSlotInNee ? nullptr : reinterpret_cast<uint32_t *>(qb + 3u * kShadowRing);
     }
     if (wave >= wave_last) return;
     const uint32_t lane = lane_id();
@@ -1180,8 +1195,13 @@ void k_shade(const RenderParams P) {
                     const uint32_t k = (q_head + q_count + mask_rank(ms)) & (kShadowRing - 1u);
                     ring.o[k] = make_float4(df.so.x, df.so.y, df.so.z, df.smint);
                     ring.d[k] = make_float4(df.sd.x, df.sd.y, df.sd.z, df.smaxt);
-                    ring.nee[k] = make_float4(df.nee[0], df.nee[1], df.nee[2], df.nee[3]);
-                    ring.slot[k] = (uint32_t) (oidx - base);      // may exceed the segment (gathering): an offset from `base` all the same
+                    const uint32_t rslot = (uint32_t) (oidx - base);      // may exceed the segment (gathering): an offset from `base` all the same
+                    if (ShadowRing<State>::kSlotInNee) {
+                        ring.nee[k] = make_float4(df.nee[0], df.nee[1], df.nee[2], __uint_as_float(rslot));
+                    } else {
+                        ring.nee[k] = make_float4(df.nee[0], df.nee[1], df.nee[2], df.nee[3]);
+                        ring.slot[k] = rslot;
+                    }
                 } else {
                     const size_t q = base + n_sh + mask_rank(ms);
                     st_stream<kNT>(P.out.sh_o + q, make_float4(df.so.x, df.so.y, df.so.z, df.smint));
@@ -1641,9 +1661,8 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
     if (p.split == 3) {       // LDS-resident scene, one kernel: shadow rays collected in a per-wave LDS ring and resolved 64 at a time
         const uint32_t n_launch = (p.wave_last ? p.wave_last : p.n_waves) - p.wave_first;
         const uint32_t shade_blocks = p.gather_w > 4u ? (n_launch + p.gather_w - 1u) / p.gather_w : (n_launch * 64u + kBlock - 1) / kBlock;
-        const size_t scene_bytes = (bounce_lds_bytes(p.sv) + 15u) & ~(size_t) 15u;
-        p.lds_queue_offset = (uint32_t) (scene_bytes / 16u);
-        const size_t lds = scene_bytes + (size_t) (kBlock / 64u) * kShadowRing * 52u;
+        p.lds_queue_offset = (uint32_t) (shade_ring_offset(p.sv, kBlock) / 16u);
+        const size_t lds = shade_ring_lds_bytes(p.sv, p.spectral != 0, p.gather_w);
         if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else if (p.spectral) hipLaunchKernelGGL((k_shade<PathStateS, false, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else if (p.sv.general) hipLaunchKernelGGL((k_shade<PathState, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
