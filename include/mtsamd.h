@@ -323,6 +323,15 @@ MTSAMD_API int mtsamd_scene_set_bsdf_param(mtsamd_scene *scene, uint32_t bsdf, i
 MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
                                 const float *film_dev, uint32_t bsdf, int32_t param, int32_t component, float h,
                                 float *grad1_dev, void *stream);
+/* The derivative with respect to bitmap texels ('bsdf.reflectance.data', src/textures/bitmap.cpp:295-299) in ANY RGB scene the path
+ * integrator renders -- any emitter mix, any of the supported BSDFs -- of mitsuba.python.autodiff.render (autodiff.py:6-91): the texels of
+ * bitmaps used as diffuse.reflectance or (rough)plastic.diffuse_reflectance (plain or inside `twosided`).  Every camera sample is replayed
+ * with its PCG32 stream through the general path step, its vertices are swept backwards; BSDF values are differentiated in closed form at
+ * the directions of the primal path (lobe probabilities, MIS weights and the specular sampling weight of plastic are held fixed), and
+ * the Russian-roulette factor as mtsamd_render_adjoint does.  grad_textures_dev: the layout of mtsamd_render_adjoint (all textures
+ * concatenated, offsets from mtsamd_scene_texture_info), ACCUMULATED into.  Needs 0 <= max_depth <= 16; no blendbsdf / mask. */
+MTSAMD_API int mtsamd_render_adjoint_textures(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
+                                   const float *film_dev, float *grad_textures_dev, void *stream);
 MTSAMD_API int mtsamd_scene_update_envmap(mtsamd_scene *scene, const float *rgb, int32_t rebuild_distribution);
 /* Size of a bitmap texture and its float offset inside the concatenated texture-gradient buffer. */
 /* RoughPlastic precomputation (roughplastic.cpp:380-399) of BSDF `bsdf`: out65[0..63] = external transmittance at

@@ -6,7 +6,8 @@ diffuse reflectances, constant (``'<bsdf>.reflectance.value'``, ``src/spectra/sr
 The reference records the whole render in Enoki's autodiff graph and calls ``ek.backward``.  Here the forward pass is
 the ordinary wavefront render into an R,G,B,A,W film, and the backward pass is ``mtsamd_render_adjoint``: every camera
 sample is replayed with the same PCG32 stream and its vertices are swept backwards (``k_adjoint`` in
-``csrc/kernels.hip``).  PyTorch only provides the autograd plumbing (as ``render_torch`` does in the reference,
+``csrc/kernels.hip``); outside diffuse scenes bitmap texels of diffuse / (rough)plastic reflectances go through
+``mtsamd_render_adjoint_textures`` (``k_adjoint_tex``, the same sweep over the general path step).  PyTorch only provides the autograd plumbing (as ``render_torch`` does in the reference,
 ``autodiff.py:380-482``).
 """
 import ctypes as C
@@ -26,6 +27,21 @@ _DERIV_SEED_OFFSET = 0x9E3779B97F4A7C15      # decorrelates the derivative pass 
 
 def _is_spectral(scene):
     return getattr(scene, "_variant", getattr(scene, "variant", "rgb")) == "spectral"
+
+
+def _texture_parameters(records):
+    """The bitmap texels mtsamd_render_adjoint_textures differentiates outside diffuse scenes: diffuse.reflectance and
+    (rough)plastic.diffuse_reflectance of the top-level BSDF records, plain or inside `twosided` (whose nested BSDF is "brdf_0",
+    twosided.cpp:183-186).  Returns (key, record index, texels) triples; children of blendbsdf / mask and procedural textures have none."""
+    names = {B.DIFFUSE: "reflectance", B.PLASTIC: "diffuse_reflectance", B.ROUGHPLASTIC: "diffuse_reflectance"}
+    out = []
+    for i, b in enumerate(records):
+        refl = b["reflectance"]
+        if b["type"] not in names or not isinstance(refl, dict) or refl.get("type") != "bitmap":
+            continue
+        name = b.get("id", "bsdf_%d" % i) + (".brdf_0" if b.get("twosided") else "")
+        out.append(("%s.%s.data" % (name, names[b["type"]]), i, refl["data"]))
+    return out
 
 
 class ParameterMap:
@@ -53,6 +69,7 @@ class ParameterMap:
         # diffuse BSDFs (plain or inside `twosided`) lit by area lights only
         diffuse_scene = all(b["type"] == 0 for b in scene._bsdf_records) and \
             all(em.get("type", "area") == "area" for em in emitters)
+        self._diffuse_scene = diffuse_scene
         for i, b in enumerate(scene._bsdf_records if diffuse_scene else []):
             if b["type"] != 0:            # only diffuse reflectances are exposed (the adjoint pass covers those)
                 continue
@@ -96,6 +113,10 @@ class ParameterMap:
                 key = name + ".alpha.value"
                 self.properties[key] = torch.as_tensor([float(b["alpha_u"])], dtype=torch.float32, device=dev)
                 self._kind[key] = ("bsdf_param", flat_index, 4)
+        # bitmap texels of diffuse reflectances in every other RGB scene: the general path replay (mtsamd_render_adjoint_textures)
+        for key, i, data in (_texture_parameters(scene._bsdf_records) if not diffuse_scene and not _is_spectral(scene) else []):
+            self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
+            self._kind[key] = ("texture", scene.texture_index(i), i)
         # 'shape.emitter.radiance.value' of area lights (docs/src/inverse_rendering/diff_render.rst:76)
         for i, m in enumerate(scene._dict["meshes"] if diffuse_scene else []):
             e = m.get("emitter", -1)
@@ -243,8 +264,10 @@ class _Render(torch.autograd.Function):
         if _is_spectral(scene):
             return (None, None, None, None) + tuple(_spectral_gradient(scene, d, pmap, k, gi.reshape(-1)) for k in keys)
         kinds = {pmap._kind[k][0] for k in keys}
-        if kinds - {"envmap", "bsdf_param"}:
+        if pmap._diffuse_scene and kinds - {"envmap", "bsdf_param"}:
             L.check(L.lib().mtsamd_render_adjoint(scene._handle, C.byref(d), _ptr(gi), _ptr(film), _ptr(g_bsdf), _ptr(g_tex), _ptr(g_em), _stream()))
+        elif "texture" in kinds:          # texels in any other scene: the replay through the general step
+            L.check(L.lib().mtsamd_render_adjoint_textures(scene._handle, C.byref(d), _ptr(gi), _ptr(film), _ptr(g_tex), _stream()))
         g_env = None
         if "envmap" in kinds:
             g_env = torch.zeros_like(next(pmap[k] for k in keys if pmap._kind[k][0] == "envmap"))

@@ -1847,6 +1847,20 @@ int mtsamd_render_adjoint_envmap(mtsamd_scene *s, const mtsamd_render_desc *d, c
     return MTSAMD_OK;
 }
 
+int mtsamd_render_adjoint_textures(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, float *grad_tex,
+                                   void *stream_) {
+    AdjointParams a{};
+    if (int rc = fill_adjoint(s, d, dimage, film, a)) return rc;
+    if (!grad_tex) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (d->max_depth < 0 || d->max_depth > 16)
+        return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the texture adjoint does not handle blendbsdf / mask materials");
+    if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
+    a.grad_tex = grad_tex;
+    HIP_TRY(launch_adjoint_tex(a, (hipStream_t) stream_));
+    return MTSAMD_OK;
+}
+
 int mtsamd_scene_update_envmap(mtsamd_scene *s, const float *rgb, int32_t rebuild_distribution) {
     if (!s || !rgb) return fail(MTSAMD_ERR_INVALID, "null argument");
     if (s->environment < 0 || !s->d_envmap) return fail(MTSAMD_ERR_UNSUPPORTED, "the scene has no envmap emitter");

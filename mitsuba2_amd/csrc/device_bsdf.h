@@ -514,6 +514,55 @@ MTS_DEV void bsdf_eval_pdf_n(const DevBsdf &b, const BsdfChannels<N> &c, f3 wi, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Derivatives with respect to the (textured) diffuse reflectance at FIXED directions, per channel (the Jacobian is diagonal), for the
+// reverse replay of k_adjoint_tex.  `diffuse` is linear in the reflectance; (rough)plastic depends on it through plastic_diffuse() alone
+// (the specular lobe has no reflectance term).  The specular sampling weight kr that sets the lobe probabilities comes from the
+// texture mean in parameters_changed() (plastic.cpp:163-177, roughplastic.cpp:364-376) and is held fixed, as are pdfs and MIS weights.
+// Other models have no diffuse reflectance: zero.
+MTS_DEV float plastic_diffuse_drefl(const DevBsdf &b, float refl) {       // d plastic_diffuse / d refl
+    if (b.flags & kBsdfNonlinear) {
+        const float den = 1.0f - refl * b.eb;
+        return 1.0f / (den * den);
+    }
+    return 1.0f / (1.0f - b.eb);
+}
+// d BSDF::eval / d refl at (wi, wo): bsdf_eval_pdf_n above, differentiated
+MTS_DEV f3 bsdf_dvalue_drefl(const DevBsdf &b, f3 refl, f3 wi, f3 wo) {
+    const f3 zero = mk3(0.0f, 0.0f, 0.0f);
+    if (b.flags & kBsdfTwoSided) {
+        if (wi.z == 0.0f) return zero;
+        if (wi.z < 0.0f) { wi.z = -wi.z; wo.z = -wo.z; }
+    }
+    const float cos_theta_i = wi.z, cos_theta_o = wo.z;
+    if (!(cos_theta_i > 0.0f && cos_theta_o > 0.0f)) return zero;
+    if (b.type == kBsdfDiffuse) {
+        const float k = kInvPi * wo.z;
+        return mk3(k, k, k);
+    }
+    float k;
+    if (b.type == kBsdfPlastic) {
+        const float f_i = fresnel(cos_theta_i, b.er).r, f_o = fresnel(cos_theta_o, b.er).r;
+        k = (kInvPi * wo.z) * b.eg * (1.0f - f_i) * (1.0f - f_o);
+    } else if (b.type == kBsdfRoughPlastic) {
+        const float t_i = lerp_gather(b.table, cos_theta_i, kRoughTableRes), t_o = lerp_gather(b.table, cos_theta_o, kRoughTableRes);
+        k = kInvPi * b.eg * cos_theta_o * t_i * t_o;
+    } else {
+        return zero;
+    }
+    return mk3(plastic_diffuse_drefl(b, refl.x) * k, plastic_diffuse_drefl(b, refl.y) * k, plastic_diffuse_drefl(b, refl.z) * k);
+}
+// d weight / d refl of a sample of bsdf_sample_n at its direction: `diffuse` samples weight = refl (1); the diffuse lobe of plastic and
+// both lobes of roughplastic weigh value / pdf with the pdf detached (d value / d refl / pdf); delta lobes carry no reflectance term
+MTS_DEV f3 bsdf_dweight_drefl(const DevBsdf &b, f3 refl, f3 wi, const BsdfSample &bs) {
+    if (bs.delta || !(bs.pdf > 0.0f)) return mk3(0.0f, 0.0f, 0.0f);
+    if (b.type == kBsdfDiffuse) return mk3(1.0f, 1.0f, 1.0f);
+    if (b.type != kBsdfPlastic && b.type != kBsdfRoughPlastic) return mk3(0.0f, 0.0f, 0.0f);
+    const f3 dv = bsdf_dvalue_drefl(b, refl, wi, bs.wo);
+    const float ip = 1.0f / bs.pdf;
+    return mk3(dv.x * ip, dv.y * ip, dv.z * ip);
+}
+
 // Tables of RoughPlastic::parameters_changed (roughplastic.cpp:380-399, microfacet.h:462-553) for one incident cosine:
 // Gauss-Legendre quadrature over the visible-normal sampling domain of the transmitted / internally reflected energy.
 MTS_DEV float rough_transmittance(const Mdf &d, f3 wi, float eta, int res, const float *nodes, const float *weights) {

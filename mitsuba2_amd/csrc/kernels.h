@@ -175,6 +175,7 @@ hipError_t launch_direct(const RenderParams &p, uint64_t n, hipStream_t s);
 hipError_t launch_adjoint(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_env(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_param(const AdjointParams &a, hipStream_t s);
+hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s);      // k_adjoint_tex: into grad_tex (not null)
 // end of a pass: every path of p.in (counts p.count_in) is run to its end in one launch; needs dry sample cursors (kernels.hip, k_finish)
 hipError_t launch_finish(const RenderParams &p, uint64_t alive, hipStream_t s);
 hipError_t launch_mega(const RenderParams &p, hipStream_t s);      // small passes: the whole pass in one launch of persistent lanes

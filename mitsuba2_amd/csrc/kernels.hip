@@ -67,6 +67,20 @@ struct VertexRec {
     float ew, nk; int32_t em_hit, em_nee;
 };
 
+// What k_adjoint_tex remembers about one vertex of a path through the general step (any BSDF model, any emitter).  With T the
+// throughput arriving at the vertex and T' = T * invq after Russian roulette (q = min(hmax(T) eta^2, .95)):
+//   radiance += T * E + T' * Nc;  T_next = T' * W,
+// E = emission collected (MIS weight included), Nc = mis * bv * spec of the emitter sample, W = the BSDF-sample weight, and dNc / dW
+// their derivatives with respect to the textured reflectance at the vertex (diagonal per channel; zero unless `texel` is valid).
+struct VertexRecG {
+    f3 T; float invq;
+    f3 E; float eta2;               // eta^2 of the path at the vertex (the factor of q)
+    f3 Nc; int32_t rr_channel;      // channel that sets q (-1: none / q clamped)
+    f3 W; uint32_t texel;           // bilinear footprint of the texture lookup (kNoPrim: constant or procedural reflectance)
+    f3 dNc; int32_t texture;
+    f3 dW; f2 w1;
+};
+
 // Split ("wavefront") pipeline: the two ray queries of a segment run in their own kernels.  `hit` / `found` carry the
 // closest hit computed by k_trace<false> into the shading step; the shadow ray and the contribution it guards are
 // handed back for k_trace<true>, which adds `nee` to the path's radiance if the ray is unoccluded.
@@ -112,18 +126,25 @@ MTS_DEV void env_grad_add(const DevEnvmap &e, float u, float v, f3 coeff, const 
 // derivative of the image.
 struct ParamGradCtx { int32_t bsdf; DevBsdf bp, bm; float inv_2h; f3 dthr, dres; };
 
+// REC: the vertex is recorded for a reverse sweep -- into `rec` (VertexRec) by the diffuse-only step, into `rg` (VertexRecG) by the
+// general one (k_adjoint_tex).
 template <bool FLAT, bool REC = false, int DEFER = 0, bool GENERAL = false, bool ENVGRAD = false, bool NEST = false, bool PGRAD = false>
 MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c, VertexRec *rec = nullptr,
-                         Deferred *df = nullptr, const EnvGradCtx *eg = nullptr, ParamGradCtx *pg = nullptr) {
+                         Deferred *df = nullptr, const EnvGradCtx *eg = nullptr, ParamGradCtx *pg = nullptr, VertexRecG *rg = nullptr) {
     static_assert(!PGRAD || (GENERAL && DEFER == 0 && !ENVGRAD && !NEST && !REC), "the parameter gradient rides on the general fused step");
-    static_assert(!(REC && GENERAL), "the adjoint replay handles diffuse BSDFs only");
+    static_assert(!(REC && GENERAL) || (DEFER == 0 && !ENVGRAD && !NEST), "the general adjoint replay runs the plain fused step");
     static_assert(!ENVGRAD || (GENERAL && DEFER == 0), "the envmap gradient rides on the general fused step");
     static_assert(!NEST || (GENERAL && DEFER == 0 && !ENVGRAD), "blendbsdf / mask run the general fused step");
     const SceneView &sv = P.sv;
-    if (REC) {
+    if (REC && !GENERAL) {
         rec->E = rec->Nc = rec->Tp = rec->rho = mk3(0.0f, 0.0f, 0.0f);
         rec->invq = 1.0f; rec->rr_channel = -1; rec->T = s.thr; rec->texel = kNoPrim; rec->w1.x = rec->w1.y = 0.0f; rec->bsdf = -1; rec->has_bsdf = 0u;
         rec->ew = rec->nk = 0.0f; rec->em_hit = rec->em_nee = -1;
+    }
+    if (REC && GENERAL) {
+        rg->T = s.thr; rg->invq = 1.0f; rg->eta2 = s.eta * s.eta; rg->rr_channel = -1;
+        rg->E = rg->Nc = rg->W = rg->dNc = rg->dW = mk3(0.0f, 0.0f, 0.0f);
+        rg->texel = kNoPrim; rg->texture = -1; rg->w1.x = rg->w1.y = 0.0f;
     }
     const Geo<FLAT> geo{ sv, lds };
     Hit hit;
@@ -153,16 +174,18 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
             if (si.wi.z > 0.0f) {                           // AreaLight::eval (area.cpp:71-79)
                 s.res.x += (ew * s.thr.x) * e.r; s.res.y += (ew * s.thr.y) * e.g; s.res.z += (ew * s.thr.z) * e.b;
                 if (PGRAD) pg->dres = mk3(pg->dres.x + (ew * pg->dthr.x) * e.r, pg->dres.y + (ew * pg->dthr.y) * e.g, pg->dres.z + (ew * pg->dthr.z) * e.b);
-                if (REC) { rec->E = mk3(ew * e.r, ew * e.g, ew * e.b); rec->ew = ew; rec->em_hit = emitter; }
+                if (REC && !GENERAL) { rec->E = mk3(ew * e.r, ew * e.g, ew * e.b); rec->ew = ew; rec->em_hit = emitter; }
+                if (REC && GENERAL) rg->E = mk3(ew * e.r, ew * e.g, ew * e.b);
             }
         }
     }
-    if (GENERAL && !REC && !found && sv.env_emitter >= 0) {  // si.emitter(scene) of an escaped ray: the environment
+    if (GENERAL && !found && sv.env_emitter >= 0) {          // si.emitter(scene) of an escaped ray: the environment
         const DevEmitter e = geo.emitter((uint32_t) sv.env_emitter);
         float ew = 1.0f;
         if (s.depth > 1u) ew = mis_weight(s.bs_pdf, (GENERAL && (s.flags & kFlagDelta)) ? 0.0f : pdf_environment(sv, e, s.d));
         const f3 le = environment_radiance(sv, e, s.d);
         s.res.x += (ew * s.thr.x) * le.x; s.res.y += (ew * s.thr.y) * le.y; s.res.z += (ew * s.thr.z) * le.z;
+        if (REC && GENERAL) rg->E = mk3(ew * le.x, ew * le.y, ew * le.z);
         if (PGRAD) pg->dres = mk3(pg->dres.x + (ew * pg->dthr.x) * le.x, pg->dres.y + (ew * pg->dthr.y) * le.y, pg->dres.z + (ew * pg->dthr.z) * le.z);
         if (ENVGRAD && e.pad0 == kEmitterEnvmap) {
             float u, v;
@@ -178,9 +201,13 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
         float q = fminf(hm * (s.eta * s.eta), 0.95f);
         if (active) active = pcg_next_f32(s.rng) < q;
         float rq = rcp(q);
-        if (REC) {
+        if (REC && !GENERAL) {
             rec->invq = rq;
             if (hm * (s.eta * s.eta) < 0.95f) rec->rr_channel = s.thr.x == hm ? 0 : (s.thr.y == hm ? 1 : 2);
+        }
+        if (REC && GENERAL) {
+            rg->invq = rq;
+            if (hm * (s.eta * s.eta) < 0.95f) rg->rr_channel = s.thr.x == hm ? 0 : (s.thr.y == hm ? 1 : 2);
         }
         s.thr = s.thr * rq;
         if (PGRAD) pg->dthr = pg->dthr * rq;
@@ -203,11 +230,14 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
         bsdf_eval_pdf(pg->bm, rm, si.wi, wo_l, vm, pm);
         return mk3((vp.x - vm.x) * pg->inv_2h, (vp.y - vm.y) * pg->inv_2h, (vp.z - vm.z) * pg->inv_2h);
     };
-    if (REC) { rec->Tp = s.thr; rec->rho = refl; rec->texel = texel; rec->w1 = tw1; rec->bsdf = si.shape_rec.bsdf; rec->has_bsdf = 1u; }
+    if (REC && !GENERAL) { rec->Tp = s.thr; rec->rho = refl; rec->texel = texel; rec->w1 = tw1; rec->bsdf = si.shape_rec.bsdf; rec->has_bsdf = 1u; }
+    // general replay: derivatives with respect to the textured reflectance are taken only where a bitmap was looked up
+    const bool tex_here = REC && GENERAL && texel != kNoPrim;
+    if (REC && GENERAL) { rg->texel = texel; rg->w1 = tw1; rg->texture = bsdf.texture; }
     // adjoint replay of a `twosided` diffuse BSDF (twosided.cpp:94-175; the primal render of such a scene runs the GENERAL kernels, whose
     // diffuse branch does the same arithmetic): the back side scatters like the front side, mirrored
     f3 wi_b = si.wi;
-    const bool flip = REC && (bsdf.flags & kBsdfTwoSided) != 0u && wi_b.z < 0.0f;
+    const bool flip = REC && !GENERAL && (bsdf.flags & kBsdfTwoSided) != 0u && wi_b.z < 0.0f;
     if (flip) wi_b.z = -wi_b.z;
 
     // --------------------- Emitter sampling (path.cpp:153-172) ---------------------
@@ -215,7 +245,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
         f2 s2; s2.x = pcg_next_f32(s.rng); s2.y = pcg_next_f32(s.rng);
         DirectionSample ds; f3 spec;
         float em_geo = 0.0f;                                 // REC: spec / radiance of an area light
-        if (REC) {
+        if (REC && !GENERAL) {
             float r1, r2;
             sample_emitter_direction<FLAT, GENERAL>(geo, si.p, s2, ds, r1, r2);
             spec = mk3(0.0f, 0.0f, 0.0f);
@@ -246,6 +276,16 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
             float mis = (GENERAL && ds.delta) ? 1.0f : mis_weight(ds.pdf, bp);      // path.cpp:170
             f3 contrib = mk3(((mis * s.thr.x) * bv.x) * spec.x, ((mis * s.thr.y) * bv.y) * spec.y,
                              ((mis * s.thr.z) * bv.z) * spec.z);
+            // general replay: Nc = mis * bv * spec and dNc / d(refl) (mis and spec do not depend on the reflectance)
+            f3 nc = mk3(0.0f, 0.0f, 0.0f), dnc = mk3(0.0f, 0.0f, 0.0f);
+            if (REC && GENERAL) {
+                nc = mk3((mis * bv.x) * spec.x, (mis * bv.y) * spec.y, (mis * bv.z) * spec.z);
+                if (tex_here) {
+                    const f3 dbv = bsdf_dvalue_drefl(bsdf, refl, si.wi, wo);
+                    dnc = mk3((mis * dbv.x) * spec.x, (mis * dbv.y) * spec.y, (mis * dbv.z) * spec.z);
+                }
+            }
+            const bool rec_nee = REC && GENERAL && (nc.x != 0.0f || nc.y != 0.0f || nc.z != 0.0f || dnc.x != 0.0f || dnc.y != 0.0f || dnc.z != 0.0f);
             // The visibility test only ever zeroes `spec` (scene.cpp:178-182): trace the shadow
             // ray only if an unoccluded sample would contribute.
             if (DEFER) {
@@ -255,7 +295,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
                     df->smint = kRayEpsilon * (1.0f + hmax_abs(si.p)); df->smaxt = ds.dist * (1.0f - kShadowEpsilon);
                     df->nee[0] = contrib.x; df->nee[1] = contrib.y; df->nee[2] = contrib.z; df->nee[3] = 0.0f;
                 }
-            } else if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f || ((REC || ENVGRAD) && em_geo != 0.0f) || pg_here) {
+            } else if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f || ((REC || ENVGRAD) && em_geo != 0.0f) || pg_here || rec_nee) {
                 Hit sh;
                 ++c.any;
 #if defined(MTS_ABLATE_SHADOW)   // diagnostic build only: wrong image, used to price the any-hit loop in situ
@@ -277,11 +317,12 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
                         env_grad_add(*sv.envmap, ds.uv.x, ds.uv.y, mk3(((mis * s.thr.x) * bv.x) * em_geo, ((mis * s.thr.y) * bv.y) * em_geo,
                                                                          ((mis * s.thr.z) * bv.z) * em_geo), *eg);
                     const float wo_bz = flip ? -wo.z : wo.z;      // the BSDF's side of the surface (twosided)
-                    if (REC && wi_b.z > 0.0f && wo_bz > 0.0f) {     // d(contrib)/d(rho) / T'_k
+                    if (REC && !GENERAL && wi_b.z > 0.0f && wo_bz > 0.0f) {     // d(contrib)/d(rho) / T'_k
                         float k = mis * (kInvPi * wo_bz);
                         rec->Nc = mk3(k * spec.x, k * spec.y, k * spec.z);
                         if (em_geo != 0.0f) { rec->nk = k * em_geo; rec->em_nee = (int32_t) ds.emitter; }
                     }
+                    if (REC && GENERAL) { rg->Nc = nc; rg->dNc = dnc; }
                 }
             }
         }
@@ -297,6 +338,10 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
         wo = bs.wo; pdf = bs.pdf;
         s.eta *= bs.eta;                                     // harmless for a failed sample: the path ends below
         s.flags = bs.delta ? (s.flags | kFlagDelta) : (s.flags & ~kFlagDelta);
+        if (REC) {            // T_next = T' * W; dW / d(refl) at the sampled direction (pdf and lobe choice detached)
+            rg->W = weight;
+            if (tex_here) rg->dW = bsdf_dweight_drefl(bsdf, refl, si.wi, bs);
+        }
         if (PGRAD) {          // d(thr weight) = dthr weight + thr dweight;  dweight = d(value)/d(theta) / pdf at the sampled direction
             f3 dw = mk3(0.0f, 0.0f, 0.0f);
             if (pg_here && !bs.delta && bs.pdf > 0.0f) {
@@ -1927,6 +1972,66 @@ hipError_t launch_adjoint_param(const AdjointParams &a, hipStream_t s) {
     if (blocks > 2048) blocks = 2048;
     if (a.rp.sv.flat) hipLaunchKernelGGL(k_adjoint_param<true>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
     else hipLaunchKernelGGL(k_adjoint_param<false>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
+    return hipGetLastError();
+}
+
+// Derivative w.r.t. the texels of bitmap reflectances (diffuse.reflectance, (rough)plastic.diffuse_reflectance) in ANY RGB scene: the
+// sweep of k_adjoint over the records of the general step (VertexRecG).  With a = dLoss/dT_{v+1} and delta = dLoss/dRadiance,
+//   dL/drho_v = delta * T'_v * dNc_v + a * T'_v * dW_v,     b_v = delta * Nc_v + W_v * a,
+//   dL/dT_v   = delta * E_v + invq_v * b_v  -  [q not clamped] invq_v^2 eta_v^2 (b_v . T_v) on the channel that sets q.
+// On a diffuse scene (W = rho, Nc = rho * dNc, dW = 1) this is k_adjoint's arithmetic.
+template <bool FLAT>
+__global__ __launch_bounds__(kBlock) void k_adjoint_tex(const AdjointParams A) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = A.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    const uint32_t spp = (uint32_t) P.spp;
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        PathState s; float2 pos;
+        generate_path(P, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
+        const f3 delta = adjoint_delta(A, pos);
+        if (delta.x == 0.0f && delta.y == 0.0f && delta.z == 0.0f) continue;       // every term below is proportional to delta
+        VertexRecG rec[kAdjointMaxDepth];
+        int n = 0;
+        Counters c = { 0u, 0u, 0u, 0u };
+        bool alive = true;
+        while (alive && n < kAdjointMaxDepth) {
+            alive = bounce_step<FLAT, true, 0, true>(P, lds, s, c, nullptr, nullptr, nullptr, nullptr, &rec[n]);
+            ++n;
+        }
+        f3 a = mk3(0.0f, 0.0f, 0.0f);
+        for (int v = n - 1; v >= 0; --v) {
+            const VertexRecG &r = rec[v];
+            if (r.texel != kNoPrim) {
+                const f3 Tp = r.T * r.invq;
+                const float gg[3] = { Tp.x * fmaf(delta.x, r.dNc.x, a.x * r.dW.x), Tp.y * fmaf(delta.y, r.dNc.y, a.y * r.dW.y),
+                                      Tp.z * fmaf(delta.z, r.dNc.z, a.z * r.dW.z) };
+                const DevTexture t = P.sv.textures[r.texture];
+                float *gt = A.grad_tex + t.grad_offset + 3u * (size_t) r.texel;
+                const float w00 = (1.0f - r.w1.y) * (1.0f - r.w1.x), w10 = (1.0f - r.w1.y) * r.w1.x,
+                            w01 = r.w1.y * (1.0f - r.w1.x), w11 = r.w1.y * r.w1.x;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    atomicAdd(gt + ch, gg[ch] * w00); atomicAdd(gt + 3 + ch, gg[ch] * w10);
+                    atomicAdd(gt + 3 * t.w + ch, gg[ch] * w01); atomicAdd(gt + 3 * t.w + 3 + ch, gg[ch] * w11);
+                }
+            }
+            const f3 b = mk3(fmaf(delta.x, r.Nc.x, r.W.x * a.x), fmaf(delta.y, r.Nc.y, r.W.y * a.y), fmaf(delta.z, r.Nc.z, r.W.z * a.z));
+            a = mk3(delta.x * r.E.x + r.invq * b.x, delta.y * r.E.y + r.invq * b.y, delta.z * r.E.z + r.invq * b.z);
+            if (r.rr_channel >= 0) {
+                const float corr = ((r.invq * r.invq) * r.eta2) * (b.x * r.T.x + b.y * r.T.y + b.z * r.T.z);
+                if (r.rr_channel == 0) a.x -= corr; else if (r.rr_channel == 1) a.y -= corr; else a.z -= corr;
+            }
+        }
+    }
+}
+
+hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s) {
+    if (a.n_samples == 0) return hipSuccess;
+    uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
+    if (blocks > 2048) blocks = 2048;
+    if (a.rp.sv.flat) hipLaunchKernelGGL(k_adjoint_tex<true>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
+    else hipLaunchKernelGGL(k_adjoint_tex<false>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
     return hipGetLastError();
 }
 

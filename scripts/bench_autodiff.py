@@ -21,7 +21,11 @@ def main():
     ap.add_argument("--spp", type=int, default=1)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--texture", type=int, default=0, help="optimise a texture of this resolution on floor + back wall instead of the red wall colour")
+    ap.add_argument("--general", action="store_true", help="general scene: textured roughplastic floor + back wall under an envmap "
+                    "(texels through mtsamd_render_adjoint_textures); times one biased iteration and the adjoint kernel alone")
     args = ap.parse_args()
+    if args.general:
+        return bench_general(args)
     tex = None
     if args.texture:
         tex = np.full((args.texture, args.texture, 3), 0.5, np.float32)
@@ -54,6 +58,61 @@ def main():
         err = ((ref - params[key].detach()) ** 2).mean().item()
         print("cbox %dx%d spp=%d max_depth=3 box filter, %s, unbiased=%s: %.2f ms per iteration (fwd+adjoint+Adam), param mse %.3g"
               % (args.res, args.res, args.spp, key, unbiased, ms, err))
+
+
+def bench_general(args):
+    """Cornell box without ceiling and area light, the floor and back wall a textured roughplastic (--texture, default 16), a conductor
+    tall box, an envmap sky: one biased iteration (primal + texel adjoint + Adam) and the texel adjoint alone"""
+    import ctypes as C
+    from mitsuba2_amd import _lib as L
+    from mitsuba2_amd.render import _ptr, _stream
+    n = args.texture or 16
+    tex = np.full((n, n, 3), 0.5, np.float32)
+    sd = scenes.cornell_box(texture=tex)
+    sd["bsdfs"][4] = {"type": "roughplastic", "id": "textured", "alpha": 0.2, "distribution": "ggx", "diffuse_reflectance": {"type": "bitmap", "data": tex}}
+    sd["bsdfs"] = list(sd["bsdfs"]) + [{"type": "conductor", "eta": [0.2, 0.92, 1.1], "k": [3.9, 2.45, 2.14]}]
+    sd["meshes"][7] = dict(sd["meshes"][7], bsdf=len(sd["bsdfs"]) - 1)
+    sd["meshes"] = [m for i, m in enumerate(sd["meshes"]) if i not in (1, 5)]
+    sky = np.random.RandomState(7).uniform(0.3, 1.2, size=(32, 64, 3)).astype(np.float32)
+    sd["emitters"] = [{"type": "envmap", "data": sky, "scale": 0.8}]
+    p = scenes.cornell_box_sensor(args.res, args.res, args.spp, max_depth=3, rfilter="box")
+    scene = render.Scene(sd, sensor=render.make_sensor(p), integrator=render.PathIntegrator(max_depth=3))
+    params = autodiff.traverse(scene)
+    key = "textured.diffuse_reflectance.data"
+    params.keep([key])
+    image_ref = autodiff.render(scene, spp=8).detach()
+    params[key] = torch.full_like(params[key], 0.8)
+    params.update()
+    opt = autodiff.Adam(params, lr=0.02)
+
+    def iteration():
+        img = autodiff.render(scene, optimizer=opt, spp=args.spp)
+        (((img - image_ref) ** 2).sum() / img.numel()).backward()
+        opt.step()
+    for it in range(5):
+        iteration()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(args.iters):
+        iteration()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / args.iters
+    # the texel adjoint alone, for the film and dLoss/dImage of one render
+    d = autodiff._desc(scene, scene.sensors()[0], scene.integrator(), args.spp, 1)
+    film = autodiff._render_film(scene, d)
+    dimage = torch.ones(args.res * args.res * 3, device="cuda")
+    g = torch.zeros(n * n * 3, device="cuda")
+    call = lambda: L.check(L.lib().mtsamd_render_adjoint_textures(scene._handle, C.byref(d), _ptr(dimage), _ptr(film), _ptr(g), _stream()))
+    for it in range(3):
+        call()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(args.iters):
+        call()
+    torch.cuda.synchronize()
+    ms_adj = (time.perf_counter() - t0) * 1e3 / args.iters
+    print("general scene %dx%d spp=%d max_depth=3: textured roughplastic (%dx%d) + conductor + envmap, %s, biased: %.2f ms per iteration "
+          "(fwd+adjoint+Adam), texel adjoint alone %.2f ms" % (args.res, args.res, args.spp, n, n, key, ms, ms_adj))
 
 
 if __name__ == "__main__":
