@@ -508,3 +508,186 @@ def test_spectral_variant_gradients_and_inversion(gpu, oracle):
     got = params["red.reflectance.value"].detach().cpu().numpy()
     assert last < 0.2 * first, (first, last)
     assert np.abs(got - red0).max() < 0.12, got
+
+
+# ---------------------------------------------------------------------------------------------
+# Launch edges of the adjoint kernels (Cornell box, flat path): the second trip of the launchers' grid-stride loops, the depth cap,
+# a crop window, and a sample count that is neither a multiple of the workgroup size nor of the wave size.
+# Observed on an MI355X, worst deviation in units of the bound (rtol 2e-2, atol 2e-3 max|oracle|): grid-stride loop 1.7e-3 (k_adjoint),
+# 3.7e-4 (k_adjoint_tex), and 3.9e-7 against the 2e-3 of k_adjoint_param; depth cap 1.2e-4; crop window 4.7e-5.  Libraries with one wrong
+# line each were tried once: a loop that makes a single trip fails the three grid-stride tests (k_adjoint_param by 5.2 %), a delta
+# without crop_x fails the crop test by 72 times the bound, 15 records instead of 16 fail the depth-cap test by 1.75 times the bound.
+
+def _all_gradients(scene, d, film, dimage, sd, tex):
+    from mitsuba2_amd import _lib as L
+    g_bsdf = torch.zeros((len(sd["bsdfs"]), 3), device="cuda")
+    g_tex = torch.zeros(tex.size, device="cuda")
+    g_em = torch.zeros((len(sd["emitters"]), 3), device="cuda")
+    di = torch.from_numpy(dimage).cuda()
+    L.check(L.lib().mtsamd_render_adjoint(scene._handle, C.byref(d), C.c_void_p(di.data_ptr()), C.c_void_p(film.data_ptr()),
+                                          C.c_void_p(g_bsdf.data_ptr()), C.c_void_p(g_tex.data_ptr()), C.c_void_p(g_em.data_ptr()), None))
+    torch.cuda.synchronize()
+    return g_bsdf.cpu().numpy(), g_tex.cpu().numpy(), g_em.cpu().numpy()
+
+
+def _oracle_gradients(S, desc, dimage, film_o, sd, tex):
+    gs_o, gt_o, ge_o = S.render_adjoint(desc, dimage, film_o, len(sd["meshes"]), tex.size, n_emitters=len(sd["emitters"]))
+    gb_o = np.zeros((len(sd["bsdfs"]), 3), np.float32)
+    for si, m in enumerate(sd["meshes"]):
+        gb_o[m["bsdf"]] += gs_o[si]
+    return gb_o, gt_o, ge_o
+
+
+def _assert_close(what, got, want, rtol=2e-2, atol_rel=2e-3):
+    """np.allclose(got, want, rtol, atol_rel * max|want|), with the worst deviation in units of the bound in the message"""
+    want = np.asarray(want)
+    atol = atol_rel * np.abs(want).max()
+    worst = float(np.max(np.abs(np.asarray(got, np.float64) - want) / (atol + rtol * np.abs(want.astype(np.float64)))))
+    print("%s: worst deviation %.3g of the bound" % (what, worst))
+    assert np.allclose(got, want, rtol=rtol, atol=atol), "%s: worst deviation %.3g x the bound" % (what, worst)
+
+
+def _compare_with_oracle(gpu, oracle, sd, tex, p, scene, dimage_seed=2):
+    """the checks of test_adjoint_matches_oracle for an arbitrary sensor dictionary (crop window included)"""
+    from mitsuba2_amd import autodiff
+    d = autodiff._desc(scene, scene.sensors()[0], scene.integrator(), None, p["seed"])
+    film = autodiff._render_film(scene, d)
+    desc = oracle.make_desc(p, analytic=True, film_rgb=True)
+    S = oracle.OracleScene(sd, naive=True)
+    _, film_o = S.render_image(desc)
+    assert film.shape == film_o.shape == (p["crop"][3], p["crop"][2], 5)
+    assert np.allclose(film.cpu().numpy()[..., 4], film_o[..., 4], rtol=1e-5, atol=1e-6)
+    assert np.mean((film.cpu().numpy()[..., :3] - film_o[..., :3]) ** 2 / (film_o[..., :3] ** 2 + 1e-2)) < 1e-5
+    dimage = np.random.RandomState(dimage_seed).randn(p["crop"][3], p["crop"][2], 3).astype(np.float32)
+    gb_o, gt_o, ge_o = _oracle_gradients(S, desc, dimage, film_o, sd, tex)
+    gb, gt, ge = _all_gradients(scene, d, film, dimage, sd, tex)
+    assert np.abs(ge_o).min() > 1e-3 and np.abs(gt_o).max() > 1e-3 and np.abs(gb_o).max() > 1e-3
+    _assert_close("emitter radiance", ge, ge_o)
+    _assert_close("texels", gt, gt_o)
+    _assert_close("constant reflectances", gb, gb_o)
+    assert (gb[4] == 0).all()
+    return d, film, dimage, (gb_o, gt_o, ge_o)
+
+
+GRID_W, GRID_H, GRID_SPP = 128, 96, 48           # 589 824 samples: more than the launchers' 2048 workgroups x 256 threads
+
+
+def test_adjoint_grid_stride_loop(gpu, oracle):
+    """k_adjoint beyond one sample per thread: the launch is capped at 2048 workgroups and strides over the rest"""
+    assert GRID_W * GRID_H * GRID_SPP > 2048 * 256
+    tex = (0.3 + 0.5 * np.random.RandomState(1).rand(4, 5, 3)).astype(np.float32)
+    sd, p, scene = _scene(gpu, tex, GRID_W, GRID_H, GRID_SPP, 4, "box")
+    _compare_with_oracle(gpu, oracle, sd, tex, p, scene)
+
+
+def test_texture_adjoint_grid_stride_loop(gpu, oracle):
+    """k_adjoint_tex's own copy of the loop, on the same 589 824 samples: the oracle's texel gradient"""
+    from mitsuba2_amd import autodiff, _lib as L
+    tex = (0.3 + 0.5 * np.random.RandomState(1).rand(4, 5, 3)).astype(np.float32)
+    sd, p, scene = _scene(gpu, tex, GRID_W, GRID_H, GRID_SPP, 4, "box")
+    d = autodiff._desc(scene, scene.sensors()[0], scene.integrator(), None, p["seed"])
+    film = autodiff._render_film(scene, d)
+    desc = oracle.make_desc(p, analytic=True, film_rgb=True)
+    S = oracle.OracleScene(sd, naive=True)
+    _, film_o = S.render_image(desc)
+    assert np.mean((film.cpu().numpy()[..., :3] - film_o[..., :3]) ** 2 / (film_o[..., :3] ** 2 + 1e-2)) < 1e-5
+    dimage = np.random.RandomState(2).randn(GRID_H, GRID_W, 3).astype(np.float32)
+    _, gt_o, _ = _oracle_gradients(S, desc, dimage, film_o, sd, tex)
+    g = torch.zeros(tex.size, device="cuda")
+    di = torch.from_numpy(dimage).cuda()
+    L.check(L.lib().mtsamd_render_adjoint_textures(scene._handle, C.byref(d), C.c_void_p(di.data_ptr()), C.c_void_p(film.data_ptr()),
+                                                   C.c_void_p(g.data_ptr()), None))
+    torch.cuda.synchronize()
+    assert np.abs(gt_o).max() > 1e-3
+    _assert_close("texels (k_adjoint_tex)", g.cpu().numpy(), gt_o)
+
+
+def test_bsdf_parameter_adjoint_grid_stride_loop(gpu, oracle):
+    """k_adjoint_param's own copy of the loop: one parameter of the rough conductor on 589 824 samples"""
+    from mitsuba2_amd import autodiff, _lib as L
+    mats = ({"type": "roughconductor", "alpha": 0.3, "distribution": "ggx", "eta": [0.2, 0.92, 1.1], "k": [3.9, 2.45, 2.14], "specular_reflectance": [0.9, 0.8, 0.7]},
+            {"type": "plastic", "diffuse_reflectance": [0.2, 0.5, 0.3], "int_ior": 1.6})
+    sd, p, scene = _material_scene(gpu, mats, w=GRID_W, h=GRID_H, spp=GRID_SPP, max_depth=4)
+    d = autodiff._desc(scene, scene.sensors()[0], scene.integrator(), None, p["seed"])
+    film = autodiff._render_film(scene, d)
+    S = oracle.OracleScene(sd)
+    desc = oracle.make_desc(p, analytic=True, film_rgb=True)
+    _, film_o = S.render_image(desc)
+    assert np.allclose(film.cpu().numpy(), film_o, rtol=2e-5, atol=1e-6)
+    dimage = np.random.RandomState(4).uniform(-1.0, 1.0, (GRID_H, GRID_W, 3)).astype(np.float32)
+    di = torch.from_numpy(dimage).cuda()
+    bsdf_index = len(sd["bsdfs"]) - 2
+    shapes = [i for i, m in enumerate(sd["meshes"]) if m["bsdf"] == bsdf_index]
+    g = torch.zeros(1, device="cuda")
+    L.check(L.lib().mtsamd_render_adjoint_param(scene._handle, C.byref(d), C.c_void_p(di.data_ptr()), C.c_void_p(film.data_ptr()), bsdf_index, 1, 0,
+                                                0.01, C.c_void_p(g.data_ptr()), None))
+    torch.cuda.synchronize()
+    want = S.render_adjoint_param(desc, dimage, film_o, shapes, 1, 0, 0.01)
+    assert abs(want) > 1e-3
+    print("specular_reflectance[0]: %.6g, oracle %.6g, deviation %.3g (bound 2e-3)" % (float(g.item()), want, abs(float(g.item()) - want) / abs(want)))
+    assert abs(float(g.item()) - want) < 2e-3 * abs(want) + 1e-5, (float(g.item()), want, abs(float(g.item()) - want) / abs(want))
+
+
+def _bright_box(tex_seed=1):
+    """a Cornell box in which paths live long and meet light late: reflectances of 0.9 and more, texels in 0.9 .. 0.98, and the whole
+    ceiling a second (dim) area light beside the lamp"""
+    tex = (0.9 + 0.08 * np.random.RandomState(tex_seed).rand(4, 5, 3)).astype(np.float32)
+    sd = scenes.cornell_box(texture=tex)
+    for b, c in zip(sd["bsdfs"], ([0.97, 0.96, 0.95], [0.97, 0.9, 0.9], [0.9, 0.97, 0.9], [0.95, 0.95, 0.95])):
+        b["reflectance"] = np.array(c, np.float32)
+    sd["emitters"] = list(sd["emitters"]) + [dict(type="area", radiance=np.array([2.0, 3.0, 4.0], np.float32))]
+    sd["meshes"][1] = dict(sd["meshes"][1], emitter=1)
+    return sd, tex
+
+
+def test_adjoint_at_the_depth_cap(gpu, oracle):
+    """max_depth = 16 = kAdjointMaxDepth with rr_depth = 16 (no Russian roulette ends a path early): a path that lives that long fills
+    all 16 vertex records, the last one by the step that only collects the emission met at depth 16.  That the comparison sees that
+    record was established on the oracle, whose replay has the same loop: with its record loop cut to 15 its texel and reflectance
+    gradients of this very case (bright box, 24 x 20 @ 4 spp, seed 5) move by 14 times the bound below, the radiance gradient by 1.7
+    times; on the ordinary Cornell box (reflectances around 0.7, a small lamp) the same cut moves them by 2e-4 of the bound only."""
+    from mitsuba2_amd import autodiff
+    sd, tex = _bright_box()
+    p = scenes.cornell_box_sensor(24, 20, 4, seed=5, max_depth=16, rr_depth=16, rfilter="box")
+    scene = gpu.Scene(sd, sensor=gpu.make_sensor(p), integrator=gpu.PathIntegrator(max_depth=16, rr_depth=16))
+    d = autodiff._desc(scene, scene.sensors()[0], scene.integrator(), None, p["seed"])
+    assert d.max_depth == 16 and d.rr_depth == 16
+    _compare_with_oracle(gpu, oracle, sd, tex, p, scene)
+
+
+@pytest.mark.parametrize("max_depth", [17, -1])
+def test_adjoint_refuses_depths_beyond_the_cap(gpu, max_depth):
+    """more vertices than records: both record-keeping replays say so instead of truncating the path"""
+    from mitsuba2_amd import autodiff, _lib as L
+    MTSAMD_ERR_UNSUPPORTED = -5
+    tex = np.full((2, 2, 3), 0.5, np.float32)
+    sd, p, scene = _scene(gpu, tex, 8, 8, 1, 4, "box")
+    d = autodiff._desc(scene, scene.sensors()[0], scene.integrator(), None, p["seed"])
+    film = autodiff._render_film(scene, d)
+    di = torch.zeros((8, 8, 3), device="cuda")
+    g_bsdf, g_tex = torch.zeros((len(sd["bsdfs"]), 3), device="cuda"), torch.zeros(tex.size, device="cuda")
+    d.max_depth = max_depth
+    rc = L.lib().mtsamd_render_adjoint(scene._handle, C.byref(d), C.c_void_p(di.data_ptr()), C.c_void_p(film.data_ptr()),
+                                       C.c_void_p(g_bsdf.data_ptr()), C.c_void_p(g_tex.data_ptr()), None, None)
+    assert rc == MTSAMD_ERR_UNSUPPORTED
+    rc = L.lib().mtsamd_render_adjoint_textures(scene._handle, C.byref(d), C.c_void_p(di.data_ptr()), C.c_void_p(film.data_ptr()),
+                                                C.c_void_p(g_tex.data_ptr()), None)
+    assert rc == MTSAMD_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert float(g_bsdf.abs().max()) == 0.0 and float(g_tex.abs().max()) == 0.0          # nothing was launched
+    with pytest.raises(RuntimeError, match="max_depth <= 16"):
+        L.check(rc)
+
+
+def test_adjoint_in_a_crop_window(gpu, oracle):
+    """adjoint_delta subtracts the crop origin: a 19 x 11 window at (5, 3) of a 37 x 23 film, gaussian filter; dimage and the film have
+    the window's shape.  3 spp: 627 samples, neither a multiple of 256 nor of 64 and fewer than three workgroups -- most threads of
+    the last workgroup skip the loop and still take part in the barrier and the reductions after it."""
+    tex = (0.3 + 0.5 * np.random.RandomState(1).rand(4, 5, 3)).astype(np.float32)
+    sd = scenes.cornell_box(texture=tex)
+    sd["meshes"][5]["id"] = "lamp"
+    p = scenes.cornell_box_sensor(37, 23, 3, seed=5, max_depth=4, rfilter="gaussian")
+    p["crop"] = (5, 3, 19, 11)
+    assert (19 * 11 * 3) % 64 != 0
+    scene = gpu.Scene(sd, sensor=gpu.make_sensor(p), integrator=gpu.PathIntegrator(max_depth=4))
+    _compare_with_oracle(gpu, oracle, sd, tex, p, scene)

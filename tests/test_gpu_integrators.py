@@ -293,3 +293,29 @@ def test_cluster_culling_on_random_flat_scenes(seed):
         # every operation of the path is shared bit for bit with the oracle (round 3: explicit elementary functions on both sides):
         # all samples identical -- rounds 1-2 accepted 99-99.9 % "close" here
         parity_util.check("per-sample radiance", rgb.cpu().numpy(), want[:, :3])
+
+
+@pytest.mark.parametrize("integrator", ["direct", "depth"])
+def test_direct_and_depth_on_the_full_size_mesh(integrator):
+    """k_direct<false> with the traversal stack of the 261 k-triangle mesh (BASELINE config 3: far above 64 KiB of dynamic LDS; the
+    hierarchy cases above stop at bumpy_sphere(32, 64)): per-sample equality with the oracle, as test_direct_matches_oracle and
+    test_depth_matches_ray_intersect assert it"""
+    from mitsuba2_amd import render as R, scenes
+    sd, sp = scenes.bumpy_sphere(256, 512), scenes.bumpy_sphere_sensor(48, 36, 2, seed=13)
+    scene, sensor = R.Scene(sd), R.make_sensor(sp)
+    assert scene.info()["primitives"] > 64
+    n = 48 * 36 * 2
+    if integrator == "direct":
+        integ = R.DirectIntegrator(emitter_samples=3, bsdf_samples=2)
+        op = dict(sp, integrator="direct", emitter_samples=integ.emitter_samples, bsdf_samples=integ.bsdf_samples, hide_emitters=integ.hide_emitters)
+    else:
+        integ, op = R.DepthIntegrator(), dict(sp, integrator="depth")
+    rgb, mask, pos = integ.sample(scene, sensor, 0, n)
+    want, wpos = ob.OracleScene(sd).sample_radiance(ob.make_desc(op), 0, n)
+    assert np.array_equal(pos.cpu().numpy(), wpos) and np.array_equal(mask.cpu().numpy(), want[:, 3] > 0.5)
+    assert mask.cpu().numpy().any() and not mask.cpu().numpy().all()
+    if integrator == "direct":
+        assert (want[:, :3] > 0).any()
+        parity_util.check("per-sample radiance", rgb.cpu().numpy(), want[:, :3])
+    else:
+        assert np.array_equal(rgb.cpu().numpy(), want[:, :3])
