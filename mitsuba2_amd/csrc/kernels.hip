@@ -56,31 +56,6 @@ MTS_DEV void store_state(const PoolView &p, size_t i, const PathState &s) {
 
 struct Counters { uint32_t closest, any, segments, tri_tests; };
 
-// What the adjoint pass remembers about one path vertex k.  With T_k the throughput arriving at the vertex,
-//   radiance += T_k * E_k;  T'_k = T_k * invq_k (Russian roulette);  radiance += T'_k * rho_k * Nc_k (next-event
-//   estimation);  T_{k+1} = T'_k * rho_k (diffuse BSDF sample weight).
-struct VertexRec {
-    f3 E, Nc, Tp, rho; float invq;
-    f3 T; int32_t rr_channel;       // throughput before Russian roulette; channel that sets q (-1: none / q clamped)
-    uint32_t texel; f2 w1; int32_t bsdf; uint32_t has_bsdf;
-    // radiance-free coefficients for d/d(emitter radiance): E = ew * Le[em_hit], Nc = nk * Le[em_nee] (-1: none)
-    float ew, nk; int32_t em_hit, em_nee;
-};
-
-// What k_adjoint_tex remembers about one vertex of a path through the general step (any BSDF model, any emitter).  With T the
-// throughput arriving at the vertex and T' = T * invq after Russian roulette (q = min(hmax(T) eta^2, .95)):
-//   radiance += T * E + T' * Nc;  T_next = T' * W,
-// E = emission collected (MIS weight included), Nc = mis * bv * spec of the emitter sample, W = the BSDF-sample weight, and dNc / dW
-// their derivatives with respect to the textured reflectance at the vertex (diagonal per channel; zero unless `texel` is valid).
-struct VertexRecG {
-    f3 T; float invq;
-    f3 E; float eta2;               // eta^2 of the path at the vertex (the factor of q)
-    f3 Nc; int32_t rr_channel;      // channel that sets q (-1: none / q clamped)
-    f3 W; uint32_t texel;           // bilinear footprint of the texture lookup (kNoPrim: constant or procedural reflectance)
-    f3 dNc; int32_t texture;
-    f3 dW; f2 w1;
-};
-
 // Split ("wavefront") pipeline: the two ray queries of a segment run in their own kernels.  `hit` / `found` carry the
 // closest hit computed by k_trace<false> into the shading step; the shadow ray and the contribution it guards are
 // handed back for k_trace<true>, which adds `nee` to the path's radiance if the ray is unoccluded.
@@ -95,57 +70,46 @@ struct Deferred {
 // GENERAL = true: switch over the BSDF models of device_bsdf.h (delta lobes, eta, twosided).
 constexpr uint32_t kFlagDelta = 4u;       // the ray was spawned by a delta lobe: no emitter-sampling counterpart (path.cpp:198-203)
 
+// What the emitter-sampling block of the step shows a probe: the sample adds ((mis * thr) * bv) * spec to the radiance if it is unoccluded.
+struct NeeTerms {
+    const DirectionSample &ds; f3 wi, wo;     // wi, wo: local directions on the BSDF's side of the surface (see kMirrorTwoSided)
+    f3 bv, spec; float mis;
+    float r1, r2; uint32_t kind;              // kFactoredEmitter: spec = (radiance * r1) * r2 of an emitter of this kind (DevEmitter::pad0)
+};
+
+// A probe watches the step: a plain struct whose member functions the step calls where something observable happens, in the order below.
+// A derivative of the image is a probe next to the kernel that runs it (k_adjoint*); the step itself holds the primal path and nothing
+// else.  NoProbe, the probe of every render kernel, sees nothing: its calls and everything computed only for them compile away.
+struct NoProbe {
+    static constexpr bool kFactoredEmitter = false;      // the emitter sample keeps r1, r2 and the emitter's kind for NeeTerms
+    static constexpr bool kMirrorTwoSided = false;       // the diffuse-only step mirrors wi / wo on the back of a `twosided` diffuse BSDF
+    // the probe is shown the emitter sample and the BSDF sample (the last three calls).  The step does not spell those calls out for a probe
+    // that does not look: building their arguments alone changed the register allocation of the render kernels (scripts/isa_compare.py)
+    static constexpr bool kSamples = false;
+    // the step starts (thr, eta on arrival); the probe rejects the modes of the step it cannot ride on
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) { }
+    // emission picked up, ew = its MIS weight: the area light `emitter` was hit / the ray escaped into the environment `e`
+    MTS_DEV void emitted(float ew, int32_t emitter, f3 le) { }
+    MTS_DEV void escaped(const SceneView &sv, const PathState &s, const DevEmitter &e, float ew, f3 le) { }
+    // Russian roulette: thr before the division by q = 1 / rq, hm = hmax(thr); `free`: q was not clamped to .95
+    MTS_DEV void roulette(f3 thr, float hm, float rq, bool free) { }
+    // the path goes on at a surface whose reflectance `refl` was looked up (texel, tw1: bilinear footprint); thr after roulette
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, uint32_t texel, f2 tw1, f3 thr) { }
+    // an emitter sample was evaluated.  true: trace its shadow ray even if it contributes nothing; then, if the ray is unoccluded:
+    MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &bsdf, f3 refl, const NeeTerms &t) { return false; }
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &si, f3 thr, const NeeTerms &t) { }
+    // the general step drew the BSDF sample `bs` with the numbers s1, s2; thr before it is multiplied by `weight`
+    MTS_DEV void bsdf_sampled(const SceneView &sv, const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, f3 thr, const BsdfSample &bs, f3 weight, float s1, f2 s2) { }
+};
+
 // DEFER: 0 = both ray queries inline (fused kernel); 1 = closest hit precomputed + shadow ray queued (split pipeline of
 // hierarchy scenes); 2 = closest hit inline, shadow ray queued (flat scenes: the any-hit loop then runs on dense batches)
-// ENVGRAD (k_adjoint_env): besides the radiance, d(loss)/d(envmap texels) = delta * d(radiance)/d(texels) is scattered into `grad`
-// (h * w * 3) -- the radiance is linear in the texels at its two uses, the emission an escaped ray picks up and the emitter sample;
-// the sampling distribution built from their luminances is not differentiated (envmap.cpp:220-253 rebuilds it from plain floats)
-struct EnvGradCtx { f3 delta; float *grad; };
-MTS_DEV void env_grad_add(const DevEnvmap &e, float u, float v, f3 coeff, const EnvGradCtx &eg) {
-    u *= (float) (e.w - 1); v *= (float) (e.h - 1);                  // the bilinear footprint of envmap_lookup
-    const uint32_t px = min((uint32_t) u, (uint32_t) (e.w - 2)), py = min((uint32_t) v, (uint32_t) (e.h - 2));
-    const float w1x = u - (float) px, w1y = v - (float) py, w0x = 1.0f - w1x, w0y = 1.0f - w1y;
-    const float wt[4] = { (w0y * w0x) * e.scale, (w0y * w1x) * e.scale, (w1y * w0x) * e.scale, (w1y * w1x) * e.scale };
-    const uint32_t idx[4] = { py * (uint32_t) e.w + px, py * (uint32_t) e.w + px + 1u, (py + 1u) * (uint32_t) e.w + px, (py + 1u) * (uint32_t) e.w + px + 1u };
-    const f3 c = mk3(eg.delta.x * coeff.x, eg.delta.y * coeff.y, eg.delta.z * coeff.z);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float *g = eg.grad + 3u * (size_t) idx[i];
-        atomicAdd(g, c.x * wt[i]); atomicAdd(g + 1, c.y * wt[i]); atomicAdd(g + 2, c.z * wt[i]);
-    }
-}
-
-// PGRAD (k_adjoint_param): derivative of the path's radiance w.r.t. ONE scalar parameter of ONE BSDF record of any model (roughness,
-// complex IOR, reflectances ...), carried forward beside the path as a dual part (dthr = d throughput, dres = d radiance).  Sampling is
-// DETACHED: the replay takes the decisions and directions of the primal path (same PCG32 stream, same parameter value), and
-// differentiates what depends on the parameter for fixed directions -- the BSDF value f(wi, wo) cos in the emitter-sampling term and in
-// the sample weight f cos / pdf (pdf, lobe probabilities, MIS weights and Russian-roulette probabilities are held fixed: any fixed
-// partition of unity keeps the estimator unbiased).  d f / d theta at fixed (wi, wo) is a central difference of the model code itself
-// between two records perturbed by +-h (bp / bm): a smooth closed form at fixed arguments, O(h^2) truncation, no decision can flip.
-// The reference differentiates the attached estimator through Enoki's graph (src/python/python/autodiff.py:6-91); both estimate the same
-// derivative of the image.
-struct ParamGradCtx { int32_t bsdf; DevBsdf bp, bm; float inv_2h; f3 dthr, dres; };
-
-// REC: the vertex is recorded for a reverse sweep -- into `rec` (VertexRec) by the diffuse-only step, into `rg` (VertexRecG) by the
-// general one (k_adjoint_tex).
-template <bool FLAT, bool REC = false, int DEFER = 0, bool GENERAL = false, bool ENVGRAD = false, bool NEST = false, bool PGRAD = false>
-MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c, VertexRec *rec = nullptr,
-                         Deferred *df = nullptr, const EnvGradCtx *eg = nullptr, ParamGradCtx *pg = nullptr, VertexRecG *rg = nullptr) {
-    static_assert(!PGRAD || (GENERAL && DEFER == 0 && !ENVGRAD && !NEST && !REC), "the parameter gradient rides on the general fused step");
-    static_assert(!(REC && GENERAL) || (DEFER == 0 && !ENVGRAD && !NEST), "the general adjoint replay runs the plain fused step");
-    static_assert(!ENVGRAD || (GENERAL && DEFER == 0), "the envmap gradient rides on the general fused step");
-    static_assert(!NEST || (GENERAL && DEFER == 0 && !ENVGRAD), "blendbsdf / mask run the general fused step");
+template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false, class Probe = NoProbe>
+MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c, Probe &&probe = Probe{}, Deferred *df = nullptr) {
+    using Pr = std::remove_reference_t<Probe>;
+    static_assert(!NEST || (GENERAL && DEFER == 0), "blendbsdf / mask run the general fused step");
     const SceneView &sv = P.sv;
-    if (REC && !GENERAL) {
-        rec->E = rec->Nc = rec->Tp = rec->rho = mk3(0.0f, 0.0f, 0.0f);
-        rec->invq = 1.0f; rec->rr_channel = -1; rec->T = s.thr; rec->texel = kNoPrim; rec->w1.x = rec->w1.y = 0.0f; rec->bsdf = -1; rec->has_bsdf = 0u;
-        rec->ew = rec->nk = 0.0f; rec->em_hit = rec->em_nee = -1;
-    }
-    if (REC && GENERAL) {
-        rg->T = s.thr; rg->invq = 1.0f; rg->eta2 = s.eta * s.eta; rg->rr_channel = -1;
-        rg->E = rg->Nc = rg->W = rg->dNc = rg->dW = mk3(0.0f, 0.0f, 0.0f);
-        rg->texel = kNoPrim; rg->texture = -1; rg->w1.x = rg->w1.y = 0.0f;
-    }
+    probe.template begin<DEFER, GENERAL, NEST>(s);
     const Geo<FLAT> geo{ sv, lds };
     Hit hit;
     ++c.closest; ++c.segments;
@@ -173,9 +137,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
             }
             if (si.wi.z > 0.0f) {                           // AreaLight::eval (area.cpp:71-79)
                 s.res.x += (ew * s.thr.x) * e.r; s.res.y += (ew * s.thr.y) * e.g; s.res.z += (ew * s.thr.z) * e.b;
-                if (PGRAD) pg->dres = mk3(pg->dres.x + (ew * pg->dthr.x) * e.r, pg->dres.y + (ew * pg->dthr.y) * e.g, pg->dres.z + (ew * pg->dthr.z) * e.b);
-                if (REC && !GENERAL) { rec->E = mk3(ew * e.r, ew * e.g, ew * e.b); rec->ew = ew; rec->em_hit = emitter; }
-                if (REC && GENERAL) rg->E = mk3(ew * e.r, ew * e.g, ew * e.b);
+                probe.emitted(ew, emitter, mk3(e.r, e.g, e.b));
             }
         }
     }
@@ -185,13 +147,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
         if (s.depth > 1u) ew = mis_weight(s.bs_pdf, (GENERAL && (s.flags & kFlagDelta)) ? 0.0f : pdf_environment(sv, e, s.d));
         const f3 le = environment_radiance(sv, e, s.d);
         s.res.x += (ew * s.thr.x) * le.x; s.res.y += (ew * s.thr.y) * le.y; s.res.z += (ew * s.thr.z) * le.z;
-        if (REC && GENERAL) rg->E = mk3(ew * le.x, ew * le.y, ew * le.z);
-        if (PGRAD) pg->dres = mk3(pg->dres.x + (ew * pg->dthr.x) * le.x, pg->dres.y + (ew * pg->dthr.y) * le.y, pg->dres.z + (ew * pg->dthr.z) * le.z);
-        if (ENVGRAD && e.pad0 == kEmitterEnvmap) {
-            float u, v;
-            env_dir_to_uv(mat3_apply(sv.envmap->to_local, s.d), u, v);
-            env_grad_add(*sv.envmap, u, v, mk3(ew * s.thr.x, ew * s.thr.y, ew * s.thr.z), *eg);
-        }
+        probe.escaped(sv, s, e, ew, le);
     }
     bool active = found;
 
@@ -201,16 +157,8 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
         float q = fminf(hm * (s.eta * s.eta), 0.95f);
         if (active) active = pcg_next_f32(s.rng) < q;
         float rq = rcp(q);
-        if (REC && !GENERAL) {
-            rec->invq = rq;
-            if (hm * (s.eta * s.eta) < 0.95f) rec->rr_channel = s.thr.x == hm ? 0 : (s.thr.y == hm ? 1 : 2);
-        }
-        if (REC && GENERAL) {
-            rg->invq = rq;
-            if (hm * (s.eta * s.eta) < 0.95f) rg->rr_channel = s.thr.x == hm ? 0 : (s.thr.y == hm ? 1 : 2);
-        }
+        probe.roulette(s.thr, hm, rq, hm * (s.eta * s.eta) < 0.95f);
         s.thr = s.thr * rq;
-        if (PGRAD) pg->dthr = pg->dthr * rq;
     }
     if (s.depth >= (uint32_t) P.max_depth || !active) return false;
 
@@ -220,72 +168,43 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
     const NestInfo ni = nest_info<NEST>(bsdf, refl.x, refl.y, refl.z);
     auto child_refl = [&](const DevBsdf &rec) { uint32_t t; f2 w; return eval_reflectance(sv, rec, si.uv, t, w); };      // blend / mask children
     const bool smooth = !GENERAL || bsdf_is_smooth(bsdf);
-    // PGRAD: is this the record whose parameter is differentiated?  d(value)/d(theta) of the model at fixed directions
-    const bool pg_here = PGRAD && si.shape_rec.bsdf == pg->bsdf;
-    auto pg_dvalue = [&](f3 wo_l) -> f3 {
-        uint32_t tt; f2 tw;
-        const f3 rp = eval_reflectance(sv, pg->bp, si.uv, tt, tw), rm = eval_reflectance(sv, pg->bm, si.uv, tt, tw);
-        f3 vp, vm; float pp, pm;
-        bsdf_eval_pdf(pg->bp, rp, si.wi, wo_l, vp, pp);      // the model code itself (two-sided adapter included), no nesting
-        bsdf_eval_pdf(pg->bm, rm, si.wi, wo_l, vm, pm);
-        return mk3((vp.x - vm.x) * pg->inv_2h, (vp.y - vm.y) * pg->inv_2h, (vp.z - vm.z) * pg->inv_2h);
-    };
-    if (REC && !GENERAL) { rec->Tp = s.thr; rec->rho = refl; rec->texel = texel; rec->w1 = tw1; rec->bsdf = si.shape_rec.bsdf; rec->has_bsdf = 1u; }
-    // general replay: derivatives with respect to the textured reflectance are taken only where a bitmap was looked up
-    const bool tex_here = REC && GENERAL && texel != kNoPrim;
-    if (REC && GENERAL) { rg->texel = texel; rg->w1 = tw1; rg->texture = bsdf.texture; }
-    // adjoint replay of a `twosided` diffuse BSDF (twosided.cpp:94-175; the primal render of such a scene runs the GENERAL kernels, whose
+    probe.surface(si, bsdf, refl, texel, tw1, s.thr);
+    // kMirrorTwoSided: a `twosided` diffuse BSDF (twosided.cpp:94-175; the primal render of such a scene runs the GENERAL kernels, whose
     // diffuse branch does the same arithmetic): the back side scatters like the front side, mirrored
     f3 wi_b = si.wi;
-    const bool flip = REC && !GENERAL && (bsdf.flags & kBsdfTwoSided) != 0u && wi_b.z < 0.0f;
+    const bool flip = Pr::kMirrorTwoSided && !GENERAL && (bsdf.flags & kBsdfTwoSided) != 0u && wi_b.z < 0.0f;
     if (flip) wi_b.z = -wi_b.z;
 
     // --------------------- Emitter sampling (path.cpp:153-172) ---------------------
     if (smooth) {                                            // active_e: only BSDFs with a smooth component (path.cpp:154)
         f2 s2; s2.x = pcg_next_f32(s.rng); s2.y = pcg_next_f32(s.rng);
         DirectionSample ds; f3 spec;
-        float em_geo = 0.0f;                                 // REC: spec / radiance of an area light
-        if (REC && !GENERAL) {
-            float r1, r2;
-            sample_emitter_direction<FLAT, GENERAL>(geo, si.p, s2, ds, r1, r2);
-            spec = mk3(0.0f, 0.0f, 0.0f);
-            if (sv.n_emitters != 0u) {
-                const DevEmitter e = geo.emitter(ds.emitter);
-                spec = mk3(e.r * r1, e.g * r1, e.b * r1);
-                if (sv.n_emitters > 1u) spec = spec * r2;
-                em_geo = r1 * r2;
-            }
-        } else if (ENVGRAD) {          // the wrapper below, keeping spec / radiance
-            float r1, r2;
+        float r1 = 0.0f, r2 = 0.0f; uint32_t kind = 0u;
+        if (Pr::kFactoredEmitter) {          // the wrapper below, keeping its factors
             sample_emitter_direction<FLAT, GENERAL>(geo, si.p, s2, ds, r1, r2);
             spec = mk3(0.0f, 0.0f, 0.0f);
             if (sv.n_emitters != 0u) {
                 const DevEmitter e = geo.emitter(ds.emitter);
                 f3 rad = mk3(e.r, e.g, e.b);
-                if (e.pad0 == kEmitterEnvmap) { rad = envmap_lookup(*sv.envmap, ds.uv.x, ds.uv.y); em_geo = sv.n_emitters > 1u ? r1 * r2 : r1; }
-                if (ds.delta) rad = mk3(rad.x * ds.falloff, rad.y * ds.falloff, rad.z * ds.falloff);
+                if (GENERAL && e.pad0 == kEmitterEnvmap) rad = envmap_lookup(*sv.envmap, ds.uv.x, ds.uv.y);
+                if (GENERAL && ds.delta) rad = mk3(rad.x * ds.falloff, rad.y * ds.falloff, rad.z * ds.falloff);
                 spec = mk3(rad.x * r1, rad.y * r1, rad.z * r1);
                 if (sv.n_emitters > 1u) spec = spec * r2;
+                kind = e.pad0;
             }
         } else sample_emitter_direction<FLAT, GENERAL>(geo, si.p, s2, ds, spec);
         if (ds.pdf != 0.0f) {
             f3 wo = to_local(si.sh, ds.d);
+            const f3 wo_b = flip ? mk3(wo.x, wo.y, -wo.z) : wo;
             f3 bv; float bp;
             if (GENERAL) surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, [&](uint32_t i) { return geo.bsdf(i); }, child_refl, si.wi, wo, bv, bp);
-            else diffuse_eval_pdf(refl, wi_b, flip ? mk3(wo.x, wo.y, -wo.z) : wo, bv, bp);
+            else diffuse_eval_pdf(refl, wi_b, wo_b, bv, bp);
             float mis = (GENERAL && ds.delta) ? 1.0f : mis_weight(ds.pdf, bp);      // path.cpp:170
             f3 contrib = mk3(((mis * s.thr.x) * bv.x) * spec.x, ((mis * s.thr.y) * bv.y) * spec.y,
                              ((mis * s.thr.z) * bv.z) * spec.z);
-            // general replay: Nc = mis * bv * spec and dNc / d(refl) (mis and spec do not depend on the reflectance)
-            f3 nc = mk3(0.0f, 0.0f, 0.0f), dnc = mk3(0.0f, 0.0f, 0.0f);
-            if (REC && GENERAL) {
-                nc = mk3((mis * bv.x) * spec.x, (mis * bv.y) * spec.y, (mis * bv.z) * spec.z);
-                if (tex_here) {
-                    const f3 dbv = bsdf_dvalue_drefl(bsdf, refl, si.wi, wo);
-                    dnc = mk3((mis * dbv.x) * spec.x, (mis * dbv.y) * spec.y, (mis * dbv.z) * spec.z);
-                }
-            }
-            const bool rec_nee = REC && GENERAL && (nc.x != 0.0f || nc.y != 0.0f || nc.z != 0.0f || dnc.x != 0.0f || dnc.y != 0.0f || dnc.z != 0.0f);
+            auto nee = [&] { return NeeTerms{ ds, wi_b, wo_b, bv, spec, mis, r1, r2, kind }; };
+            bool watched = false;
+            if (Pr::kSamples) watched = probe.emitter_sample(sv, bsdf, refl, nee());
             // The visibility test only ever zeroes `spec` (scene.cpp:178-182): trace the shadow
             // ray only if an unoccluded sample would contribute.
             if (DEFER) {
@@ -295,7 +214,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
                     df->smint = kRayEpsilon * (1.0f + hmax_abs(si.p)); df->smaxt = ds.dist * (1.0f - kShadowEpsilon);
                     df->nee[0] = contrib.x; df->nee[1] = contrib.y; df->nee[2] = contrib.z; df->nee[3] = 0.0f;
                 }
-            } else if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f || ((REC || ENVGRAD) && em_geo != 0.0f) || pg_here || rec_nee) {
+            } else if (contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f || watched) {
                 Hit sh;
                 ++c.any;
 #if defined(MTS_ABLATE_SHADOW)   // diagnostic build only: wrong image, used to price the any-hit loop in situ
@@ -306,23 +225,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
 #endif
                 if (!occluded) {
                     s.res = s.res + contrib;
-                    if (PGRAD) {          // d(mis thr bv spec) with mis and spec fixed
-                        f3 dbv = mk3(0.0f, 0.0f, 0.0f);
-                        if (pg_here) dbv = pg_dvalue(wo);
-                        pg->dres = mk3(pg->dres.x + (mis * fmaf(pg->dthr.x, bv.x, s.thr.x * dbv.x)) * spec.x,
-                                       pg->dres.y + (mis * fmaf(pg->dthr.y, bv.y, s.thr.y * dbv.y)) * spec.y,
-                                       pg->dres.z + (mis * fmaf(pg->dthr.z, bv.z, s.thr.z * dbv.z)) * spec.z);
-                    }
-                    if (ENVGRAD && em_geo != 0.0f)
-                        env_grad_add(*sv.envmap, ds.uv.x, ds.uv.y, mk3(((mis * s.thr.x) * bv.x) * em_geo, ((mis * s.thr.y) * bv.y) * em_geo,
-                                                                         ((mis * s.thr.z) * bv.z) * em_geo), *eg);
-                    const float wo_bz = flip ? -wo.z : wo.z;      // the BSDF's side of the surface (twosided)
-                    if (REC && !GENERAL && wi_b.z > 0.0f && wo_bz > 0.0f) {     // d(contrib)/d(rho) / T'_k
-                        float k = mis * (kInvPi * wo_bz);
-                        rec->Nc = mk3(k * spec.x, k * spec.y, k * spec.z);
-                        if (em_geo != 0.0f) { rec->nk = k * em_geo; rec->em_nee = (int32_t) ds.emitter; }
-                    }
-                    if (REC && GENERAL) { rg->Nc = nc; rg->dNc = dnc; }
+                    if (Pr::kSamples) probe.unoccluded(sv, si, s.thr, nee());
                 }
             }
         }
@@ -338,31 +241,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
         wo = bs.wo; pdf = bs.pdf;
         s.eta *= bs.eta;                                     // harmless for a failed sample: the path ends below
         s.flags = bs.delta ? (s.flags | kFlagDelta) : (s.flags & ~kFlagDelta);
-        if (REC) {            // T_next = T' * W; dW / d(refl) at the sampled direction (pdf and lobe choice detached)
-            rg->W = weight;
-            if (tex_here) rg->dW = bsdf_dweight_drefl(bsdf, refl, si.wi, bs);
-        }
-        if (PGRAD) {          // d(thr weight) = dthr weight + thr dweight;  dweight = d(value)/d(theta) / pdf at the sampled direction
-            f3 dw = mk3(0.0f, 0.0f, 0.0f);
-            if (pg_here && !bs.delta && bs.pdf > 0.0f) {
-                const f3 dv = pg_dvalue(bs.wo);
-                const float ip = rcp(bs.pdf);
-                dw = mk3(dv.x * ip, dv.y * ip, dv.z * ip);
-            } else if (pg_here && bs.delta) {
-                // a discrete lobe: its weight is a closed form of the parameters (Fresnel term x specular colour / lobe probability);
-                // the same lobe is re-evaluated with the perturbed records and the same random numbers, and counts only if both land on
-                // the very direction of the primal sample (a refracted direction moves with the index of refraction: detached -> no term)
-                uint32_t tt; f2 tw;
-                const f3 rp = eval_reflectance(sv, pg->bp, si.uv, tt, tw), rm = eval_reflectance(sv, pg->bm, si.uv, tt, tw);
-                BsdfSample bp_, bm_; f3 wp, wm;
-                const bool okp = bsdf_sample(pg->bp, rp, si.wi, s1, s2, bp_, wp);
-                const bool okm = bsdf_sample(pg->bm, rm, si.wi, s1, s2, bm_, wm);
-                if (okp && okm && bp_.delta && bm_.delta && bp_.wo.x == bs.wo.x && bp_.wo.y == bs.wo.y && bp_.wo.z == bs.wo.z &&
-                    bm_.wo.x == bs.wo.x && bm_.wo.y == bs.wo.y && bm_.wo.z == bs.wo.z)
-                    dw = mk3((wp.x - wm.x) * pg->inv_2h, (wp.y - wm.y) * pg->inv_2h, (wp.z - wm.z) * pg->inv_2h);
-            }
-            pg->dthr = mk3(fmaf(pg->dthr.x, weight.x, s.thr.x * dw.x), fmaf(pg->dthr.y, weight.y, s.thr.y * dw.y), fmaf(pg->dthr.z, weight.z, s.thr.z * dw.z));
-        }
+        if (Pr::kSamples) probe.bsdf_sampled(sv, si, bsdf, refl, s.thr, bs, weight, s1, s2);
     } else {
         diffuse_sample(refl, wi_b, s2, wo, pdf, weight);     // eta *= bs.eta (== 1)
         if (flip) wo.z = -wo.z;
@@ -461,7 +340,7 @@ void k_bounce(const RenderParams P) {
         bool alive = false;
         if (i0 + lane < n_in) {
             load_state(P.in, base + i0 + lane, s);
-            alive = bounce_step<FLAT, false, 0, GENERAL, false, NEST>(P, lds, s, c);
+            alive = bounce_step<FLAT, 0, GENERAL, NEST>(P, lds, s, c);
             if (!alive) store_result(P, s);
         }
         // wavefront ballot + prefix rank: compact the survivors to the front of the output segment
@@ -1004,7 +883,7 @@ constexpr uint32_t kFlagZombie = 2u;      // path already terminated, kept one i
 
 template <bool GENERAL, bool FLAT>
 MTS_DEV bool step_deferred(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c, Deferred &df) {
-    return bounce_step<FLAT, false, FLAT ? 2 : 1, GENERAL>(P, lds, s, c, nullptr, &df);
+    return bounce_step<FLAT, FLAT ? 2 : 1, GENERAL>(P, lds, s, c, NoProbe{}, &df);
 }
 template <bool GENERAL, bool FLAT>
 MTS_DEV bool step_deferred(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c, Deferred &df) {
@@ -1315,7 +1194,7 @@ void k_shade(const RenderParams P) {
 // the floating-point operations on a sample and their order are those of the other schedules, the film is unchanged).
 constexpr uint32_t kFinishMaxPer = 1024u, kFinishLdsDepth = 8u;      // the spill area is sized for k_trace AND for this depth (trace_spill_words)
 template <bool GENERAL, bool FLAT>
-MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c) { return bounce_step<FLAT, false, 0, GENERAL>(P, lds, s, c); }
+MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c) { return bounce_step<FLAT, 0, GENERAL>(P, lds, s, c); }
 template <bool GENERAL, bool FLAT>
 MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c) { return bounce_step_spectral<FLAT, false, GENERAL>(P, lds, s, c); }
 
@@ -1789,13 +1668,8 @@ MTS_DEV float filter_weight(const FilterView &f, float x) {
 
 
 // ---------------------------------------------------------------------------------------------
-// Reverse-mode derivative of the rendered image with respect to diffuse reflectances (constant colours and
-// bitmap texels), the role Enoki's autodiff plays for mitsuba.python.autodiff.render (autodiff.py:6-91,121-194).
-// One thread replays one camera sample with the same PCG32 stream as the primal pass, records its vertices,
-// and sweeps them backwards:   Y_k = Nc_k + X_{k+1},  dL/drho_k = delta * T'_k * Y_k,  X_k = E_k + invq_k rho_k Y_k,
-// where delta = dLoss/dRadiance of this sample = sum over its filter footprint of w * dLoss/dImage / (W + 1e-8)
-// (Image = values / (weight + 1e-8), autodiff.py:80-91); the sweep below also carries the derivative of the
-// Russian-roulette factor 1/q(T) (path.cpp:137-141), as Enoki's autodiff does.
+// Derivatives of the rendered image.  Each k_adjoint* kernel below replays every camera sample through bounce_step with a probe of its own,
+// which turns what the step shows it into a gradient.  A new derivative is a probe and a kernel here; nothing is added to the step.
 constexpr int kAdjointMaxDepth = 16;
 
 // dLoss/dRadiance of the camera sample at film position `pos`: the adjoint of ImageBlock::put (imageblock.cpp:117-169, block = the
@@ -1829,6 +1703,85 @@ MTS_DEV f3 adjoint_delta(const AdjointParams &A, float2 pos) {
     return delta;
 }
 
+// The camera samples of a launch are dealt to its threads grid-stride (the loop at the top of each kernel; launch_adjoint_kernel caps
+// the grid).  Sample k is regenerated with the PCG32 stream of the primal pass (`s`: the path state at its camera ray); returns
+// dLoss/dRadiance of the sample.
+MTS_DEV f3 adjoint_sample(const AdjointParams &A, uint64_t k, PathState &s) {
+    const uint32_t spp = (uint32_t) A.rp.spp;
+    float2 pos;
+    generate_path(A.rp, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
+    return adjoint_delta(A, pos);
+}
+
+// g (per channel) times the bilinear weights of a texture lookup, added to the gradient of its four texels
+MTS_DEV void scatter_texel_grad(float *grad_tex, const DevTexture &t, uint32_t texel, f2 w1, const float g[3]) {
+    float *gt = grad_tex + t.grad_offset + 3u * (size_t) texel;
+    const float w00 = (1.0f - w1.y) * (1.0f - w1.x), w10 = (1.0f - w1.y) * w1.x, w01 = w1.y * (1.0f - w1.x), w11 = w1.y * w1.x;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        atomicAdd(gt + ch, g[ch] * w00); atomicAdd(gt + 3 + ch, g[ch] * w10);
+        atomicAdd(gt + 3 * t.w + ch, g[ch] * w01); atomicAdd(gt + 3 * t.w + 3 + ch, g[ch] * w11);
+    }
+}
+
+// One workgroup per 256 samples, at most 2048 workgroups (the sample loop strides); the scene is staged like k_bounce's
+template <void (*K_FLAT)(const AdjointParams), void (*K_TREE)(const AdjointParams)>
+static hipError_t launch_adjoint_kernel(const AdjointParams &a, hipStream_t s) {
+    if (a.n_samples == 0) return hipSuccess;
+    uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(a.rp.sv.flat ? K_FLAT : K_TREE, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Reverse-mode derivative of the rendered image with respect to diffuse reflectances (constant colours and
+// bitmap texels), the role Enoki's autodiff plays for mitsuba.python.autodiff.render (autodiff.py:6-91,121-194).
+// One thread replays one camera sample with the same PCG32 stream as the primal pass, records its vertices,
+// and sweeps them backwards:   Y_k = Nc_k + X_{k+1},  dL/drho_k = delta * T'_k * Y_k,  X_k = E_k + invq_k rho_k Y_k,
+// where delta = dLoss/dRadiance of this sample = sum over its filter footprint of w * dLoss/dImage / (W + 1e-8)
+// (Image = values / (weight + 1e-8), autodiff.py:80-91); the sweep below also carries the derivative of the
+// Russian-roulette factor 1/q(T) (path.cpp:137-141), as Enoki's autodiff does.
+//
+// What the adjoint pass remembers about one path vertex k.  With T_k the throughput arriving at the vertex,
+//   radiance += T_k * E_k;  T'_k = T_k * invq_k (Russian roulette);  radiance += T'_k * rho_k * Nc_k (next-event
+//   estimation);  T_{k+1} = T'_k * rho_k (diffuse BSDF sample weight).
+struct VertexRec {
+    f3 E, Nc, Tp, rho; float invq;
+    f3 T; int32_t rr_channel;       // throughput before Russian roulette; channel that sets q (-1: none / q clamped)
+    uint32_t texel; f2 w1; int32_t bsdf; uint32_t has_bsdf;
+    // radiance-free coefficients for d/d(emitter radiance): E = ew * Le[em_hit], Nc = nk * Le[em_nee] (-1: none)
+    float ew, nk; int32_t em_hit, em_nee;
+};
+
+// Fills the VertexRec of one diffuse-only step.  The back of a `twosided` diffuse BSDF is replayed mirrored (kMirrorTwoSided).
+struct DiffuseRecorder {
+    static constexpr bool kFactoredEmitter = true, kMirrorTwoSided = true, kSamples = true;
+    VertexRec &r;
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) {
+        static_assert(!GENERAL && DEFER == 0 && !NEST, "the diffuse adjoint replay runs the diffuse-only fused step");
+        r.E = r.Nc = r.Tp = r.rho = mk3(0.0f, 0.0f, 0.0f);
+        r.invq = 1.0f; r.rr_channel = -1; r.T = s.thr; r.texel = kNoPrim; r.w1.x = r.w1.y = 0.0f; r.bsdf = -1; r.has_bsdf = 0u;
+        r.ew = r.nk = 0.0f; r.em_hit = r.em_nee = -1;
+    }
+    MTS_DEV void emitted(float ew, int32_t emitter, f3 le) { r.E = mk3(ew * le.x, ew * le.y, ew * le.z); r.ew = ew; r.em_hit = emitter; }
+    MTS_DEV void escaped(const SceneView &, const PathState &, const DevEmitter &, float, f3) { }
+    MTS_DEV void roulette(f3 thr, float hm, float rq, bool free) { r.invq = rq; if (free) r.rr_channel = thr.x == hm ? 0 : (thr.y == hm ? 1 : 2); }
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &, f3 refl, uint32_t texel, f2 tw1, f3 thr) {
+        r.Tp = thr; r.rho = refl; r.texel = texel; r.w1 = tw1; r.bsdf = si.shape_rec.bsdf; r.has_bsdf = 1u;
+    }
+    MTS_DEV bool emitter_sample(const SceneView &, const DevBsdf &, f3, const NeeTerms &t) { return t.r1 * t.r2 != 0.0f; }
+    MTS_DEV void unoccluded(const SceneView &, const SurfaceInteraction &, f3, const NeeTerms &t) {
+        if (t.wi.z > 0.0f && t.wo.z > 0.0f) {     // d(contrib)/d(rho) / T'_k
+            float k = t.mis * (kInvPi * t.wo.z);
+            r.Nc = mk3(k * t.spec.x, k * t.spec.y, k * t.spec.z);
+            const float em_geo = t.r1 * t.r2;      // spec / radiance of an area light
+            if (em_geo != 0.0f) { r.nk = k * em_geo; r.em_nee = (int32_t) t.ds.emitter; }
+        }
+    }
+    MTS_DEV void bsdf_sampled(const SceneView &, const SurfaceInteraction &, const DevBsdf &, f3, f3, const BsdfSample &, f3, float, f2) { }
+};
+
 template <bool FLAT>
 __global__ __launch_bounds__(kBlock) void k_adjoint(const AdjointParams A) {
     extern __shared__ float4 smem[];
@@ -1838,17 +1791,14 @@ __global__ __launch_bounds__(kBlock) void k_adjoint(const AdjointParams A) {
     __shared__ float s_grad_em[3 * 32];                    // ... and for the radiance of area lights
     for (uint32_t i = threadIdx.x; i < 3u * 32u; i += kBlock) s_grad[i] = s_grad_em[i] = 0.0f;
     __syncthreads();
-    const uint32_t spp = (uint32_t) P.spp;
     for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
-        PathState s; float2 pos;
-        generate_path(P, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
-        const f3 delta = adjoint_delta(A, pos);
+        PathState s; const f3 delta = adjoint_sample(A, k, s);
         // ---- replay the path, remembering its vertices
         VertexRec rec[kAdjointMaxDepth];
         int n = 0;
         Counters c = { 0u, 0u, 0u, 0u };
         bool alive = true;
-        while (alive && n < kAdjointMaxDepth) { alive = bounce_step<FLAT, true>(P, lds, s, c, &rec[n]); ++n; }
+        while (alive && n < kAdjointMaxDepth) { alive = bounce_step<FLAT>(P, lds, s, c, DiffuseRecorder{ rec[n] }); ++n; }
         // ---- backward sweep; a = dLoss/dT_v.  q = min(hmax(T) eta^2, .95) is differentiated like Enoki does (the
         // gradient flows to the maximal channel when q is not clamped); the survival test is not differentiable.
         f3 a = mk3(0.0f, 0.0f, 0.0f);
@@ -1870,17 +1820,8 @@ __global__ __launch_bounds__(kBlock) void k_adjoint(const AdjointParams A) {
             const f3 b = mk3(r.rho.x * Y.x, r.rho.y * Y.y, r.rho.z * Y.z);
             if (r.texel != kNoPrim) {
                 const DevTexture t = P.sv.textures[P.sv.bsdfs[r.bsdf].texture];
-                if (A.grad_tex) {
-                    float *gt = A.grad_tex + t.grad_offset + 3u * (size_t) r.texel;
-                    const float w00 = (1.0f - r.w1.y) * (1.0f - r.w1.x), w10 = (1.0f - r.w1.y) * r.w1.x,
-                                w01 = r.w1.y * (1.0f - r.w1.x), w11 = r.w1.y * r.w1.x;
-                    const float gg[3] = { g.x, g.y, g.z };
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) {
-                        atomicAdd(gt + ch, gg[ch] * w00); atomicAdd(gt + 3 + ch, gg[ch] * w10);
-                        atomicAdd(gt + 3 * t.w + ch, gg[ch] * w01); atomicAdd(gt + 3 * t.w + 3 + ch, gg[ch] * w11);
-                    }
-                }
+                const float gg[3] = { g.x, g.y, g.z };
+                if (A.grad_tex) scatter_texel_grad(A.grad_tex, t, r.texel, r.w1, gg);
             } else if (A.grad_bsdf && r.bsdf >= 0 && r.bsdf < 32) {
                 atomicAdd(&s_grad[3 * r.bsdf], g.x); atomicAdd(&s_grad[3 * r.bsdf + 1], g.y); atomicAdd(&s_grad[3 * r.bsdf + 2], g.z);
             }
@@ -1900,59 +1841,141 @@ __global__ __launch_bounds__(kBlock) void k_adjoint(const AdjointParams A) {
             if (s_grad_em[i] != 0.0f) atomicAdd(A.grad_emitter + i, s_grad_em[i]);
 }
 
-hipError_t launch_adjoint(const AdjointParams &a, hipStream_t s) {
-    if (a.n_samples == 0) return hipSuccess;
-    uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
-    if (blocks > 2048) blocks = 2048;
-    if (a.rp.sv.flat) hipLaunchKernelGGL(k_adjoint<true>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    else hipLaunchKernelGGL(k_adjoint<false>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    return hipGetLastError();
-}
+hipError_t launch_adjoint(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint<true>, k_adjoint<false>>(a, s); }
 
 // Derivative w.r.t. the texels of the `envmap` emitter ('data', envmap.cpp:214-218; docs/examples/10_inverse_rendering/invert_bunny.py):
 // one thread replays one camera sample with the PCG32 stream of the primal pass through the general fused step -- any BSDF, any depth
-// -- and scatters delta * d(radiance)/d(texel) at every use of the map (bounce_step, ENVGRAD).
+// -- and scatters d(loss)/d(envmap texels) = delta * d(radiance)/d(texels) into `grad` (h * w * 3) at every use of the map.  The radiance
+// is linear in the texels at its two uses, the emission an escaped ray picks up and the emitter sample; the sampling distribution built
+// from their luminances is not differentiated (envmap.cpp:220-253 rebuilds it from plain floats).
+struct EnvGradProbe {
+    static constexpr bool kFactoredEmitter = true, kMirrorTwoSided = false, kSamples = true;
+    f3 delta; float *grad;
+    MTS_DEV void add(const DevEnvmap &e, float u, float v, f3 coeff) const {
+        u *= (float) (e.w - 1); v *= (float) (e.h - 1);                  // the bilinear footprint of envmap_lookup
+        const uint32_t px = min((uint32_t) u, (uint32_t) (e.w - 2)), py = min((uint32_t) v, (uint32_t) (e.h - 2));
+        const float w1x = u - (float) px, w1y = v - (float) py, w0x = 1.0f - w1x, w0y = 1.0f - w1y;
+        const float wt[4] = { (w0y * w0x) * e.scale, (w0y * w1x) * e.scale, (w1y * w0x) * e.scale, (w1y * w1x) * e.scale };
+        const uint32_t idx[4] = { py * (uint32_t) e.w + px, py * (uint32_t) e.w + px + 1u, (py + 1u) * (uint32_t) e.w + px, (py + 1u) * (uint32_t) e.w + px + 1u };
+        const f3 c = mk3(delta.x * coeff.x, delta.y * coeff.y, delta.z * coeff.z);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float *g = grad + 3u * (size_t) idx[i];
+            atomicAdd(g, c.x * wt[i]); atomicAdd(g + 1, c.y * wt[i]); atomicAdd(g + 2, c.z * wt[i]);
+        }
+    }
+    // spec / radiance of an envmap sample (0 for every other emitter)
+    MTS_DEV static float em_geo(const SceneView &sv, const NeeTerms &t) { return t.kind == kEmitterEnvmap ? (sv.n_emitters > 1u ? t.r1 * t.r2 : t.r1) : 0.0f; }
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &) { static_assert(GENERAL && DEFER == 0 && !NEST, "the envmap gradient rides on the general fused step"); }
+    MTS_DEV void emitted(float, int32_t, f3) { }
+    MTS_DEV void escaped(const SceneView &sv, const PathState &s, const DevEmitter &e, float ew, f3) {
+        if (e.pad0 == kEmitterEnvmap) {
+            float u, v;
+            env_dir_to_uv(mat3_apply(sv.envmap->to_local, s.d), u, v);
+            add(*sv.envmap, u, v, mk3(ew * s.thr.x, ew * s.thr.y, ew * s.thr.z));
+        }
+    }
+    MTS_DEV void roulette(f3, float, float, bool) { }
+    MTS_DEV void surface(const SurfaceInteraction &, const DevBsdf &, f3, uint32_t, f2, f3) { }
+    MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &, f3, const NeeTerms &t) { return em_geo(sv, t) != 0.0f; }
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &, f3 thr, const NeeTerms &t) {
+        const float g = em_geo(sv, t);
+        if (g != 0.0f) add(*sv.envmap, t.ds.uv.x, t.ds.uv.y, mk3(((t.mis * thr.x) * t.bv.x) * g, ((t.mis * thr.y) * t.bv.y) * g, ((t.mis * thr.z) * t.bv.z) * g));
+    }
+    MTS_DEV void bsdf_sampled(const SceneView &, const SurfaceInteraction &, const DevBsdf &, f3, f3, const BsdfSample &, f3, float, f2) { }
+};
+
 template <bool FLAT>
 __global__ __launch_bounds__(kBlock) void k_adjoint_env(const AdjointParams A) {
     extern __shared__ float4 smem[];
     const RenderParams &P = A.rp;
     const LdsView lds = lds_stage<FLAT>(P.sv, smem);
-    const uint32_t spp = (uint32_t) P.spp;
     for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
-        PathState s; float2 pos;
-        generate_path(P, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
-        const EnvGradCtx eg = { adjoint_delta(A, pos), A.grad_env };
+        PathState s; const f3 delta = adjoint_sample(A, k, s);
+        EnvGradProbe eg = { delta, A.grad_env };
         Counters c = { 0u, 0u, 0u, 0u };
-        while (bounce_step<FLAT, false, 0, true, true>(P, lds, s, c, nullptr, nullptr, &eg)) { }
+        while (bounce_step<FLAT, 0, true>(P, lds, s, c, eg)) { }
     }
 }
 
-hipError_t launch_adjoint_env(const AdjointParams &a, hipStream_t s) {
-    if (a.n_samples == 0) return hipSuccess;
-    uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
-    if (blocks > 2048) blocks = 2048;
-    if (a.rp.sv.flat) hipLaunchKernelGGL(k_adjoint_env<true>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    else hipLaunchKernelGGL(k_adjoint_env<false>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    return hipGetLastError();
-}
+hipError_t launch_adjoint_env(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_env<true>, k_adjoint_env<false>>(a, s); }
 
-// d(loss)/d(one scalar BSDF parameter): every camera sample is replayed through the general fused step with the dual part of
-// bounce_step<PGRAD>; its contribution delta . d(radiance)/d(theta) is summed over the workgroup and added to A.grad_param[0].
+// d(loss)/d(one scalar BSDF parameter): derivative of the path's radiance w.r.t. ONE scalar parameter of ONE BSDF record of any model
+// (roughness, complex IOR, reflectances ...), carried forward beside the path as a dual part (dthr = d throughput, dres = d radiance).
+// Sampling is DETACHED: the replay takes the decisions and directions of the primal path (same PCG32 stream, same parameter value), and
+// differentiates what depends on the parameter for fixed directions -- the BSDF value f(wi, wo) cos in the emitter-sampling term and in
+// the sample weight f cos / pdf (pdf, lobe probabilities, MIS weights and Russian-roulette probabilities are held fixed: any fixed
+// partition of unity keeps the estimator unbiased).  d f / d theta at fixed (wi, wo) is a central difference of the model code itself
+// between two records perturbed by +-h (bp / bm): a smooth closed form at fixed arguments, O(h^2) truncation, no decision can flip.
+// The reference differentiates the attached estimator through Enoki's graph (src/python/python/autodiff.py:6-91); both estimate the same
+// derivative of the image.
+struct ParamGradProbe {
+    static constexpr bool kFactoredEmitter = false, kMirrorTwoSided = false, kSamples = true;
+    int32_t bsdf; DevBsdf bp, bm; float inv_2h; f3 dthr, dres;
+    bool here;                  // is the surface's record the one whose parameter is differentiated?
+    // the reflectances of the two perturbed records at the surface
+    MTS_DEV void perturbed_refl(const SceneView &sv, const SurfaceInteraction &si, f3 &rp, f3 &rm) const {
+        uint32_t tt; f2 tw;
+        rp = eval_reflectance(sv, bp, si.uv, tt, tw); rm = eval_reflectance(sv, bm, si.uv, tt, tw);
+    }
+    // d(value)/d(theta) of the model at fixed directions
+    MTS_DEV f3 dvalue(const SceneView &sv, const SurfaceInteraction &si, f3 wo_l) const {
+        f3 rp, rm, vp, vm; float pp, pm;
+        perturbed_refl(sv, si, rp, rm);
+        bsdf_eval_pdf(bp, rp, si.wi, wo_l, vp, pp);      // the model code itself (two-sided adapter included), no nesting
+        bsdf_eval_pdf(bm, rm, si.wi, wo_l, vm, pm);
+        return mk3((vp.x - vm.x) * inv_2h, (vp.y - vm.y) * inv_2h, (vp.z - vm.z) * inv_2h);
+    }
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &) { static_assert(GENERAL && DEFER == 0 && !NEST, "the parameter gradient rides on the general fused step"); }
+    MTS_DEV void emitted(float ew, int32_t, f3 le) { dres = mk3(dres.x + (ew * dthr.x) * le.x, dres.y + (ew * dthr.y) * le.y, dres.z + (ew * dthr.z) * le.z); }
+    MTS_DEV void escaped(const SceneView &, const PathState &, const DevEmitter &, float ew, f3 le) { emitted(ew, -1, le); }
+    MTS_DEV void roulette(f3, float, float rq, bool) { dthr = dthr * rq; }
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &, f3, uint32_t, f2, f3) { here = si.shape_rec.bsdf == bsdf; }
+    MTS_DEV bool emitter_sample(const SceneView &, const DevBsdf &, f3, const NeeTerms &) { return here; }
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &si, f3 thr, const NeeTerms &t) {      // d(mis thr bv spec) with mis and spec fixed
+        f3 dbv = mk3(0.0f, 0.0f, 0.0f);
+        if (here) dbv = dvalue(sv, si, t.wo);
+        dres = mk3(dres.x + (t.mis * fmaf(dthr.x, t.bv.x, thr.x * dbv.x)) * t.spec.x,
+                   dres.y + (t.mis * fmaf(dthr.y, t.bv.y, thr.y * dbv.y)) * t.spec.y,
+                   dres.z + (t.mis * fmaf(dthr.z, t.bv.z, thr.z * dbv.z)) * t.spec.z);
+    }
+    // d(thr weight) = dthr weight + thr dweight;  dweight = d(value)/d(theta) / pdf at the sampled direction
+    MTS_DEV void bsdf_sampled(const SceneView &sv, const SurfaceInteraction &si, const DevBsdf &, f3, f3 thr, const BsdfSample &bs, f3 weight, float s1, f2 s2) {
+        f3 dw = mk3(0.0f, 0.0f, 0.0f);
+        if (here && !bs.delta && bs.pdf > 0.0f) {
+            const f3 dv = dvalue(sv, si, bs.wo);
+            const float ip = rcp(bs.pdf);
+            dw = mk3(dv.x * ip, dv.y * ip, dv.z * ip);
+        } else if (here && bs.delta) {
+            // a discrete lobe: its weight is a closed form of the parameters (Fresnel term x specular colour / lobe probability);
+            // the same lobe is re-evaluated with the perturbed records and the same random numbers, and counts only if both land on
+            // the very direction of the primal sample (a refracted direction moves with the index of refraction: detached -> no term)
+            f3 rp, rm, wp, wm; BsdfSample bp_, bm_;
+            perturbed_refl(sv, si, rp, rm);
+            const bool okp = bsdf_sample(bp, rp, si.wi, s1, s2, bp_, wp);
+            const bool okm = bsdf_sample(bm, rm, si.wi, s1, s2, bm_, wm);
+            if (okp && okm && bp_.delta && bm_.delta && bp_.wo.x == bs.wo.x && bp_.wo.y == bs.wo.y && bp_.wo.z == bs.wo.z &&
+                bm_.wo.x == bs.wo.x && bm_.wo.y == bs.wo.y && bm_.wo.z == bs.wo.z)
+                dw = mk3((wp.x - wm.x) * inv_2h, (wp.y - wm.y) * inv_2h, (wp.z - wm.z) * inv_2h);
+        }
+        dthr = mk3(fmaf(dthr.x, weight.x, thr.x * dw.x), fmaf(dthr.y, weight.y, thr.y * dw.y), fmaf(dthr.z, weight.z, thr.z * dw.z));
+    }
+};
+
+// Every camera sample is replayed through the general fused step with the dual part of ParamGradProbe; its contribution
+// delta . d(radiance)/d(theta) is summed over the workgroup and added to A.grad_param[0].
 template <bool FLAT>
 __global__ __launch_bounds__(kBlock) void k_adjoint_param(const AdjointParams A) {
     extern __shared__ float4 smem[];
     __shared__ float s_sum[kBlock / 64];
     const RenderParams &P = A.rp;
     const LdsView lds = lds_stage<FLAT>(P.sv, smem);
-    const uint32_t spp = (uint32_t) P.spp;
     float acc = 0.0f;
     for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
-        PathState s; float2 pos;
-        generate_path(P, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
-        const f3 delta = adjoint_delta(A, pos);
-        ParamGradCtx pg = { A.pg_bsdf, A.pg_plus, A.pg_minus, A.pg_inv_2h, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 0.0f) };
+        PathState s; const f3 delta = adjoint_sample(A, k, s);
+        ParamGradProbe pg = { A.pg_bsdf, A.pg_plus, A.pg_minus, A.pg_inv_2h, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 0.0f), false };
         Counters c = { 0u, 0u, 0u, 0u };
-        while (bounce_step<FLAT, false, 0, true, false, false, true>(P, lds, s, c, nullptr, nullptr, nullptr, &pg)) { }
+        while (bounce_step<FLAT, 0, true>(P, lds, s, c, pg)) { }
         const float g = fmaf(delta.z, pg.dres.z, fmaf(delta.y, pg.dres.y, delta.x * pg.dres.x));
         if (isfinite(g)) acc += g;
     }
@@ -1966,39 +1989,77 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_param(const AdjointParams A)
     }
 }
 
-hipError_t launch_adjoint_param(const AdjointParams &a, hipStream_t s) {
-    if (a.n_samples == 0) return hipSuccess;
-    uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
-    if (blocks > 2048) blocks = 2048;
-    if (a.rp.sv.flat) hipLaunchKernelGGL(k_adjoint_param<true>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    else hipLaunchKernelGGL(k_adjoint_param<false>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    return hipGetLastError();
-}
+hipError_t launch_adjoint_param(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_param<true>, k_adjoint_param<false>>(a, s); }
 
 // Derivative w.r.t. the texels of bitmap reflectances (diffuse.reflectance, (rough)plastic.diffuse_reflectance) in ANY RGB scene: the
 // sweep of k_adjoint over the records of the general step (VertexRecG).  With a = dLoss/dT_{v+1} and delta = dLoss/dRadiance,
 //   dL/drho_v = delta * T'_v * dNc_v + a * T'_v * dW_v,     b_v = delta * Nc_v + W_v * a,
 //   dL/dT_v   = delta * E_v + invq_v * b_v  -  [q not clamped] invq_v^2 eta_v^2 (b_v . T_v) on the channel that sets q.
 // On a diffuse scene (W = rho, Nc = rho * dNc, dW = 1) this is k_adjoint's arithmetic.
+//
+// What k_adjoint_tex remembers about one vertex of a path through the general step (any BSDF model, any emitter).  With T the
+// throughput arriving at the vertex and T' = T * invq after Russian roulette (q = min(hmax(T) eta^2, .95)):
+//   radiance += T * E + T' * Nc;  T_next = T' * W,
+// E = emission collected (MIS weight included), Nc = mis * bv * spec of the emitter sample, W = the BSDF-sample weight, and dNc / dW
+// their derivatives with respect to the textured reflectance at the vertex (diagonal per channel; zero unless `texel` is valid).
+struct VertexRecG {
+    f3 T; float invq;
+    f3 E; float eta2;               // eta^2 of the path at the vertex (the factor of q)
+    f3 Nc; int32_t rr_channel;      // channel that sets q (-1: none / q clamped)
+    f3 W; uint32_t texel;           // bilinear footprint of the texture lookup (kNoPrim: constant or procedural reflectance)
+    f3 dNc; int32_t texture;
+    f3 dW; f2 w1;
+};
+
+// Fills the VertexRecG of one general step.  Derivatives with respect to the textured reflectance are taken only where a bitmap was
+// looked up (`tex`); mis, spec, the pdf and the lobe choice do not depend on the reflectance (detached).
+struct GeneralRecorder {
+    static constexpr bool kFactoredEmitter = false, kMirrorTwoSided = false, kSamples = true;
+    VertexRecG &r;
+    bool tex; f3 nc, dnc;           // Nc and dNc / d(refl) of the emitter sample, recorded once it is known to be unoccluded
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) {
+        static_assert(GENERAL && DEFER == 0 && !NEST, "the general adjoint replay runs the plain fused step");
+        r.T = s.thr; r.invq = 1.0f; r.eta2 = s.eta * s.eta; r.rr_channel = -1;
+        r.E = r.Nc = r.W = r.dNc = r.dW = mk3(0.0f, 0.0f, 0.0f);
+        r.texel = kNoPrim; r.texture = -1; r.w1.x = r.w1.y = 0.0f;
+    }
+    MTS_DEV void emitted(float ew, int32_t, f3 le) { r.E = mk3(ew * le.x, ew * le.y, ew * le.z); }
+    MTS_DEV void escaped(const SceneView &, const PathState &, const DevEmitter &, float ew, f3 le) { emitted(ew, -1, le); }
+    MTS_DEV void roulette(f3 thr, float hm, float rq, bool free) { r.invq = rq; if (free) r.rr_channel = thr.x == hm ? 0 : (thr.y == hm ? 1 : 2); }
+    MTS_DEV void surface(const SurfaceInteraction &, const DevBsdf &bsdf, f3, uint32_t texel, f2 tw1, f3) {
+        tex = texel != kNoPrim;
+        r.texel = texel; r.w1 = tw1; r.texture = bsdf.texture;
+    }
+    MTS_DEV bool emitter_sample(const SceneView &, const DevBsdf &bsdf, f3 refl, const NeeTerms &t) {
+        nc = mk3((t.mis * t.bv.x) * t.spec.x, (t.mis * t.bv.y) * t.spec.y, (t.mis * t.bv.z) * t.spec.z);
+        dnc = mk3(0.0f, 0.0f, 0.0f);
+        if (tex) {
+            const f3 dbv = bsdf_dvalue_drefl(bsdf, refl, t.wi, t.wo);
+            dnc = mk3((t.mis * dbv.x) * t.spec.x, (t.mis * dbv.y) * t.spec.y, (t.mis * dbv.z) * t.spec.z);
+        }
+        return nc.x != 0.0f || nc.y != 0.0f || nc.z != 0.0f || dnc.x != 0.0f || dnc.y != 0.0f || dnc.z != 0.0f;
+    }
+    MTS_DEV void unoccluded(const SceneView &, const SurfaceInteraction &, f3, const NeeTerms &) { r.Nc = nc; r.dNc = dnc; }
+    // T_next = T' * W; dW / d(refl) at the sampled direction
+    MTS_DEV void bsdf_sampled(const SceneView &, const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, f3, const BsdfSample &bs, f3 weight, float, f2) {
+        r.W = weight;
+        if (tex) r.dW = bsdf_dweight_drefl(bsdf, refl, si.wi, bs);
+    }
+};
+
 template <bool FLAT>
 __global__ __launch_bounds__(kBlock) void k_adjoint_tex(const AdjointParams A) {
     extern __shared__ float4 smem[];
     const RenderParams &P = A.rp;
     const LdsView lds = lds_stage<FLAT>(P.sv, smem);
-    const uint32_t spp = (uint32_t) P.spp;
     for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
-        PathState s; float2 pos;
-        generate_path(P, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
-        const f3 delta = adjoint_delta(A, pos);
+        PathState s; const f3 delta = adjoint_sample(A, k, s);
         if (delta.x == 0.0f && delta.y == 0.0f && delta.z == 0.0f) continue;       // every term below is proportional to delta
         VertexRecG rec[kAdjointMaxDepth];
         int n = 0;
         Counters c = { 0u, 0u, 0u, 0u };
         bool alive = true;
-        while (alive && n < kAdjointMaxDepth) {
-            alive = bounce_step<FLAT, true, 0, true>(P, lds, s, c, nullptr, nullptr, nullptr, nullptr, &rec[n]);
-            ++n;
-        }
+        while (alive && n < kAdjointMaxDepth) { alive = bounce_step<FLAT, 0, true>(P, lds, s, c, GeneralRecorder{ rec[n] }); ++n; }
         f3 a = mk3(0.0f, 0.0f, 0.0f);
         for (int v = n - 1; v >= 0; --v) {
             const VertexRecG &r = rec[v];
@@ -2007,14 +2068,7 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_tex(const AdjointParams A) {
                 const float gg[3] = { Tp.x * fmaf(delta.x, r.dNc.x, a.x * r.dW.x), Tp.y * fmaf(delta.y, r.dNc.y, a.y * r.dW.y),
                                       Tp.z * fmaf(delta.z, r.dNc.z, a.z * r.dW.z) };
                 const DevTexture t = P.sv.textures[r.texture];
-                float *gt = A.grad_tex + t.grad_offset + 3u * (size_t) r.texel;
-                const float w00 = (1.0f - r.w1.y) * (1.0f - r.w1.x), w10 = (1.0f - r.w1.y) * r.w1.x,
-                            w01 = r.w1.y * (1.0f - r.w1.x), w11 = r.w1.y * r.w1.x;
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    atomicAdd(gt + ch, gg[ch] * w00); atomicAdd(gt + 3 + ch, gg[ch] * w10);
-                    atomicAdd(gt + 3 * t.w + ch, gg[ch] * w01); atomicAdd(gt + 3 * t.w + 3 + ch, gg[ch] * w11);
-                }
+                scatter_texel_grad(A.grad_tex, t, r.texel, r.w1, gg);
             }
             const f3 b = mk3(fmaf(delta.x, r.Nc.x, r.W.x * a.x), fmaf(delta.y, r.Nc.y, r.W.y * a.y), fmaf(delta.z, r.Nc.z, r.W.z * a.z));
             a = mk3(delta.x * r.E.x + r.invq * b.x, delta.y * r.E.y + r.invq * b.y, delta.z * r.E.z + r.invq * b.z);
@@ -2026,14 +2080,7 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_tex(const AdjointParams A) {
     }
 }
 
-hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s) {
-    if (a.n_samples == 0) return hipSuccess;
-    uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
-    if (blocks > 2048) blocks = 2048;
-    if (a.rp.sv.flat) hipLaunchKernelGGL(k_adjoint_tex<true>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    else hipLaunchKernelGGL(k_adjoint_tex<false>, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    return hipGetLastError();
-}
+hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_tex<true>, k_adjoint_tex<false>>(a, s); }
 
 // ---------------------------------------------------------------------------------------------
 // ImageBlock::put as a gather: one wave per film pixel, lanes stride over the samples of the

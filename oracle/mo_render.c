@@ -417,7 +417,7 @@ static void env_grad_add(const mo_envmap *env, float u, float v, const float coe
         for (int k = 0; k < 3; ++k) eg->grad[3 * (size_t) idx[i] + k] += (eg->delta[k] * coeff[k]) * w[i];
 }
 /* pg != NULL: forward-mode derivative of the radiance w.r.t. ONE scalar parameter (kind, comp) of the BSDF of the masked shapes, carried
- * beside the path with DETACHED sampling -- the checker of mtsamd_render_adjoint_param (kernels.hip, bounce_step<PGRAD>): the same terms
+ * beside the path with DETACHED sampling -- the checker of mtsamd_render_adjoint_param (kernels.hip, ParamGradProbe): the same terms
  * in the same order; d(value)/d(theta) at fixed directions = central difference of the model code between records perturbed by +-h */
 typedef struct { const uint8_t *shape_mask; int kind, comp; float h; float dthr[3], dres[3]; } param_grad;
 static void bsdf_perturbed(const mo_bsdf *b, const float refl[3], int kind, int comp, float step, mo_bsdf *out, float refl_out[3]) {

@@ -581,7 +581,7 @@ def test_adjoint_grid_stride_loop(gpu, oracle):
 
 
 def test_texture_adjoint_grid_stride_loop(gpu, oracle):
-    """k_adjoint_tex's own copy of the loop, on the same 589 824 samples: the oracle's texel gradient"""
+    """k_adjoint_tex's grid-stride loop (its launch shares the cap of 2048 workgroups), on the same 589 824 samples: the oracle's texel gradient"""
     from mitsuba2_amd import autodiff, _lib as L
     tex = (0.3 + 0.5 * np.random.RandomState(1).rand(4, 5, 3)).astype(np.float32)
     sd, p, scene = _scene(gpu, tex, GRID_W, GRID_H, GRID_SPP, 4, "box")
@@ -603,7 +603,7 @@ def test_texture_adjoint_grid_stride_loop(gpu, oracle):
 
 
 def test_bsdf_parameter_adjoint_grid_stride_loop(gpu, oracle):
-    """k_adjoint_param's own copy of the loop: one parameter of the rough conductor on 589 824 samples"""
+    """k_adjoint_param's grid-stride loop and per-thread accumulator: one parameter of the rough conductor on 589 824 samples"""
     from mitsuba2_amd import autodiff, _lib as L
     mats = ({"type": "roughconductor", "alpha": 0.3, "distribution": "ggx", "eta": [0.2, 0.92, 1.1], "k": [3.9, 2.45, 2.14], "specular_reflectance": [0.9, 0.8, 0.7]},
             {"type": "plastic", "diffuse_reflectance": [0.2, 0.5, 0.3], "int_ior": 1.6})
