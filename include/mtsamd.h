@@ -285,6 +285,43 @@ MTSAMD_API int mtsamd_cancel(mtsamd_scene *scene);
 MTSAMD_API int mtsamd_sample_radiance(mtsamd_scene *scene, const mtsamd_render_desc *desc, uint64_t first,
                            uint64_t count, float *rgba_dev, float *pos_dev, void *stream);
 
+/* ---- aov integrator (src/integrators/aov.cpp) ----------------------------------
+ * Fields of the camera ray's SurfaceInteraction as film channels (aov.cpp:92-134): depth = si.t (1 channel), position = si.p,
+ * geo_normal = si.n, sh_normal = si.sh_frame.n, dp_du, dp_dv (3 channels each), uv (2 channels); duv_dx / duv_dy (2 channels each) are
+ * accepted and always zero, as in the reference: kdtree.h:2353 zeroes them and aov.cpp never calls compute_partials.  Every channel is 0
+ * where the camera ray misses (aov.cpp:171-172). */
+typedef enum { MTSAMD_AOV_DEPTH = 0, MTSAMD_AOV_POSITION, MTSAMD_AOV_UV, MTSAMD_AOV_GEO_NORMAL, MTSAMD_AOV_SH_NORMAL,
+               MTSAMD_AOV_DP_DU, MTSAMD_AOV_DP_DV, MTSAMD_AOV_DUV_DX, MTSAMD_AOV_DUV_DY } mtsamd_aov_type;
+/* SamplingIntegrator::render (src/librender/integrator.cpp:52-176) for the `aov` integrator (aov.cpp:166-219) followed by Film::put.  The
+ * film has the channels X,Y,Z,A,W, then the C channels of the n_aovs entries of aov_types in order (integrator.cpp:68-77), then -- nested != 0
+ * -- R,G,B,A of the nested integrator desc->integrator (path / direct / depth; aov.cpp:195-213), which also fills X,Y,Z,A (nested == 0:
+ * they stay 0, aov.cpp:215-216).  Every channel of a sample is splatted with the same filter weights, and the block is created with
+ * warn_negative = false (integrator.cpp:249-270): a sample is dropped from all channels when one of them is not finite
+ * (imageblock.cpp:85-109), negative values are kept.  The AOVs draw no random numbers: X,Y,Z,A,W equal those of mtsamd_render with the
+ * same desc, R,G,B,A those of film_rgb = 1.  Spectral variant: X,Y,Z are the stream of mtsamd_render (which also drops samples below
+ * -1e-5) and R,G,B its linear transform, where the reference converts the spectrum itself (equal up to rounding).
+ * film_dev: crop_height * crop_width * (5 + C [+ 4]) floats, ADDED into.  desc->moment and desc->film_rgb must be 0, C <= 32, and
+ * n_aovs == 0 needs nested != 0.  Row window, tile partition, crop, samples_per_pass, max_pass_log2, timeout and cancel act as in
+ * mtsamd_render.  A render of several passes whose sample streams fit the scene's keep limit (below) keeps them for the duration of
+ * the call and splats them once, so that its film equals the one-pass film bit for bit; above the limit every pass is splatted before the
+ * next is traced and film rows reached from two passes may differ from the one-pass film in the last bits, as they do for mtsamd_render.
+ * stats_host as for mtsamd_render; [0] and [7] include the
+ * queries of the AOV kernel, [5] its device time, [6] the splats of every channel group (the stream kernel that unifies the drops, the
+ * scratch-film clear and the channel interleave are in neither).  Two calls give the same bits. */
+MTSAMD_API int mtsamd_render_aov(mtsamd_scene *scene, const mtsamd_render_desc *desc, const int32_t *aov_types, uint32_t n_aovs,
+                      int32_t nested, float *film_dev, uint64_t *stats_host, void *stream);
+/* Device memory a multi-pass mtsamd_render_aov may take to keep the streams of all its passes (see above): per sample 16 bytes for every
+ * three AOV channels, 16 (32 with a nested integrator) for the radiance stream(s) and 8 for the film position (integrator.cpp:224-246
+ * hands these to ImageBlock::put one sample at a time).  Default 2^30 bytes; 0: never keep, always splat pass by pass.  The choice
+ * depends on the description and this limit only; if the device cannot provide memory within the limit, the render fails with
+ * MTSAMD_ERR_NOMEM.  The memory is freed when the render returns. */
+MTSAMD_API int mtsamd_scene_set_aov_keep_limit(mtsamd_scene *scene, uint64_t bytes);
+/* The AOV part of AOVIntegrator::sample (aov.cpp:166-193) for whole sample indices, as mtsamd_sample_radiance: the C channel values of
+ * the samples [first, first + count) of the render described by desc, without film accumulation.  aovs_dev: count * C floats,
+ * sample-major; pos_dev (may be NULL): count * 2 floats, the film position (integrator.cpp:224-246).  Synchronous. */
+MTSAMD_API int mtsamd_sample_aovs(mtsamd_scene *scene, const mtsamd_render_desc *desc, const int32_t *aov_types, uint32_t n_aovs,
+                       uint64_t first, uint64_t count, float *aovs_dev, float *pos_dev, void *stream);
+
 /* Reverse-mode derivative of mitsuba.python.autodiff.render (src/python/python/autodiff.py:6-91,121-194) with respect
  * to diffuse reflectances -- what `ek.backward()` propagates into 'bsdf.reflectance.value' (src/spectra/srgb.cpp:59-61)
  * and 'bsdf.reflectance.data' (src/textures/bitmap.cpp:295-299).  The image is values / (weight + 1e-8) of a film

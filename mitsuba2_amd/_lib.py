@@ -85,6 +85,9 @@ SYMBOLS = {
     "mtsamd_ray_test": (C.c_int, [vp, C.c_uint64, C.POINTER(Rays), vp, vp]),
     "mtsamd_ray_intersect_si": (C.c_int, [vp, C.c_uint64, C.POINTER(Rays), vp, vp, vp, vp, vp]),
     "mtsamd_render": (C.c_int, [vp, C.POINTER(RenderDesc), vp, u64p, vp]),
+    "mtsamd_render_aov": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(C.c_int32), C.c_uint32, C.c_int32, vp, u64p, vp]),
+    "mtsamd_sample_aovs": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(C.c_int32), C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp]),
+    "mtsamd_scene_set_aov_keep_limit": (C.c_int, [vp, C.c_uint64]),
     "mtsamd_cancel": (C.c_int, [vp]),
     "mtsamd_rgb2spec_build": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),
     "mtsamd_srgb_model_fetch": (C.c_int, [C.c_char_p, f32p, f32p]),

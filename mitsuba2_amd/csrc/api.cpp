@@ -208,6 +208,9 @@ struct Workspace {
     float4 *out_rgba2 = nullptr; float2 *out_pos2 = nullptr; uint64_t pass_cap2 = 0;      // second sample stream: pass k + 1 is traced while pass k is splatted
     hipStream_t film_stream = nullptr; hipEvent_t film_done[2] = {};
     float *moment_film = nullptr; uint64_t moment_pixels = 0;     // moment integrator: two scratch 5-channel films
+    float4 *aov_stream = nullptr; uint64_t aov_stream_slots = 0;  // aov integrator: channel groups of a pass (+ the nested stream's second colour space)
+    float *aov_film = nullptr; uint64_t aov_film_floats = 0;      // ... and its scratch 5-channel films
+    float4 *aov_keep = nullptr;                                   // ... and, during a render of several passes, the streams + positions of all of them
     float *film_partials = nullptr; size_t film_partial_floats = 0;      // tiled film splat: one scratch tile per 16x16 source tile of a pass
     uint32_t *trace_spill = nullptr; size_t trace_spill_words = 0;      // k_trace: deep stack entries
     uint32_t *h_counts = nullptr;        // pinned, 4 * n_waves
@@ -236,6 +239,9 @@ struct Workspace {
         (void) hipFree(count_shadow); count_shadow = nullptr;
         (void) hipFree(trace_spill); trace_spill = nullptr; trace_spill_words = 0;
         (void) hipFree(moment_film); moment_film = nullptr; moment_pixels = 0;
+        (void) hipFree(aov_stream); aov_stream = nullptr; aov_stream_slots = 0;
+        (void) hipFree(aov_film); aov_film = nullptr; aov_film_floats = 0;
+        (void) hipFree(aov_keep); aov_keep = nullptr;
         (void) hipFree(film_partials); film_partials = nullptr; film_partial_floats = 0;
         (void) hipFree(out_rgba); (void) hipFree(out_pos);
         (void) hipFree(out_rgba2); (void) hipFree(out_pos2); out_rgba2 = nullptr; out_pos2 = nullptr; pass_cap2 = 0;
@@ -371,6 +377,7 @@ struct mtsamd_scene {
     bool spectral = false;
     Workspace ws;
     std::atomic<int> cancel{ 0 };
+    uint64_t aov_keep_limit = 1ull << 30;      // mtsamd_scene_set_aov_keep_limit
 };
 
 extern "C" {
@@ -1715,6 +1722,268 @@ int mtsamd_render(mtsamd_scene *s, const mtsamd_render_desc *d, float *film, uin
     }
     if (film_sq) HIP_TRY(launch_moment_pack(film_target, film_sq, film, n_pixels, stream));
     if (int rc = collect_stats(j, total, stats_host)) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+    return MTSAMD_OK;
+}
+
+// ---- aov integrator (src/integrators/aov.cpp) -------------------------------------------------
+// AOV types -> the SurfaceInteraction field every film channel shows (aov.cpp:92-134)
+static int aov_channels(const int32_t *types, uint32_t n_aovs, AovParams &a) {
+    if (n_aovs && !types) return fail(MTSAMD_ERR_INVALID, "null argument");
+    a.n_channels = 0;
+    for (uint32_t i = 0; i < n_aovs; ++i) {
+        uint32_t src, cnt;
+        switch (types[i]) {
+        case MTSAMD_AOV_DEPTH: src = kAovT; cnt = 1; break;
+        case MTSAMD_AOV_POSITION: src = kAovP; cnt = 3; break;
+        case MTSAMD_AOV_UV: src = kAovUV; cnt = 2; break;
+        case MTSAMD_AOV_GEO_NORMAL: src = kAovN; cnt = 3; break;
+        case MTSAMD_AOV_SH_NORMAL: src = kAovShN; cnt = 3; break;
+        case MTSAMD_AOV_DP_DU: src = kAovDpDu; cnt = 3; break;
+        case MTSAMD_AOV_DP_DV: src = kAovDpDv; cnt = 3; break;
+        case MTSAMD_AOV_DUV_DX: case MTSAMD_AOV_DUV_DY: src = kAovZero; cnt = 2; break;      // never computed by the reference: zeros
+        default: return fail(MTSAMD_ERR_INVALID, "Invalid AOV type %d", types[i]);           // aov.cpp:131
+        }
+        if (a.n_channels + cnt > kAovMaxChannels) return fail(MTSAMD_ERR_UNSUPPORTED, "more than %u AOV channels", kAovMaxChannels);
+        for (uint32_t k = 0; k < cnt; ++k) a.source[a.n_channels++] = (uint8_t) (src == kAovZero ? src : src + k);
+    }
+    return 0;
+}
+
+// setup_job for a pass that also holds n_streams float4 per sample in ws.aov_stream: they count when the pass is sized -- if the device
+// cannot provide them the pass is halved, as setup_job halves it for the sample stream
+static int setup_aov_job(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, hipStream_t stream, uint64_t max_pass, uint32_t n_streams) {
+    for (;;) {
+        if (int rc = setup_job(j, s, d, stream, max_pass)) return rc;
+        Workspace &w = s->ws;
+        const uint64_t slots = j.pass_cap * n_streams;
+        if (w.aov_stream_slots >= slots) return 0;
+        (void) hipFree(w.aov_stream); w.aov_stream = nullptr; w.aov_stream_slots = 0;
+        const int rc = ws_alloc((void **) &w.aov_stream, slots * sizeof(float4));
+        if (rc == MTSAMD_ERR_NOMEM && j.pass_cap > (1ull << 22)) { max_pass = j.pass_cap >> 1; continue; }
+        if (rc) return rc;
+        w.aov_stream_slots = slots;
+        return 0;
+    }
+}
+
+// the part of RenderParams k_aov reads (generate_path, the scene, the statistics); first_ordinal / plane_pix0 are set per pass
+static void aov_render_params(const Job &j, RenderParams &p) {
+    p = RenderParams{};
+    p.sv = j.s->view; p.cam = j.cam;
+    p.wave_stats = j.s->ws.wave_stats; p.n_waves = j.n_waves;
+    p.out_pos = j.s->ws.out_pos;          // the values the nested integrator's sample wrote there, or the only copy
+    p.base_seed = j.d->seed; p.rows = j.rows;
+    p.spp = j.d->sample_count; p.crop_x = j.d->crop_x; p.crop_y = j.d->crop_y; p.crop_w = j.d->crop_width; p.crop_h = j.d->crop_height;
+    p.spectral = j.s->spectral ? 1 : 0;
+}
+
+int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32_t *aov_types, uint32_t n_aovs, int32_t nested, float *film,
+                      uint64_t *stats_host, void *stream_) {
+    if (!s || !film) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (int rc = check_desc(d_)) return rc;
+    if (d_->moment) return fail(MTSAMD_ERR_UNSUPPORTED, "the aov integrator nests path, direct or depth, not moment (desc->moment must be 0)");
+    if (d_->film_rgb) return fail(MTSAMD_ERR_UNSUPPORTED, "the aov integrator writes X,Y,Z,A,W and its own R,G,B,A channels (film_rgb must be 0)");
+    AovParams ap{};
+    if (int rc = aov_channels(aov_types, n_aovs, ap)) return rc;
+    if (ap.n_channels == 0 && !nested) return fail(MTSAMD_ERR_INVALID, "the aov integrator needs an AOV or a nested integrator");
+    mtsamd_render_desc dd = *d_;
+    if (!nested) dd.integrator = 0;       // nothing is traced: the scheduler only sizes the pass
+    const mtsamd_render_desc *d = &dd;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t) stream_;
+    RowMap rows{};
+    if (int rc = make_rows(d, rows)) return rc;
+    const uint64_t per_row = (uint64_t) d->crop_width * (uint64_t) d->sample_count;
+    const uint64_t total = per_row * (uint64_t) rows.local_rows;
+    const uint32_t C = ap.n_channels, n_groups = (C + 2u) / 3u, n_films = 1u + n_groups + (nested ? 1u : 0u);
+    Job j;
+    if (int rc = setup_aov_job(j, s, d, stream, total, n_groups + (nested ? 1u : 0u))) return rc;
+    // the linear-RGB stream drops non-finite samples only, the rule of a film with AOVs (integrator.cpp:249-251); spectral variant: XYZ
+    j.rows = rows; j.store_xyz = s->spectral ? 1 : 2;
+    const int mode = !nested ? 0 : (s->spectral ? 2 : 1);
+    const int R = (int) std::ceil(j.filter.radius);
+    if (per_row > j.pass_cap) return fail(MTSAMD_ERR_UNSUPPORTED, "one film row (%llu samples) exceeds the pass capacity", (unsigned long long) per_row);
+    // passes hold whole local rows, cut into source tiles for the film kernel as in mtsamd_render
+    uint64_t rows_per_pass = std::max<uint64_t>(1, j.pass_cap / per_row);
+    int32_t film_tile_h = 16;
+    if (rows.count > 1) while (rows.tile_rows % film_tile_h) film_tile_h >>= 1;
+    const int32_t tile_h_one = film_tile_h;          // source tile height of a one-pass render
+    if (rows.count > 1) {
+        if (rows_per_pass >= (uint64_t) film_tile_h) rows_per_pass -= rows_per_pass % (uint64_t) film_tile_h;
+        else { while (rows_per_pass & (rows_per_pass - 1)) rows_per_pass &= rows_per_pass - 1; film_tile_h = (int32_t) rows_per_pass; }
+    }
+    const bool tiled = film_tiles_supported(j.filter);
+    Workspace &ws = s->ws;
+    const uint64_t n_pixels = (uint64_t) d->crop_width * (uint64_t) d->crop_height;
+    // one scratch 5-channel film per stream: X,Y,Z,A,W | the channel groups | R,G,B,A (k_aov_pack interleaves them)
+    if (ws.aov_film_floats < n_films * 5 * n_pixels) {
+        (void) hipFree(ws.aov_film); ws.aov_film = nullptr; ws.aov_film_floats = 0;
+        if (int rc = ws_alloc((void **) &ws.aov_film, n_films * 5 * n_pixels * sizeof(float))) return rc;
+        ws.aov_film_floats = n_films * 5 * n_pixels;
+    }
+    HIP_TRY(hipMemsetAsync(ws.aov_film, 0, n_films * 5 * n_pixels * sizeof(float), stream));
+    // A film splatted pass by pass is not the film of one pass bit for bit: the film kernels sum per source tile of a pass, so rows
+    // reached from two passes are added in another order (tests/test_gpu_lifecycle.py accepts that for mtsamd_render).  A render of
+    // several passes whose streams fit the scene's keep limit (mtsamd_scene_set_aov_keep_limit, 1 GiB by default) therefore keeps the
+    // streams of all passes -- n_kept float4 + one float2 position per sample -- and splats them once, with the tile grid of a one-pass
+    // render: passes then bound the tracing workspace and are where a timeout / cancel stops, and never show in the film.  The buffer
+    // lives for this call only.  Whether it is used follows from the description and the limit alone, never from the memory that happens
+    // to be free: if the device cannot provide it the call fails.  Above the limit each pass is splatted before the next is traced, as
+    // mtsamd_render does.
+    const uint64_t n_passes = ((uint64_t) rows.local_rows + rows_per_pass - 1) / rows_per_pass;
+    const uint32_t n_kept = n_groups + (nested ? 2u : 1u);          // groups, second colour space, the nested stream
+    const uint64_t keep_slots = total * n_kept + total / 2 + 1;
+    const bool retain = n_passes > 1 && total <= (1ull << 30) && keep_slots * sizeof(float4) <= s->aov_keep_limit;
+    struct Keep { Workspace &w; ~Keep() { (void) hipFree(w.aov_keep); w.aov_keep = nullptr; } } keep{ ws };
+    if (retain) {
+        if (tiled) {          // the scratch tiles of the one splat first: they must not fail after the streams took the memory
+            FilmParams f{};
+            f.crop_w = d->crop_width; f.pass_rows = rows.local_rows; f.tile_h = tile_h_one; f.spp = d->sample_count;
+            film_tile_grid(f);
+            const size_t need = film_partial_floats(f);
+            if (need > ws.film_partial_floats) {
+                (void) hipFree(ws.film_partials); ws.film_partials = nullptr; ws.film_partial_floats = 0;
+                if (int rc = ws_alloc((void **) &ws.film_partials, need * sizeof(float))) return rc;
+                ws.film_partial_floats = need;
+            }
+        }
+        (void) hipFree(ws.aov_keep); ws.aov_keep = nullptr;
+        if (int rc = ws_alloc((void **) &ws.aov_keep, keep_slots * sizeof(float4))) return rc;
+    }
+    float4 *groups = retain ? ws.aov_keep : ws.aov_stream;
+    const uint64_t stride = retain ? total : j.pass_cap;            // slots per stream
+    float4 *conv = nested ? groups + (size_t) n_groups * stride : nullptr;
+    float4 *strm = retain ? groups + (size_t) (n_kept - 1u) * stride : ws.out_rgba;
+    float2 *spos = retain ? reinterpret_cast<float2 *>(groups + (size_t) n_kept * stride) : ws.out_pos;
+    aov_render_params(j, ap.rp);
+    ap.group_stride = stride;
+    size_t film_events = 0;
+    // Film::put of the streams of the local rows [lr0, lr0 + nrows), held from slot `off` on, into their scratch films
+    auto splat = [&](uint64_t lr0, uint64_t nrows, uint64_t off, int32_t tile_h) -> int {
+        FilmParams f{};
+        f.out_pos = spos + off; f.filter = j.filter;
+        f.first_ordinal = lr0 * per_row; f.n_samples = nrows * per_row; f.spp = d->sample_count; f.rows = rows;
+        f.plane_pix0 = (uint32_t) (lr0 * (uint64_t) d->crop_width); f.plane_pixels = 0u;
+        f.crop_x = d->crop_x; f.crop_y = d->crop_y; f.crop_w = d->crop_width; f.crop_h = d->crop_height;
+        const int32_t l0 = (int32_t) lr0, l1 = (int32_t) (lr0 + nrows - 1);
+        int32_t g0, g1;
+        if (rows.count <= 1) { g0 = rows.row0 + l0; g1 = rows.row0 + l1; }
+        else {   // global rows are monotone in the local row index
+            int32_t t0 = l0 / rows.tile_rows, t1 = l1 / rows.tile_rows;
+            g0 = (t0 * rows.count + rows.part) * rows.tile_rows + (l0 - t0 * rows.tile_rows);
+            g1 = (t1 * rows.count + rows.part) * rows.tile_rows + (l1 - t1 * rows.tile_rows);
+        }
+        f.row0 = std::max<int32_t>(0, g0 - R); f.row1 = std::min<int32_t>(d->crop_height, g1 + R + 1);
+        if (tiled) {
+            f.pass_lr0 = (int32_t) lr0; f.pass_rows = (int32_t) nrows; f.tile_h = tile_h;
+            film_tile_grid(f);
+            const size_t need = film_partial_floats(f);
+            if (need > ws.film_partial_floats) {
+                HIP_TRY(hipStreamSynchronize(stream));               // an earlier splat may still read the scratch tiles
+                (void) hipFree(ws.film_partials); ws.film_partials = nullptr; ws.film_partial_floats = 0;
+                if (int rc = ws_alloc((void **) &ws.film_partials, need * sizeof(float))) return rc;
+                ws.film_partial_floats = need;
+            }
+            f.partials = ws.film_partials;
+        }
+        while (ws.film_ev.size() < 2 * (film_events + 1)) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(hipEventCreate(&e)); ws.film_ev.push_back(e);
+        }
+        HIP_TRY(hipEventRecord(ws.film_ev[2 * film_events], stream));
+        for (uint32_t k = 0; k < n_films; ++k) {
+            if (k == 0) f.out_rgba = (mode == 1 ? conv : strm) + off;                // X, Y, Z, A
+            else if (k <= n_groups) f.out_rgba = groups + (size_t) (k - 1u) * stride + off;
+            else f.out_rgba = (mode == 1 ? strm : conv) + off;                       // R, G, B, A
+            f.film = ws.aov_film + (size_t) k * 5 * n_pixels;
+            if (tiled) HIP_TRY(launch_film_tiles(f, stream));
+            else HIP_TRY(launch_film_gather(f, stream));
+        }
+        HIP_TRY(hipEventRecord(ws.film_ev[2 * film_events + 1], stream));
+        ++film_events;
+        return 0;
+    };
+    int rc_loop = 0;
+    uint64_t rows_done = 0;
+    for (uint64_t lr0 = 0; lr0 < (uint64_t) rows.local_rows; lr0 += rows_per_pass) {
+        const uint64_t nrows = std::min<uint64_t>(rows_per_pass, (uint64_t) rows.local_rows - lr0);
+        const uint64_t a = lr0 * per_row, n = nrows * per_row, off = retain ? a : 0;
+        j.plane_pix0 = (uint32_t) (lr0 * (uint64_t) d->crop_width);
+        j.plane_pixels = 0u;          // sample stream: pixel-major
+        j.buf = 0;
+        if (s->cancel.load(std::memory_order_relaxed)) { rc_loop = fail(MTSAMD_ERR_CANCELLED, "render cancelled"); break; }
+        if (j.expired()) { j.timed_out = true; break; }
+        if (nested) {
+            if (int rc = trace_pass(j, a, n)) {
+                if (rc > 0) break;               // timeout inside the pass: its samples are dropped
+                rc_loop = rc;
+                break;
+            }
+            if (retain) HIP_TRY(hipMemcpyAsync(strm + off, ws.out_rgba, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        }
+        j.passes += 1;
+        ap.rp.first_ordinal = a; ap.rp.plane_pix0 = j.plane_pix0; ap.rp.plane_pixels = 0u;
+        ap.rp.out_pos = spos + off; ap.groups = groups + off;
+        HIP_TRY(hipEventRecord(ws.tev[0], stream));
+        HIP_TRY(launch_aov(ap, n, stream));
+        HIP_TRY(hipEventRecord(ws.tev[1], stream));
+        HIP_TRY(launch_aov_finish(strm + off, conv ? conv + off : nullptr, groups + off, stride, n_groups, mode, n, stream));
+        if (!retain) { if (int rc = splat(lr0, nrows, 0, film_tile_h)) return rc; }
+        HIP_TRY(hipEventSynchronize(ws.tev[1]));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ws.tev[0], ws.tev[1]));
+        j.bounce_ms += ms; j.iterations += 1;
+        rows_done = lr0 + nrows;
+    }
+    if (retain && rows_done > 0 && !rc_loop) { if (int rc = splat(0, rows_done, 0, tile_h_one)) return rc; }
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (rc_loop) return rc_loop;
+    for (size_t k = 0; k < film_events; ++k) {
+        float fms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&fms, ws.film_ev[2 * k], ws.film_ev[2 * k + 1]));
+        j.film_ms += fms;
+    }
+    HIP_TRY(launch_aov_pack(ws.aov_film, n_pixels, C, nested ? 1 : 0, film, stream));
+    if (int rc = collect_stats(j, total, stats_host)) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+    return MTSAMD_OK;
+}
+
+int mtsamd_scene_set_aov_keep_limit(mtsamd_scene *s, uint64_t bytes) {
+    if (!s) return fail(MTSAMD_ERR_INVALID, "null argument");
+    s->aov_keep_limit = bytes;
+    return MTSAMD_OK;
+}
+
+int mtsamd_sample_aovs(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32_t *aov_types, uint32_t n_aovs, uint64_t first, uint64_t count,
+                       float *aovs, float *pos, void *stream_) {
+    if (!s || !aovs) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (int rc = check_desc(d_)) return rc;
+    AovParams ap{};
+    if (int rc = aov_channels(aov_types, n_aovs, ap)) return rc;
+    if (ap.n_channels == 0) return fail(MTSAMD_ERR_INVALID, "no AOV requested");
+    mtsamd_render_desc dd = *d_;
+    dd.integrator = 0;                    // nothing is traced: the scheduler only sizes the pass
+    const mtsamd_render_desc *d = &dd;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t) stream_;
+    const uint64_t total = (uint64_t) d->crop_width * d->crop_height * (uint64_t) d->sample_count;
+    if (first + count > total) return fail(MTSAMD_ERR_INVALID, "sample range exceeds W*H*sample_count");
+    if (count == 0) return MTSAMD_OK;
+    const uint32_t n_groups = (ap.n_channels + 2u) / 3u;
+    Job j;
+    if (int rc = setup_aov_job(j, s, d, stream, count, n_groups)) return rc;
+    j.rows = RowMap{ 0, d->crop_height, std::max(d->crop_height, 1), 0, 1 };
+    aov_render_params(j, ap.rp);
+    ap.groups = s->ws.aov_stream; ap.group_stride = j.pass_cap;
+    for (uint64_t a = 0; a < count; a += j.pass_cap) {
+        const uint64_t n = std::min<uint64_t>(j.pass_cap, count - a);
+        ap.rp.first_ordinal = first + a;
+        HIP_TRY(launch_aov(ap, n, stream));
+        HIP_TRY(launch_aov_unpack(s->ws.aov_stream, j.pass_cap, ap.n_channels, n, aovs + (size_t) ap.n_channels * a, stream));
+        if (pos) HIP_TRY(hipMemcpyAsync(pos + 2 * a, s->ws.out_pos, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
+    }
     HIP_TRY(hipStreamSynchronize(stream));
     return MTSAMD_OK;
 }

@@ -172,6 +172,33 @@ uint32_t trace_group();          // scheduling waves per k_trace workgroup (a po
 size_t trace_spill_words(const SceneView &sv, uint32_t n_waves);
 // `direct` / `depth` integrators: every sample of [first_ordinal, first_ordinal + n) is finished by one thread
 hipError_t launch_direct(const RenderParams &p, uint64_t n, hipStream_t s);
+// `aov` integrator (src/integrators/aov.cpp:166-219): k_aov re-traces the camera ray of every sample of [first_ordinal, first_ordinal + n)
+// and writes the requested SurfaceInteraction fields as groups of three channels: groups[g * group_stride + slot] = (channel 3g, 3g + 1,
+// 3g + 2, 0 | -1 if a channel of the group is not finite; launch_aov_finish extends the flag to the whole sample) -- the (X, Y, Z, alpha | -1) layout of the sample stream, so that the
+// 5-channel film kernels splat a group as they splat radiance.  rp needs sv, cam, wave_stats, n_waves, out_pos (may be null), the sampler and
+// film fields generate_path reads; no path pool.
+constexpr uint32_t kAovMaxChannels = 32u;
+// what a channel shows: t, p.xyz, uv, n.xyz, sh_frame.n.xyz, dp_du.xyz, dp_dv.xyz, or nothing (duv_dx / duv_dy: kdtree.h:2353 zeroes
+// them and aov.cpp never calls compute_partials)
+enum AovSource : uint8_t { kAovT = 0, kAovP = 1, kAovUV = 4, kAovN = 6, kAovShN = 9, kAovDpDu = 12, kAovDpDv = 15, kAovZero = 18 };
+struct AovParams {
+    RenderParams rp;
+    float4 *groups;
+    uint64_t group_stride;      // slots per group
+    uint32_t n_channels;        // <= kAovMaxChannels; (n_channels + 2) / 3 groups
+    uint8_t source[kAovMaxChannels];
+};
+hipError_t launch_aov(const AovParams &a, uint64_t n, hipStream_t s);
+// Samples of an AOV pass agree on what is dropped: sample i is dropped in `stream` and in every group if it is dropped in one of them
+// (ImageBlock::put drops a sample when any channel is not finite, imageblock.cpp:85-109).  mode 0: no nested integrator, stream[i] =
+// (0, 0, 0, 0 | -1); 1: stream holds linear RGB (store_xyz = 2), conv[i] = its XYZ (integrator.cpp:254-262); 2: stream holds XYZ (spectral
+// variant), conv[i] = its linear RGB
+hipError_t launch_aov_finish(float4 *stream, float4 *conv, float4 *groups, uint64_t group_stride, uint32_t n_groups, int mode, uint64_t n, hipStream_t s);
+// films5: 1 + n_groups (+ 1 with `nested`) films of n_pixels x 5 floats -> film (n_pixels x (5 + n_channels (+ 4))), accumulating:
+// X, Y, Z, A, W of film 0, channel c from film 1 + c / 3, then R, G, B, A of the last film
+hipError_t launch_aov_pack(const float *films5, uint64_t n_pixels, uint32_t n_channels, int nested, float *film, hipStream_t s);
+// groups -> out[i * n_channels + c] (mtsamd_sample_aovs)
+hipError_t launch_aov_unpack(const float4 *groups, uint64_t group_stride, uint32_t n_channels, uint64_t n, float *out, hipStream_t s);
 hipError_t launch_adjoint(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_env(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_param(const AdjointParams &a, hipStream_t s);

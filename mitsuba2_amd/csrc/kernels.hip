@@ -873,6 +873,84 @@ hipError_t launch_direct(const RenderParams &p, uint64_t n, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// `aov` (src/integrators/aov.cpp:166-219): si = scene.ray_intersect(ray) for the camera ray of every sample, zeroed on a miss
+// (aov.cpp:171-172), and one film channel per requested field.  The intersection draws no random numbers, so the nested integrator's
+// sample -- traced by the render kernels, untouched -- and this one share the ray, the film position and the slot s.ordinal.  One thread
+// per camera sample, as k_direct; GENERAL only selects the thin-lens aperture sample.
+MTS_DEV float aov_value(const SurfaceInteraction &si, float t, uint32_t source) {
+    switch (source) {       // wave-uniform
+    case kAovT: return t;
+    case kAovP: return si.p.x; case kAovP + 1: return si.p.y; case kAovP + 2: return si.p.z;
+    case kAovUV: return si.uv.x; case kAovUV + 1: return si.uv.y;
+    case kAovN: return si.n.x; case kAovN + 1: return si.n.y; case kAovN + 2: return si.n.z;
+    case kAovShN: return si.sh.n.x; case kAovShN + 1: return si.sh.n.y; case kAovShN + 2: return si.sh.n.z;
+    case kAovDpDu: return si.dp_du.x; case kAovDpDu + 1: return si.dp_du.y; case kAovDpDu + 2: return si.dp_du.z;
+    case kAovDpDv: return si.dp_dv.x; case kAovDpDv + 1: return si.dp_dv.y; case kAovDpDv + 2: return si.dp_dv.z;
+    default: return 0.0f;
+    }
+}
+
+template <bool FLAT, bool GENERAL>
+__global__ __launch_bounds__(kBlock) void k_aov(const AovParams A, uint64_t n) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = A.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    const uint64_t gid = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
+    Counters c = { 0u, 0u, 0u, 0u };
+    if (gid < n) {
+        const SceneView &sv = P.sv;
+        const Geo<FLAT> geo{ sv, lds };
+        const uint64_t ordinal = P.first_ordinal + gid;
+        const uint32_t lp = (uint32_t) (ordinal / (uint64_t) P.spp), j = (uint32_t) (ordinal - (uint64_t) lp * (uint64_t) P.spp);
+        PathState s;
+        generate_path<GENERAL>(P, ordinal, lp, j, s);
+        Hit hit;
+        ++c.closest;
+        const bool found = traverse<FLAT, false>(sv, lds, s.o, s.d, s.mint, s.maxt, hit, c.tri_tests, FLAT);      // camera rays of consecutive samples: cluster culling
+        SurfaceInteraction si;
+        if (found) fill_si(geo, s.d, hit.prim, hit.u, hit.v, si);
+        const float t = found ? hit.t : 0.0f;
+        // a group is flagged when one of its own channels is not finite; k_aov_finish extends the flag to every stream of the sample
+        // (ImageBlock::put drops the whole sample, imageblock.cpp:85-109, warn_negative = false)
+        float4 *out = A.groups + s.ordinal;
+        for (uint32_t ch = 0; ch < A.n_channels; ch += 3u, out += A.group_stride) {
+            float v[3];
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; ++k) v[k] = (found && ch + k < A.n_channels) ? aov_value(si, t, A.source[ch + k]) : 0.0f;
+            const bool finite = isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]);
+            *out = make_float4(v[0], v[1], v[2], finite ? 0.0f : -1.0f);
+        }
+    }
+    uint32_t tot[4] = { c.closest, c.any, c.segments, c.tri_tests };
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (int off = 32; off > 0; off >>= 1) tot[k] += __shfl_xor(tot[k], off);
+    if (lane_id() == 0) {
+        unsigned long long *ws = reinterpret_cast<unsigned long long *>(P.wave_stats + 4u * (size_t) ((gid >> 6) % P.n_waves));
+        for (int k = 0; k < 4; ++k) if (tot[k]) atomicAdd(ws + k, (unsigned long long) tot[k]);
+    }
+}
+
+static hipError_t allow_lds(const void *fn, size_t bytes);
+hipError_t launch_aov(const AovParams &a, uint64_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t) ((n + kBlock - 1) / kBlock);
+    const size_t lds = bounce_lds_bytes(a.rp.sv);          // hierarchy scenes: the whole traversal stack of the 256 lanes, as k_direct
+    const bool lens = a.rp.cam.aperture_radius > 0.0f;
+    const void *fn = a.rp.sv.flat ? (lens ? (const void *) &k_aov<true, true> : (const void *) &k_aov<true, false>)
+                                  : (lens ? (const void *) &k_aov<false, true> : (const void *) &k_aov<false, false>);
+    if (hipError_t e = allow_lds(fn, lds)) return e;       // deep hierarchies ask for more than 48 KiB
+    if (a.rp.sv.flat) {
+        if (lens) hipLaunchKernelGGL((k_aov<true, true>), dim3(blocks), dim3(kBlock), lds, s, a, n);
+        else hipLaunchKernelGGL((k_aov<true, false>), dim3(blocks), dim3(kBlock), lds, s, a, n);
+    } else {
+        if (lens) hipLaunchKernelGGL((k_aov<false, true>), dim3(blocks), dim3(kBlock), lds, s, a, n);
+        else hipLaunchKernelGGL((k_aov<false, false>), dim3(blocks), dim3(kBlock), lds, s, a, n);
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Split pipeline for hierarchy scenes.  In the fused kernel the BVH walks inherit the shading code's ~100 VGPRs
 // (4 waves / SIMD) and are latency-bound at that occupancy: 1.5 Gray/s on a 261 k-triangle mesh against ~5 Gray/s
 // for a kernel that only traverses.  So here every iteration runs k_trace<false> (closest hits of the in-flight
@@ -2771,6 +2849,68 @@ hipError_t launch_square_stream(float4 *rgba, uint64_t n, hipStream_t s) {
 }
 hipError_t launch_moment_pack(const float *values5, const float *squares5, float *film11, uint64_t n_pixels, hipStream_t s) {
     if (n_pixels) hipLaunchKernelGGL(k_moment_pack, dim3((uint32_t) ((n_pixels + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, values5, squares5, film11, n_pixels);
+    return hipGetLastError();
+}
+
+// aov integrator: the sample streams of a pass -- the nested integrator's and the channel groups of k_aov -- are made to drop the same
+// samples, and the nested stream gets its second colour space (kernels.h, launch_aov_finish)
+__global__ __launch_bounds__(kBlock) void k_aov_finish(float4 *stream, float4 *conv, float4 *groups, uint64_t group_stride, uint32_t n_groups,
+                                                       int mode, uint64_t n) {
+    const uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = v;
+    if (mode != 0) v = stream[i];
+    bool drop = v.w < 0.0f;
+    if (mode == 1) {                // integrator.cpp:254-262, the arithmetic of store_result
+        const f3 xyz = srgb_to_xyz(mk3(v.x, v.y, v.z));
+        c = make_float4(xyz.x, xyz.y, xyz.z, v.w);
+    } else if (mode == 2) {         // the matrix of k_film_develop, before the film's sum instead of after it
+        float r = 0.0f, g = 0.0f, b = 0.0f;
+        r += 3.240479f * v.x; r += -1.537150f * v.y; r += -0.498535f * v.z;
+        g += -0.969256f * v.x; g += 1.875991f * v.y; g += 0.041556f * v.z;
+        b += 0.055648f * v.x; b += -0.204043f * v.y; b += 1.057311f * v.z;
+        c = make_float4(r, g, b, v.w);
+    }
+    drop = drop || !(isfinite(c.x) && isfinite(c.y) && isfinite(c.z));
+    for (uint32_t g = 0; g < n_groups; ++g) drop = drop || groups[(size_t) g * group_stride + i].w < 0.0f;
+    if (drop) {
+        for (uint32_t g = 0; g < n_groups; ++g) groups[(size_t) g * group_stride + i].w = -1.0f;
+        v.w = c.w = -1.0f;
+    }
+    if (mode == 0 || drop) stream[i] = v;
+    if (mode != 0) conv[i] = c;
+}
+__global__ __launch_bounds__(kBlock) void k_aov_pack(const float *films5, uint64_t n_pixels, uint32_t n_channels, int nested, float *film) {
+    const uint32_t stride = 5u + n_channels + (nested ? 4u : 0u);
+    const uint64_t e = (uint64_t) blockIdx.x * kBlock + threadIdx.x;       // one thread per float of the film
+    if (e >= n_pixels * stride) return;
+    const uint64_t i = e / stride;
+    const uint32_t c = (uint32_t) (e - i * stride);
+    uint32_t f = 0u, k = c;                                                // film, channel inside it
+    if (c >= 5u + n_channels) { f = 1u + (n_channels + 2u) / 3u; k = c - 5u - n_channels; }
+    else if (c >= 5u) { f = 1u + (c - 5u) / 3u; k = (c - 5u) % 3u; }
+    film[e] += films5[((size_t) f * n_pixels + i) * 5u + k];
+}
+__global__ __launch_bounds__(kBlock) void k_aov_unpack(const float4 *groups, uint64_t group_stride, uint32_t n_channels, uint64_t n, float *out) {
+    const uint64_t e = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
+    if (e >= n * n_channels) return;
+    const uint64_t i = e / n_channels;
+    const uint32_t c = (uint32_t) (e - i * n_channels);
+    const float4 v = groups[(size_t) (c / 3u) * group_stride + i];
+    out[e] = c % 3u == 0u ? v.x : (c % 3u == 1u ? v.y : v.z);
+}
+hipError_t launch_aov_finish(float4 *stream, float4 *conv, float4 *groups, uint64_t group_stride, uint32_t n_groups, int mode, uint64_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_aov_finish, dim3((uint32_t) ((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, stream, conv, groups, group_stride, n_groups, mode, n);
+    return hipGetLastError();
+}
+hipError_t launch_aov_pack(const float *films5, uint64_t n_pixels, uint32_t n_channels, int nested, float *film, hipStream_t s) {
+    const uint64_t n = n_pixels * (5u + n_channels + (nested ? 4u : 0u));
+    if (n) hipLaunchKernelGGL(k_aov_pack, dim3((uint32_t) ((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, films5, n_pixels, n_channels, nested, film);
+    return hipGetLastError();
+}
+hipError_t launch_aov_unpack(const float4 *groups, uint64_t group_stride, uint32_t n_channels, uint64_t n, float *out, hipStream_t s) {
+    const uint64_t e = n * n_channels;
+    if (e) hipLaunchKernelGGL(k_aov_unpack, dim3((uint32_t) ((e + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, groups, group_stride, n_channels, n, out);
     return hipGetLastError();
 }
 

@@ -220,6 +220,7 @@ class HDRFilm:
         self.set_crop_window(co, cs)
         self._filter = rfilter if rfilter is not None else GaussianFilter()
         self._storage = None
+        self._channels = []
         self._dest_file = None
         self._hq_edges = bool(high_quality_edges)
         # hdrfilm.cpp:42-123: parameter validation and the per-format overrides
@@ -260,8 +261,14 @@ class HDRFilm:
         root, cur = os.path.splitext(self._dest_file)
         filename = self._dest_file if cur.lower() == ext else root + ext
         raw = self.bitmap(raw=True)
-        if raw.shape[2] != 5:
-            raise RuntimeError("HDRFilm::develop(): only the X, Y, Z, A, W storage layout can be written")
+        if raw.shape[2] != 5:           # hdrfilm.cpp:263-317: a film with AOVs is written as a multichannel image
+            if self._file_format != "exr":
+                raise RuntimeError("HDRFilm::develop(): only the X, Y, Z, A, W storage layout can be written")
+            px = self.bitmap().cpu().numpy()
+            names = ["R", "G", "B", "A"] + list(self._channels[5:])
+            dt = {"float16": np.float16, "float32": np.float32, "uint32": np.uint32}[self._component_format]
+            B.write_exr(filename, {n: np.ascontiguousarray(px[..., i]).astype(dt) for i, n in enumerate(names)})
+            return filename
         if self._pixel_format in ("rgb", "rgba"):
             px = self.bitmap().cpu().numpy()
             px = px if self._pixel_format == "rgba" else px[..., :3]
@@ -297,20 +304,33 @@ class HDRFilm:
             raise RuntimeError("Film::prepare(): duplicate channel name")
         self._storage = ImageBlock(self._crop_size, len(channels), device=device)
         self._storage.set_offset(self._crop_offset)
+        self._channels = list(channels)
+
+    def channels(self):
+        """the channel names of the storage, as given to prepare()"""
+        return list(self._channels)
 
     def put(self, block):
         self._storage.put(block)
 
     def bitmap(self, raw=False):
-        """hdrfilm.cpp:249-320: raw=True -> XYZAW storage, else RGBA float32 (H, W, 4)."""
+        """hdrfilm.cpp:249-320: raw=True -> the storage (X, Y, Z, A, W and the AOVs), else RGBA float32 (H, W, 4).  A storage with
+        AOVs (n > 5 channels) gives the reference's multichannel bitmap (H, W, n - 1) (hdrfilm.cpp:263-317): R, G, B, A, then every
+        AOV divided by the weight W (0 where W is 0); W itself is removed."""
         if self._storage is None:
             raise RuntimeError("HDRFilm::bitmap(): no storage (render first)")
         data = self._storage.data()
         if raw:
             return data
+        n = data.shape[2]
+        xyzaw = data if n == 5 else data[..., :5].contiguous()
         out = torch.empty((data.shape[0], data.shape[1], 4), dtype=torch.float32, device=data.device)
-        L.check(L.lib().mtsamd_film_develop(_ptr(data), data.shape[0] * data.shape[1], _ptr(out), _stream()))
-        return out
+        L.check(L.lib().mtsamd_film_develop(_ptr(xyzaw), data.shape[0] * data.shape[1], _ptr(out), _stream()))
+        if n == 5:
+            return out
+        w = data[..., 4:5]
+        aovs = torch.where(w != 0, data[..., 5:] / torch.where(w != 0, w, torch.ones_like(w)), torch.zeros_like(data[..., 5:]))
+        return torch.cat([out, aovs], dim=2)
 
 
 LIBM_FUNCTIONS = ("sin", "cos", "tan", "exp", "log", "erf", "acos", "atan2", "atanh", "cosh")
@@ -631,6 +651,11 @@ class Scene:
         v = [float(x) for x in values] + [0.0, 0.0]
         L.check(L.lib().mtsamd_scene_set_bsdf_param(self._handle, int(index), int(kind), (C.c_float * 3)(*v[:3])))
 
+    def set_aov_keep_limit(self, nbytes):
+        """Device memory a multi-pass `aov` render may take to keep the streams of all passes, which makes its film equal the one-pass film
+        bit for bit (default 2^30; 0: always splat pass by pass)."""
+        L.check(L.lib().mtsamd_scene_set_aov_keep_limit(self._handle, int(nbytes)))
+
     def set_emitter_radiance(self, index, rgb):
         L.check(L.lib().mtsamd_scene_set_emitter_radiance(self._handle, int(index), (C.c_float * 3)(*[float(x) for x in rgb])))
 
@@ -817,6 +842,95 @@ class MomentIntegrator(PathIntegrator):
         inv = torch.where(w != 0, 1.0 / torch.where(w != 0, w, torch.ones_like(w)), torch.zeros_like(w))
         mean, m2 = raw[..., 5:8] * inv, raw[..., 8:11] * inv
         return mean, m2 - mean * mean
+
+
+AOV_TYPES = {"depth": (0, [""]), "position": (1, [".X", ".Y", ".Z"]), "uv": (2, [".U", ".V"]), "geo_normal": (3, [".X", ".Y", ".Z"]),
+             "sh_normal": (4, [".X", ".Y", ".Z"]), "dp_du": (5, [".X", ".Y", ".Z"]), "dp_dv": (6, [".X", ".Y", ".Z"]),
+             "duv_dx": (7, [".U", ".V"]), "duv_dy": (8, [".U", ".V"])}      # mtsamd_aov_type, channel suffixes (aov.cpp:92-134)
+
+
+class AOVIntegrator(PathIntegrator):
+    """src/integrators/aov.cpp: fields of the camera ray's surface interaction -- ``depth``, ``position``, ``uv``, ``geo_normal``,
+    ``sh_normal``, ``dp_du``, ``dp_dv`` -- as film channels beside the render of a nested integrator.  ``aovs`` is a string of
+    ``<name>:<type>`` pairs separated by commas or spaces.  ``duv_dx`` and ``duv_dy`` are accepted and always zero, as in the
+    reference (kdtree.h:2353 zeroes them and aov.cpp never calls compute_partials).  `nested` (a path, direct or depth integrator, named
+    `name`) adds ``<name>.R/G/B/A`` after the AOVs and fills X, Y, Z, A; exactly one nested integrator is supported.  Spectral variant:
+    ``<name>.R/G/B`` is the linear transform of the XYZ sample, where the reference converts the spectrum itself (equal up to rounding)."""
+
+    def __init__(self, aovs, nested=None, name="integrator_0"):
+        if isinstance(nested, (list, tuple)):
+            if len(nested) > 1:
+                raise RuntimeError("aov: exactly one nested integrator is supported by this backend")
+            nested = nested[0] if nested else None
+        if nested is not None and (not isinstance(nested, PathIntegrator) or isinstance(nested, (MomentIntegrator, AOVIntegrator))):
+            raise RuntimeError("aov: the nested integrator must be a path, direct or depth integrator")
+        knobs = nested if nested is not None else PathIntegrator()
+        super().__init__(paths_per_wave=knobs.paths_per_wave, pipeline=knobs.pipeline)
+        self.nested, self.name = nested, str(name)
+        self._names, self._types = [], []
+        for tok in [t for t in str(aovs).replace(",", " ").split() if t]:      # string::tokenize(aovs, " ,") (aov.cpp:88-91)
+            item = tok.split(":")
+            if len(item) != 2 or not item[0] or not item[1]:
+                raise RuntimeError("Invalid AOV specification: require <name>:<type> pair")
+            if item[1] not in AOV_TYPES:
+                raise RuntimeError('Invalid AOV type "%s"!' % item[1])
+            kind, suffixes = AOV_TYPES[item[1]]
+            self._types.append(kind)
+            self._names += [item[0] + sfx for sfx in suffixes]
+        if not self._types and nested is None:
+            raise RuntimeError("aov: no AOV and no nested integrator")
+
+    def aov_names(self):
+        """aov.cpp:221-223: the string's AOVs, then per nested integrator its own AOVs (none here) and <name>.R/G/B/A (aov.cpp:136-151)"""
+        out = list(self._names)
+        if self.nested is not None:
+            out += ["%s.%s" % (self.name, n) for n in self.nested.aov_names()] + ["%s.%s" % (self.name, c) for c in "RGBA"]
+        return out
+
+    def _desc(self, sensor, rows=None, partition=None):
+        d = (self.nested if self.nested is not None else PathIntegrator(paths_per_wave=self.paths_per_wave))._desc(sensor, rows, partition)
+        if self.nested is None:
+            d.max_pass_log2, d.samples_per_pass, d.timeout = int(self.max_pass_log2), self.samples_per_pass, self.timeout
+        return d
+
+    def _aov_types(self):
+        return (C.c_int32 * max(len(self._types), 1))(*self._types), len(self._types)
+
+    def render(self, scene, sensor=None, rows=None, partition=None):
+        sensor = sensor if sensor is not None else scene.sensors()[0]
+        film = sensor.film()
+        film.prepare(self.aov_channels(), device="cuda:%d" % scene._device_index)
+        d = self._desc(sensor, rows, partition)
+        stats = (C.c_uint64 * 16)()
+        types, n = self._aov_types()
+        self._scene = scene
+        rc = L.lib().mtsamd_render_aov(scene._handle, C.byref(d), types, n, 0 if self.nested is None else 1, _ptr(film._storage.data()),
+                                       stats, _stream())
+        self._scene = None
+        if rc == -4:
+            return False
+        L.check(rc)
+        self.stats = dict(zip(("closest_hit_rays", "any_hit_rays", "samples", "iterations", "segments", "bounce_ns", "film_ns", "tri_tests",
+                               "trace_closest_ns", "trace_closest_launches", "trace_any_ns", "trace_any_launches", "shade_ns", "shade_launches",
+                               "passes", "timed_out"), [int(x) for x in stats]))
+        return True
+
+    def sample_aovs(self, scene, sensor, first, count):
+        """The AOV part of AOVIntegrator::sample (aov.cpp:166-193) for whole sample indices: (values (N, C), position (N, 2)), C = the
+        channels of the `aovs` string in order."""
+        d = self._desc(sensor)
+        dev = torch.device("cuda", scene._device_index)
+        values = torch.empty((count, len(self._names)), dtype=torch.float32, device=dev)
+        pos = torch.empty((count, 2), dtype=torch.float32, device=dev)
+        types, n = self._aov_types()
+        L.check(L.lib().mtsamd_sample_aovs(scene._handle, C.byref(d), types, n, int(first), int(count), _ptr(values), _ptr(pos), _stream()))
+        return values, pos
+
+    def sample(self, scene, sensor, first, count):
+        """the nested integrator's result (aov.cpp:195-213: the first nested integrator's radiance is the integrator's own)"""
+        if self.nested is None:
+            raise RuntimeError("aov: no nested integrator to sample")
+        return self.nested.sample(scene, sensor, first, count)
 
 
 def make_sensor(params):

@@ -599,8 +599,20 @@ def _integrator(ctx, it):
         if len(nested) != 1 or nested[0][1].tag != "integrator":
             raise XMLError("moment: exactly one nested integrator is supported by this backend")
         out = dict(type="moment", name=nested[0][0], nested=_integrator(ctx, nested[0][1]))
+    elif it.type == "aov":                               # aov.cpp:86-151: the `aovs` string, nested integrators named by their property name
+        aovs = it.get("aovs", kind="string")
+        nested = [(k, _resolve(ctx, v)) for k, v in it.props.items() if isinstance(v, Node) or (isinstance(v, tuple) and v and v[0] == "ref")]
+        nested += [("integrator_%d" % i, _resolve(ctx, c)) for i, c in enumerate(it.children)]
+        nested = [(k, v) for k, v in nested if isinstance(v, Node)]
+        for k, _ in nested:          # only the nested objects: a stray scalar property stays unqueried and is reported
+            it.queried.add(k)
+        if len(nested) > 1 or any(v.tag != "integrator" for _, v in nested):
+            raise XMLError("aov: exactly one nested integrator is supported by this backend")
+        out = dict(type="aov", aovs=aovs)
+        if nested:
+            out.update(name=nested[0][0], nested=_integrator(ctx, nested[0][1]))
     else:
-        raise XMLError('Integrator plugin "%s" is not supported by this backend (path, direct, depth, moment)' % it.type)
+        raise XMLError('Integrator plugin "%s" is not supported by this backend (path, direct, depth, moment, aov)' % it.type)
     return out
 
 
@@ -609,6 +621,8 @@ def _make_integrator(spec):
     args = {k: v for k, v in spec.items() if k not in ("type", "nested", "name")}
     if spec.get("type") == "moment":
         return R.MomentIntegrator(_make_integrator(spec["nested"]), spec.get("name", "nested"))
+    if spec.get("type") == "aov":
+        return R.AOVIntegrator(spec["aovs"], _make_integrator(spec["nested"]) if "nested" in spec else None, spec.get("name", "integrator_0"))
     return {"path": R.PathIntegrator, "direct": R.DirectIntegrator, "depth": R.DepthIntegrator}[spec.get("type", "path")](**args)
 
 
@@ -740,7 +754,7 @@ def load_file(path, device=0, variant="rgb", **params):
 
 # -------------------------------------------------------------------------------------------- load_dict
 _PLUGIN_CLASS = {"twosided": "bsdf", "blendbsdf": "bsdf", "mask": "bsdf", "conductor": "bsdf", "roughconductor": "bsdf", "dielectric": "bsdf", "plastic": "bsdf", "roughplastic": "bsdf", "roughdielectric": "bsdf", "thindielectric": "bsdf", "path": "integrator", "perspective": "sensor", "thinlens": "sensor", "hdrfilm": "film", "independent": "sampler", "gaussian": "rfilter", "box": "rfilter", "tent": "rfilter", "catmullrom": "rfilter", "mitchell": "rfilter", "lanczos": "rfilter",
-                 "direct": "integrator", "depth": "integrator", "moment": "integrator", "obj": "shape", "ply": "shape", "serialized": "shape", "rectangle": "shape", "diffuse": "bsdf", "area": "emitter", "constant": "emitter", "envmap": "emitter", "point": "emitter", "spot": "emitter", "directional": "emitter", "bitmap": "texture", "checkerboard": "texture", "scene": "scene"}
+                 "direct": "integrator", "depth": "integrator", "moment": "integrator", "aov": "integrator", "obj": "shape", "ply": "shape", "serialized": "shape", "rectangle": "shape", "diffuse": "bsdf", "area": "emitter", "constant": "emitter", "envmap": "emitter", "point": "emitter", "spot": "emitter", "directional": "emitter", "bitmap": "texture", "checkerboard": "texture", "scene": "scene"}
 
 
 def _node_from_dict(d, ctx):
@@ -778,7 +792,7 @@ def _node_from_dict(d, ctx):
                         if rid in ctx.instances:
                             raise XMLError("%s has duplicate id: %s" % (k, rid))
                         ctx.instances[rid] = child
-                if child.tag == "texture":
+                if child.tag == "texture" or (node.type == "aov" and child.tag == "integrator"):      # aov names its nested integrators by their key
                     node.set(k, child)
                 else:
                     node.children.append(child)

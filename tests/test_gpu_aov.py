@@ -1,0 +1,384 @@
+"""The `aov` integrator (src/integrators/aov.cpp) on the GPU: per-sample values and film channels against the oracle, the nested render
+left untouched, launch edges, the spectral variant, file output and refusals.
+
+Worst observed ratio |got - want| / (K * 2^-23 * S) of the film tests, over every scene, filter and channel, on an MI355X: 0.093 (the
+bound itself is derived: reordering of K-term fp32 sums)."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import oracle_binding as ob
+
+pytestmark = pytest.mark.gpu
+
+# the always-zero kinds first: the last, partial channel group (channel 21 = dv.Z alone) carries data
+ALL = "dx:duv_dx dy:duv_dy d:depth p:position uv:uv gn:geo_normal sn:sh_normal du:dp_du dv:dp_dv"
+N_ALL = 22
+F32 = np.float32
+
+
+@functools.lru_cache(maxsize=None)
+def _scene_dict(key):
+    from mitsuba2_amd import scenes
+    if key == "cbox":           # flat; texcoords but no vertex normals
+        return scenes.cornell_box(texture=(0.2 + 0.6 * np.random.RandomState(2).rand(4, 4, 3)).astype(F32))
+    return scenes.bumpy_sphere(12, 24, with_normals=(key == "sphere_n"))          # hierarchy
+
+
+@functools.lru_cache(maxsize=None)
+def _gpu_scene(key, variant="rgb"):
+    from mitsuba2_amd import render as R
+    return R.Scene(_scene_dict(key), variant=variant)
+
+
+def _sensor_params(key, w, h, spp, **kw):
+    from mitsuba2_amd import scenes
+    sp = scenes.cornell_box_sensor(w, h, spp, seed=11) if key == "cbox" else scenes.bumpy_sphere_sensor(w, h, spp, seed=3)
+    return dict(sp, **kw)
+
+
+def _expected(key, sp):
+    """per-sample (position, the 22 channels of ALL) from oracle calls only: the film positions of sample_radiance, camera_rays at
+    (pos - crop_offset) / crop_size in float32 as generate_path computes it, ray_intersect, fill_si; zeros on a miss"""
+    cx, cy, cw, ch = sp["crop"]
+    n = cw * ch * sp["sample_count"]
+    d = ob.make_desc(sp)
+    o = ob.OracleScene(_scene_dict(key))
+    _, pos = o.sample_radiance(d, 0, n)
+    sx = (pos[:, 0] - F32(cx)) / F32(cw)
+    sy = (pos[:, 1] - F32(cy)) / F32(ch)
+    ro, rd, mint, maxt = ob.camera_rays(d, sx.astype(F32), sy.astype(F32))
+    t, prim, _, u, v = o.ray_intersect(ro, rd, mint, maxt)
+    hit = np.isfinite(t)
+    want = np.zeros((n, N_ALL), F32)
+    si = o.fill_si(rd[hit], prim[hit], u[hit], v[hit])          # p(3) n(3) uv(2) s(3) t(3) sh_n(3) dp_du(3) dp_dv(3) wi(3)
+    want[hit, 4] = t[hit]          # channels 0..3: duv_dx, duv_dy = 0
+    want[hit, 5:8], want[hit, 8:10], want[hit, 10:13] = si[:, 0:3], si[:, 6:8], si[:, 3:6]
+    want[hit, 13:16], want[hit, 16:19], want[hit, 19:22] = si[:, 14:17], si[:, 17:20], si[:, 20:23]
+    assert (want[:, 21] != 0).any() and (want[:, 18:21] != 0).any()          # the last two channel groups are not all zero
+    return pos, want, hit
+
+
+@functools.lru_cache(maxsize=None)
+def _expected_small(key):
+    return _expected(key, _sensor_params(key, 32, 24, 2))
+
+
+def _oracle_film(sp, pos, vals):
+    """(want, S): the oracle's splat of the 5 + C channel samples (0, 0, 0, 0, 1, aovs) and of their absolute values.  The oracle's put
+    drops negative values (warn_negative = true), so positive and negative parts are splatted apart; want = P - N exactly (float64)."""
+    cx, cy, cw, ch = sp["crop"]
+    full = np.concatenate([np.zeros((len(vals), 4), F32), np.ones((len(vals), 1), F32), vals], 1)
+    rp = sp["rfilter_param"]
+    put = lambda v: ob.imageblock_put(cw, ch, cx, cy, full.shape[1], ob.RFILTERS[sp["rfilter"]], rp, False, pos, v)
+    P, N = put(np.maximum(full, 0)), put(np.maximum(-full, 0))
+    return P.astype(np.float64) - N.astype(np.float64), P.astype(np.float64) + N.astype(np.float64)
+
+
+WORST = [0.0]
+
+
+def _check_film(got, want, S, spp, what):
+    """|got - want| <= K * 2^-23 * S with K = 25 * spp terms (radius-2 filter): the reordering bound of fp32 sums"""
+    bound = 25 * spp * 2.0 ** -23 * S
+    err = np.abs(got.astype(np.float64) - want)
+    ratio = float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.where(err > 0, np.inf, 0))))
+    WORST[0] = max(WORST[0], ratio)
+    print("%s: worst |got - want| / bound = %.4f (all film tests so far: %.4f)" % (what, ratio, WORST[0]))
+    assert (err <= bound).all(), (what, ratio)
+
+
+# ---- 1. per-sample values, every bit
+@pytest.mark.parametrize("key", ["cbox", "sphere_n", "sphere_flat"])
+def test_sample_aovs_match_the_oracle_bit_for_bit(key):
+    from mitsuba2_amd import render as R
+    sp = _sensor_params(key, 32, 24, 2)
+    pos, want, hit = _expected_small(key)
+    got, gpos = R.AOVIntegrator(ALL).sample_aovs(_gpu_scene(key), R.make_sensor(sp), 0, 32 * 24 * 2)
+    got, gpos = got.cpu().numpy(), gpos.cpu().numpy()
+    assert np.array_equal(gpos, pos)
+    names = R.AOVIntegrator(ALL).aov_names()
+    for c in range(N_ALL):
+        assert np.array_equal(got[:, c], want[:, c]), (names[c], int((got[:, c] != want[:, c]).sum()))
+    assert (got[:, :4] == 0).all()          # duv_dx, duv_dy: always zero, as in the reference
+    assert (got[~hit] == 0).all()
+    if key != "cbox":                        # both branches of the kernel, on the hierarchy
+        assert 0.05 <= hit.mean() <= 0.95
+    if key == "sphere_n":                    # the shading normal is not the geometric one here
+        assert (want[:, 13:16] != want[:, 10:13]).any()
+    # a range in the middle of the film
+    part, ppos = R.AOVIntegrator("n:sh_normal d:depth").sample_aovs(_gpu_scene(key), R.make_sensor(sp), 333, 700)
+    assert np.array_equal(part.cpu().numpy(), want[333:1033][:, [13, 14, 15, 4]]) and np.array_equal(ppos.cpu().numpy(), pos[333:1033])
+
+
+# ---- 2. thin lens: the same camera sample and the same query as the depth integrator
+def test_thin_lens_depth_equals_the_depth_integrator():
+    from mitsuba2_amd import render as R
+    sp = _sensor_params("cbox", 16, 16, 2, aperture_radius=20.0, focus_distance=1000.0)
+    scene, sensor = _gpu_scene("cbox"), R.make_sensor(sp)
+    got, pos = R.AOVIntegrator("d:depth").sample_aovs(scene, sensor, 0, 512)
+    rgb, _, dpos = R.DepthIntegrator().sample(scene, sensor, 0, 512)
+    assert torch.equal(got[:, 0], rgb[:, 0]) and torch.equal(pos, dpos) and (got > 0).any()
+    pin, _ = R.AOVIntegrator("d:depth").sample_aovs(scene, R.make_sensor(_sensor_params("cbox", 16, 16, 2)), 0, 512)
+    assert not torch.equal(pin, got)          # the aperture sample is used
+
+
+# ---- 3. the nested render is untouched
+def _plain_films(scene, sensor, integ):
+    """(X, Y, Z, A, W film of the plain render, R, G, B, A, W film of mtsamd_render with film_rgb = 1)"""
+    from mitsuba2_amd import _lib as L, render as R
+    assert integ.render(scene, sensor)
+    xyz = sensor.film().bitmap(raw=True).clone()
+    d = integ._desc(sensor)
+    d.film_rgb = 1
+    rgb = torch.zeros_like(xyz)
+    L.check(L.lib().mtsamd_render(scene._handle, C.byref(d), R._ptr(rgb), None, R._stream()))
+    return xyz, rgb
+
+
+@pytest.mark.parametrize("key,pipeline", [("cbox", 0), ("sphere_n", 0), ("sphere_n", 2)])
+def test_nested_render_is_untouched(key, pipeline):
+    from mitsuba2_amd import render as R
+    sp = _sensor_params(key, 32, 24, 4)
+    scene, sensor = _gpu_scene(key), R.make_sensor(sp)
+    xyz, rgb = _plain_films(scene, sensor, R.PathIntegrator(max_depth=5, pipeline=pipeline))
+    integ = R.AOVIntegrator("d:depth n:sh_normal", R.PathIntegrator(max_depth=5, pipeline=pipeline), name="img")
+    assert integ.render(scene, sensor)
+    raw = sensor.film().bitmap(raw=True)
+    assert raw.shape == (24, 32, 5 + 4 + 4) and sensor.film().channels()[-4:] == ["img.R", "img.G", "img.B", "img.A"]
+    assert torch.equal(raw[..., :5], xyz) and float(xyz[..., :3].max()) > 0
+    assert torch.equal(raw[..., -4:], rgb[..., :4])
+    assert integ.stats["closest_hit_rays"] > 32 * 24 * 4 and integ.stats["samples"] == 32 * 24 * 4
+
+
+# ---- 4. film channels against the oracle's splat
+@pytest.mark.parametrize("rfilter", ["gaussian", "box"])
+@pytest.mark.parametrize("key", ["cbox", "sphere_n"])
+def test_aov_film_matches_the_oracle_splat(key, rfilter):
+    from mitsuba2_amd import render as R
+    sp = _sensor_params(key, 32, 24, 2, rfilter=rfilter, rfilter_param=0.5)
+    pos, vals, _ = _expected_small(key)
+    scene, sensor = _gpu_scene(key), R.make_sensor(sp)
+    integ = R.AOVIntegrator(ALL)
+    assert integ.render(scene, sensor)
+    raw = sensor.film().bitmap(raw=True).cpu().numpy()
+    assert raw.shape == (24, 32, 5 + N_ALL) and (raw[..., :4] == 0).all()          # no nested integrator: X, Y, Z, A stay 0
+    want, S = _oracle_film(sp, pos, vals)
+    _check_film(raw, want, S, 2, "%s / %s" % (key, rfilter))
+    assert integ.stats["closest_hit_rays"] == 32 * 24 * 2 and integ.stats["any_hit_rays"] == 0 and integ.stats["tri_tests"] > 0
+    assert R.PathIntegrator(max_depth=1).render(scene, sensor)
+    assert np.array_equal(sensor.film().bitmap(raw=True).cpu().numpy()[..., 4], raw[..., 4])          # the same W, exactly
+
+
+# ---- 5. shapes that break launches
+def test_crop_window():
+    from mitsuba2_amd import render as R
+    sp = _sensor_params("sphere_n", 32, 24, 3, crop=(5, 3, 19, 11))
+    pos, vals, hit = _expected("sphere_n", sp)
+    scene, sensor = _gpu_scene("sphere_n"), R.make_sensor(sp)
+    integ = R.AOVIntegrator(ALL)
+    got, gpos = integ.sample_aovs(scene, sensor, 0, 19 * 11 * 3)
+    assert np.array_equal(gpos.cpu().numpy(), pos) and np.array_equal(got.cpu().numpy(), vals) and hit.any() and not hit.all()
+    assert integ.render(scene, sensor)
+    raw = sensor.film().bitmap(raw=True).cpu().numpy()
+    assert raw.shape == (11, 19, 5 + N_ALL)
+    want, S = _oracle_film(sp, pos, vals)
+    _check_film(raw, want, S, 3, "crop")
+
+
+def _render_raw(integ, scene, sensor, **kw):
+    assert integ.render(scene, sensor, **kw)
+    return sensor.film().bitmap(raw=True).clone(), integ.stats["passes"]
+
+
+def _nested_aov(**kw):
+    from mitsuba2_amd import render as R
+    return R.AOVIntegrator("d:depth p:position n:sh_normal", R.PathIntegrator(max_depth=3, **kw), name="img")
+
+
+def test_forced_passes_equal_the_one_pass_film():
+    """32 x 24 at 4 spp: max_pass_log2 = 10 gives three passes of eight rows, samples_per_pass = 2 two passes; both must be torch.equal
+    to the one-pass film.
+
+    The film kernels sum per source tile of a pass, so the library keeps the streams of all passes and splats them once (api.cpp,
+    mtsamd_render_aov); splatted pass by pass the films differed by 8.5e-08 / 1.7e-07 of the largest value in 512 / 1658 of 12288 floats."""
+    from mitsuba2_amd import render as R
+    sp = _sensor_params("sphere_n", 32, 24, 4)
+    scene, sensor = _gpu_scene("sphere_n"), R.make_sensor(sp)
+    one, passes = _render_raw(_nested_aov(), scene, sensor)
+    assert passes == 1
+    small = _nested_aov()
+    small.nested.max_pass_log2 = 10           # 1024 samples = 8 rows of 32 x 4
+    films = [("max_pass_log2 = 10", 3) + _render_raw(small, scene, sensor), ("samples_per_pass = 2", 2) + _render_raw(_nested_aov(samples_per_pass=2), scene, sensor)]
+    alone = R.AOVIntegrator(ALL)              # AOVs alone: the scheduler knobs are the integrator's own
+    full, passes = _render_raw(alone, scene, sensor)
+    assert passes == 1
+    alone.max_pass_log2 = 10
+    films.append(("aov alone, max_pass_log2 = 10", 3) + _render_raw(alone, scene, sensor))
+    for what, want_passes, film, passes in films:
+        ref = full if what.startswith("aov alone") else one
+        print("%s: %d passes, max |many - one| / max |one| = %.3g, unequal floats %d of %d" %
+              (what, passes, float((film - ref).abs().max() / ref.abs().max()), int((film != ref).sum()), film.numel()))
+    for what, want_passes, film, passes in films:
+        assert passes == want_passes
+        assert torch.equal(film, full if what.startswith("aov alone") else one), what
+
+
+class _keep_limit:
+    """scoped mtsamd_scene_set_aov_keep_limit"""
+
+    def __init__(self, scene, nbytes):
+        self.scene, self.nbytes = scene, nbytes
+
+    def __enter__(self):
+        self.scene.set_aov_keep_limit(self.nbytes)
+
+    def __exit__(self, *exc):
+        self.scene.set_aov_keep_limit(1 << 30)
+
+
+def test_pass_by_pass_splat_above_the_keep_limit():
+    """Keep limit 0: every pass is splatted before the next is traced (the route of renders whose streams do not fit the limit).  The
+    film keeps the oracle bound, W and the nested channels equal those of the plain render cut into the same passes; a limit that
+    just fits gives the one-pass film again."""
+    from mitsuba2_amd import render as R
+    sp = _sensor_params("sphere_n", 32, 24, 4)
+    scene, sensor = _gpu_scene("sphere_n"), R.make_sensor(sp)
+    pos, vals, _ = _expected("sphere_n", sp)
+    want, S = _oracle_film(sp, pos, vals)
+    alone, plain = R.AOVIntegrator(ALL), R.PathIntegrator(max_depth=3)
+    one, _ = _render_raw(alone, scene, sensor)
+    alone.max_pass_log2 = plain.max_pass_log2 = 10           # three passes of eight rows
+    keep_bytes = 16 * (32 * 24 * 4 * 9 + 32 * 24 * 4 // 2 + 1)          # 8 groups + the stream, the positions
+    with _keep_limit(scene, keep_bytes):
+        film, passes = _render_raw(alone, scene, sensor)
+        assert passes == 3 and torch.equal(film, one)
+    with _keep_limit(scene, keep_bytes - 1):
+        film, passes = _render_raw(alone, scene, sensor)
+        assert passes == 3
+        _check_film(film.cpu().numpy(), want, S, 4, "pass by pass")
+        pw, ppasses = _render_raw(plain, scene, sensor)
+        assert ppasses == 3 and torch.equal(pw[..., 4], film[..., 4])
+    with _keep_limit(scene, 0):
+        # interleaved tiles of four rows (this call owns rows 0-3, 8-11, 16-19): passes of eight local rows, source tiles of four
+        part, passes = _render_raw(alone, scene, sensor, partition=(0, 2, 4))
+        assert passes == 2
+        rows = (np.arange(32 * 24 * 4) // 4) // 32
+        own = (rows // 4) % 2 == 0
+        pwant, pS = _oracle_film(sp, pos[own], vals[own])
+        _check_film(part.cpu().numpy(), pwant, pS, 4, "pass by pass, partition (0, 2, 4)")
+        pw, ppasses = _render_raw(plain, scene, sensor, partition=(0, 2, 4))
+        assert ppasses == 2 and torch.equal(pw[..., 4], part[..., 4])
+        # nested: X, Y, Z, A, W are the plain render's in the same passes, bit for bit
+        nested = _nested_aov()
+        nested.nested.max_pass_log2 = 10
+        film, passes = _render_raw(nested, scene, sensor)
+        pw, _ = _render_raw(plain, scene, sensor)
+        assert passes == 3 and torch.equal(film[..., :5], pw) and float(pw[..., :3].max()) > 0
+    assert torch.equal(_render_raw(alone, scene, sensor)[0], one)           # back under the default limit
+
+
+def test_rows_add_up_and_renders_are_deterministic():
+    from mitsuba2_amd import render as R
+    sp = _sensor_params("sphere_n", 32, 24, 4)
+    scene, sensor = _gpu_scene("sphere_n"), R.make_sensor(sp)
+    one, _ = _render_raw(_nested_aov(), scene, sensor)
+    assert torch.equal(_render_raw(_nested_aov(), scene, sensor)[0], one)          # two identical renders: every bit
+    alone = R.AOVIntegrator(ALL)
+    full, _ = _render_raw(alone, scene, sensor)
+    assert torch.equal(_render_raw(alone, scene, sensor)[0], full)
+    halves = _render_raw(alone, scene, sensor, rows=(0, 12))[0] + _render_raw(alone, scene, sensor, rows=(12, 24))[0]
+    pos, vals, _ = _expected("sphere_n", sp)
+    want, S = _oracle_film(sp, pos, vals)
+    _check_film(halves.cpu().numpy(), want, S, 4, "rows (0, 12) + (12, 24)")
+    _check_film(full.cpu().numpy(), want, S, 4, "4 spp")
+    # forced passes against the oracle's splat: the bound of the film tests holds whatever the order of the passes
+    alone.max_pass_log2 = 10
+    many, passes = _render_raw(alone, scene, sensor)
+    assert passes == 3
+    _check_film(many.cpu().numpy(), want, S, 4, "three passes")
+
+
+# ---- 6. spectral variant
+def test_spectral_variant():
+    from mitsuba2_amd import render as R
+    sp = _sensor_params("cbox", 16, 16, 2)
+    sensor = R.make_sensor(sp)
+    spec = _gpu_scene("cbox", "spectral")
+    integ = R.AOVIntegrator("d:depth n:sh_normal p:position", R.PathIntegrator(max_depth=4), name="img")
+    a, apos = integ.sample_aovs(spec, sensor, 0, 512)
+    b, bpos = integ.sample_aovs(_gpu_scene("cbox"), sensor, 0, 512)
+    assert torch.equal(a, b) and torch.equal(apos, bpos) and (a != 0).any()
+    assert integ.render(spec, sensor)
+    raw = sensor.film().bitmap(raw=True)
+    plain = R.PathIntegrator(max_depth=4)
+    bm = sensor.film().bitmap()
+    assert plain.render(spec, sensor)
+    assert torch.equal(sensor.film().bitmap(raw=True), raw[..., :5])
+    # the same matrix before or after a linear sum (derived, not measured): 1e-5 of the largest value
+    rgb = raw[..., -4:-1] / raw[..., 4:5]
+    assert float((rgb - bm[..., :3]).abs().max()) <= 1e-5 * float(bm[..., :3].abs().max()) and float(bm[..., :3].max()) > 0
+    assert torch.equal(raw[..., -1], raw[..., 3])
+
+
+# ---- 7. output
+def test_bitmap_and_exr_output(tmp_path):
+    from mitsuba2_amd import _lib as L, bitmap as B, render as R
+    sp = _sensor_params("cbox", 16, 12, 2)
+    film = R.HDRFilm(16, 12, rfilter=R.GaussianFilter(0.5), component_format="float32")
+    sensor = R.PerspectiveCamera(to_world=sp["to_world"], fov=sp["fov"], near_clip=sp["near_clip"], far_clip=sp["far_clip"], film=film,
+                                 sampler=R.IndependentSampler(2, 11))
+    integ = R.AOVIntegrator("dd.y:depth nn:sh_normal", R.PathIntegrator(max_depth=3), name="img")
+    assert integ.render(_gpu_scene("cbox"), sensor)
+    raw, bm = film.bitmap(raw=True), film.bitmap()
+    n = raw.shape[2]
+    assert n == 5 + 4 + 4 and bm.shape == (12, 16, n - 1)
+    rgba = torch.empty((12, 16, 4), dtype=torch.float32, device=raw.device)
+    L.check(L.lib().mtsamd_film_develop(R._ptr(raw[..., :5].contiguous()), 12 * 16, R._ptr(rgba), R._stream()))
+    assert torch.equal(bm[..., :4], rgba)
+    assert torch.equal(bm[..., 4:], raw[..., 5:] / raw[..., 4:5]) and float(bm[..., 4].max()) > 100          # depth / W
+    film.set_destination_file(str(tmp_path / "out.exr"))
+    data, _ = B.read_exr(film.develop())
+    names = ["R", "G", "B", "A", "dd.y", "nn.X", "nn.Y", "nn.Z", "img.R", "img.G", "img.B", "img.A"]
+    assert sorted(data) == sorted(names)
+    for i, name in enumerate(names):
+        assert data[name].dtype == np.float32 and np.array_equal(data[name], bm[..., i].cpu().numpy()), name
+    for fmt in ("pfm", "rgbe"):
+        other = R.HDRFilm(16, 12, file_format=fmt)
+        other.prepare(integ.aov_channels(), device="cuda")
+        other.set_destination_file(str(tmp_path / "out"))
+        with pytest.raises(RuntimeError, match="only the X, Y, Z, A, W storage layout"):
+            other.develop()
+
+
+# ---- 8. refusals: an error with a message, never a launch
+def test_refusals():
+    from mitsuba2_amd import _lib as L, render as R
+    scene, sensor = _gpu_scene("cbox"), R.make_sensor(_sensor_params("cbox", 16, 16, 1))
+    lib = L.lib()
+    film = torch.zeros((16, 16, 64), dtype=torch.float32, device="cuda")
+    stats = (C.c_uint64 * 16)()
+
+    def call(types, nested=0, out=film, **fields):
+        d = R.PathIntegrator()._desc(sensor)
+        for k, v in fields.items():
+            setattr(d, k, v)
+        rc = lib.mtsamd_render_aov(scene._handle, C.byref(d), (C.c_int32 * max(len(types), 1))(*types), len(types), nested, R._ptr(out), stats, R._stream())
+        return rc, lib.mtsamd_last_error().decode()
+
+    for (rc, msg), code, text in ((call([0], moment=1), -5, "moment"), (call([0], film_rgb=1), -5, "film_rgb"),
+                                  (call([1] * 11), -5, "more than 32 AOV channels"), (call([9]), -1, "Invalid AOV type 9"),
+                                  (call([-1]), -1, "Invalid AOV type -1"), (call([], 0), -1, "needs an AOV or a nested integrator")):
+        assert rc == code and text in msg, (rc, msg)
+    assert (film == 0).all()
+    most = torch.zeros((16, 16, 5 + 32), dtype=torch.float32, device="cuda")
+    assert call([1] * 10 + [2], out=most)[0] == 0 and (most[..., 4] > 0).all() and (film == 0).all()          # 32 channels are served
+    out = torch.zeros((256, 4), dtype=torch.float32, device="cuda")
+    d = R.PathIntegrator()._desc(sensor)
+    assert lib.mtsamd_sample_aovs(scene._handle, C.byref(d), (C.c_int32 * 1)(12), 1, 0, 256, R._ptr(out), None, R._stream()) == -1
+    assert lib.mtsamd_sample_aovs(scene._handle, C.byref(d), (C.c_int32 * 1)(0), 1, 1, 256, R._ptr(out), None, R._stream()) == -1          # past the last sample
+    with pytest.raises(RuntimeError, match="duplicate channel name"):
+        R.AOVIntegrator("a:depth,a:depth").render(scene, sensor)
