@@ -158,7 +158,8 @@ MTSAMD_API int mtsamd_scene_info(const mtsamd_scene *scene, uint32_t *out6);
 MTSAMD_API int mtsamd_scene_set_bsdf_reflectance(mtsamd_scene *scene, uint32_t bsdf, const float *rgb);
 MTSAMD_API int mtsamd_scene_set_emitter_radiance(mtsamd_scene *scene, uint32_t emitter, const float *rgb);
 /* BitmapTexture `data` parameter (bitmap.cpp:295-299): rgb is a host OR device pointer to height*width*3 floats;
- * asynchronous on `stream`. */
+ * asynchronous on `stream`.  Spectral variant: the texels are clamped to [0, 1] and converted to model coefficients on the host, as
+ * scene creation converts them (the call waits for `stream` first and returns when the scene holds the new texels). */
 MTSAMD_API int mtsamd_scene_update_texture(mtsamd_scene *scene, uint32_t texture, const float *rgb, void *stream);
 
 /* ---- scene queries on SoA ray streams --------------------------------------
@@ -369,6 +370,18 @@ MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_ren
  * concatenated, offsets from mtsamd_scene_texture_info), ACCUMULATED into.  Needs 0 <= max_depth <= 16; no blendbsdf / mask. */
 MTSAMD_API int mtsamd_render_adjoint_textures(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
                                    const float *film_dev, float *grad_textures_dev, void *stream);
+/* Spectral variant: the derivative with respect to the reflectance family -- diffuse.reflectance and (rough)plastic.diffuse_reflectance
+ * (plain or inside `twosided`), given as a constant `srgb` colour or as a bitmap -- in ANY spectral scene the path integrator renders.
+ * The film channels differentiated are the X, Y, Z the spectral variant writes (with or without film_rgb).  Every camera sample is
+ * replayed with its PCG32 stream through the general spectral path step and swept backwards on its four wavelengths; ALL sampling is
+ * held fixed, the Russian-roulette probability included (the estimator of the true derivative of the image; mtsamd_render_adjoint*
+ * differentiate that probability as Enoki does).  The gradient reaches RGB through the model coefficients: dS/dc in the kernel, then the
+ * transposed Jacobian of srgb_model_fetch at each colour (kept by the scene).  grad_bsdf_dev: bsdf_count x 3 linear RGB (rows of other
+ * records stay untouched); grad_textures_dev: the layout of mtsamd_render_adjoint.  Both are ACCUMULATED into; either may be NULL.
+ * Needs 1 <= max_depth <= 16, no blendbsdf / mask, at most 32 BSDFs with grad_bsdf_dev.  The coefficient gradients and the Jacobians
+ * live in scratch buffers the scene owns: calls for ONE scene must be ordered on one stream (or otherwise serialised). */
+MTSAMD_API int mtsamd_render_adjoint_spectral(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
+                                   const float *film_dev, float *grad_bsdf_dev, float *grad_textures_dev, void *stream);
 MTSAMD_API int mtsamd_scene_update_envmap(mtsamd_scene *scene, const float *rgb, int32_t rebuild_distribution);
 /* Size of a bitmap texture and its float offset inside the concatenated texture-gradient buffer. */
 /* RoughPlastic precomputation (roughplastic.cpp:380-399) of BSDF `bsdf`: out65[0..63] = external transmittance at
@@ -383,6 +396,9 @@ MTSAMD_API int mtsamd_scene_texture_info(const mtsamd_scene *scene, uint32_t tex
 MTSAMD_API int mtsamd_rgb2spec_build(const char *path, int32_t resolution, int32_t threads);
 /* srgb_model_fetch (src/librender/srgb.cpp:14-40): coefficients of the smooth spectrum for a linear sRGB colour. */
 MTSAMD_API int mtsamd_srgb_model_fetch(const char *path, const float *rgb3, float *coeff3);
+/* Its derivative: jac9[3 c + j] = d coeff_j / d rgb_c, the analytic derivative of the trilinear table lookup inside the cell of `rgb3`.
+ * Zero for pure black and pure white (their coefficients are sentinels), a zero row for a component outside [0, 1].  Host only. */
+MTSAMD_API int mtsamd_srgb_model_fetch_jacobian(const char *path, const float *rgb3, float *jac9);
 
 /* PerspectiveCamera::sample_ray (perspective.cpp:153-188) / ThinLensCamera::sample_ray (thinlens.cpp:175-214) for n
  * film-plane samples in [0,1)^2 and, for a thin lens, n aperture samples (NULL: 0.5, as integrator.cpp:229 initialises them)

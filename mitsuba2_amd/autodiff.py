@@ -48,8 +48,11 @@ class ParameterMap:
     """Dictionary-like view of the differentiable scene parameters (util.py:16-130): torch tensors on the scene's GPU.
     Writes take effect in the scene after :meth:`update` (``parameters_changed``)."""
 
-    def __init__(self, scene):
+    def __init__(self, scene, replay=False):
         self._scene = scene
+        # spectral variant only: differentiate the reflectance family (constant srgb colours and bitmap texels of diffuse.reflectance /
+        # (rough)plastic.diffuse_reflectance) by the spectral path replay, mtsamd_render_adjoint_spectral, instead of central differences
+        self._replay = bool(replay) and _is_spectral(scene)
         self.rebuild_envmap_distribution = True      # what parameters_changed() does (envmap.cpp:220-253); False: tests of linearity
         self.fd_step = 0.0                           # BSDF-model parameters: step of the central difference of the model code (0: 1 % of the value)
         self.properties = {}
@@ -117,6 +120,10 @@ class ParameterMap:
         for key, i, data in (_texture_parameters(scene._bsdf_records) if not diffuse_scene and not _is_spectral(scene) else []):
             self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
             self._kind[key] = ("texture", scene.texture_index(i), i)
+        # spectral variant with `replay`: the same texel keys, in diffuse and general scenes alike (mtsamd_render_adjoint_spectral)
+        for key, i, data in (_texture_parameters(scene._bsdf_records) if self._replay else []):
+            self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
+            self._kind[key] = ("texture", scene.texture_index(i), i)
         # 'shape.emitter.radiance.value' of area lights (docs/src/inverse_rendering/diff_render.rst:76)
         for i, m in enumerate(scene._dict["meshes"] if diffuse_scene else []):
             e = m.get("emitter", -1)
@@ -159,7 +166,7 @@ class ParameterMap:
             if last is not None and last[0] is v and last[1] == v._version:      # (the tensor itself is kept: an id can be reused)
                 continue
             kind, idx, _ = self._kind[k]
-            if _is_spectral(self._scene) and (kind == "bsdf" or (kind == "bsdf_param" and self._kind[k][2] != 4)):
+            if _is_spectral(self._scene) and (kind in ("bsdf", "texture") or (kind == "bsdf_param" and self._kind[k][2] != 4)):
                 # spectral variant: an srgb colour lives in [0, 1]^3 (srgb.cpp:34-35); an optimiser step that leaves the box is projected
                 # back onto it (the parameter tensor itself, so that the optimiser's state and the scene agree)
                 with torch.no_grad():
@@ -178,9 +185,22 @@ class ParameterMap:
                 self._scene.set_bsdf_reflectance(idx, v.detach().cpu().tolist())
 
 
-def traverse(scene):
-    """mitsuba.python.util.traverse (util.py:132-179) for the supported parameters."""
-    return ParameterMap(scene)
+def traverse(scene, replay=False):
+    """mitsuba.python.util.traverse (util.py:132-179) for the supported parameters.  ``replay=True`` (spectral scenes; ignored for RGB
+    ones) adds the bitmap texels of the reflectance family and differentiates that family with the spectral path replay."""
+    return ParameterMap(scene, replay=replay)
+
+
+def _replayed(pmap, key):
+    """Does the spectral path replay differentiate this key?  Texels, and the constant (diffuse_)reflectance colours."""
+    kind, _, extra = pmap._kind[key]
+    return pmap._replay and (kind in ("texture", "bsdf") or (kind == "bsdf_param" and extra == 0))
+
+
+def _texture_slice(scene, g_tex, idx):
+    off, w, h = C.c_uint64(), C.c_int32(), C.c_int32()
+    L.check(L.lib().mtsamd_scene_texture_info(scene._handle, idx, C.byref(w), C.byref(h), C.byref(off)))
+    return g_tex[off.value: off.value + 3 * w.value * h.value].reshape(h.value, w.value, 3).clone()
 
 
 def _desc(scene, sensor, integrator, spp, seed):
@@ -212,7 +232,7 @@ def _spectral_gradient(scene, d, pmap, key, gi):
     spectral ParameterMap is limited to a handful of constants -- texels and envmaps raise."""
     kind, idx, extra = pmap._kind[key]
     if kind in ("texture", "envmap"):
-        raise RuntimeError("the spectral variant differentiates constant colours, radiances and roughnesses only (%s is a %s)" % (key, kind))
+        raise RuntimeError("the spectral variant differentiates constant colours, radiances and roughnesses only (%s is a %s; texels need traverse(scene, replay=True))" % (key, kind))
     value = [float(x) for x in pmap[key].detach().cpu().reshape(-1).tolist()]
 
     def push(vals):
@@ -225,19 +245,21 @@ def _spectral_gradient(scene, d, pmap, key, gi):
 
     grad = torch.zeros(len(value), dtype=torch.float32, device=gi.device)
     colour = kind != "emitter" and not (kind == "bsdf_param" and extra == 4)
-    for c in range(len(value)):
-        h = float(pmap.fd_step) if pmap.fd_step > 0 else 0.01 * max(abs(value[c]), 0.05)
-        hi, lo = value[c] + h, value[c] - h
-        if colour:
-            hi, lo = min(hi, 1.0), max(lo, 0.0)                       # srgb colours live in [0, 1] (srgb.cpp:34-35)
-        elif kind == "bsdf_param":
-            lo = max(lo, 1e-4)                                        # roughness
-        images = []
-        for x in (hi, lo):
-            push(value[:c] + [x] + value[c + 1:])
-            images.append(_image_of(_render_film(scene, d)))
-        grad[c] = torch.dot(gi, images[0] - images[1]) / (hi - lo)
-    push(value)
+    try:
+        for c in range(len(value)):
+            h = float(pmap.fd_step) if pmap.fd_step > 0 else 0.01 * max(abs(value[c]), 0.05)
+            hi, lo = value[c] + h, value[c] - h
+            if colour:
+                hi, lo = min(hi, 1.0), max(lo, 0.0)                       # srgb colours live in [0, 1] (srgb.cpp:34-35)
+            elif kind == "bsdf_param":
+                lo = max(lo, 1e-4)                                        # roughness
+            images = []
+            for x in (hi, lo):
+                push(value[:c] + [x] + value[c + 1:])
+                images.append(_image_of(_render_film(scene, d)))
+            grad[c] = torch.dot(gi, images[0] - images[1]) / (hi - lo)
+    finally:
+        push(value)               # an exception on the way leaves the scene at the parameter's value
     return grad.reshape(pmap[key].shape)
 
 
@@ -262,7 +284,20 @@ class _Render(torch.autograd.Function):
         g_em = torch.zeros((max(len(scene._dict.get("emitters", [])), 1), 3), dtype=torch.float32, device=dev)
         gi = grad_image.to(dev, torch.float32).contiguous()
         if _is_spectral(scene):
-            return (None, None, None, None) + tuple(_spectral_gradient(scene, d, pmap, k, gi.reshape(-1)) for k in keys)
+            grads = {}
+            replayed = {pmap._kind[k][0] for k in keys if _replayed(pmap, k)}
+            if replayed:      # one replay for the whole reflectance family; a gradient nobody asked for is not computed (null)
+                L.check(L.lib().mtsamd_render_adjoint_spectral(scene._handle, C.byref(d), _ptr(gi), _ptr(film), _ptr(g_bsdf) if replayed - {"texture"} else None,
+                                                               _ptr(g_tex) if "texture" in replayed else None, _stream()))
+            for k in keys:
+                kind, idx, _ = pmap._kind[k]
+                if not _replayed(pmap, k):
+                    grads[k] = _spectral_gradient(scene, d, pmap, k, gi.reshape(-1))
+                elif kind == "texture":
+                    grads[k] = _texture_slice(scene, g_tex, idx)
+                else:
+                    grads[k] = g_bsdf[idx].clone().reshape(pmap[k].shape)
+            return (None, None, None, None) + tuple(grads[k] for k in keys)
         kinds = {pmap._kind[k][0] for k in keys}
         if pmap._diffuse_scene and kinds - {"envmap", "bsdf_param"}:
             L.check(L.lib().mtsamd_render_adjoint(scene._handle, C.byref(d), _ptr(gi), _ptr(film), _ptr(g_bsdf), _ptr(g_tex), _ptr(g_em), _stream()))
@@ -290,9 +325,7 @@ class _Render(torch.autograd.Function):
             elif kind == "emitter":
                 grads.append(g_em[idx].clone())
             else:
-                off, w, h = C.c_uint64(), C.c_int32(), C.c_int32()
-                L.check(L.lib().mtsamd_scene_texture_info(scene._handle, idx, C.byref(w), C.byref(h), C.byref(off)))
-                grads.append(g_tex[off.value: off.value + 3 * w.value * h.value].reshape(h.value, w.value, 3).clone())
+                grads.append(_texture_slice(scene, g_tex, idx))
         return (None, None, None, None) + tuple(grads)
 
 

@@ -345,6 +345,20 @@ static void gauss_legendre(int n, float *nodes, float *weights) {
     }
 }
 
+// Spectral variant: bitmap texels -> model coefficients (bitmap.cpp:116-123) and their Jacobians, 9 floats per texel at 3 * grad_offset
+// of `jac`; returns the sum of srgb_model_mean over the texels (Texture::mean() times their number)
+static double spectral_texels(const Rgb2Spec &model, const float *rgb, size_t n_texels, std::vector<float> &coeffs, std::vector<float> &jac, uint32_t grad_offset) {
+    coeffs.resize(3 * n_texels);
+    if (jac.size() < 3 * (size_t) grad_offset + 9 * n_texels) jac.resize(3 * (size_t) grad_offset + 9 * n_texels, 0.0f);
+    double mean = 0.0;
+    for (size_t i = 0; i < n_texels; ++i) {
+        srgb_model_fetch(model, rgb + 3 * i, coeffs.data() + 3 * i);
+        srgb_model_fetch_jacobian(model, rgb + 3 * i, jac.data() + 3 * (size_t) grad_offset + 9 * i);
+        mean += (double) srgb_model_mean(coeffs.data() + 3 * i);
+    }
+    return mean;
+}
+
 struct mtsamd_scene {
     int32_t environment = -1;        // index of the `constant` emitter
     bool general_bsdfs = false;      // any BSDF other than one-sided `diffuse`: the kernels with the BSDF switch are used
@@ -372,6 +386,12 @@ struct mtsamd_scene {
     std::vector<float> spec_mean;           // per BSDF: mean of specular_reflectance
     std::vector<float> diff_mean;           // spectral variant, per BSDF: Texture::mean() of a constant reflectance
     Rgb2Spec rgb2spec;                      // spectral variant: the upsampling model, kept for parameter updates
+    // spectral variant: d(model coefficients) / d(rgb) (srgb_model_fetch_jacobian) of every constant reflectance (9 floats per BSDF) and of
+    // every bitmap texel (9 floats per texel, at 3 * grad_offset), recomputed whenever a colour is converted; d_jac = [bsdfs | texels] on
+    // the device (uploaded by mtsamd_render_adjoint_spectral when `jac_dirty`), d_cgrad = its coefficient-gradient scratch (3 floats each)
+    std::vector<float> jac_bsdf, jac_tex;
+    float *d_jac = nullptr, *d_cgrad = nullptr;
+    bool jac_dirty = true;
     DevTexture *d_textures = nullptr;
     SceneView view{};
     bool spectral = false;
@@ -404,7 +424,7 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
     (void) hipFree(s->d_area_pmf); (void) hipFree(s->d_area_cdf); (void) hipFree(s->d_rough_tables);
     (void) hipFree(s->d_env_texels); (void) hipFree(s->d_env_warp); (void) hipFree(s->d_envmap); (void) hipFree(s->d_flat); (void) hipFree(s->d_pairs);
     for (auto &t : s->textures) (void) hipFree((void *) t.data);
-    (void) hipFree(s->d_textures);
+    (void) hipFree(s->d_textures); (void) hipFree(s->d_jac); (void) hipFree(s->d_cgrad);
     delete s;
 }
 
@@ -648,6 +668,10 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
                 srgb_model_fetch(model, c, coeff);
                 coeffs[p][0] = coeff[0]; coeffs[p][1] = coeff[1]; coeffs[p][2] = coeff[2];
                 means[p] = srgb_model_mean(coeff);
+                if (p == 0) {
+                    s->jac_bsdf.resize(9 * (size_t) desc->bsdf_count, 0.0f);
+                    srgb_model_fetch_jacobian(model, c, s->jac_bsdf.data() + 9 * (size_t) b);
+                }
             }
             if (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic) d.kr = means[1] / (means[0] + means[1]);
             spec_mean[b] = means[1];
@@ -693,11 +717,7 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
         const float *src = td.data;
         double mean = 0.0;
         if (desc->spectral) {
-            coeffs.resize(3 * n_texels);
-            for (size_t i = 0; i < n_texels; ++i) {
-                srgb_model_fetch(model, td.data + 3 * i, coeffs.data() + 3 * i);
-                mean += (double) srgb_model_mean(coeffs.data() + 3 * i);
-            }
+            mean = spectral_texels(model, td.data, n_texels, coeffs, s->jac_tex, dt.grad_offset);
             src = coeffs.data();
         } else {
             for (size_t i = 0; i < n_texels; ++i) {
@@ -959,7 +979,12 @@ static int spectral_set_colour(mtsamd_scene *s, uint32_t bsdf, int p, const floa
     srgb_model_fetch(s->rgb2spec, rgb, coeff);
     float *dst = p == 0 ? &d.c0 : (p == 1 ? &d.sc0 : &d.tc0);
     dst[0] = coeff[0]; dst[1] = coeff[1]; dst[2] = coeff[2];
-    if (p == 0) { d.r = rgb[0]; d.g = rgb[1]; d.b = rgb[2]; s->diff_mean[bsdf] = srgb_model_mean(coeff); }
+    if (p == 0) {
+        d.r = rgb[0]; d.g = rgb[1]; d.b = rgb[2]; s->diff_mean[bsdf] = srgb_model_mean(coeff);
+        s->jac_bsdf.resize(9 * s->bsdfs.size(), 0.0f);
+        srgb_model_fetch_jacobian(s->rgb2spec, rgb, s->jac_bsdf.data() + 9 * (size_t) bsdf);
+        s->jac_dirty = true;
+    }
     if (p == 1) { d.sr = rgb[0]; d.sg = rgb[1]; d.sb = rgb[2]; s->spec_mean[bsdf] = srgb_model_mean(coeff); }
     if (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic) {
         const float d_mean = d.texture >= 0 ? s->textures[d.texture].mean : s->diff_mean[bsdf];
@@ -998,7 +1023,24 @@ int mtsamd_scene_update_texture(mtsamd_scene *s, uint32_t texture, const float *
     HIP_TRY(hipSetDevice(s->device));
     const DevTexture &t = s->textures[texture];
     if (t.kind != 0) return fail(MTSAMD_ERR_INVALID, "texture %u is not a bitmap", texture);
-    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "texture updates are implemented for the RGB variant only (the texels hold model coefficients)");
+    if (s->spectral) {       // the texels hold model coefficients: converted on the host as mtsamd_scene_create does, after the clamp of an srgb colour
+        const size_t n_texels = (size_t) t.w * t.h;
+        std::vector<float> host(3 * n_texels), coeffs;
+        HIP_TRY(hipStreamSynchronize((hipStream_t) stream));          // whatever writes `rgb`, and the renders that read the old texels
+        HIP_TRY(hipMemcpy(host.data(), rgb, host.size() * sizeof(float), hipMemcpyDefault));
+        for (float &v : host) v = std::max(std::min(v, 1.0f), 0.0f);
+        const double mean = spectral_texels(s->rgb2spec, host.data(), n_texels, coeffs, s->jac_tex, t.grad_offset);
+        s->jac_dirty = true;
+        HIP_TRY(hipMemcpy((void *) t.data, coeffs.data(), coeffs.size() * sizeof(float), hipMemcpyHostToDevice));
+        s->textures[texture].mean = (float) (mean / (double) n_texels);
+        for (size_t b = 0; b < s->bsdfs.size(); ++b) {       // parameters_changed(): the plastic lobe weights read the mean
+            DevBsdf &d = s->bsdfs[b];
+            if (d.texture != (int32_t) texture || (d.type != kBsdfPlastic && d.type != kBsdfRoughPlastic)) continue;
+            d.kr = s->spec_mean[b] / (s->textures[texture].mean + s->spec_mean[b]);
+            HIP_TRY(hipMemcpy(s->d_bsdfs + b, &d, sizeof(DevBsdf), hipMemcpyHostToDevice));
+        }
+        return MTSAMD_OK;
+    }
     HIP_TRY(hipMemcpyAsync((void *) t.data, rgb, sizeof(float) * 3 * (size_t) t.w * t.h, hipMemcpyDefault, (hipStream_t) stream));
     // parameters_changed() (bitmap.cpp:308-322): the mean follows the data; only plastic lobe weights read it
     bool used = false;
@@ -1989,11 +2031,12 @@ int mtsamd_sample_aovs(mtsamd_scene *s, const mtsamd_render_desc *d_, const int3
 }
 
 // sensor / sampler / film part of an adjoint launch: the whole crop window of `d`, the primal film's weights, dLoss/dImage
-static int fill_adjoint(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, AdjointParams &a) {
+static int fill_adjoint(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, AdjointParams &a, bool spectral = false) {
     if (!s || !dimage || !film) return fail(MTSAMD_ERR_INVALID, "null argument");
     if (int rc = check_desc(d)) return rc;
     if (d->part_count > 1 || d->row_begin != 0 || d->row_end > 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass renders the whole crop window");
-    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass is implemented for the RGB variant only");
+    if (s->spectral && !spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass is implemented for the RGB variant only");
+    if (!s->spectral && spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint pass needs a scene of the spectral variant");
     HIP_TRY(hipSetDevice(s->device));
     if (int rc = make_camera(*d, a.rp.cam)) return rc;
     if (int rc = make_filter(d->rfilter, d->rfilter_param, d->rfilter_param2, d->rfilter_analytic, a.filter)) return rc;
@@ -2130,6 +2173,49 @@ int mtsamd_render_adjoint_textures(mtsamd_scene *s, const mtsamd_render_desc *d,
     return MTSAMD_OK;
 }
 
+int mtsamd_render_adjoint_spectral(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, float *grad_bsdf,
+                                   float *grad_tex, void *stream_) {
+    AdjointParams a{};
+    if (int rc = fill_adjoint(s, d, dimage, film, a, true)) return rc;
+    if (d->max_depth < 1 || d->max_depth > 16)
+        return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle blendbsdf / mask materials");
+    if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
+    if (s->bsdfs.size() > 32 && grad_bsdf) return fail(MTSAMD_ERR_UNSUPPORTED, "at most 32 BSDFs with constant-reflectance gradients");
+    if (!grad_bsdf && !grad_tex) return MTSAMD_OK;
+    hipStream_t stream = (hipStream_t) stream_;
+    // coefficient gradients and Jacobians: [BSDF records | texels of all bitmaps in the texture-gradient layout]
+    const size_t n_bsdf = s->bsdfs.size();
+    const size_t n_texels = s->textures.empty() ? 0 : (s->textures.back().grad_offset + 3u * (size_t) s->textures.back().w * s->textures.back().h) / 3u;
+    const size_t n_colours = n_bsdf + n_texels;
+    if (!s->d_jac) { HIP_TRY(hipMalloc((void **) &s->d_jac, 9 * n_colours * sizeof(float))); s->jac_dirty = true; }
+    if (!s->d_cgrad) HIP_TRY(hipMalloc((void **) &s->d_cgrad, 3 * n_colours * sizeof(float)));
+    if (s->jac_dirty) {
+        s->jac_bsdf.resize(9 * n_bsdf, 0.0f); s->jac_tex.resize(9 * n_texels, 0.0f);
+        // d(c0, c1, c2) / d rgb -> d(a, b, c) / d rgb of the centred basis the kernel accumulates in: l = m + h u gives
+        // a = h^2 c0, b = 2 m h c0 + h c1, c = m^2 c0 + m c1 + c2
+        std::vector<float> centred(9 * n_colours);
+        const double m = kCoeffMid, h = kCoeffHalf;
+        for (size_t i = 0; i < 3 * n_colours; ++i) {
+            const float *j = i < 3 * n_bsdf ? s->jac_bsdf.data() + 3 * i : s->jac_tex.data() + 3 * (i - 3 * n_bsdf);
+            centred[3 * i] = (float) (h * h * j[0]);
+            centred[3 * i + 1] = (float) (2.0 * m * h * j[0] + h * j[1]);
+            centred[3 * i + 2] = (float) (m * m * j[0] + m * j[1] + j[2]);
+        }
+        HIP_TRY(hipStreamSynchronize(stream));               // an earlier launch may still read the old Jacobians
+        HIP_TRY(hipMemcpy(s->d_jac, centred.data(), centred.size() * sizeof(float), hipMemcpyHostToDevice));
+        s->jac_dirty = false;
+    }
+    HIP_TRY(hipMemsetAsync(s->d_cgrad, 0, 3 * n_colours * sizeof(float), stream));
+    a.grad_bsdf = grad_bsdf ? s->d_cgrad : nullptr;
+    a.grad_tex = grad_tex && n_texels ? s->d_cgrad + 3 * n_bsdf : nullptr;
+    a.rp.spectral = 1;
+    HIP_TRY(launch_adjoint_spectral(a, stream));
+    if (a.grad_bsdf) HIP_TRY(launch_coeff_grad_to_rgb(s->d_cgrad, s->d_jac, grad_bsdf, (uint32_t) n_bsdf, stream));
+    if (a.grad_tex) HIP_TRY(launch_coeff_grad_to_rgb(s->d_cgrad + 3 * n_bsdf, s->d_jac + 9 * n_bsdf, grad_tex, (uint32_t) n_texels, stream));
+    return MTSAMD_OK;
+}
+
 int mtsamd_scene_update_envmap(mtsamd_scene *s, const float *rgb, int32_t rebuild_distribution) {
     if (!s || !rgb) return fail(MTSAMD_ERR_INVALID, "null argument");
     if (s->environment < 0 || !s->d_envmap) return fail(MTSAMD_ERR_UNSUPPORTED, "the scene has no envmap emitter");
@@ -2159,15 +2245,30 @@ int mtsamd_rgb2spec_build(const char *path, int32_t resolution, int32_t threads)
     return MTSAMD_OK;
 }
 
-int mtsamd_srgb_model_fetch(const char *path, const float *rgb, float *coeff) {
-    if (!path || !rgb || !coeff) return fail(MTSAMD_ERR_INVALID, "null argument");
+// the model of the host-only lookups below, loaded once per thread and path (null: could not be loaded)
+static const Rgb2Spec *cached_model(const char *path) {
     static thread_local std::string cached_path;
     static thread_local Rgb2Spec cached;
     if (cached_path != path) {
-        if (!rgb2spec_load(path, cached)) { cached_path.clear(); return fail(MTSAMD_ERR_INVALID, "Could not load sRGB-to-spectrum upsampling model ('%s')", path); }
+        if (!rgb2spec_load(path, cached)) { cached_path.clear(); fail(MTSAMD_ERR_INVALID, "Could not load sRGB-to-spectrum upsampling model ('%s')", path); return nullptr; }
         cached_path = path;
     }
-    srgb_model_fetch(cached, rgb, coeff);
+    return &cached;
+}
+
+int mtsamd_srgb_model_fetch(const char *path, const float *rgb, float *coeff) {
+    if (!path || !rgb || !coeff) return fail(MTSAMD_ERR_INVALID, "null argument");
+    const Rgb2Spec *m = cached_model(path);
+    if (!m) return MTSAMD_ERR_INVALID;
+    srgb_model_fetch(*m, rgb, coeff);
+    return MTSAMD_OK;
+}
+
+int mtsamd_srgb_model_fetch_jacobian(const char *path, const float *rgb, float *jac) {
+    if (!path || !rgb || !jac) return fail(MTSAMD_ERR_INVALID, "null argument");
+    const Rgb2Spec *m = cached_model(path);
+    if (!m) return MTSAMD_ERR_INVALID;
+    srgb_model_fetch_jacobian(*m, rgb, jac);
     return MTSAMD_OK;
 }
 

@@ -527,6 +527,57 @@ MTS_DEV float plastic_diffuse_drefl(const DevBsdf &b, float refl) {       // d p
     }
     return 1.0f / (1.0f - b.eb);
 }
+// d BSDF::eval / d refl at (wi, wo): bsdf_eval_pdf_n above, differentiated, on N channels (the spectral replay: k_adjoint_spectral)
+template <int N>
+MTS_DEV void bsdf_dvalue_drefl_n(const DevBsdf &b, const float (&refl)[N], f3 wi, f3 wo, float (&out)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = 0.0f;
+    if (b.flags & kBsdfTwoSided) {
+        if (wi.z == 0.0f) return;
+        if (wi.z < 0.0f) { wi.z = -wi.z; wo.z = -wo.z; }
+    }
+    const float cos_theta_i = wi.z, cos_theta_o = wo.z;
+    if (!(cos_theta_i > 0.0f && cos_theta_o > 0.0f)) return;
+    if (b.type == kBsdfDiffuse) {
+        const float k = kInvPi * wo.z;
+#pragma unroll
+        for (int i = 0; i < N; ++i) out[i] = k;
+        return;
+    }
+    float k;
+    if (b.type == kBsdfPlastic) {
+        const float f_i = fresnel(cos_theta_i, b.er).r, f_o = fresnel(cos_theta_o, b.er).r;
+        k = (kInvPi * wo.z) * b.eg * (1.0f - f_i) * (1.0f - f_o);
+    } else if (b.type == kBsdfRoughPlastic) {
+        const float t_i = lerp_gather(b.table, cos_theta_i, kRoughTableRes), t_o = lerp_gather(b.table, cos_theta_o, kRoughTableRes);
+        k = kInvPi * b.eg * cos_theta_o * t_i * t_o;
+    } else {
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = plastic_diffuse_drefl(b, refl[i]) * k;
+}
+// d weight / d refl of a sample of bsdf_sample_n at its direction: `diffuse` samples weight = refl (1); the diffuse lobe of plastic and
+// both lobes of roughplastic weigh value / pdf with the pdf detached (d value / d refl / pdf); delta lobes carry no reflectance term
+template <int N>
+MTS_DEV void bsdf_dweight_drefl_n(const DevBsdf &b, const float (&refl)[N], f3 wi, const BsdfSample &bs, float (&out)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = 0.0f;
+    if (bs.delta || !(bs.pdf > 0.0f)) return;
+    if (b.type == kBsdfDiffuse) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) out[i] = 1.0f;
+        return;
+    }
+    if (b.type != kBsdfPlastic && b.type != kBsdfRoughPlastic) return;
+    bsdf_dvalue_drefl_n<N>(b, refl, wi, bs.wo, out);
+    const float ip = 1.0f / bs.pdf;
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] *= ip;
+}
+// RGB variant (k_adjoint_tex).  The same closed forms a second time, on purpose: written as wrappers of the templates above, these two
+// functions made both k_adjoint_tex kernels assemble to different register numbers (profiles/r09_isa_identity_spectral.txt), and the
+// existing kernels are to stay bit for bit what they were.  A change to one pair belongs in the other.
 // d BSDF::eval / d refl at (wi, wo): bsdf_eval_pdf_n above, differentiated
 MTS_DEV f3 bsdf_dvalue_drefl(const DevBsdf &b, f3 refl, f3 wi, f3 wo) {
     const f3 zero = mk3(0.0f, 0.0f, 0.0f);

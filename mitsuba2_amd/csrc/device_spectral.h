@@ -56,6 +56,18 @@ MTS_DEV float table_eval(const float *tbl, float scale, float l) {
     return fmaf(w0, y0, w1 * y1);
 }
 
+// cie1931_xyz (spectrum.h:127-163): the observer's colour matching functions at wavelength l, the table interpolation of spectrum_to_xyz
+// below (which keeps its own copy: folding it into this helper changed the machine code of the render kernels)
+MTS_DEV f3 cie1931_xyz(float l) {
+    float t = (l - kCieMin) * ((95 - 1) / (kCieMax - kCieMin));
+    bool active = l >= kCieMin && l <= kCieMax;
+    int i0 = min(max((int) t, 0), 93);
+    float w1 = t - (float) i0, w0 = 1.0f - w1;
+    return mk3(active ? fmaf(w0, g_spectral.x[i0], w1 * g_spectral.x[i0 + 1]) : 0.0f,
+               active ? fmaf(w0, g_spectral.y[i0], w1 * g_spectral.y[i0 + 1]) : 0.0f,
+               active ? fmaf(w0, g_spectral.z[i0], w1 * g_spectral.z[i0 + 1]) : 0.0f);
+}
+
 MTS_DEV f3 spectrum_to_xyz(const Spec4 &value, const Spec4 &wav) {
     float X[kWav], Y[kWav], Z[kWav];
 #pragma unroll

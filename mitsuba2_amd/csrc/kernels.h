@@ -203,6 +203,12 @@ hipError_t launch_adjoint(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_env(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_param(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s);      // k_adjoint_tex: into grad_tex (not null)
+// k_adjoint_spectral accumulates in the coefficients (a, b, c) of x = a u^2 + b u + c over the centred wavelength u = (l - kCoeffMid) / kCoeffHalf
+constexpr float kCoeffMid = 595.0f, kCoeffHalf = 235.0f;
+// k_adjoint_spectral: gradients w.r.t. the srgb MODEL COEFFICIENTS (centred basis) of the reflectance family, into grad_bsdf / grad_tex (either may be null)
+hipError_t launch_adjoint_spectral(const AdjointParams &a, hipStream_t s);
+// out[i] += J_i^T cgrad[i] for n colours (3 floats each): jac[9 i + 3 c + j] = d coeff_j / d rgb_c (centred basis)
+hipError_t launch_coeff_grad_to_rgb(const float *cgrad, const float *jac, float *out, uint32_t n, hipStream_t s);
 // end of a pass: every path of p.in (counts p.count_in) is run to its end in one launch; needs dry sample cursors (kernels.hip, k_finish)
 hipError_t launch_finish(const RenderParams &p, uint64_t alive, hipStream_t s);
 hipError_t launch_mega(const RenderParams &p, hipStream_t s);      // small passes: the whole pass in one launch of persistent lanes

@@ -469,8 +469,10 @@ MTS_DEV Spec4 envmap_lookup_spectral(const DevEnvmap &e, float u, float v, const
     return r;
 }
 // textured reflectance in the spectral variant: bitmap texels hold srgb model coefficients, evaluated at the four corners and
-// then interpolated (bitmap.cpp:274-286); checkerboard colours are `srgb` spectra (checkerboard.cpp:46-63)
-MTS_DEV Spec4 eval_reflectance_spectral(const SceneView &sv, const DevBsdf &b, f2 uv, const Spec4 &wav) {
+// then interpolated (bitmap.cpp:274-286); checkerboard colours are `srgb` spectra (checkerboard.cpp:46-63).  texel, w1: the bilinear
+// footprint of a bitmap lookup, as eval_reflectance hands it out (kNoPrim: a checkerboard)
+MTS_DEV Spec4 eval_reflectance_spectral(const SceneView &sv, const DevBsdf &b, f2 uv, const Spec4 &wav, uint32_t &texel, f2 &w1) {
+    texel = kNoPrim; w1.x = w1.y = 0.0f;
     const DevTexture t = sv.textures[b.texture];
     {
         const float u2 = fmaf(t.uvm[0], uv.x, fmaf(t.uvm[1], uv.y, t.uvm[2])), v2 = fmaf(t.uvm[3], uv.x, fmaf(t.uvm[4], uv.y, t.uvm[5]));
@@ -489,6 +491,7 @@ MTS_DEV Spec4 eval_reflectance_spectral(const SceneView &sv, const DevBsdf &b, f
     ux *= (float) (uint32_t) (t.w - 1); uy *= (float) (uint32_t) (t.h - 1);
     const uint32_t px = min((uint32_t) ux, (uint32_t) (t.w - 2)), py = min((uint32_t) uy, (uint32_t) (t.h - 2));
     const float w1x = ux - (float) px, w1y = uy - (float) py, w0x = 1.0f - w1x, w0y = 1.0f - w1y;
+    texel = px + py * (uint32_t) t.w; w1.x = w1x; w1.y = w1y;
     const float *v00 = t.data + 3u * (size_t) (px + py * (uint32_t) t.w), *v01 = v00 + 3u * (size_t) t.w;
 #pragma unroll
     for (int k = 0; k < kWav; ++k) {
@@ -508,9 +511,36 @@ MTS_DEV Spec4 emitter_spectrum(const SceneView &sv, const DevEmitter &e, const S
     return r;
 }
 
-template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false>
-MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c, Deferred *df = nullptr) {
+// What the emitter-sampling block of the spectral step shows a probe: the sample adds ((mis * thr) * bv) * spec per wavelength if it is unoccluded.
+struct NeeTermsS {
+    const DirectionSample &ds; f3 wi, wo;     // local directions as the BSDF models take them (they mirror a `twosided` record themselves)
+    Spec4 bv, spec; float mis;
+};
+
+// The probe of the spectral step: the hooks of NoProbe (bounce_step) in the same order, on four wavelengths.  NoProbeS, the probe of
+// every spectral render kernel, sees nothing: the step spells out a hook and what it builds for it only for another probe (kWatch
+// there), because even the unused per-wavelength copies changed the machine code of the render kernels (scripts/isa_compare.py).
+struct NoProbeS {
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathStateS &s) { }
+    MTS_DEV void emitted(float ew, int32_t emitter, const Spec4 &le) { }
+    MTS_DEV void escaped(const SceneView &sv, const PathStateS &s, const DevEmitter &e, float ew, const Spec4 &le) { }
+    // thr before the division by q = 1 / rq, hm = hmax(thr); `free`: q was not clamped to .95
+    MTS_DEV void roulette(const Spec4 &thr, float hm, float rq, bool free) { }
+    // the reflectance spectrum `refl` of the record was evaluated (texel, tw1: footprint of a bitmap lookup, whose four corner
+    // coefficient triples the probe re-reads from sv.textures[bsdf.texture]); thr after roulette
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, const Spec4 &refl, uint32_t texel, f2 tw1, const Spec4 &thr) { }
+    MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &bsdf, const Spec4 &refl, const NeeTermsS &t) { return false; }
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &si, const Spec4 &thr, const NeeTermsS &t) { }
+    // the general step drew the BSDF sample `bs`; thr before it is multiplied by `weight`
+    MTS_DEV void bsdf_sampled(const SceneView &sv, const SurfaceInteraction &si, const DevBsdf &bsdf, const Spec4 &refl, const Spec4 &thr, const BsdfSample &bs,
+                              const float (&weight)[kWav]) { }
+};
+
+template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false, class Probe = NoProbeS>
+MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c, Deferred *df = nullptr, Probe &&probe = Probe{}) {
+    constexpr bool kWatch = !std::is_same_v<std::remove_reference_t<Probe>, NoProbeS>;
     const SceneView &sv = P.sv;
+    if constexpr (kWatch) probe.template begin<DEFER, GENERAL, NEST>(s);
     const Geo<FLAT> geo{ sv, lds };
     Hit hit;
     ++c.closest; ++c.segments;
@@ -536,11 +566,14 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
                 ew = mis_weight(s.bs_pdf, (GENERAL && (s.flags & kFlagDelta)) ? 0.0f : pe);
             }
             if (si.wi.z > 0.0f) {
+                Spec4 le4;
 #pragma unroll
                 for (int k = 0; k < kWav; ++k) {       // SRGBEmitterSpectrum::eval = d65 * srgb_model_eval (srgb_d65.cpp:54-62)
                     float le = table_eval(g_spectral.d65, e.d65_scale, s.wav.v[k]) * srgb_model_eval(e.c0, e.c1, e.c2, s.wav.v[k]);
                     s.res.v[k] += (ew * s.thr.v[k]) * le;
+                    if constexpr (kWatch) le4.v[k] = le;
                 }
+                if constexpr (kWatch) probe.emitted(ew, emitter, le4);
             }
         }
     }
@@ -553,6 +586,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
         const Spec4 le = emitter_spectrum(sv, e, s.wav, uv);
 #pragma unroll
         for (int k = 0; k < kWav; ++k) s.res.v[k] += (ew * s.thr.v[k]) * le.v[k];
+        if constexpr (kWatch) probe.escaped(sv, s, e, ew, le);
     }
     bool active = found;
 
@@ -561,6 +595,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
         float q = fminf(hm * (s.eta * s.eta), 0.95f);
         if (active) active = pcg_next_f32(s.rng) < q;
         float rq = rcp(q);
+        if constexpr (kWatch) probe.roulette(s.thr, hm, rq, hm * (s.eta * s.eta) < 0.95f);
 #pragma unroll
         for (int k = 0; k < kWav; ++k) s.thr.v[k] *= rq;
     }
@@ -571,7 +606,9 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
 #pragma unroll
     for (int k = 0; k < kWav; ++k)       // srgb.cpp:45-52 / uniform.cpp
         refl.v[k] = (bsdf.flags & kBsdfUniformRefl) ? bsdf.r : srgb_model_eval(bsdf.c0, bsdf.c1, bsdf.c2, s.wav.v[k]);
-    if (bsdf.texture >= 0) refl = eval_reflectance_spectral(sv, bsdf, si.uv, s.wav);
+    uint32_t texel = kNoPrim; f2 tw1; tw1.x = tw1.y = 0.0f;
+    if (bsdf.texture >= 0) refl = eval_reflectance_spectral(sv, bsdf, si.uv, s.wav, texel, tw1);
+    if constexpr (kWatch) probe.surface(si, bsdf, refl, texel, tw1, s.thr);
     BsdfChannels<kWav> chan;
     if (GENERAL) {
         chan = spectral_channels(bsdf, s.wav);
@@ -597,6 +634,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
             if (GENERAL) surface_bsdf_eval_pdf<NEST, kWav>(bsdf, ni, [&](uint32_t i) { return geo.bsdf(i); }, chan_of, si.wi, wo, bvs, bp);
             float mis = (GENERAL && ds.delta) ? 1.0f : mis_weight(ds.pdf, bp);
             Spec4 contrib; bool nz = false;
+            Spec4 bv4, spec4;                   // for the probe
             const Spec4 le4 = emitter_spectrum(sv, e, s.wav, ds.uv);
 #pragma unroll
             for (int k = 0; k < kWav; ++k) {
@@ -606,7 +644,11 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
                 float bv = GENERAL ? bvs[k] : (front ? (refl.v[k] * kInvPi) * wo.z : 0.0f);
                 contrib.v[k] = ((mis * s.thr.v[k]) * bv) * spec;
                 nz = nz || contrib.v[k] != 0.0f;
+                if constexpr (kWatch) { bv4.v[k] = bv; spec4.v[k] = spec; }
             }
+            auto nee = [&] { return NeeTermsS{ ds, si.wi, wo, bv4, spec4, mis }; };
+            bool watched = false;
+            if constexpr (kWatch) watched = probe.emitter_sample(sv, bsdf, refl, nee());
             if (DEFER) {
                 if (nz) {
                     ++c.any;
@@ -615,7 +657,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
 #pragma unroll
                     for (int k = 0; k < kWav; ++k) df->nee[k] = contrib.v[k];
                 }
-            } else if (nz) {
+            } else if (nz || watched) {
                 Hit sh;
                 ++c.any;
                 bool occluded = traverse<FLAT, true>(sv, lds, si.p, ds.d, kRayEpsilon * (1.0f + hmax_abs(si.p)),
@@ -623,6 +665,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
                 if (!occluded) {
 #pragma unroll
                     for (int k = 0; k < kWav; ++k) s.res.v[k] += contrib.v[k];
+                    if constexpr (kWatch) probe.unoccluded(sv, si, s.thr, nee());
                 }
             }
         }
@@ -638,6 +681,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
         wo = bs.wo; pdf = bs.pdf;
         s.eta *= bs.eta;
         s.flags = bs.delta ? (s.flags | kFlagDelta) : (s.flags & ~kFlagDelta);
+        if constexpr (kWatch) probe.bsdf_sampled(sv, si, bsdf, refl, s.thr, bs, w);
 #pragma unroll
         for (int k = 0; k < kWav; ++k) { s.thr.v[k] = s.thr.v[k] * w[k]; nz = nz || s.thr.v[k] != 0.0f; }
     } else {
@@ -659,7 +703,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
     return true;
 }
 
-MTS_DEV void generate_path_spectral(const RenderParams &P, uint64_t ordinal, uint32_t lp, uint32_t j, PathStateS &s) {
+MTS_DEV void generate_path_spectral(const RenderParams &P, uint64_t ordinal, uint32_t lp, uint32_t j, PathStateS &s, float2 *pos_out = nullptr) {
     const uint32_t w = (uint32_t) P.crop_w;
     const uint32_t lr = lp / w, px = lp - lr * w;
     const uint32_t py = (uint32_t) row_to_global(P.rows, (int32_t) lr);
@@ -679,6 +723,7 @@ MTS_DEV void generate_path_spectral(const RenderParams &P, uint64_t ordinal, uin
     s.ordinal = P.plane_pixels ? j * P.plane_pixels + (lp - P.plane_pix0) : (uint32_t) (ordinal - P.first_ordinal);
     s.depth = 1u; s.flags = 0u;
     if (P.out_pos) P.out_pos[s.ordinal] = make_float2(psx, psy);
+    if (pos_out) *pos_out = make_float2(psx, psy);
 }
 
 MTS_DEV void store_result_spectral(const RenderParams &P, const PathStateS &s) {
@@ -2159,6 +2204,179 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_tex(const AdjointParams A) {
 }
 
 hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_tex<true>, k_adjoint_tex<false>>(a, s); }
+
+// ---------------------------------------------------------------------------------------------
+// Spectral variant: derivative w.r.t. the reflectance family -- diffuse.reflectance and (rough)plastic.diffuse_reflectance, as a constant
+// srgb colour or as bitmap texels -- in ANY spectral scene.  One thread replays one camera sample through the general spectral step with
+// the PCG32 stream of the primal pass, records its vertices and sweeps them backwards on the four wavelengths, as k_adjoint_tex does on
+// three channels:   g_refl_v = T'_v (delta dNc_v + a dW_v),   b_v = delta Nc_v + W_v a,   dL/dT_v = delta E_v + invq_v b_v.
+// ALL sampling is detached: directions, pdfs, lobe choices, MIS weights, the plastic lobe weight kr AND the roulette probability q are
+// held fixed (only invq is recorded; there is no rr_channel term).  k_adjoint and k_adjoint_tex follow Enoki's attached roulette
+// instead; any fixed q keeps the estimator unbiased, so the detached form estimates the true derivative of the image -- what central
+// differences of the rendered image estimate too, and what tests/test_gpu_adjoint_spectral.py checks statistically.
+// The film channels of the spectral variant are X, Y, Z (store_result_spectral), so the sweep is seeded per wavelength with
+//   delta_k = wavelength_weight(l_k) / 4 * (xbar(l_k) dX + ybar(l_k) dY + zbar(l_k) dZ).
+// The reflectance spectrum is S(x) = 1/2 + x / (2 sqrt(1 + x^2)), x = c0 l^2 + c1 l + c2 (srgb_model_eval): g_refl goes on to the model
+// coefficients with dS/dc = (1 + x^2)^(-3/2) / 2 * (l^2, l, 1) and k_coeff_grad_to_rgb takes the coefficient gradients to RGB.
+struct VertexRecS {
+    Spec4 T, E, Nc, W, dNc, dW;     // as VertexRecG, per wavelength
+    float invq; uint32_t texel; f2 w1;
+    int32_t bsdf;                   // record whose reflectance is differentiated at this vertex (-1: none)
+};
+
+struct SpectralRecorder {
+    VertexRecS &r;
+    bool diff; Spec4 nc, dnc;       // Nc and dNc / d(refl) of the emitter sample, recorded once it is known to be unoccluded
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathStateS &s) {
+        static_assert(GENERAL && DEFER == 0 && !NEST, "the spectral adjoint replay runs the plain general fused step");
+        r.T = s.thr; r.invq = 1.0f; r.texel = kNoPrim; r.w1.x = r.w1.y = 0.0f; r.bsdf = -1;
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) r.E.v[k] = r.Nc.v[k] = r.W.v[k] = r.dNc.v[k] = r.dW.v[k] = 0.0f;
+    }
+    MTS_DEV void emitted(float ew, int32_t, const Spec4 &le) {
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) r.E.v[k] = ew * le.v[k];
+    }
+    MTS_DEV void escaped(const SceneView &, const PathStateS &, const DevEmitter &, float ew, const Spec4 &le) { emitted(ew, -1, le); }
+    MTS_DEV void roulette(const Spec4 &, float, float rq, bool) { r.invq = rq; }
+    // an srgb colour or a bitmap of the reflectance family (uniform spectra and checkerboards have no RGB parameter here)
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, const Spec4 &, uint32_t texel, f2 tw1, const Spec4 &) {
+        diff = (bsdf.type == kBsdfDiffuse || bsdf.type == kBsdfPlastic || bsdf.type == kBsdfRoughPlastic) && !(bsdf.flags & kBsdfUniformRefl) &&
+               (bsdf.texture < 0 || texel != kNoPrim);
+        r.texel = texel; r.w1 = tw1; r.bsdf = diff ? si.shape_rec.bsdf : -1;
+    }
+    MTS_DEV bool emitter_sample(const SceneView &, const DevBsdf &bsdf, const Spec4 &refl, const NeeTermsS &t) {
+        float dbv[kWav];
+        bsdf_dvalue_drefl_n<kWav>(bsdf, refl.v, t.wi, t.wo, dbv);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) {
+            nc.v[k] = (t.mis * t.bv.v[k]) * t.spec.v[k];
+            dnc.v[k] = diff ? (t.mis * dbv[k]) * t.spec.v[k] : 0.0f;
+            any = any || nc.v[k] != 0.0f || dnc.v[k] != 0.0f;
+        }
+        return any;
+    }
+    MTS_DEV void unoccluded(const SceneView &, const SurfaceInteraction &, const Spec4 &, const NeeTermsS &) { r.Nc = nc; r.dNc = dnc; }
+    MTS_DEV void bsdf_sampled(const SceneView &, const SurfaceInteraction &si, const DevBsdf &bsdf, const Spec4 &refl, const Spec4 &, const BsdfSample &bs,
+                              const float (&weight)[kWav]) {
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) r.W.v[k] = weight[k];
+        if (diff) bsdf_dweight_drefl_n<kWav>(bsdf, refl.v, si.wi, bs, r.dW.v);
+    }
+};
+
+// acc += sum_k g[k] dS/dc(c, l_k): zero for the black / white sentinels (c2 = -+inf) and where srgb_model_eval clamps at 0.
+// The sums are kept in the basis (u^2, u, 1) of the centred wavelength u = (l - kCoeffMid) / kCoeffHalf in [-1, 1], i.e. as the gradient
+// w.r.t. (a, b, c) of x = a u^2 + b u + c: in (l^2, l, 1) with l in nanometres the three float32 sums cancel tenfold when the Jacobian
+// recombines them.  The Jacobians on the device are composed with d(a, b, c) / d(c0, c1, c2) to match (mtsamd_render_adjoint_spectral).
+MTS_DEV void model_coeff_grad(const float *c, const Spec4 &wav, const float (&g)[kWav], float (&acc)[3]) {
+    const float c0 = c[0], c1 = c[1], c2 = c[2];
+    if (isinf(c2)) return;
+#pragma unroll
+    for (int k = 0; k < kWav; ++k) {
+        const float l = wav.v[k];
+        const float x = fmaf(fmaf(c0, l, c1), l, c2);
+        const float t = 1.0f / sqrtf(fmaf(x, x, 1.0f));
+        if (!(fmaf(0.5f * x, t, 0.5f) > 0.0f)) continue;
+        const float d = ((0.5f * t) * (t * t)) * g[k], u = (l - kCoeffMid) * (1.0f / kCoeffHalf);
+        acc[0] = fmaf(d * u, u, acc[0]); acc[1] = fmaf(d, u, acc[1]); acc[2] += d;
+    }
+}
+
+template <bool FLAT>
+__global__ __launch_bounds__(kBlock) void k_adjoint_spectral(const AdjointParams A) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = A.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    __shared__ float s_grad[3 * 32];                       // per-workgroup coefficient gradients of constant colours
+    for (uint32_t i = threadIdx.x; i < 3u * 32u; i += kBlock) s_grad[i] = 0.0f;
+    __syncthreads();
+    const uint32_t spp = (uint32_t) P.spp;
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        PathStateS s; float2 pos;
+        generate_path_spectral(P, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
+        const f3 dxyz = adjoint_delta(A, pos);
+        if (dxyz.x == 0.0f && dxyz.y == 0.0f && dxyz.z == 0.0f) continue;       // every term below is proportional to delta
+        VertexRecS rec[kAdjointMaxDepth];
+        int n = 0;
+        Counters c = { 0u, 0u, 0u, 0u };
+        bool alive = true;
+        while (alive && n < kAdjointMaxDepth) { alive = bounce_step_spectral<FLAT, 0, true>(P, lds, s, c, nullptr, SpectralRecorder{ rec[n] }); ++n; }
+        // the adjoint of store_result_spectral; a sample the primal pass drops (alpha = -1) contributes nothing
+        Spec4 delta, value;
+#pragma unroll
+        for (int w = 0; w < kWav; ++w) {
+            const float l = s.wav.v[w], ww = wavelength_weight(l);
+            const f3 cie = cie1931_xyz(l);
+            value.v[w] = ww * s.res.v[w];
+            delta.v[w] = (ww * 0.25f) * fmaf(cie.z, dxyz.z, fmaf(cie.y, dxyz.y, cie.x * dxyz.x));
+        }
+        const f3 xyz = spectrum_to_xyz(value, s.wav);
+        if (!((xyz.x >= -1e-5f) && (xyz.y >= -1e-5f) && (xyz.z >= -1e-5f) && isfinite(xyz.x) && isfinite(xyz.y) && isfinite(xyz.z))) continue;
+        float a[kWav] = { 0.0f, 0.0f, 0.0f, 0.0f };         // dLoss/dT_{v+1}
+        for (int v = n - 1; v >= 0; --v) {
+            const VertexRecS &r = rec[v];
+            if (r.bsdf >= 0) {
+                float g[kWav];
+#pragma unroll
+                for (int w = 0; w < kWav; ++w) g[w] = (r.T.v[w] * r.invq) * fmaf(delta.v[w], r.dNc.v[w], a[w] * r.dW.v[w]);
+                const DevBsdf &b = P.sv.bsdfs[r.bsdf];
+                if (r.texel != kNoPrim) {
+                    if (A.grad_tex) {      // w_ij * sum_k g[k] dS/dc(texel_ij, l_k) for the four corners of the lookup
+                        const DevTexture t = P.sv.textures[b.texture];
+                        const float wt[4] = { (1.0f - r.w1.y) * (1.0f - r.w1.x), (1.0f - r.w1.y) * r.w1.x, r.w1.y * (1.0f - r.w1.x), r.w1.y * r.w1.x };
+                        const uint32_t at[4] = { r.texel, r.texel + 1u, r.texel + (uint32_t) t.w, r.texel + (uint32_t) t.w + 1u };
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            float gc[3] = { 0.0f, 0.0f, 0.0f };
+                            model_coeff_grad(t.data + 3u * (size_t) at[i], s.wav, g, gc);
+                            float *gt = A.grad_tex + t.grad_offset + 3u * (size_t) at[i];
+                            atomicAdd(gt, gc[0] * wt[i]); atomicAdd(gt + 1, gc[1] * wt[i]); atomicAdd(gt + 2, gc[2] * wt[i]);
+                        }
+                    }
+                } else if (A.grad_bsdf && r.bsdf < 32) {
+                    float gc[3] = { 0.0f, 0.0f, 0.0f };
+                    model_coeff_grad(&b.c0, s.wav, g, gc);
+                    atomicAdd(&s_grad[3 * r.bsdf], gc[0]); atomicAdd(&s_grad[3 * r.bsdf + 1], gc[1]); atomicAdd(&s_grad[3 * r.bsdf + 2], gc[2]);
+                }
+            }
+#pragma unroll
+            for (int w = 0; w < kWav; ++w) {
+                const float bw = fmaf(delta.v[w], r.Nc.v[w], r.W.v[w] * a[w]);
+                a[w] = fmaf(delta.v[w], r.E.v[w], r.invq * bw);
+            }
+        }
+    }
+    __syncthreads();
+    if (A.grad_bsdf)
+        for (uint32_t i = threadIdx.x; i < 3u * min(P.sv.n_bsdfs, 32u); i += kBlock)
+            if (s_grad[i] != 0.0f) atomicAdd(A.grad_bsdf + i, s_grad[i]);
+}
+
+hipError_t launch_adjoint_spectral(const AdjointParams &a, hipStream_t s) {
+    const size_t lds = bounce_lds_bytes(a.rp.sv);
+    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral<true>), lds)) return e;
+    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral<false>), lds)) return e;
+    return launch_adjoint_kernel<k_adjoint_spectral<true>, k_adjoint_spectral<false>>(a, s);
+}
+
+// out[i] += J_i^T cgrad[i]: the gradient w.r.t. the model coefficients of colour i (a BSDF record or a texel) taken to its RGB value
+// through jac[9 i + 3 c + j] = d coeff_j / d rgb_c (srgb_model_fetch_jacobian), both in the centred basis of model_coeff_grad
+__global__ __launch_bounds__(kBlock) void k_coeff_grad_to_rgb(const float *cgrad, const float *jac, float *out, uint32_t n) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float g0 = cgrad[3u * i], g1 = cgrad[3u * i + 1u], g2 = cgrad[3u * i + 2u];
+    if (g0 == 0.0f && g1 == 0.0f && g2 == 0.0f) return;
+    const float *j = jac + 9u * (size_t) i;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3u * i + c] += fmaf(j[3 * c + 2], g2, fmaf(j[3 * c + 1], g1, j[3 * c] * g0));
+}
+hipError_t launch_coeff_grad_to_rgb(const float *cgrad, const float *jac, float *out, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_coeff_grad_to_rgb, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, cgrad, jac, out, n);
+    return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------------------------
 // ImageBlock::put as a gather: one wave per film pixel, lanes stride over the samples of the

@@ -237,6 +237,47 @@ void srgb_model_fetch(const Rgb2Spec &m, const float rgb[3], float out[3]) {
     rgb2spec_fetch(m, rgb, out);
 }
 
+// d srgb_model_fetch / d rgb: jac[3 c + j] = d coeff_j / d rgb_c, the analytic derivative of the trilinear interpolant of
+// rgb2spec_fetch inside its cell -- x = rgb[i + 1] (res - 1) / z and y likewise depend on the maximal component z = rgb[i] too, and z
+// indexes the non-uniform m.scale axis.  Zero for the black / white sentinels; a zero row for a component clamped to [0, 1].
+void srgb_model_fetch_jacobian(const Rgb2Spec &m, const float rgb_[3], float jac[9]) {
+    for (int k = 0; k < 9; ++k) jac[k] = 0.0f;
+    if (rgb_[0] == 0.0f && rgb_[1] == 0.0f && rgb_[2] == 0.0f) return;
+    if (rgb_[0] == 1.0f && rgb_[1] == 1.0f && rgb_[2] == 1.0f) return;
+    const int res = (int) m.res;
+    float rgb[3];
+    for (int j = 0; j < 3; ++j) rgb[j] = std::max(std::min(rgb_[j], 1.0f), 0.0f);
+    int i = 0;
+    for (int j = 1; j < 3; ++j) if (rgb[j] >= rgb[i]) i = j;
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+    const float z = rgb[i];
+    if (!(z > 0.0f)) return;
+    const float scale = (res - 1) / z, x = rgb[i1] * scale, y = rgb[i2] * scale;
+    const uint32_t xi = std::min((uint32_t) x, (uint32_t) (res - 2)), yi = std::min((uint32_t) y, (uint32_t) (res - 2));
+    int left = 0, last = res - 2, size = last;
+    while (size > 0) {
+        int half = size >> 1, middle = left + half + 1;
+        if (m.scale[middle] <= z) { left = middle; size -= half + 1; } else size = half;
+    }
+    const uint32_t zi = (uint32_t) std::min(left, last);
+    const size_t offset = ((((size_t) i * res + zi) * res + yi) * res + xi) * 3;
+    const size_t dx = 3, dy = 3 * (size_t) res, dz = 3 * (size_t) res * res;
+    const double dscale = (double) m.scale[zi + 1] - (double) m.scale[zi];
+    const double x1 = (double) x - xi, x0 = 1.0 - x1, y1 = (double) y - yi, y0 = 1.0 - y1, z1 = ((double) z - m.scale[zi]) / dscale, z0 = 1.0 - z1;
+    const float *d = m.data.data() + offset;
+    for (int j = 0; j < 3; ++j, ++d) {
+        const double c000 = d[0], c100 = d[dx], c010 = d[dy], c110 = d[dy + dx], c001 = d[dz], c101 = d[dz + dx], c011 = d[dz + dy], c111 = d[dz + dy + dx];
+        const double ddx = ((c100 - c000) * y0 + (c110 - c010) * y1) * z0 + ((c101 - c001) * y0 + (c111 - c011) * y1) * z1;
+        const double ddy = ((c010 - c000) * x0 + (c110 - c100) * x1) * z0 + ((c011 - c001) * x0 + (c111 - c101) * x1) * z1;
+        const double ddz = ((c001 - c000) * x0 + (c101 - c100) * x1) * y0 + ((c011 - c010) * x0 + (c111 - c110) * x1) * y1;
+        jac[3 * i1 + j] = (float) (ddx * scale);
+        jac[3 * i2 + j] = (float) (ddy * scale);
+        jac[3 * i + j] = (float) (ddz / dscale - (ddx * x + ddy * y) / z);
+    }
+    for (int c = 0; c < 3; ++c)
+        if (rgb_[c] < 0.0f || rgb_[c] > 1.0f) jac[3 * c] = jac[3 * c + 1] = jac[3 * c + 2] = 0.0f;
+}
+
 float srgb_model_mean(const float c[3]) {
     float sum = 0.0f;
     for (int i = 0; i < 16; ++i) {

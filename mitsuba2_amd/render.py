@@ -632,6 +632,15 @@ class Scene:
                 raise RuntimeError("texture data has shape %s, expected %s" % (tuple(a.shape), tuple(shape)))
             L.check(L.lib().mtsamd_scene_update_texture(self._handle, int(texture), a.ctypes.data_as(C.c_void_p), _stream()))
             torch.cuda.current_stream().synchronize()
+        if self._variant == "spectral":
+            # the scene description follows the device (as update_envmap): a ParameterMap built afterwards starts from the new texels,
+            # clamped to [0, 1] as the scene holds them.  A record's texture dictionary IS the one inside self._dict (bsdfs.normalize keeps
+            # the object), so this writes both.  The spectral update converts the texels on the host anyway, so the copy of a device
+            # tensor costs it nothing new; the RGB update stays an asynchronous device copy and is not mirrored
+            new = data.detach().cpu().numpy() if isinstance(data, torch.Tensor) else data
+            for i, t in self._bsdf_texture.items():
+                if t == int(texture) and i < len(self._bsdf_records):
+                    self._bsdf_records[i]["reflectance"]["data"] = np.clip(np.array(new, np.float32).reshape(shape), 0.0, 1.0)
 
     def update_envmap(self, data, rebuild_distribution=True):
         """parameters_changed() for the envmap emitter's `data` (envmap.cpp:220-253); data: (H, W, 3) linear RGB tensor or array.

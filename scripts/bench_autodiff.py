@@ -23,9 +23,13 @@ def main():
     ap.add_argument("--texture", type=int, default=0, help="optimise a texture of this resolution on floor + back wall instead of the red wall colour")
     ap.add_argument("--general", action="store_true", help="general scene: textured roughplastic floor + back wall under an envmap "
                     "(texels through mtsamd_render_adjoint_textures); times one biased iteration and the adjoint kernel alone")
+    ap.add_argument("--spectral-replay", action="store_true", help="spectral Cornell box: one backward pass for the red wall's constant "
+                    "colour through the path replay (mtsamd_render_adjoint_spectral) and through central differences (six renders)")
     args = ap.parse_args()
     if args.general:
         return bench_general(args)
+    if args.spectral_replay:
+        return bench_spectral_replay(args)
     tex = None
     if args.texture:
         tex = np.full((args.texture, args.texture, 3), 0.5, np.float32)
@@ -113,6 +117,36 @@ def bench_general(args):
     ms_adj = (time.perf_counter() - t0) * 1e3 / args.iters
     print("general scene %dx%d spp=%d max_depth=3: textured roughplastic (%dx%d) + conductor + envmap, %s, biased: %.2f ms per iteration "
           "(fwd+adjoint+Adam), texel adjoint alone %.2f ms" % (args.res, args.res, args.spp, n, n, key, ms, ms_adj))
+
+
+def bench_spectral_replay(args):
+    """One backward pass (no primal render, no optimiser step) of the spectral Cornell box for one constant colour, three components:
+    the spectral path replay against the central-difference route (six renders), same scene, same spp, same dLoss/dImage"""
+    sd = scenes.cornell_box()
+    for b, n in zip(sd["bsdfs"], ["white", "red", "green", "light"]):
+        b["id"] = n
+    p = scenes.cornell_box_sensor(args.res, args.res, args.spp, max_depth=3, rfilter="box")
+    scene = render.Scene(sd, variant="spectral", sensor=render.make_sensor(p), integrator=render.PathIntegrator(max_depth=3))
+    dimage = torch.from_numpy(np.random.RandomState(1).randn(args.res * args.res * 3).astype(np.float32)).cuda()
+    out = {}
+    for replay in (True, False):
+        params = autodiff.traverse(scene, replay=replay)
+        params.keep(["red.reflectance.value"])
+        params["red.reflectance.value"].requires_grad_(True)
+        times = []
+        for it in range(3 + args.iters):
+            loss = (autodiff.render(scene, params=params, spp=args.spp) * dimage).sum()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss.backward()
+            torch.cuda.synchronize()
+            if it >= 3:          # three warm-up passes
+                times.append((time.perf_counter() - t0) * 1e3)
+        out[replay] = (float(np.median(times)), float(np.min(times)), float(np.max(times)), params["red.reflectance.value"].grad.cpu().numpy() / (3 + args.iters))
+    for replay, name in ((True, "spectral path replay"), (False, "central differences (6 renders)")):
+        ms, lo, hi, g = out[replay]
+        print("spectral cbox %dx%d spp=%d max_depth=3 box filter, red.reflectance.value, backward pass through %s: median %.2f ms (min %.2f, max %.2f) over %d passes; "
+              "mean gradient %s" % (args.res, args.res, args.spp, name, ms, lo, hi, args.iters, np.array2string(g, precision=4)))
 
 
 if __name__ == "__main__":

@@ -28,7 +28,7 @@ def kernels(path):
     start = {l.split(":")[0]: i for i, l in enumerate(lines) if l.startswith("_Z") and ":" in l}
     meta_at = lines.index("amdhsa.kernels:")
     meta = {}
-    for entry in "\n".join(lines[meta_at + 1:]).split("\n  - ."):
+    for entry in ("\n" + "\n".join(lines[meta_at + 1:])).split("\n  - ."):       # (the first entry has no line before it)
         m = re.search(r"^\s+\.name:\s+(\S+)$", entry, re.M)
         if m:
             meta[m.group(1)] = entry.split("\namdhsa.")[0]
