@@ -343,7 +343,8 @@ MTSAMD_API int mtsamd_render_adjoint_envmap(mtsamd_scene *scene, const mtsamd_re
                                  const float *film_dev, float *grad_envmap_dev, void *stream);
 /* New texels for the envmap emitter (host pointer, height * width * 3 linear RGB; parameters_changed of envmap.cpp:220-253).
  * rebuild_distribution = 0 keeps the importance-sampling hierarchy of the previous texels (a render is then exactly linear in the
- * texels: finite-difference tests); the reference always rebuilds.  Synchronises the device.  RGB variant. */
+ * texels: finite-difference tests); the reference always rebuilds.  Synchronises the device.  Spectral variant: the texels are converted
+ * to (model coefficients, scale) on the host as scene creation converts them; the hierarchy is built from the RGB luminances either way. */
 /* Parameters of the BSDF models beyond `diffuse` (what traverse() exposes of e.g. roughconductor.cpp:393-404, plastic.cpp:299-307):
  * REFLECTANCE = diffuse.reflectance / (rough)plastic.diffuse_reflectance, SPECULAR_REFLECTANCE, SPECULAR_TRANSMITTANCE (dielectrics),
  * ETA / K (conductors), ALPHA (isotropic roughness of roughconductor / roughdielectric; one component). */
@@ -382,6 +383,23 @@ MTSAMD_API int mtsamd_render_adjoint_textures(mtsamd_scene *scene, const mtsamd_
  * live in scratch buffers the scene owns: calls for ONE scene must be ordered on one stream (or otherwise serialised). */
 MTSAMD_API int mtsamd_render_adjoint_spectral(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
                                    const float *film_dev, float *grad_bsdf_dev, float *grad_textures_dev, void *stream);
+/* Spectral variant: the derivative with respect to the emitter family -- the texels of the `envmap` emitter ('data', envmap.cpp:214-218)
+ * and the radiance / intensity / irradiance of area, `constant`, `point`, `spot` and `directional` emitters -- in ANY spectral scene the
+ * path integrator renders; film channels and seed as mtsamd_render_adjoint_spectral.  Such a colour is stored as (model coefficients c of
+ * n = rgb / sc, scale sc = 2 max(r, g, b)).  The path's throughput, directions, pdfs, MIS weights and roulette do not depend on the emitted
+ * spectrum, so every camera sample is replayed once with its PCG32 stream and each use of an emitter colour -- emission picked up, an
+ * unoccluded emitter sample -- adds into the (c, sc) gradients of the colours it read; a finishing kernel takes them to RGB through
+ * d c / d rgb (the Jacobian of srgb_model_fetch at n composed with d n / d rgb, kept by the scene) and d sc / d rgb.  Conventions:
+ *  - the sampling distribution (the envmap hierarchy built from the luminances, the choice among emitters) is NOT differentiated;
+ *  - a colour whose largest component is 0 is not differentiable (n = 0 / 0, sentinel coefficients): its gradient is 0, and it puts no
+ *    NaN into the texels that share a bilinear footprint with it;
+ *  - on a tie for the maximum, d sc / d rgb goes to the lowest channel that attains it (the one max(max(r, g), b) returns): a subgradient;
+ *  - a sample the primal pass drops (negative or non-finite XYZ) contributes nothing.
+ * grad_emitters_dev: emitter_count x 3 linear RGB (the row of an `envmap` emitter stays untouched); grad_envmap_dev: envmap height * width
+ * * 3.  Both are ACCUMULATED into; either may be NULL.  Needs 1 <= max_depth <= 16, no blendbsdf / mask, at most 32 emitters with
+ * grad_emitters_dev, an envmap with grad_envmap_dev.  Scratch buffers of the scene: calls for ONE scene must be ordered on one stream. */
+MTSAMD_API int mtsamd_render_adjoint_spectral_emitters(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
+                                            const float *film_dev, float *grad_emitters_dev, float *grad_envmap_dev, void *stream);
 MTSAMD_API int mtsamd_scene_update_envmap(mtsamd_scene *scene, const float *rgb, int32_t rebuild_distribution);
 /* Size of a bitmap texture and its float offset inside the concatenated texture-gradient buffer. */
 /* RoughPlastic precomputation (roughplastic.cpp:380-399) of BSDF `bsdf`: out65[0..63] = external transmittance at
@@ -399,6 +417,10 @@ MTSAMD_API int mtsamd_srgb_model_fetch(const char *path, const float *rgb3, floa
 /* Its derivative: jac9[3 c + j] = d coeff_j / d rgb_c, the analytic derivative of the trilinear table lookup inside the cell of `rgb3`.
  * Zero for pure black and pure white (their coefficients are sentinels), a zero row for a component outside [0, 1].  Host only. */
 MTSAMD_API int mtsamd_srgb_model_fetch_jacobian(const char *path, const float *rgb3, float *jac9);
+/* An emitter colour of the spectral variant (envmap texel, radiance): coeff_scale4 = (c0, c1, c2, sc) with sc = 2 max(r, g, b) and
+ * c = srgb_model_fetch(rgb3 / max(1e-8, sc)); jac9[3 ch + j] = d c_j / d rgb_ch, the Jacobian above composed with d n / d rgb (n of the
+ * maximal channel is the constant 0.5; ties: the lowest such channel).  All zero for a colour whose largest component is <= 0.  Host only. */
+MTSAMD_API int mtsamd_srgb_emitter_fetch_jacobian(const char *path, const float *rgb3, float *coeff_scale4, float *jac9);
 
 /* PerspectiveCamera::sample_ray (perspective.cpp:153-188) / ThinLensCamera::sample_ray (thinlens.cpp:175-214) for n
  * film-plane samples in [0,1)^2 and, for a thin lens, n aperture samples (NULL: 0.5, as integrator.cpp:229 initialises them)

@@ -51,7 +51,9 @@ class ParameterMap:
     def __init__(self, scene, replay=False):
         self._scene = scene
         # spectral variant only: differentiate the reflectance family (constant srgb colours and bitmap texels of diffuse.reflectance /
-        # (rough)plastic.diffuse_reflectance) by the spectral path replay, mtsamd_render_adjoint_spectral, instead of central differences
+        # (rough)plastic.diffuse_reflectance) by the spectral path replay, mtsamd_render_adjoint_spectral, instead of central differences,
+        # and the emitter family (envmap texels; radiance / intensity / irradiance of every other emitter) by
+        # mtsamd_render_adjoint_spectral_emitters
         self._replay = bool(replay) and _is_spectral(scene)
         self.rebuild_envmap_distribution = True      # what parameters_changed() does (envmap.cpp:220-253); False: tests of linearity
         self.fd_step = 0.0                           # BSDF-model parameters: step of the central difference of the model code (0: 1 % of the value)
@@ -133,6 +135,16 @@ class ParameterMap:
             rad = np.broadcast_to(np.asarray(scene._dict["emitters"][e]["radiance"], np.float32), (3,))
             self.properties[key] = torch.as_tensor(rad.copy(), dtype=torch.float32, device=dev)
             self._kind[key] = ("emitter", e, i)
+        # spectral variant with `replay`: the emitted colour of the emitters that have no shape -- `constant`, `point`, `spot`, `directional` --
+        # under their own id ('<emitter>.radiance.value', '.intensity.value', '.irradiance.value').  Area lights keep the keys above
+        from . import emitters as E
+        for e, em in enumerate(emitters if self._replay else []):
+            t = em.get("type", "area")
+            if t in ("envmap", "area"):
+                continue
+            key = "%s.%s.value" % (em.get("id", "emitter_%d" % e), E._VALUE_KEY[t])
+            self.properties[key] = torch.as_tensor(E.normalize(em)["radiance"], dtype=torch.float32, device=dev)
+            self._kind[key] = ("emitter", e, e)
 
     def __getitem__(self, k): return self.properties[k]
     def __contains__(self, k): return k in self.properties
@@ -171,6 +183,11 @@ class ParameterMap:
                 # back onto it (the parameter tensor itself, so that the optimiser's state and the scene agree)
                 with torch.no_grad():
                     v.clamp_(0.0, 1.0)
+            if _is_spectral(self._scene) and kind == "envmap":
+                # spectral variant: a texel is upsampled as a scale times a colour in [0, 1]^3 (envmap.cpp:96-109), so it is projected onto
+                # >= 0, on the parameter tensor itself as above
+                with torch.no_grad():
+                    v.clamp_(min=0.0)
             seen[k] = (v, v._version)
             if kind == "texture":
                 self._scene.update_texture(idx, v)
@@ -187,14 +204,21 @@ class ParameterMap:
 
 def traverse(scene, replay=False):
     """mitsuba.python.util.traverse (util.py:132-179) for the supported parameters.  ``replay=True`` (spectral scenes; ignored for RGB
-    ones) adds the bitmap texels of the reflectance family and differentiates that family with the spectral path replay."""
+    ones) adds the bitmap texels of the reflectance family and the emitted colour of shapeless emitters, and differentiates the reflectance
+    family and the emitter family (envmap texels included) with one spectral path replay each per backward pass."""
     return ParameterMap(scene, replay=replay)
 
 
 def _replayed(pmap, key):
-    """Does the spectral path replay differentiate this key?  Texels, and the constant (diffuse_)reflectance colours."""
+    """Which spectral path replay differentiates this key?  "reflectance": texels and the constant (diffuse_)reflectance colours
+    (mtsamd_render_adjoint_spectral); "emitter": envmap texels and emitter radiances (mtsamd_render_adjoint_spectral_emitters); None:
+    central differences."""
     kind, _, extra = pmap._kind[key]
-    return pmap._replay and (kind in ("texture", "bsdf") or (kind == "bsdf_param" and extra == 0))
+    if not pmap._replay:
+        return None
+    if kind in ("texture", "bsdf") or (kind == "bsdf_param" and extra == 0):
+        return "reflectance"
+    return "emitter" if kind in ("envmap", "emitter") else None
 
 
 def _texture_slice(scene, g_tex, idx):
@@ -232,7 +256,7 @@ def _spectral_gradient(scene, d, pmap, key, gi):
     spectral ParameterMap is limited to a handful of constants -- texels and envmaps raise."""
     kind, idx, extra = pmap._kind[key]
     if kind in ("texture", "envmap"):
-        raise RuntimeError("the spectral variant differentiates constant colours, radiances and roughnesses only (%s is a %s; texels need traverse(scene, replay=True))" % (key, kind))
+        raise RuntimeError("the spectral variant differentiates constant colours, radiances and roughnesses only (%s is a %s; texels and envmaps need traverse(scene, replay=True))" % (key, kind))
     value = [float(x) for x in pmap[key].detach().cpu().reshape(-1).tolist()]
 
     def push(vals):
@@ -285,14 +309,25 @@ class _Render(torch.autograd.Function):
         gi = grad_image.to(dev, torch.float32).contiguous()
         if _is_spectral(scene):
             grads = {}
-            replayed = {pmap._kind[k][0] for k in keys if _replayed(pmap, k)}
+            replayed = {pmap._kind[k][0] for k in keys if _replayed(pmap, k) == "reflectance"}
             if replayed:      # one replay for the whole reflectance family; a gradient nobody asked for is not computed (null)
                 L.check(L.lib().mtsamd_render_adjoint_spectral(scene._handle, C.byref(d), _ptr(gi), _ptr(film), _ptr(g_bsdf) if replayed - {"texture"} else None,
                                                                _ptr(g_tex) if "texture" in replayed else None, _stream()))
+            emitted = {pmap._kind[k][0] for k in keys if _replayed(pmap, k) == "emitter"}
+            g_env = None
+            if emitted:       # and one for the whole emitter family
+                if "envmap" in emitted:
+                    g_env = torch.zeros_like(next(pmap[k] for k in keys if pmap._kind[k][0] == "envmap"))
+                L.check(L.lib().mtsamd_render_adjoint_spectral_emitters(scene._handle, C.byref(d), _ptr(gi), _ptr(film), _ptr(g_em) if "emitter" in emitted else None,
+                                                                        _ptr(g_env) if g_env is not None else None, _stream()))
             for k in keys:
                 kind, idx, _ = pmap._kind[k]
                 if not _replayed(pmap, k):
                     grads[k] = _spectral_gradient(scene, d, pmap, k, gi.reshape(-1))
+                elif kind == "envmap":
+                    grads[k] = g_env
+                elif kind == "emitter":
+                    grads[k] = g_em[idx].clone().reshape(pmap[k].shape)
                 elif kind == "texture":
                     grads[k] = _texture_slice(scene, g_tex, idx)
                 else:

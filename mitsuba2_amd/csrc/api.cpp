@@ -359,6 +359,60 @@ static double spectral_texels(const Rgb2Spec &model, const float *rgb, size_t n_
     return mean;
 }
 
+// Spectral variant: the RGBA texels of an envmap -> (model coefficients of the colour scaled to a 50% maximum, scale), in place
+// (envmap.cpp:96-109); black: (0, 0, -inf), evaluates to 0 (srgb.cpp:31-33)
+static void spectral_envmap_texels(const Rgb2Spec &model, float *texels4, size_t n_texels) {
+    for (size_t i = 0; i < n_texels; ++i) {
+        float *px = texels4 + 4 * i;
+        const float sc = std::max(std::max(px[0], px[1]), px[2]) * 2.0f, dn = std::max(1e-8f, sc);
+        float rgb_norm[3] = { px[0] / dn, px[1] / dn, px[2] / dn }, coeff[3];
+        srgb_model_fetch(model, rgb_norm, coeff);
+        px[0] = coeff[0]; px[1] = coeff[1]; px[2] = coeff[2]; px[3] = sc;
+    }
+}
+
+// An emitter colour of the spectral variant (an envmap texel, a radiance / intensity / irradiance) is stored as (c, sc) with
+// sc = 2 max(r, g, b), n = rgb / max(1e-8, sc), c = srgb_model_fetch(n).  out4 = (c0, c1, c2, sc); jn[3 ch + j] = d c_j / d rgb_ch, composed
+// in double from the Jacobian of the fetch at n:  d n_j / d rgb_j = 1 / sc for j != m,  d n_j / d rgb_m = -n_j / rgb_m,  n_m = 0.5 is a
+// constant; *m_out = m, the channel that attains the maximum -- the lowest one on a tie, which is the value std::max(std::max(r, g), b)
+// returns.  A colour whose largest component is <= 0 is not differentiable (n = 0 / 0, sentinel coefficients): jn = 0 and m = -1.
+static void emitter_colour_jacobian(const Rgb2Spec &model, const float rgb[3], float out4[4], double jn[9], int *m_out) {
+    const float sc = std::max(std::max(rgb[0], rgb[1]), rgb[2]) * 2.0f, dn = std::max(1e-8f, sc);
+    const float n[3] = { rgb[0] / dn, rgb[1] / dn, rgb[2] / dn };
+    srgb_model_fetch(model, n, out4);
+    out4[3] = sc;
+    for (int k = 0; k < 9; ++k) jn[k] = 0.0;
+    *m_out = -1;
+    if (!(sc > 0.0f)) return;
+    const int m = (rgb[0] >= rgb[1] && rgb[0] >= rgb[2]) ? 0 : (rgb[1] >= rgb[2] ? 1 : 2);
+    *m_out = m;
+    float jf[9];
+    srgb_model_fetch_jacobian(model, n, jf);
+    for (int ch = 0; ch < 3; ++ch)
+        for (int j = 0; j < 3; ++j) {
+            if (sc < 1e-8f) jn[3 * ch + j] = (double) jf[3 * ch + j] / (double) dn;        // below the clamp of the divisor n is linear in rgb
+            else if (ch != m) {
+                jn[3 * ch + j] = (double) jf[3 * ch + j] / (double) sc;
+                jn[3 * m + j] -= (double) n[ch] / (double) rgb[m] * (double) jf[3 * ch + j];
+            }
+        }
+}
+
+// 12 floats of the device table of k_emitter_grad_to_rgb for one emitter colour: jn in the centred basis of model_coeff_grad
+// (l = mid + half u gives a = half^2 c0, b = 2 mid half c0 + half c1, c = mid^2 c0 + mid c1 + c2), then d scale / d rgb
+static void emitter_jacobian_row(const Rgb2Spec &model, const float rgb[3], float row[12]) {
+    float out4[4]; double jn[9]; int m;
+    emitter_colour_jacobian(model, rgb, out4, jn, &m);
+    const double mid = kCoeffMid, half = kCoeffHalf;
+    for (int ch = 0; ch < 3; ++ch) {
+        const double *j = jn + 3 * ch;
+        row[3 * ch] = (float) (half * half * j[0]);
+        row[3 * ch + 1] = (float) (2.0 * mid * half * j[0] + half * j[1]);
+        row[3 * ch + 2] = (float) (mid * mid * j[0] + mid * j[1] + j[2]);
+        row[9 + ch] = ch == m ? 2.0f : 0.0f;
+    }
+}
+
 struct mtsamd_scene {
     int32_t environment = -1;        // index of the `constant` emitter
     bool general_bsdfs = false;      // any BSDF other than one-sided `diffuse`: the kernels with the BSDF switch are used
@@ -392,6 +446,12 @@ struct mtsamd_scene {
     std::vector<float> jac_bsdf, jac_tex;
     float *d_jac = nullptr, *d_cgrad = nullptr;
     bool jac_dirty = true;
+    // spectral variant, emitter colours: the RGB texels of the envmap as the scene holds them (the device keeps coefficients), and the
+    // table of mtsamd_render_adjoint_spectral_emitters, 12 floats per colour for [emitters | envmap texels] (emitter_jacobian_row), rebuilt
+    // when `ejac_dirty`; d_egrad = its 4-float (coefficient, scale) gradient rows
+    std::vector<float> env_rgb;
+    float *d_ejac = nullptr, *d_egrad = nullptr;
+    bool ejac_dirty = true;
     DevTexture *d_textures = nullptr;
     SceneView view{};
     bool spectral = false;
@@ -424,7 +484,7 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
     (void) hipFree(s->d_area_pmf); (void) hipFree(s->d_area_cdf); (void) hipFree(s->d_rough_tables);
     (void) hipFree(s->d_env_texels); (void) hipFree(s->d_env_warp); (void) hipFree(s->d_envmap); (void) hipFree(s->d_flat); (void) hipFree(s->d_pairs);
     for (auto &t : s->textures) (void) hipFree((void *) t.data);
-    (void) hipFree(s->d_textures); (void) hipFree(s->d_jac); (void) hipFree(s->d_cgrad);
+    (void) hipFree(s->d_textures); (void) hipFree(s->d_jac); (void) hipFree(s->d_cgrad); (void) hipFree(s->d_ejac); (void) hipFree(s->d_egrad);
     delete s;
 }
 
@@ -860,13 +920,8 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
         if (desc->spectral) {
             // envmap.cpp:96-109: every texel becomes (model coefficients of the colour scaled to a 50% maximum, scale); the
             // sampling hierarchy stays the one built from the RGB luminance
-            for (size_t i = 0; i < eh.texels.size() / 4; ++i) {
-                float *px = eh.texels.data() + 4 * i;
-                const float sc = std::max(std::max(px[0], px[1]), px[2]) * 2.0f, dn = std::max(1e-8f, sc);
-                float rgb_norm[3] = { px[0] / dn, px[1] / dn, px[2] / dn }, coeff[3];
-                srgb_model_fetch(model, rgb_norm, coeff);             // black: (0, 0, -inf), evaluates to 0 (srgb.cpp:31-33)
-                px[0] = coeff[0]; px[1] = coeff[1]; px[2] = coeff[2]; px[3] = sc;
-            }
+            s->env_rgb.assign(ed.envmap_data, ed.envmap_data + 3 * (size_t) ed.envmap_width * ed.envmap_height);
+            spectral_envmap_texels(model, eh.texels.data(), eh.texels.size() / 4);
         }
         DevEnvmap de{};
         std::vector<DevEnvmap> one(1);
@@ -1075,6 +1130,7 @@ int mtsamd_scene_set_emitter_radiance(mtsamd_scene *s, uint32_t emitter, const f
         d65_scale *= 1.0f / 10568.0f;                      // d65.cpp:44-50
         DevEmitter &d = s->emitters[emitter];
         d.c0 = coeff[0]; d.c1 = coeff[1]; d.c2 = coeff[2]; d.d65_scale = d65_scale;
+        s->ejac_dirty = true;
     }
     HIP_TRY(hipMemcpy(s->d_emitters + emitter, &s->emitters[emitter], sizeof(DevEmitter), hipMemcpyHostToDevice));
     return MTSAMD_OK;
@@ -2216,13 +2272,56 @@ int mtsamd_render_adjoint_spectral(mtsamd_scene *s, const mtsamd_render_desc *d,
     return MTSAMD_OK;
 }
 
+int mtsamd_render_adjoint_spectral_emitters(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film,
+                                            float *grad_emitters, float *grad_envmap, void *stream_) {
+    AdjointParams a{};
+    if (int rc = fill_adjoint(s, d, dimage, film, a, true)) return rc;
+    if (d->max_depth < 1 || d->max_depth > 16)
+        return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle blendbsdf / mask materials");
+    if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
+    if (s->emitters.size() > 32 && grad_emitters) return fail(MTSAMD_ERR_UNSUPPORTED, "at most 32 emitters with radiance gradients");
+    if (grad_envmap && (s->environment < 0 || !s->d_envmap)) return fail(MTSAMD_ERR_UNSUPPORTED, "the scene has no envmap emitter");
+    if (!grad_emitters && !grad_envmap) return MTSAMD_OK;
+    hipStream_t stream = (hipStream_t) stream_;
+    // gradient rows and Jacobians: [emitters | envmap texels]
+    const size_t n_em = s->emitters.size(), n_texels = s->d_envmap ? (size_t) s->env_w * s->env_h : 0, n_colours = n_em + n_texels;
+    if (!s->d_ejac) { HIP_TRY(hipMalloc((void **) &s->d_ejac, 12 * n_colours * sizeof(float))); s->ejac_dirty = true; }
+    if (!s->d_egrad) HIP_TRY(hipMalloc((void **) &s->d_egrad, 4 * n_colours * sizeof(float)));
+    if (s->ejac_dirty) {
+        std::vector<float> table(12 * n_colours, 0.0f);
+        for (size_t i = 0; i < n_em; ++i) {
+            const DevEmitter &e = s->emitters[i];
+            const float rgb[3] = { e.r, e.g, e.b };
+            if (e.pad0 != kEmitterEnvmap) emitter_jacobian_row(s->rgb2spec, rgb, table.data() + 12 * i);      // (an envmap's `radiance` is not a parameter)
+        }
+        for (size_t i = 0; i < n_texels && 3 * n_texels == s->env_rgb.size(); ++i)
+            emitter_jacobian_row(s->rgb2spec, s->env_rgb.data() + 3 * i, table.data() + 12 * (n_em + i));
+        HIP_TRY(hipStreamSynchronize(stream));               // an earlier launch may still read the old table
+        HIP_TRY(hipMemcpy(s->d_ejac, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+        s->ejac_dirty = false;
+    }
+    HIP_TRY(hipMemsetAsync(s->d_egrad, 0, 4 * n_colours * sizeof(float), stream));
+    a.grad_emitter = grad_emitters ? s->d_egrad : nullptr;
+    a.grad_env = grad_envmap ? s->d_egrad + 4 * n_em : nullptr;
+    a.rp.spectral = 1;
+    HIP_TRY(launch_adjoint_spectral_emitters(a, stream));
+    if (a.grad_emitter) HIP_TRY(launch_emitter_grad_to_rgb(s->d_egrad, s->d_ejac, grad_emitters, (uint32_t) n_em, stream));
+    if (a.grad_env) HIP_TRY(launch_emitter_grad_to_rgb(s->d_egrad + 4 * n_em, s->d_ejac + 12 * n_em, grad_envmap, (uint32_t) n_texels, stream));
+    return MTSAMD_OK;
+}
+
 int mtsamd_scene_update_envmap(mtsamd_scene *s, const float *rgb, int32_t rebuild_distribution) {
     if (!s || !rgb) return fail(MTSAMD_ERR_INVALID, "null argument");
     if (s->environment < 0 || !s->d_envmap) return fail(MTSAMD_ERR_UNSUPPORTED, "the scene has no envmap emitter");
-    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "envmap updates are implemented for the RGB variant only");
     HIP_TRY(hipSetDevice(s->device));
     EnvmapHost eh;
     if (!build_envmap(rgb, s->env_w, s->env_h, eh)) return fail(MTSAMD_ERR_INVALID, "envmap: unsupported image size");
+    if (s->spectral) {       // the texels hold (model coefficients, scale), converted as mtsamd_scene_create converts them; the hierarchy stays RGB
+        s->env_rgb.assign(rgb, rgb + 3 * (size_t) s->env_w * s->env_h);
+        spectral_envmap_texels(s->rgb2spec, eh.texels.data(), eh.texels.size() / 4);
+        s->ejac_dirty = true;
+    }
     HIP_TRY(hipDeviceSynchronize());           // renders in flight read the old texels
     HIP_TRY(hipMemcpy(s->d_env_texels, eh.texels.data(), eh.texels.size() * sizeof(float), hipMemcpyHostToDevice));
     if (rebuild_distribution) HIP_TRY(hipMemcpy(s->d_env_warp, eh.warp.data(), eh.warp.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -2269,6 +2368,16 @@ int mtsamd_srgb_model_fetch_jacobian(const char *path, const float *rgb, float *
     const Rgb2Spec *m = cached_model(path);
     if (!m) return MTSAMD_ERR_INVALID;
     srgb_model_fetch_jacobian(*m, rgb, jac);
+    return MTSAMD_OK;
+}
+
+int mtsamd_srgb_emitter_fetch_jacobian(const char *path, const float *rgb, float *coeff_scale, float *jac) {
+    if (!path || !rgb || !coeff_scale || !jac) return fail(MTSAMD_ERR_INVALID, "null argument");
+    const Rgb2Spec *m = cached_model(path);
+    if (!m) return MTSAMD_ERR_INVALID;
+    double jn[9]; int ch;
+    emitter_colour_jacobian(*m, rgb, coeff_scale, jn, &ch);
+    for (int k = 0; k < 9; ++k) jac[k] = (float) jn[k];
     return MTSAMD_OK;
 }
 

@@ -209,6 +209,12 @@ constexpr float kCoeffMid = 595.0f, kCoeffHalf = 235.0f;
 hipError_t launch_adjoint_spectral(const AdjointParams &a, hipStream_t s);
 // out[i] += J_i^T cgrad[i] for n colours (3 floats each): jac[9 i + 3 c + j] = d coeff_j / d rgb_c (centred basis)
 hipError_t launch_coeff_grad_to_rgb(const float *cgrad, const float *jac, float *out, uint32_t n, hipStream_t s);
+// k_adjoint_spectral_emitters: gradients w.r.t. the (model coefficients in the centred basis, scale) of the emitter colours, as 4-float rows:
+// a.grad_emitter = n_emitters rows, a.grad_env = envmap height * width rows (either may be null)
+hipError_t launch_adjoint_spectral_emitters(const AdjointParams &a, hipStream_t s);
+// out[i] += Jn_i^T rows[i].xyz + sel_i rows[i].w for n emitter colours: jac[12 i + 3 c + j] = d coeff_j / d rgb_c (centred basis),
+// jac[12 i + 9 + c] = d scale / d rgb_c
+hipError_t launch_emitter_grad_to_rgb(const float *rows, const float *jac, float *out, uint32_t n, hipStream_t s);
 // end of a pass: every path of p.in (counts p.count_in) is run to its end in one launch; needs dry sample cursors (kernels.hip, k_finish)
 hipError_t launch_finish(const RenderParams &p, uint64_t alive, hipStream_t s);
 hipError_t launch_mega(const RenderParams &p, hipStream_t s);      // small passes: the whole pass in one launch of persistent lanes

@@ -515,6 +515,7 @@ MTS_DEV Spec4 emitter_spectrum(const SceneView &sv, const DevEmitter &e, const S
 struct NeeTermsS {
     const DirectionSample &ds; f3 wi, wo;     // local directions as the BSDF models take them (they mirror a `twosided` record themselves)
     Spec4 bv, spec; float mis;
+    float r1, r2; uint32_t kind;              // spec = ((radiance * falloff) * r1) * r2 (r2: several emitters only) of an emitter of this kind (DevEmitter::pad0)
 };
 
 // The probe of the spectral step: the hooks of NoProbe (bounce_step) in the same order, on four wavelengths.  NoProbeS, the probe of
@@ -646,7 +647,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
                 nz = nz || contrib.v[k] != 0.0f;
                 if constexpr (kWatch) { bv4.v[k] = bv; spec4.v[k] = spec; }
             }
-            auto nee = [&] { return NeeTermsS{ ds, si.wi, wo, bv4, spec4, mis }; };
+            auto nee = [&] { return NeeTermsS{ ds, si.wi, wo, bv4, spec4, mis, r1, r2, e.pad0 }; };
             bool watched = false;
             if constexpr (kWatch) watched = probe.emitter_sample(sv, bsdf, refl, nee());
             if (DEFER) {
@@ -2375,6 +2376,191 @@ __global__ __launch_bounds__(kBlock) void k_coeff_grad_to_rgb(const float *cgrad
 hipError_t launch_coeff_grad_to_rgb(const float *cgrad, const float *jac, float *out, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_coeff_grad_to_rgb, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, cgrad, jac, out, n);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Spectral variant: derivative w.r.t. the emitter family -- the texels of an `envmap` ('data', envmap.cpp:214-218) and the radiance /
+// intensity / irradiance of area, `constant`, `point`, `spot` and `directional` emitters -- in ANY spectral scene.  Such a colour is stored
+// as (model coefficients c of n = rgb / sc, scale sc = 2 max(r, g, b)), and the radiance at wavelength l is
+//   envmap:  sp(l) * f * wp(l) * scale,  sp = sum_i w_i S(c_i; l),  f = sum_i w_i sc_i over the four bilinear corners, wp = D65 / 10568;
+//   others:  S(c; l) * sc * wp(l)        (d65_scale = sc / 10568): the one-texel case with w = 1 and scale = 1.
+// Throughput, directions, pdfs, MIS weights and roulette do not depend on the emitted spectrum, and the sampling hierarchy built from the
+// luminances is not differentiated (as in k_adjoint_env), so there is no backward sweep: the radiance enters at the emission a path picks
+// up (coefficient ew * thr) and at an unoccluded emitter sample (coefficient mis * thr * bv * (spec / radiance), from the factors r1, r2
+// and falloff: spec is never divided by the radiance, which may be 0).  Whether the primal pass drops a sample is known only at the end
+// of its path, so one thread replays one camera sample, records at most two uses per step, and scatters them after that test.  With
+// A_k = coefficient * delta_k (the per-wavelength seed of k_adjoint_spectral) and B_k = A_k wp_k scale, a use adds
+//   gc_i += w_i f sum_k B_k dS/dc(c_i; l_k)   (centred basis of model_coeff_grad),      gs_i += w_i sum_k B_k sp_k
+// into the 4-float row (gc, gs) of each colour it read: texel rows by float atomics in global memory, emitter rows reduced in LDS per
+// workgroup first.  k_emitter_grad_to_rgb takes the rows to RGB.  A colour whose largest component is 0 has the sentinel coefficients:
+// model_coeff_grad skips it, and its row of the Jacobian table is zero, so its gradient is exactly 0 and it puts no NaN into its neighbours.
+struct EmitterUseS {
+    Spec4 ce, cn;               // coefficients of the emission picked up at this step and of its emitter sample
+    f2 uve, uvn;                // envmap texture coordinates of the two
+    int32_t eme, emn;           // their emitters (-1: none)
+};
+
+struct EmitterGradProbeS {
+    EmitterUseS &r;
+    Spec4 thr0;                 // throughput arriving at the vertex (emission is picked up before roulette)
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathStateS &s) {
+        static_assert(GENERAL && DEFER == 0 && !NEST, "the spectral emitter gradient rides on the plain general fused step");
+        thr0 = s.thr; r.eme = r.emn = -1; r.uve.x = r.uve.y = r.uvn.x = r.uvn.y = 0.0f;
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) r.ce.v[k] = r.cn.v[k] = 0.0f;
+    }
+    MTS_DEV void emitted(float ew, int32_t emitter, const Spec4 &) {
+        r.eme = emitter;
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) r.ce.v[k] = ew * thr0.v[k];
+    }
+    MTS_DEV void escaped(const SceneView &sv, const PathStateS &s, const DevEmitter &e, float ew, const Spec4 &) {
+        emitted(ew, sv.env_emitter, s.thr);
+        if (e.pad0 == kEmitterEnvmap) env_dir_to_uv(mat3_apply(sv.envmap->to_local, s.d), r.uve.x, r.uve.y);
+    }
+    MTS_DEV void roulette(const Spec4 &, float, float, bool) { }
+    MTS_DEV void surface(const SurfaceInteraction &, const DevBsdf &, const Spec4 &, uint32_t, f2, const Spec4 &) { }
+    // spec / radiance of the emitter sample
+    MTS_DEV static float em_geo(const SceneView &sv, const NeeTermsS &t) {
+        const float g = t.ds.delta ? t.ds.falloff * t.r1 : t.r1;
+        return sv.n_emitters > 1u ? g * t.r2 : g;
+    }
+    // the shadow ray is traced whenever the derivative is non-zero, also where the radiance itself is 0
+    MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &, const Spec4 &, const NeeTermsS &t) {
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) any = any || t.bv.v[k] != 0.0f;
+        return any && em_geo(sv, t) != 0.0f;
+    }
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &, const Spec4 &thr, const NeeTermsS &t) {
+        const float g = em_geo(sv, t);
+        r.emn = (int32_t) t.ds.emitter; r.uvn = t.ds.uv;
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) r.cn.v[k] = ((t.mis * thr.v[k]) * t.bv.v[k]) * g;
+    }
+    MTS_DEV void bsdf_sampled(const SceneView &, const SurfaceInteraction &, const DevBsdf &, const Spec4 &, const Spec4 &, const BsdfSample &, const float (&)[kWav]) { }
+};
+
+// One use of emitter `em` with the per-wavelength coefficients `a` = coefficient * delta: into the texel rows of grad_env (an `envmap`)
+// or into row `em` of the workgroup's s_em (every other emitter).  Either destination may be null.
+MTS_DEV void scatter_emitter_use(const SceneView &sv, const Spec4 &wav, int32_t em, f2 uv, const Spec4 &a, float *grad_env, float *s_em) {
+    if (em < 0) return;
+    bool any = false;
+    float bk[kWav];
+#pragma unroll
+    for (int k = 0; k < kWav; ++k) { bk[k] = a.v[k] * table_eval(g_spectral.d65, 1.0f / 10568.0f, wav.v[k]); any = any || bk[k] != 0.0f; }
+    if (!any) return;
+    const DevEmitter &e = sv.emitters[em];
+    if (e.pad0 == kEmitterEnvmap) {
+        if (!grad_env) return;
+        const DevEnvmap &env = *sv.envmap;
+        const float u = uv.x * (float) (env.w - 1), v = uv.y * (float) (env.h - 1);        // the bilinear footprint of envmap_lookup_spectral
+        const uint32_t px = min((uint32_t) u, (uint32_t) (env.w - 2)), py = min((uint32_t) v, (uint32_t) (env.h - 2));
+        const float w1x = u - (float) px, w1y = v - (float) py, w0x = 1.0f - w1x, w0y = 1.0f - w1y;
+        const float wt[4] = { w0y * w0x, w0y * w1x, w1y * w0x, w1y * w1x };
+        const uint32_t at[4] = { py * (uint32_t) env.w + px, py * (uint32_t) env.w + px + 1u, (py + 1u) * (uint32_t) env.w + px, (py + 1u) * (uint32_t) env.w + px + 1u };
+        float4 tx[4];
+        float f = 0.0f, gsum = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { tx[i] = env.data[at[i]]; f = fmaf(wt[i], tx[i].w, f); }
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) {
+            bk[k] *= env.scale;
+            float sp = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sp = fmaf(wt[i], srgb_model_eval(tx[i].x, tx[i].y, tx[i].z, wav.v[k]), sp);
+            gsum = fmaf(bk[k], sp, gsum);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (wt[i] == 0.0f) continue;
+            const float c[3] = { tx[i].x, tx[i].y, tx[i].z };
+            const float g[kWav] = { bk[0] * (wt[i] * f), bk[1] * (wt[i] * f), bk[2] * (wt[i] * f), bk[3] * (wt[i] * f) };
+            float gc[3] = { 0.0f, 0.0f, 0.0f };
+            model_coeff_grad(c, wav, g, gc);
+            float *row = grad_env + 4u * (size_t) at[i];
+            atomicAdd(row, gc[0]); atomicAdd(row + 1, gc[1]); atomicAdd(row + 2, gc[2]); atomicAdd(row + 3, wt[i] * gsum);
+        }
+    } else if (s_em && em < 32) {
+        const float c[3] = { e.c0, e.c1, e.c2 };
+        const float f = e.d65_scale * 10568.0f;              // sc
+        float g[kWav], gsum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < kWav; ++k) { g[k] = bk[k] * f; gsum = fmaf(bk[k], srgb_model_eval(c[0], c[1], c[2], wav.v[k]), gsum); }
+        float gc[3] = { 0.0f, 0.0f, 0.0f };
+        model_coeff_grad(c, wav, g, gc);
+        atomicAdd(&s_em[4 * em], gc[0]); atomicAdd(&s_em[4 * em + 1], gc[1]); atomicAdd(&s_em[4 * em + 2], gc[2]); atomicAdd(&s_em[4 * em + 3], gsum);
+    }
+}
+
+// A.grad_emitter (n_emitters rows) and A.grad_env (height * width rows) are the 4-float (gc, gs) scratch rows here; either may be null
+template <bool FLAT>
+__global__ __launch_bounds__(kBlock) void k_adjoint_spectral_emitters(const AdjointParams A) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = A.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    __shared__ float s_em[4 * 32];                         // per-workgroup (gc, gs) rows of the emitters
+    for (uint32_t i = threadIdx.x; i < 4u * 32u; i += kBlock) s_em[i] = 0.0f;
+    __syncthreads();
+    const uint32_t spp = (uint32_t) P.spp;
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        PathStateS s; float2 pos;
+        generate_path_spectral(P, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
+        const f3 dxyz = adjoint_delta(A, pos);
+        if (dxyz.x == 0.0f && dxyz.y == 0.0f && dxyz.z == 0.0f) continue;       // every term below is proportional to delta
+        EmitterUseS use[kAdjointMaxDepth];
+        int n = 0;
+        Counters c = { 0u, 0u, 0u, 0u };
+        bool alive = true;
+        while (alive && n < kAdjointMaxDepth) { alive = bounce_step_spectral<FLAT, 0, true>(P, lds, s, c, nullptr, EmitterGradProbeS{ use[n] }); ++n; }
+        // the adjoint of store_result_spectral; a sample the primal pass drops (alpha = -1) contributes nothing
+        Spec4 delta, value;
+#pragma unroll
+        for (int w = 0; w < kWav; ++w) {
+            const float l = s.wav.v[w], ww = wavelength_weight(l);
+            const f3 cie = cie1931_xyz(l);
+            value.v[w] = ww * s.res.v[w];
+            delta.v[w] = (ww * 0.25f) * fmaf(cie.z, dxyz.z, fmaf(cie.y, dxyz.y, cie.x * dxyz.x));
+        }
+        const f3 xyz = spectrum_to_xyz(value, s.wav);
+        if (!((xyz.x >= -1e-5f) && (xyz.y >= -1e-5f) && (xyz.z >= -1e-5f) && isfinite(xyz.x) && isfinite(xyz.y) && isfinite(xyz.z))) continue;
+        for (int v = 0; v < n; ++v) {
+            const EmitterUseS &r = use[v];
+            Spec4 ae, an;
+#pragma unroll
+            for (int w = 0; w < kWav; ++w) { ae.v[w] = r.ce.v[w] * delta.v[w]; an.v[w] = r.cn.v[w] * delta.v[w]; }
+            scatter_emitter_use(P.sv, s.wav, r.eme, r.uve, ae, A.grad_env, A.grad_emitter ? s_em : nullptr);
+            scatter_emitter_use(P.sv, s.wav, r.emn, r.uvn, an, A.grad_env, A.grad_emitter ? s_em : nullptr);
+        }
+    }
+    __syncthreads();
+    if (A.grad_emitter)
+        for (uint32_t i = threadIdx.x; i < 4u * min(P.sv.n_emitters, 32u); i += kBlock)
+            if (s_em[i] != 0.0f) atomicAdd(A.grad_emitter + i, s_em[i]);
+}
+
+hipError_t launch_adjoint_spectral_emitters(const AdjointParams &a, hipStream_t s) {
+    const size_t lds = bounce_lds_bytes(a.rp.sv);
+    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral_emitters<true>), lds)) return e;
+    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral_emitters<false>), lds)) return e;
+    return launch_adjoint_kernel<k_adjoint_spectral_emitters<true>, k_adjoint_spectral_emitters<false>>(a, s);
+}
+
+// out[i] += Jn_i^T gc_i + sel_i gs_i for n emitter colours: rows[4 i] = (gc, gs) of colour i, jac[12 i + 3 ch + j] = d coeff_j / d rgb_ch
+// (centred basis) and jac[12 i + 9 + ch] = d scale / d rgb_ch (2 for the channel that attains the maximum, 0 otherwise; all 0 for black)
+__global__ __launch_bounds__(kBlock) void k_emitter_grad_to_rgb(const float *rows, const float *jac, float *out, uint32_t n) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float g0 = rows[4u * i], g1 = rows[4u * i + 1u], g2 = rows[4u * i + 2u], gs = rows[4u * i + 3u];
+    if (g0 == 0.0f && g1 == 0.0f && g2 == 0.0f && gs == 0.0f) return;
+    const float *j = jac + 12u * (size_t) i;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3u * i + c] += fmaf(j[9 + c], gs, fmaf(j[3 * c + 2], g2, fmaf(j[3 * c + 1], g1, j[3 * c] * g0)));
+}
+hipError_t launch_emitter_grad_to_rgb(const float *rows, const float *jac, float *out, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_emitter_grad_to_rgb, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, rows, jac, out, n);
     return hipGetLastError();
 }
 

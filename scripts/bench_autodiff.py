@@ -25,7 +25,11 @@ def main():
                     "(texels through mtsamd_render_adjoint_textures); times one biased iteration and the adjoint kernel alone")
     ap.add_argument("--spectral-replay", action="store_true", help="spectral Cornell box: one backward pass for the red wall's constant "
                     "colour through the path replay (mtsamd_render_adjoint_spectral) and through central differences (six renders)")
+    ap.add_argument("--spectral-emitters", action="store_true", help="spectral scenes under an envmap: HIP-event time of one emitter replay "
+                    "(mtsamd_render_adjoint_spectral_emitters, envmap texels + radiances) next to the primal render of the same description")
     args = ap.parse_args()
+    if args.spectral_emitters:
+        return bench_spectral_emitters(args)
     if args.general:
         return bench_general(args)
     if args.spectral_replay:
@@ -147,6 +151,47 @@ def bench_spectral_replay(args):
         ms, lo, hi, g = out[replay]
         print("spectral cbox %dx%d spp=%d max_depth=3 box filter, red.reflectance.value, backward pass through %s: median %.2f ms (min %.2f, max %.2f) over %d passes; "
               "mean gradient %s" % (args.res, args.res, args.spp, name, ms, lo, hi, args.iters, np.array2string(g, precision=4)))
+
+
+def bench_spectral_emitters(args):
+    """The emitter replay against the primal render of the same description, both timed with HIP events on the current stream: the open
+    Cornell box (flat scene) with a roughplastic block under a 64 x 32 envmap and its area light, and the displaced sphere (hierarchy scene,
+    256 x 512 segments as in the mesh benchmark) under the same map"""
+    import ctypes as C
+    from mitsuba2_amd import _lib as L
+    from mitsuba2_amd.render import _ptr, _stream
+    sky = np.random.RandomState(7).uniform(0.3, 1.2, size=(32, 64, 3)).astype(np.float32)
+    env = {"type": "envmap", "id": "my_envmap", "data": sky, "scale": 0.8}
+    cb = scenes.cornell_box()
+    cb["meshes"] = [m for i, m in enumerate(cb["meshes"]) if i not in (1, 2)]
+    cb["bsdfs"] = list(cb["bsdfs"]) + [{"type": "roughplastic", "alpha": 0.2, "distribution": "ggx", "diffuse_reflectance": [0.5, 0.35, 0.3]}]
+    cb["meshes"][-2] = dict(cb["meshes"][-2], bsdf=len(cb["bsdfs"]) - 1)
+    cb["emitters"] = list(cb["emitters"]) + [env]
+    ball = scenes.bumpy_sphere(256, 512)
+    ball["emitters"] = list(ball["emitters"]) + [env]
+    for name, sd, p in (("open cbox + roughplastic block", cb, scenes.cornell_box_sensor(args.res, args.res, args.spp, max_depth=6, rfilter="box")),
+                        ("bumpy_sphere(256, 512)", ball, dict(scenes.bumpy_sphere_sensor(96, 64, args.spp), max_depth=6))):
+        sensor = render.make_sensor(p)
+        scene = render.Scene(sd, variant="spectral", sensor=sensor, integrator=render.PathIntegrator(max_depth=6))
+        d = autodiff._desc(scene, sensor, scene.integrator(), None, 1)
+        film = autodiff._render_film(scene, d)
+        dimage = torch.from_numpy(np.random.RandomState(1).randn(p["height"] * p["width"] * 3).astype(np.float32)).cuda()
+        g_em = torch.zeros((len(sd["emitters"]), 3), device="cuda")
+        g_env = torch.zeros(sky.shape, device="cuda")
+        scratch = torch.zeros_like(film)
+        calls = {"primal render": lambda: L.check(L.lib().mtsamd_render(scene._handle, C.byref(d), _ptr(scratch), None, _stream())),
+                 "emitter replay": lambda: L.check(L.lib().mtsamd_render_adjoint_spectral_emitters(scene._handle, C.byref(d), _ptr(dimage), _ptr(film), _ptr(g_em), _ptr(g_env), _stream()))}
+        for what, call in calls.items():
+            times = []
+            for it in range(3 + args.iters):
+                scratch.zero_()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); call(); b.record()
+                torch.cuda.synchronize()
+                if it >= 3:
+                    times.append(a.elapsed_time(b))
+            print("spectral %s %dx%d spp=%d max_depth=6, 64x32 envmap + area light, %s: median %.3f ms (min %.3f, max %.3f) over %d runs"
+                  % (name, p["width"], p["height"], args.spp, what, float(np.median(times)), float(np.min(times)), float(np.max(times)), args.iters))
 
 
 if __name__ == "__main__":
