@@ -145,6 +145,49 @@ typedef struct {
 MTSAMD_API int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene **out);
 MTSAMD_API void mtsamd_scene_destroy(mtsamd_scene *scene);
 
+/* ---- tabulated and analytic spectra (spectral variant) -----------------------
+ * The spectrum plugins a spectral parameter may hold besides `srgb` / `uniform`:
+ *   REGULAR    src/spectra/regular.cpp: `size` values at equal spacing over [lambda_min, lambda_max], evaluated as
+ *              ContinuousDistribution::eval_pdf (include/mitsuba/core/distr_1d.h:378-393); `d65` (src/spectra/d65.cpp:44-66) is the
+ *              95-entry table over 360..830 nm with values data[i] * (scale / 10568), expanded by the host
+ *   IRREGULAR  src/spectra/irregular.cpp: `size` (wavelengths, values) nodes, IrregularContinuousDistribution::eval_pdf (distr_1d.h:655-677)
+ *   BLACKBODY  src/spectra/blackbody.cpp:46-83: Planck's law at `temperature` kelvin, 0 outside 360..830 nm; emitters only
+ * All are 0 outside their range.  The XML loader creates the first two from `<spectrum value="400:0.1, 500:0.7"/>` and
+ * `<spectrum filename=.../>` (src/libcore/xml.cpp:1084-1125).  Arrays are host pointers, copied by the call. */
+typedef enum { MTSAMD_SPECTRUM_REGULAR = 0, MTSAMD_SPECTRUM_IRREGULAR = 1, MTSAMD_SPECTRUM_BLACKBODY = 2 } mtsamd_spectrum_type;
+typedef struct {
+    int32_t type;              /* mtsamd_spectrum_type */
+    uint32_t size;             /* REGULAR / IRREGULAR: number of entries, >= 2 */
+    float lambda_min, lambda_max;      /* REGULAR: lambda_min < lambda_max (distr_1d.h:299) */
+    const float *wavelengths;  /* IRREGULAR: `size` strictly increasing nodes (distr_1d.h:605); otherwise ignored */
+    const float *values;       /* REGULAR / IRREGULAR: `size` non-negative values */
+    float temperature;         /* BLACKBODY */
+} mtsamd_spectrum_desc;
+/* Binds spectrum `spectrum` of the call to one parameter: of BSDF record `index` -- param = MTSAMD_PARAM_REFLECTANCE (diffuse.reflectance,
+ * (rough)plastic.diffuse_reflectance), SPECULAR_REFLECTANCE, SPECULAR_TRANSMITTANCE (dielectrics), ETA or K (conductors); children of
+ * blendbsdf / mask are records of their own -- or the radiance / intensity / irradiance of emitter `index` (param ignored), which then IS
+ * that spectrum: it is not multiplied by D65 as an `srgb_d65` colour is (src/spectra/srgb_d65.cpp:54-62).  The value the description
+ * holds for a bound parameter is ignored.  Not bindable: blendbsdf / mask weights, textured reflectances, envmaps, dielectric IORs. */
+typedef enum { MTSAMD_SPECTRUM_TARGET_BSDF = 0, MTSAMD_SPECTRUM_TARGET_EMITTER = 1 } mtsamd_spectrum_target;
+typedef struct {
+    int32_t target;            /* mtsamd_spectrum_target */
+    uint32_t index;            /* bsdf record / emitter */
+    int32_t param;             /* mtsamd_bsdf_param (BSDF targets) */
+    uint32_t spectrum;         /* index into `spectra` */
+} mtsamd_spectrum_binding;
+/* mtsamd_scene_create for a scene whose parameters hold such spectra (what the reference's loader builds when the variant is spectral,
+ * xml.cpp:1111-1125); mtsamd_scene_create is its case of no spectra.  Errors carry the reference's messages where it has them
+ * (distr_1d.h:296-339, 564-618); a spectrum in an RGB-variant scene and a blackbody on a BSDF are refused.  Texture::mean() of a table --
+ * its trapezoid integral / (830 - 360), regular.cpp:99-101, irregular.cpp:111-113 -- feeds the plastic lobe weights (plastic.cpp:170-175).
+ * The setters below refuse a parameter that holds a spectrum, and the spectral adjoint entry points refuse such a scene. */
+MTSAMD_API int mtsamd_scene_create_with_spectra(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
+                                     const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, int device, mtsamd_scene **out);
+/* Texture::eval of one spectrum (regular.cpp:68-75, irregular.cpp:76-83, blackbody.cpp:64-83) at n wavelengths: runs the device function
+ * the render kernels call.  lambda_dev / out_dev: n floats on the device.  Returns when out_dev is complete. */
+MTSAMD_API int mtsamd_spectrum_eval(const mtsamd_spectrum_desc *desc, uint64_t n, const float *lambda_dev, float *out_dev, void *stream);
+/* Texture::mean() of a REGULAR / IRREGULAR spectrum (regular.cpp:99-101, irregular.cpp:111-113).  Host only. */
+MTSAMD_API int mtsamd_spectrum_mean(const mtsamd_spectrum_desc *desc, float *mean);
+
 /* Scene::bbox (include/mitsuba/render/scene.h): out6 = min xyz, max xyz (host). */
 MTSAMD_API int mtsamd_scene_bbox(const mtsamd_scene *scene, float *out6);
 /* Scene info: out[0]=primitive count, [1]=BVH node count, [2]=BVH depth, [3]=shape count,

@@ -48,6 +48,15 @@ class SceneDesc(C.Structure):
                 ("spectral", C.c_int32), ("rgb2spec_path", C.c_char_p)]
 
 
+class SpectrumDesc(C.Structure):
+    _fields_ = [("type", C.c_int32), ("size", C.c_uint32), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
+                ("wavelengths", f32p), ("values", f32p), ("temperature", C.c_float)]
+
+
+class SpectrumBinding(C.Structure):
+    _fields_ = [("target", C.c_int32), ("index", C.c_uint32), ("param", C.c_int32), ("spectrum", C.c_uint32)]
+
+
 class Rays(C.Structure):
     _fields_ = [(n, vp) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "mint", "maxt", "active")]
 
@@ -74,6 +83,10 @@ SYMBOLS = {
     "plugin_name": (C.c_char_p, []),
     "plugin_descr": (C.c_char_p, []),
     "mtsamd_scene_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.POINTER(vp)]),
+    "mtsamd_scene_create_with_spectra": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SpectrumDesc), C.c_uint32, C.POINTER(SpectrumBinding), C.c_uint32,
+                                                   C.c_int, C.POINTER(vp)]),
+    "mtsamd_spectrum_eval": (C.c_int, [C.POINTER(SpectrumDesc), C.c_uint64, vp, vp, vp]),
+    "mtsamd_spectrum_mean": (C.c_int, [C.POINTER(SpectrumDesc), f32p]),
     "mtsamd_scene_destroy": (None, [vp]),
     "mtsamd_scene_bbox": (C.c_int, [vp, f32p]),
     "mtsamd_scene_info": (C.c_int, [vp, u32p]),

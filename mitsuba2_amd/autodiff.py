@@ -55,12 +55,16 @@ class ParameterMap:
         # and the emitter family (envmap texels; radiance / intensity / irradiance of every other emitter) by
         # mtsamd_render_adjoint_spectral_emitters
         self._replay = bool(replay) and _is_spectral(scene)
+        if self._replay and getattr(scene, "_n_spectra", 0):      # what mtsamd_render_adjoint_spectral* would answer at the first backward pass
+            raise RuntimeError("the spectral adjoint does not replay scenes with tabulated spectra (%u bound here): node values are not "
+                               "differentiated" % scene._n_spectra)
         self.rebuild_envmap_distribution = True      # what parameters_changed() does (envmap.cpp:220-253); False: tests of linearity
         self.fd_step = 0.0                           # BSDF-model parameters: step of the central difference of the model code (0: 1 % of the value)
         self.properties = {}
         self._kind = {}
         dev = torch.device("cuda", scene._device_index)
         emitters = scene._dict.get("emitters", [])
+        from . import emitters as E
         # 'my_envmap.data' (envmap.cpp:214-218): differentiable in any scene (any BSDF).  Layout: (H, W, 3) linear RGB here; the
         # reference's traverse() exposes the flat H * W * 4 buffer of its bitmap (RGB + a padding channel that carries no parameter,
         # envmap.cpp:216): a script written like invert_bunny.py reshapes with .reshape(H, W, 4)[..., :3] ("parity unpinned": no
@@ -84,8 +88,8 @@ class ParameterMap:
             refl = b["reflectance"]
             if isinstance(refl, dict) and refl.get("type") != "bitmap":
                 continue                  # procedural textures have no differentiable texels
-            if _is_spectral(scene) and (isinstance(refl, dict) or b.get("uniform_mask", 0) & 1):
-                continue                  # spectral variant: constants that are srgb colours only (_spectral_gradient)
+            if _is_spectral(scene) and (isinstance(refl, dict) or b.get("uniform_mask", 0) & 1 or 0 in b.get("spectra", {})):
+                continue                  # spectral variant: constants that are srgb colours only (_spectral_gradient), no tabulated spectra
             if isinstance(refl, dict):
                 key = name + ".reflectance.data"
                 self.properties[key] = torch.as_tensor(refl["data"], dtype=torch.float32, device=dev).clone()
@@ -109,8 +113,8 @@ class ParameterMap:
                 src = b["reflectance"] if kind == 0 else b[pname]
                 if isinstance(src, dict):
                     continue              # textured: no constant parameter
-                if _is_spectral(scene) and (kind in (2, 3) or (b.get("uniform_mask", 0) >> {0: 0, 1: 1, 5: 2}[kind]) & 1):
-                    continue              # spectral variant: eta / k and `uniform` spectra are not srgb colours
+                if _is_spectral(scene) and (kind in (2, 3) or (b.get("uniform_mask", 0) >> {0: 0, 1: 1, 5: 2}[kind]) & 1 or kind in b.get("spectra", {})):
+                    continue              # spectral variant: eta / k, `uniform` and tabulated spectra are not srgb colours
                 key = "%s.%s.value" % (name, pname)
                 self.properties[key] = torch.as_tensor([float(x) for x in src], dtype=torch.float32, device=dev)
                 self._kind[key] = ("bsdf_param", flat_index, kind)
@@ -131,17 +135,20 @@ class ParameterMap:
             e = m.get("emitter", -1)
             if e is None or e < 0 or scene._dict["emitters"][e].get("type", "area") != "area":
                 continue
+            if _is_spectral(scene) and E.normalize(scene._dict["emitters"][e]).get("spectrum") is not None:
+                continue                  # the radiance holds a tabulated spectrum: not an srgb_d65 colour, no key
             key = m.get("id", "shape_%d" % i) + ".emitter.radiance.value"
-            rad = np.broadcast_to(np.asarray(scene._dict["emitters"][e]["radiance"], np.float32), (3,))
+            rad = np.broadcast_to(np.asarray(E.normalize(scene._dict["emitters"][e])["radiance"], np.float32), (3,))      # (RGB variant: a spectrum plugin's pre-integrated colour)
             self.properties[key] = torch.as_tensor(rad.copy(), dtype=torch.float32, device=dev)
             self._kind[key] = ("emitter", e, i)
         # spectral variant with `replay`: the emitted colour of the emitters that have no shape -- `constant`, `point`, `spot`, `directional` --
         # under their own id ('<emitter>.radiance.value', '.intensity.value', '.irradiance.value').  Area lights keep the keys above
-        from . import emitters as E
         for e, em in enumerate(emitters if self._replay else []):
             t = em.get("type", "area")
             if t in ("envmap", "area"):
                 continue
+            if E.normalize(em).get("spectrum") is not None:
+                continue                  # (a scene with spectra refuses the replay above; kept for the day it does not)
             key = "%s.%s.value" % (em.get("id", "emitter_%d" % e), E._VALUE_KEY[t])
             self.properties[key] = torch.as_tensor(E.normalize(em)["radiance"], dtype=torch.float32, device=dev)
             self._kind[key] = ("emitter", e, e)

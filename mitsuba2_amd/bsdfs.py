@@ -41,6 +41,30 @@ def _is_uniform(v, default):
     return isinstance(v, (int, float)) and not isinstance(v, bool)
 
 
+# parameter -> mtsamd_bsdf_param of the spectrum binding (include/mtsamd.h)
+SPECTRUM_PARAMS = {"reflectance": 0, "diffuse_reflectance": 0, "specular_reflectance": 1, "eta": 2, "k": 3, "specular_transmittance": 5}
+
+
+def _take_spectra(b):
+    """Splits the spectrum-valued parameters off a plugin dictionary: a parameter may be a spectrum plugin (`regular`, `irregular`,
+    `d65`, `blackbody`: src/spectra/*.cpp; or the loader's `spectrum` form), and a loaded XML scene carries the spectra of its
+    wavelength:value properties under `spectra` beside their pre-integrated colours (as `spectrum` dictionaries, parsed only by a spectral
+    scene).  Returns the dictionary with such parameters replaced by the colour an RGB-variant scene uses (spectrum.to_rgb) and
+    {parameter: spectrum}."""
+    from . import spectrum as S
+    spectra = dict(b.get("spectra", {}))
+    if not spectra and not any(S.is_spectrum(v) for v in b.values()):
+        return b, {}
+    b = {k: v for k, v in b.items() if k != "spectra"}
+    for key in SPECTRUM_PARAMS:
+        if S.is_spectrum(b.get(key)):
+            spectra[key] = S.parse(b[key])
+            if spectra[key]["kind"] == "blackbody":
+                raise RuntimeError('%s: a blackbody spectrum is an emission spectrum, not a BSDF parameter' % key)
+            b[key] = S.to_rgb(spectra[key], False, key)
+    return b, spectra
+
+
 def _rgb(v, default):
     if v is None:
         v = default
@@ -75,6 +99,9 @@ def _normalize_nesting(b, t):
     a constant or a texture.  This backend nests one level: the children are plain BSDFs (their reflectance may be a `bitmap` /
     `checkerboard` texture in the RGB variant)."""
     pname = "weight" if t == "blendbsdf" else "opacity"
+    from . import spectrum as S
+    if b.get("spectra") or S.is_spectrum(b.get(pname)):       # a loaded wavelength:value weight carries its spectrum beside the colour
+        raise RuntimeError("%s: '%s' is a scalar (Texture::eval_1): a constant or a texture, not a spectrum" % (t, pname))
     bsdf_types = set(TYPE_IDS) | set(NESTING) | {"twosided"}
     children = [v for k, v in b.items() if k not in ("type", "id", pname) and isinstance(v, dict) and v.get("type", "diffuse") in bsdf_types]
     extra = [k for k, v in b.items() if k not in ("type", "id", pname) and not (isinstance(v, dict) and v.get("type", "diffuse") in bsdf_types)]
@@ -150,12 +177,22 @@ def normalize(b):
     if t not in TYPE_IDS:
         raise RuntimeError("BSDF plugin '%s' is not supported by this backend (diffuse, conductor, roughconductor, dielectric, roughdielectric, thindielectric, plastic, roughplastic, twosided, blendbsdf, mask)" % t)
     tid = TYPE_IDS[t]
+    b, spectra = _take_spectra(b)
     out = dict(type=tid, twosided=twosided, reflectance=[0.5, 0.5, 0.5], specular_reflectance=[1.0] * 3, specular_transmittance=[1.0] * 3,
                eta=[0.0] * 3, k=[1.0] * 3, int_ior=1.0, ext_ior=1.0, alpha_u=0.1, alpha_v=0.1, distribution=0, sample_visible=True,
                nonlinear=False, uniform_mask=0)
     if "id" in b:
         out["id"] = b["id"]
     known = {"type", "id"}
+    allowed = {DIFFUSE: ("reflectance",), CONDUCTOR: ("eta", "k", "specular_reflectance"), ROUGHCONDUCTOR: ("eta", "k", "specular_reflectance"),
+               DIELECTRIC: ("specular_reflectance", "specular_transmittance"), ROUGHDIELECTRIC: ("specular_reflectance", "specular_transmittance"),
+               THINDIELECTRIC: ("specular_reflectance", "specular_transmittance"), PLASTIC: ("diffuse_reflectance", "specular_reflectance"),
+               ROUGHPLASTIC: ("diffuse_reflectance", "specular_reflectance")}[tid]
+    for key, spec in spectra.items():
+        if key not in allowed:
+            raise RuntimeError('%s: "%s" takes no spectrum in this backend (spectra stand for %s)' % (t, key, ", ".join(allowed)))
+    if spectra:      # spectral variant: bound to the parameter (render.Scene); RGB variant: the pre-integrated colour under the parameter's key
+        out["spectra"] = {SPECTRUM_PARAMS[key]: spec for key, spec in spectra.items()}
     if tid == DIFFUSE:
         refl = b.get("reflectance", 0.5)                  # props.texture("reflectance", .5f): a uniform spectrum (diffuse.cpp:74)
         out["reflectance"] = refl if isinstance(refl, dict) else _rgb(refl, None)
@@ -168,7 +205,7 @@ def normalize(b):
                 raise RuntimeError("Should specify either (eta, k) or material, not both.")
             out["eta"], out["k"] = _rgb(b.get("eta"), 0.0), _rgb(b.get("k"), 1.0)
         else:
-            raise RuntimeError('conductor material "%s": the measured IOR tables (data/ior/*.spd) are not shipped; specify eta and k' % material)
+            raise RuntimeError('conductor material "%s": the measured IOR tables (data/ior/*.spd) are not shipped; specify eta and k (constants, or spectra in the spectral variant, e.g. {"type": "spectrum", "filename": "<material>.eta.spd"})' % material)
         out["specular_reflectance"] = _rgb(b.get("specular_reflectance"), 1.0)
         out["uniform_mask"] |= 2 if _is_uniform(b.get("specular_reflectance"), 1.0) else 0
         known |= {"material", "eta", "k", "specular_reflectance"}

@@ -413,6 +413,105 @@ static void emitter_jacobian_row(const Rgb2Spec &model, const float rgb[3], floa
     }
 }
 
+// ---- tabulated / analytic spectra (mtsamd_spectrum_desc) ------------------------------------------
+// the checks of ContinuousDistribution::update (distr_1d.h:293-345) and IrregularContinuousDistribution::update (distr_1d.h:561-622), with
+// their messages; *integral (may be null): the trapezoid integral both compute in double
+static int check_spectrum(const mtsamd_spectrum_desc &sp, uint32_t index, double *integral) {
+    if (integral) *integral = 0.0;
+    if (sp.type == MTSAMD_SPECTRUM_BLACKBODY) {
+        if (!(sp.temperature > 0.0f) || !std::isfinite(sp.temperature)) return fail(MTSAMD_ERR_INVALID, "spectrum %u: blackbody needs a positive temperature", index);
+        return MTSAMD_OK;
+    }
+    if (sp.type != MTSAMD_SPECTRUM_REGULAR && sp.type != MTSAMD_SPECTRUM_IRREGULAR) return fail(MTSAMD_ERR_INVALID, "spectrum %u: unknown type %d", index, sp.type);
+    const bool regular = sp.type == MTSAMD_SPECTRUM_REGULAR;
+    const char *cls = regular ? "ContinuousDistribution" : "IrregularContinuousDistribution";
+    if (sp.size < 2) return fail(MTSAMD_ERR_INVALID, "%s: needs at least two entries!", cls);
+    if (!sp.values || (!regular && !sp.wavelengths)) return fail(MTSAMD_ERR_INVALID, "spectrum %u: null array", index);
+    if (regular && !(sp.lambda_min < sp.lambda_max)) return fail(MTSAMD_ERR_INVALID, "ContinuousDistribution: invalid range!");
+    const double interval = regular ? ((double) sp.lambda_max - (double) sp.lambda_min) / (sp.size - 1) : 0.0;
+    double sum = 0.0; bool mass = false;
+    for (uint32_t i = 0; i + 1 < sp.size; ++i) {
+        const double y0 = (double) sp.values[i], y1 = (double) sp.values[i + 1];
+        double dx = interval;
+        if (!regular) {
+            const double x0 = (double) sp.wavelengths[i], x1 = (double) sp.wavelengths[i + 1];
+            if (!(x1 > x0)) return fail(MTSAMD_ERR_INVALID, "IrregularContinuousDistribution: node positions must be strictly increasing!");
+            dx = x1 - x0;
+        }
+        const double value = 0.5 * dx * (y0 + y1);
+        sum += value;
+        if (!(y0 >= 0.0) || !(y1 >= 0.0)) return fail(MTSAMD_ERR_INVALID, "%s: entries must be non-negative!", cls);
+        mass = mass || value > 0.0;
+    }
+    if (!mass) return fail(MTSAMD_ERR_INVALID, "%s: no probability mass found!", cls);
+    if (integral) *integral = sum;
+    return MTSAMD_OK;
+}
+// Texture::mean() of a table: integral / (MTS_WAVELENGTH_MAX - MTS_WAVELENGTH_MIN) (regular.cpp:99-101, irregular.cpp:111-113)
+static float spectrum_table_mean(double integral) { return (float) integral / (830.0f - 360.0f); }
+
+// headers + node / value arrays of a spectrum pool (device_spectral.h); the descs have passed check_spectrum
+static void build_spectrum_pool(const mtsamd_spectrum_desc *spectra, uint32_t n, std::vector<DevSpectrum> &headers, std::vector<float> &data) {
+    headers.assign(n, DevSpectrum{});
+    data.clear();
+    for (uint32_t i = 0; i < n; ++i) {
+        const mtsamd_spectrum_desc &sp = spectra[i];
+        DevSpectrum &h = headers[i];
+        if (sp.type == MTSAMD_SPECTRUM_BLACKBODY) { h.kind = kSpectrumBlackbody; h.temperature = sp.temperature; continue; }
+        h.size = sp.size;
+        if (sp.type == MTSAMD_SPECTRUM_REGULAR) {
+            h.kind = kSpectrumRegular; h.lambda_min = sp.lambda_min; h.lambda_max = sp.lambda_max;
+            const double interval = ((double) sp.lambda_max - (double) sp.lambda_min) / (sp.size - 1);
+            h.inv_interval = (float) (1.0 / interval);
+        } else {
+            h.kind = kSpectrumIrregular; h.lambda_min = sp.wavelengths[0]; h.lambda_max = sp.wavelengths[sp.size - 1];
+            h.nodes = (uint32_t) data.size();
+            data.insert(data.end(), sp.wavelengths, sp.wavelengths + sp.size);
+        }
+        h.values = (uint32_t) data.size();
+        data.insert(data.end(), sp.values, sp.values + sp.size);
+    }
+}
+// which spectrum slot of a record a mtsamd_bsdf_param names, or -1 if a record of this type has no such spectral parameter
+static int bsdf_spectrum_slot(int32_t type, int32_t param) {
+    const bool conductor = type == MTSAMD_BSDF_CONDUCTOR || type == MTSAMD_BSDF_ROUGHCONDUCTOR;
+    const bool dielectric = type == MTSAMD_BSDF_DIELECTRIC || type == MTSAMD_BSDF_ROUGHDIELECTRIC || type == MTSAMD_BSDF_THINDIELECTRIC;
+    const bool plastic = type == MTSAMD_BSDF_PLASTIC || type == MTSAMD_BSDF_ROUGHPLASTIC;
+    switch (param) {
+    case MTSAMD_PARAM_REFLECTANCE: return (type == MTSAMD_BSDF_DIFFUSE || plastic) ? kSpecRefl : -1;
+    case MTSAMD_PARAM_SPECULAR_REFLECTANCE: return (conductor || dielectric || plastic) ? kSpecSpec : -1;
+    case MTSAMD_PARAM_SPECULAR_TRANSMITTANCE: return dielectric ? kSpecTrans : -1;
+    case MTSAMD_PARAM_ETA: return conductor ? kSpecEta : -1;
+    case MTSAMD_PARAM_K: return conductor ? kSpecK : -1;
+    default: return -1;
+    }
+}
+static int check_spectrum_bindings(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
+                                   const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, std::vector<double> &integrals) {
+    if ((n_spectra && !spectra) || (n_bindings && !bindings)) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_create_with_spectra: null argument");
+    if ((n_spectra || n_bindings) && !desc->spectral)
+        return fail(MTSAMD_ERR_UNSUPPORTED, "tabulated spectra need the spectral variant (the RGB variants pre-integrate them on the host, xml.cpp:1126-1143)");
+    if (n_spectra > kMaxSpectra) return fail(MTSAMD_ERR_UNSUPPORTED, "at most %u spectra per scene (got %u)", kMaxSpectra, n_spectra);
+    integrals.assign(n_spectra, 0.0);
+    for (uint32_t i = 0; i < n_spectra; ++i)
+        if (int rc = check_spectrum(spectra[i], i, &integrals[i])) return rc;
+    for (uint32_t i = 0; i < n_bindings; ++i) {
+        const mtsamd_spectrum_binding &b = bindings[i];
+        if (b.spectrum >= n_spectra) return fail(MTSAMD_ERR_INVALID, "binding %u: spectrum index %u out of range", i, b.spectrum);
+        if (b.target == MTSAMD_SPECTRUM_TARGET_BSDF) {
+            if (b.index >= desc->bsdf_count) return fail(MTSAMD_ERR_INVALID, "binding %u: bsdf index %u out of range", i, b.index);
+            if (spectra[b.spectrum].type == MTSAMD_SPECTRUM_BLACKBODY) return fail(MTSAMD_ERR_INVALID, "binding %u: a blackbody spectrum is an emission spectrum, not a BSDF parameter", i);
+            const mtsamd_bsdf_desc &bd = desc->bsdfs[b.index];
+            if (bsdf_spectrum_slot(bd.type, b.param) < 0 || (b.param == MTSAMD_PARAM_REFLECTANCE && bd.texture >= 0))
+                return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: bsdf %u (type %d) takes no spectrum for parameter %d (texture weights, textured reflectances and dielectric IORs are not spectra)", i, b.index, bd.type, b.param);
+        } else if (b.target == MTSAMD_SPECTRUM_TARGET_EMITTER) {
+            if (b.index >= desc->emitter_count) return fail(MTSAMD_ERR_INVALID, "binding %u: emitter index %u out of range", i, b.index);
+            if (desc->emitters[b.index].type == MTSAMD_EMITTER_ENVMAP) return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: an envmap takes no spectrum", i);
+        } else return fail(MTSAMD_ERR_INVALID, "binding %u: unknown target %d", i, b.target);
+    }
+    return MTSAMD_OK;
+}
+
 struct mtsamd_scene {
     int32_t environment = -1;        // index of the `constant` emitter
     bool general_bsdfs = false;      // any BSDF other than one-sided `diffuse`: the kernels with the BSDF switch are used
@@ -489,8 +588,15 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
 }
 
 int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene **out) {
+    return mtsamd_scene_create_with_spectra(desc, nullptr, 0, nullptr, 0, device, out);
+}
+
+int mtsamd_scene_create_with_spectra(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
+                                     const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, int device, mtsamd_scene **out) {
     if (!desc || !out) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_create: null argument");
     *out = nullptr;
+    std::vector<double> spectrum_integrals;      // host-only checks first: they need no device
+    if (int rc = check_spectrum_bindings(desc, spectra, n_spectra, bindings, n_bindings, spectrum_integrals)) return rc;
     // an empty scene is valid (it renders to zeros: scenes.py:262-267 of the reference's integrator tests)
     if (desc->mesh_count > 0 && !desc->meshes) return fail(MTSAMD_ERR_INVALID, "scene has no shapes");
     if (desc->mesh_count > 0 && (desc->bsdf_count == 0 || !desc->bsdfs)) return fail(MTSAMD_ERR_INVALID, "scene has no BSDFs");
@@ -542,9 +648,14 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
     for (uint32_t b = 0; b < desc->bsdf_count; ++b) {
         const mtsamd_bsdf_desc &bd = desc->bsdfs[b];
         if (bd.type < MTSAMD_BSDF_DIFFUSE || bd.type > MTSAMD_BSDF_MASK) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: unknown BSDF type %d", b, bd.type);
+        auto bound = [&](int32_t param) {       // the parameter holds a tabulated spectrum: its value in the description is ignored
+            for (uint32_t i = 0; i < n_bindings; ++i)
+                if (bindings[i].target == MTSAMD_SPECTRUM_TARGET_BSDF && bindings[i].index == b && bindings[i].param == param) return true;
+            return false;
+        };
         if (desc->spectral && (bd.type == MTSAMD_BSDF_CONDUCTOR || bd.type == MTSAMD_BSDF_ROUGHCONDUCTOR) &&
-            (bd.eta[0] != bd.eta[1] || bd.eta[0] != bd.eta[2] || bd.k[0] != bd.k[1] || bd.k[0] != bd.k[2]))
-            return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: the spectral variant needs uniform (constant) eta and k spectra", b);
+            ((!bound(MTSAMD_PARAM_ETA) && (bd.eta[0] != bd.eta[1] || bd.eta[0] != bd.eta[2])) || (!bound(MTSAMD_PARAM_K) && (bd.k[0] != bd.k[1] || bd.k[0] != bd.k[2]))))
+            return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: the spectral variant needs uniform (constant) eta and k spectra, or tabulated ones (mtsamd_scene_create_with_spectra)", b);
         if (bd.texture >= 0 && bd.type != MTSAMD_BSDF_DIFFUSE && bd.type != MTSAMD_BSDF_PLASTIC && bd.type != MTSAMD_BSDF_ROUGHPLASTIC &&
             bd.type != MTSAMD_BSDF_BLEND && bd.type != MTSAMD_BSDF_MASK)
             return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: textures are implemented for diffuse.reflectance and (rough)plastic.diffuse_reflectance only", b);
@@ -719,6 +830,11 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
                 if (d.type == kBsdfBlend || d.type == kBsdfMask) break;   // the weight is a scalar; the children are records of their own
                 if (p == 0 && d.texture >= 0) continue;               // textured: coefficients per texel, mean from the texture (below)
                 if (bd.uniform_mask & (1 << p)) { means[p] = vals[p][0]; continue; }
+                bool tabulated = false;               // a bound spectrum (below) replaces the colour: no range check, no coefficients
+                for (uint32_t i = 0; i < n_bindings; ++i)
+                    tabulated = tabulated || (bindings[i].target == MTSAMD_SPECTRUM_TARGET_BSDF && bindings[i].index == b &&
+                                              bsdf_spectrum_slot(bd.type, bindings[i].param) == p);
+                if (tabulated) continue;
                 const float *c = vals[p];
                 if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] > 1 || c[1] > 1 || c[2] > 1) {
                     delete s;
@@ -739,6 +855,21 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
             s->diff_mean[b] = means[0];
         }
     }
+    // bound spectra replace the colour / constant of their parameter; Texture::mean() of the two reflectances feeds the plastic lobe weights
+    for (uint32_t i = 0; i < n_bindings; ++i) {
+        const mtsamd_spectrum_binding &bn = bindings[i];
+        if (bn.target != MTSAMD_SPECTRUM_TARGET_BSDF) continue;
+        DevBsdf &d = s->bsdfs[bn.index];
+        const int slot = bsdf_spectrum_slot(desc->bsdfs[bn.index].type, bn.param);
+        uint32_t &word = slot < 3 ? d.spectra0 : d.spectra1;
+        const int shift = 10 * (slot < 3 ? slot : slot - 3);
+        word = (word & ~(1023u << shift)) | ((bn.spectrum + 1u) << shift);
+        const float mean = spectrum_table_mean(spectrum_integrals[bn.spectrum]);
+        if (slot == kSpecRefl) s->diff_mean[bn.index] = mean;
+        if (slot == kSpecSpec) spec_mean[bn.index] = mean;
+        if (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic) d.kr = spec_mean[bn.index] / (s->diff_mean[bn.index] + spec_mean[bn.index]);
+    }
+    if (n_spectra) s->general_bsdfs = true;       // the spectrum pool is read by the general step
 
     for (uint32_t t = 0; t < desc->texture_count; ++t) {
         const mtsamd_texture_desc &td = desc->textures[t];
@@ -840,6 +971,9 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
         e.radius = std::max(kRayEpsilon, r * (1.0f + kRayEpsilon));
     }
 
+    for (uint32_t i = 0; i < n_bindings; ++i)       // a tabulated radiance is the radiance itself (no D65 factor)
+        if (bindings[i].target == MTSAMD_SPECTRUM_TARGET_EMITTER) s->emitters[bindings[i].index].spectrum = bindings[i].spectrum + 1u;
+
     std::vector<float4> nodes(4 * (size_t) s->bvh.n_nodes), tris(3 * (size_t) s->bvh.n_slots);
     std::memcpy(nodes.data(), s->bvh.nodes.data(), s->bvh.nodes.size() * sizeof(float));
     std::vector<uint4> qnodes(2 * (size_t) s->bvh.n_nodes);
@@ -901,10 +1035,22 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
             ++n_clusters; k0 = k1;
         }
     }
+    // the BSDF records, and behind them the spectrum pool: headers, then node / value arrays (spectrum_pool() in kernels.hip)
+    std::vector<DevBsdf> bsdf_block = s->bsdfs;
+    if (n_spectra) {
+        std::vector<DevSpectrum> headers; std::vector<float> data;
+        build_spectrum_pool(spectra, n_spectra, headers, data);
+        const size_t bytes = headers.size() * sizeof(DevSpectrum) + data.size() * sizeof(float);
+        bsdf_block.resize(s->bsdfs.size() + (bytes + sizeof(DevBsdf) - 1) / sizeof(DevBsdf));
+        char *dst = reinterpret_cast<char *>(bsdf_block.data() + s->bsdfs.size());
+        std::memset(dst, 0, (bsdf_block.size() - s->bsdfs.size()) * sizeof(DevBsdf));
+        std::memcpy(dst, headers.data(), headers.size() * sizeof(DevSpectrum));
+        if (!data.empty()) std::memcpy(dst + headers.size() * sizeof(DevSpectrum), data.data(), data.size() * sizeof(float));
+    }
     int rc = 0;
     if ((rc = upload(&s->d_textures, s->textures)) || (rc = upload(&s->d_flat, flat_recs)) || (rc = upload(&s->d_pairs, pair_recs)) || (rc = upload(&s->d_nodes, nodes)) || (rc = upload(&s->d_qnodes, qnodes)) || (rc = upload(&s->d_wnodes, wnodes)) || (rc = upload(&s->d_tris, tris)) || (rc = upload(&s->d_tri_pos, tri_pos)) ||
         (rc = upload(&s->d_tri_nrm, tri_nrm)) || (rc = upload(&s->d_tri_uv, tri_uv)) || (rc = upload(&s->d_prim_shape, prim_shape)) ||
-        (rc = upload(&s->d_shapes, shapes)) || (rc = upload(&s->d_bsdfs, s->bsdfs)) || (rc = upload(&s->d_emitters, s->emitters)) ||
+        (rc = upload(&s->d_shapes, shapes)) || (rc = upload(&s->d_bsdfs, bsdf_block)) || (rc = upload(&s->d_emitters, s->emitters)) ||
         (rc = upload(&s->d_area_pmf, area_pmf)) || (rc = upload(&s->d_area_cdf, area_cdf))) {
         mtsamd_scene_destroy(s);
         return rc;
@@ -999,6 +1145,7 @@ int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene 
     v.flat_recs = s->d_flat; v.flat = flat ? 1u : 0u;
     v.general = s->nested_bsdfs ? 2u : (s->general_bsdfs || s->delta_emitters || s->environment >= 0) ? 1u : 0u;       // the diffuse / area-light fast path (kernels.hip) handles none of these
     v.flat_pairs = s->d_pairs; v.n_pairs = n_pairs; v.n_clusters = n_clusters;
+    v.n_spectra = n_spectra;
     if (bounce_lds_bytes(v) > 150 * 1024) {
         mtsamd_scene_destroy(s);
         return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", v.stack_depth);
@@ -1025,6 +1172,7 @@ int mtsamd_scene_info(const mtsamd_scene *s, uint32_t *out6) {
 // (srgb.cpp:31-41, plastic.cpp:170-175).  Parameters given as `uniform` spectra and textured reflectances are not settable this way.
 static int spectral_set_colour(mtsamd_scene *s, uint32_t bsdf, int p, const float *rgb) {
     DevBsdf &d = s->bsdfs[bsdf];
+    if (bsdf_spectrum(d, p)) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: this parameter holds a tabulated spectrum; only srgb colours can be set in the spectral variant", bsdf);
     const uint32_t uniform_flag = p == 0 ? kBsdfUniformRefl : (p == 1 ? kBsdfUniformSpec : kBsdfUniformTrans);
     if (d.type == kBsdfBlend || d.type == kBsdfMask || (d.flags & uniform_flag) || (p == 0 && d.texture >= 0))
         return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: this parameter is a uniform spectrum, a texture or a nesting weight; only srgb colours can be set in the spectral variant", bsdf);
@@ -1119,6 +1267,7 @@ int mtsamd_scene_update_texture(mtsamd_scene *s, uint32_t texture, const float *
 
 int mtsamd_scene_set_emitter_radiance(mtsamd_scene *s, uint32_t emitter, const float *rgb) {
     if (!s || !rgb || emitter >= s->emitters.size()) return fail(MTSAMD_ERR_INVALID, "invalid emitter index");
+    if (s->emitters[emitter].spectrum) return fail(MTSAMD_ERR_UNSUPPORTED, "emitter %u: its radiance holds a tabulated spectrum; only srgb_d65 colours can be set", emitter);
     HIP_TRY(hipSetDevice(s->device));
     s->emitters[emitter].r = rgb[0]; s->emitters[emitter].g = rgb[1]; s->emitters[emitter].b = rgb[2];
     if (s->spectral) {       // srgb_d65 spectrum: normalised colour -> coefficients, the scale rides on the D65 curve (srgb_d65.cpp:31-46)
@@ -2160,6 +2309,8 @@ int mtsamd_scene_set_bsdf_param(mtsamd_scene *s, uint32_t bsdf, int32_t kind, co
             if (!bsdf_param_fields(s->bsdfs[bsdf], kind, 0, f0, f1)) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u (type %d) has no settable parameter of kind %d", bsdf, s->bsdfs[bsdf].type, kind);
             return spectral_set_colour(s, bsdf, kind == MTSAMD_PARAM_REFLECTANCE ? 0 : (kind == MTSAMD_PARAM_SPECULAR_REFLECTANCE ? 1 : 2), value3);
         }
+        if ((kind == MTSAMD_PARAM_ETA || kind == MTSAMD_PARAM_K) && bsdf_spectrum(s->bsdfs[bsdf], kind == MTSAMD_PARAM_ETA ? kSpecEta : kSpecK))
+            return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: this parameter holds a tabulated spectrum and cannot be set to a constant", bsdf);
         if ((kind == MTSAMD_PARAM_ETA || kind == MTSAMD_PARAM_K) && !(value3[0] == value3[1] && value3[1] == value3[2]))
             return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: the spectral variant needs uniform (constant) eta and k spectra", bsdf);
     }
@@ -2233,6 +2384,7 @@ int mtsamd_render_adjoint_spectral(mtsamd_scene *s, const mtsamd_render_desc *d,
                                    float *grad_tex, void *stream_) {
     AdjointParams a{};
     if (int rc = fill_adjoint(s, d, dimage, film, a, true)) return rc;
+    if (s->view.n_spectra) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not replay scenes with tabulated spectra (%u bound here): node values are not differentiated", s->view.n_spectra);
     if (d->max_depth < 1 || d->max_depth > 16)
         return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
     if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle blendbsdf / mask materials");
@@ -2276,6 +2428,7 @@ int mtsamd_render_adjoint_spectral_emitters(mtsamd_scene *s, const mtsamd_render
                                             float *grad_emitters, float *grad_envmap, void *stream_) {
     AdjointParams a{};
     if (int rc = fill_adjoint(s, d, dimage, film, a, true)) return rc;
+    if (s->view.n_spectra) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not replay scenes with tabulated spectra (%u bound here): node values are not differentiated", s->view.n_spectra);
     if (d->max_depth < 1 || d->max_depth > 16)
         return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
     if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle blendbsdf / mask materials");
@@ -2459,6 +2612,33 @@ int mtsamd_libm_eval(int32_t fn, uint64_t n, const float *x, const float *y, flo
     if (n && (!x || !out || (fn == 7 && !y))) return fail(MTSAMD_ERR_INVALID, "libm_eval: null buffer");
     if (n >> 40) return fail(MTSAMD_ERR_INVALID, "libm_eval: too many arguments");
     HIP_TRY(launch_libm_eval(fn, n, x, y, out, (hipStream_t) stream));
+    return MTSAMD_OK;
+}
+
+int mtsamd_spectrum_mean(const mtsamd_spectrum_desc *desc, float *mean) {
+    if (!desc || !mean) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (desc->type == MTSAMD_SPECTRUM_BLACKBODY) return fail(MTSAMD_ERR_UNSUPPORTED, "mean() of a blackbody spectrum is not used by this backend (emitters only)");
+    double integral = 0.0;
+    if (int rc = check_spectrum(*desc, 0, &integral)) return rc;
+    *mean = spectrum_table_mean(integral);
+    return MTSAMD_OK;
+}
+
+int mtsamd_spectrum_eval(const mtsamd_spectrum_desc *desc, uint64_t n, const float *lambda, float *out, void *stream) {
+    if (!desc || (n && (!lambda || !out))) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (int rc = check_spectrum(*desc, 0, nullptr)) return rc;
+    std::vector<DevSpectrum> headers; std::vector<float> data;
+    build_spectrum_pool(desc, 1, headers, data);
+    std::vector<float> block(sizeof(DevSpectrum) / sizeof(float) + data.size());
+    std::memcpy(block.data(), headers.data(), sizeof(DevSpectrum));
+    if (!data.empty()) std::memcpy(block.data() + sizeof(DevSpectrum) / sizeof(float), data.data(), data.size() * sizeof(float));
+    float *d_block = nullptr;
+    HIP_TRY(hipMalloc((void **) &d_block, block.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(d_block, block.data(), block.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_spectrum_eval(reinterpret_cast<const DevSpectrum *>(d_block), d_block + sizeof(DevSpectrum) / sizeof(float), n, lambda, out, (hipStream_t) stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t) stream);      // the pool is freed below
+    (void) hipFree(d_block);
+    if (e != hipSuccess) return fail(MTSAMD_ERR_DEVICE, "mtsamd_spectrum_eval: %s", hipGetErrorString(e));
     return MTSAMD_OK;
 }
 

@@ -203,10 +203,17 @@ struct DevBsdf {
     float sr, sg, sb; uint32_t flags;
     float er, eg, eb, alpha_u;
     float kr, kg, kb, alpha_v;
-    float sc0, sc1, sc2, pad0;               // spectral variant: srgb_model coefficients of specular_reflectance
-    float tc0, tc1, tc2, pad1;               //                   ... of specular_transmittance
+    float sc0, sc1, sc2; uint32_t spectra0;  // spectral variant: srgb_model coefficients of specular_reflectance
+    float tc0, tc1, tc2; uint32_t spectra1;  //                   ... of specular_transmittance
+    // spectra0 / spectra1: 1 + pool index of the spectrum bound to a parameter, 10 bits each, 0 = none (bsdf_spectrum());
+    // spectra0 = reflectance | specular_reflectance << 10 | specular_transmittance << 20, spectra1 = eta | k << 10
     const float *table; uint32_t nested0, nested1;      // roughplastic: external transmittance table (device memory); blend / mask: child records
 };
+constexpr uint32_t kMaxSpectra = 1023u;
+enum { kSpecRefl = 0, kSpecSpec = 1, kSpecTrans = 2, kSpecEta = 3, kSpecK = 4 };
+__host__ __device__ inline uint32_t bsdf_spectrum(const DevBsdf &b, int param) {       // 1 + pool index, or 0
+    return ((param < 3 ? b.spectra0 : b.spectra1) >> (10 * (param < 3 ? param : param - 3))) & 1023u;
+}
 constexpr int kRoughTableRes = 64;           // MTS_ROUGH_TRANSMITTANCE_RES
 
 MTS_DEV float lerp_gather(const float *data, float x, int size) {             // roughplastic.cpp:291-302

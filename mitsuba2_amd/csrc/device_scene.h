@@ -56,7 +56,7 @@ struct DevTexture {
 struct DevEmitter {
     float r, g, b; uint32_t shape;
     uint32_t first_prim, n_prims; float area_sum, area_norm;
-    uint32_t valid_lo, valid_hi; uint32_t pad0, pad1;
+    uint32_t valid_lo, valid_hi; uint32_t pad0, spectrum;      // spectrum: 1 + pool index of a tabulated / analytic radiance (it replaces D65 * srgb_model), 0 = none
     float c0, c1, c2, d65_scale;       // spectral variant: SRGBEmitterSpectrum = D65 * d65_scale * srgb_model(c) (srgb_d65.cpp:27-63)
     float cx, cy, cz, radius;          // constant emitter (pad0 == 1): the scene's bounding sphere (constant.cpp:47-51);
                                        // point / spot: position; directional: radius of the bounding sphere
@@ -105,6 +105,8 @@ struct SceneView {
     int32_t env_emitter;       // index of the environment emitter or -1 (scene.cpp:44-48)
     const DevEnvmap *envmap;   // its image + sampling hierarchy if it is an `envmap`
     uint32_t general;          // some BSDF is not a one-sided `diffuse`: kernels instantiated with the BSDF switch are used
+    uint32_t n_spectra;        // tabulated / analytic spectra bound to parameters (spectral variant): their pool lies behind the n_bsdfs records
+                               // of `bsdfs` (spectrum_pool() in kernels.hip); the word was padding, so that the layout of the kernel arguments stays
 };
 constexpr uint32_t kFlatMaxPrims = 64;
 

@@ -56,6 +56,54 @@ MTS_DEV float table_eval(const float *tbl, float scale, float l) {
     return fmaf(w0, y0, w1 * y1);
 }
 
+// Tabulated and analytic spectra a scene may bind to its spectral parameters (mtsamd_scene_create_with_spectra):
+//   regular    RegularSpectrum (src/spectra/regular.cpp:68-75)     -> ContinuousDistribution::eval_pdf (distr_1d.h:378-393)
+//   irregular  IrregularSpectrum (src/spectra/irregular.cpp:76-83) -> IrregularContinuousDistribution::eval_pdf (distr_1d.h:655-677)
+//   blackbody  BlackBodySpectrum::eval_impl (src/spectra/blackbody.cpp:46-83)
+// (`d65` is a regular table the host expands, d65.cpp:44-66.)  The pool is read-only device memory: n headers, then the node and value
+// arrays the headers index; it stays in global memory (a few KB, cache-resident).
+constexpr uint32_t kSpectrumRegular = 0u, kSpectrumIrregular = 1u, kSpectrumBlackbody = 2u;
+struct DevSpectrum {
+    uint32_t kind, size, nodes, values;                  // nodes / values: float offsets into the pool's data (nodes: irregular only)
+    float lambda_min, lambda_max, inv_interval, temperature;      // inv_interval = float(1 / (double(range) / (size - 1))) (distr_1d.h:314-344)
+};
+struct SpectrumPool { const DevSpectrum *headers; const float *data; };
+
+MTS_DEV float regular_eval(const DevSpectrum &h, const float *data, float l) {
+    if (!(l >= h.lambda_min && l <= h.lambda_max)) return 0.0f;
+    const float x = (l - h.lambda_min) * h.inv_interval;
+    const uint32_t i = min((uint32_t) x, h.size - 2u);
+    const float y0 = data[h.values + i], y1 = data[h.values + i + 1u];
+    const float w1 = x - (float) i, w0 = 1.0f - w1;
+    return fmaf(w0, y0, w1 * y1);
+}
+MTS_DEV float irregular_eval(const DevSpectrum &h, const float *data, float l) {
+    if (!(l >= h.lambda_min && l <= h.lambda_max)) return 0.0f;
+    const float *nodes = data + h.nodes;
+    uint32_t lo = 0u, hi = h.size;                      // enoki::binary_search: the first node that is not < l
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (nodes[mid] < l) lo = mid + 1u; else hi = mid;
+    }
+    const uint32_t i = max(min(lo, h.size - 1u), 1u) - 1u;
+    const float x0 = nodes[i], x1 = nodes[i + 1u], y0 = data[h.values + i], y1 = data[h.values + i + 1u];
+    const float t = (l - x0) / (x1 - x0);
+    return fmaf(t, y1 - y0, y0);
+}
+MTS_DEV float blackbody_eval(float temperature, float l) {
+    constexpr float c = 2.99792458e+8f, h = 6.62607004e-34f, k = 1.38064852e-23f;
+    constexpr float c0 = 2 * h * c * c, c1 = h * c / k;
+    if (!(l >= kCieMin && l <= kCieMax)) return 0.0f;
+    const float lambda = l * 1e-9f, lambda2 = lambda * lambda, lambda5 = (lambda2 * lambda2) * lambda;
+    return 1e-9f * c0 / (lambda5 * (lm_exp(c1 / (lambda * temperature)) - 1.0f));
+}
+MTS_DEV float spectrum_eval(const SpectrumPool &pool, uint32_t index, float l) {
+    const DevSpectrum h = pool.headers[index];
+    if (h.kind == kSpectrumRegular) return regular_eval(h, pool.data, l);
+    if (h.kind == kSpectrumIrregular) return irregular_eval(h, pool.data, l);
+    return blackbody_eval(h.temperature, l);
+}
+
 // cie1931_xyz (spectrum.h:127-163): the observer's colour matching functions at wavelength l, the table interpolation of spectrum_to_xyz
 // below (which keeps its own copy: folding it into this helper changed the machine code of the render kernels)
 MTS_DEV f3 cie1931_xyz(float l) {

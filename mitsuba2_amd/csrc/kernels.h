@@ -249,5 +249,6 @@ hipError_t launch_moment_pack(const float *values5, const float *squares5, float
 hipError_t launch_roughplastic_tables(DevBsdf *bsdfs, uint32_t index, float *table, const float *gl, int res_t, int res_r, hipStream_t s);
 hipError_t launch_film_develop(const float *xyzaw, uint64_t n, float *rgba, hipStream_t s);
 hipError_t launch_libm_eval(int fn, uint64_t n, const float *x, const float *y, float *out, hipStream_t s);
+hipError_t launch_spectrum_eval(const DevSpectrum *headers, const float *data, uint64_t n, const float *lambda, float *out, hipStream_t s);
 
 } // namespace mtsamd

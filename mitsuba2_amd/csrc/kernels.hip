@@ -402,6 +402,10 @@ struct PathStateS {
     uint32_t ordinal, depth, flags;
 };
 
+// The path state of a spectral scene that binds tabulated / analytic spectra: the same record; the type selects the instantiations of the
+// schedules (k_shade, k_mega, k_finish) whose step evaluates the spectrum pool, and leaves those of every other scene as they are.
+struct PathStateT : PathStateS { };
+
 template <bool NT = false>
 MTS_DEV void load_state(const PoolView &p, size_t i, PathStateS &s) {
     float4 a = ld_stream<NT>(p.ray_o + i), b = ld_stream<NT>(p.ray_d + i), c = ld_stream<NT>(p.thr + i), e = ld_stream<NT>(p.res + i);
@@ -431,7 +435,29 @@ MTS_DEV void store_state(const PoolView &p, size_t i, const PathStateS &s) {
 }
 
 // spectral variant: `srgb` parameters evaluate the upsampled colour at each wavelength (srgb.cpp:45-52), `uniform` ones are
-// constants; conductors carry uniform eta / k
+// constants; conductors carry uniform eta / k.  spectral_channels_tab (a scene that binds spectra, SceneView::n_spectra): a parameter
+// with a tabulated spectrum (DevBsdf::spectra0 / spectra1) evaluates it at each wavelength instead -- regular.cpp:68-75,
+// irregular.cpp:76-83 -- and that includes eta / k of conductors.  Only the step instantiated with TAB calls it.
+MTS_DEV SpectrumPool spectrum_pool(const SceneView &sv) {
+    const DevSpectrum *headers = reinterpret_cast<const DevSpectrum *>(sv.bsdfs + sv.n_bsdfs);
+    return SpectrumPool{ headers, reinterpret_cast<const float *>(headers + sv.n_spectra) };
+}
+MTS_DEV BsdfChannels<kWav> spectral_channels_tab(const DevBsdf &b, const Spec4 &wav, const SceneView &sv) {
+    BsdfChannels<kWav> c;
+    const SpectrumPool pool = spectrum_pool(sv);
+    const uint32_t t_refl = bsdf_spectrum(b, kSpecRefl), t_spec = bsdf_spectrum(b, kSpecSpec), t_trans = bsdf_spectrum(b, kSpecTrans),
+                   t_eta = bsdf_spectrum(b, kSpecEta), t_k = bsdf_spectrum(b, kSpecK);
+#pragma unroll
+    for (int k = 0; k < kWav; ++k) {
+        const float l = wav.v[k];
+        c.refl[k] = t_refl ? spectrum_eval(pool, t_refl - 1u, l) : (b.flags & kBsdfUniformRefl) ? b.r : srgb_model_eval(b.c0, b.c1, b.c2, l);
+        c.spec[k] = t_spec ? spectrum_eval(pool, t_spec - 1u, l) : (b.flags & kBsdfUniformSpec) ? b.sr : srgb_model_eval(b.sc0, b.sc1, b.sc2, l);
+        c.trans[k] = t_trans ? spectrum_eval(pool, t_trans - 1u, l) : (b.flags & kBsdfUniformTrans) ? b.kr : srgb_model_eval(b.tc0, b.tc1, b.tc2, l);
+        c.eta[k] = t_eta ? spectrum_eval(pool, t_eta - 1u, l) : b.er;
+        c.k[k] = t_k ? spectrum_eval(pool, t_k - 1u, l) : b.kr;
+    }
+    return c;
+}
 MTS_DEV BsdfChannels<kWav> spectral_channels(const DevBsdf &b, const Spec4 &wav) {
     BsdfChannels<kWav> c;
 #pragma unroll
@@ -503,9 +529,19 @@ MTS_DEV Spec4 eval_reflectance_spectral(const SceneView &sv, const DevBsdf &b, f
     }
     return r;
 }
+// TAB: a tabulated / analytic radiance (DevEmitter::spectrum) is the radiance itself, not a factor of D65
+template <bool TAB = false>
 MTS_DEV Spec4 emitter_spectrum(const SceneView &sv, const DevEmitter &e, const Spec4 &wav, f2 uv) {
     if (e.pad0 == kEmitterEnvmap) return envmap_lookup_spectral(*sv.envmap, uv.x, uv.y, wav);
     Spec4 r;
+    if constexpr (TAB) {
+        if (e.spectrum) {
+            const SpectrumPool pool = spectrum_pool(sv);
+#pragma unroll
+            for (int k = 0; k < kWav; ++k) r.v[k] = spectrum_eval(pool, e.spectrum - 1u, wav.v[k]);
+            return r;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < kWav; ++k) r.v[k] = table_eval(g_spectral.d65, e.d65_scale, wav.v[k]) * srgb_model_eval(e.c0, e.c1, e.c2, wav.v[k]);
     return r;
@@ -537,8 +573,10 @@ struct NoProbeS {
                               const float (&weight)[kWav]) { }
 };
 
-template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false, class Probe = NoProbeS>
+// TAB: the scene binds tabulated / analytic spectra (general step only): the host selects these instantiations per scene
+template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false, class Probe = NoProbeS, bool TAB = false>
 MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c, Deferred *df = nullptr, Probe &&probe = Probe{}) {
+    static_assert(!TAB || GENERAL, "spectra ride on the general step");
     constexpr bool kWatch = !std::is_same_v<std::remove_reference_t<Probe>, NoProbeS>;
     const SceneView &sv = P.sv;
     if constexpr (kWatch) probe.template begin<DEFER, GENERAL, NEST>(s);
@@ -567,10 +605,12 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
                 ew = mis_weight(s.bs_pdf, (GENERAL && (s.flags & kFlagDelta)) ? 0.0f : pe);
             }
             if (si.wi.z > 0.0f) {
-                Spec4 le4;
+                Spec4 le4, tab;
+                if constexpr (TAB) tab = emitter_spectrum<true>(sv, e, s.wav, f2{ 0.0f, 0.0f });
 #pragma unroll
                 for (int k = 0; k < kWav; ++k) {       // SRGBEmitterSpectrum::eval = d65 * srgb_model_eval (srgb_d65.cpp:54-62)
                     float le = table_eval(g_spectral.d65, e.d65_scale, s.wav.v[k]) * srgb_model_eval(e.c0, e.c1, e.c2, s.wav.v[k]);
+                    if constexpr (TAB) le = tab.v[k];      // a tabulated radiance, or the same product
                     s.res.v[k] += (ew * s.thr.v[k]) * le;
                     if constexpr (kWatch) le4.v[k] = le;
                 }
@@ -584,7 +624,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
         if (s.depth > 1u) ew = mis_weight(s.bs_pdf, (GENERAL && (s.flags & kFlagDelta)) ? 0.0f : pdf_environment(sv, e, s.d));
         f2 uv; uv.x = uv.y = 0.0f;
         if (e.pad0 == kEmitterEnvmap) env_dir_to_uv(mat3_apply(sv.envmap->to_local, s.d), uv.x, uv.y);      // envmap.cpp:135-144
-        const Spec4 le = emitter_spectrum(sv, e, s.wav, uv);
+        const Spec4 le = emitter_spectrum<TAB>(sv, e, s.wav, uv);
 #pragma unroll
         for (int k = 0; k < kWav; ++k) s.res.v[k] += (ew * s.thr.v[k]) * le.v[k];
         if constexpr (kWatch) probe.escaped(sv, s, e, ew, le);
@@ -612,7 +652,14 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
     if constexpr (kWatch) probe.surface(si, bsdf, refl, texel, tw1, s.thr);
     BsdfChannels<kWav> chan;
     if (GENERAL) {
-        chan = spectral_channels(bsdf, s.wav);
+        if constexpr (TAB) chan = spectral_channels_tab(bsdf, s.wav, sv);
+        else chan = spectral_channels(bsdf, s.wav);
+        if constexpr (TAB) {
+            if (bsdf_spectrum(bsdf, kSpecRefl)) {
+#pragma unroll
+                for (int k = 0; k < kWav; ++k) refl.v[k] = chan.refl[k];
+            }
+        }
 #pragma unroll
         for (int k = 0; k < kWav; ++k) chan.refl[k] = refl.v[k];
     }
@@ -620,7 +667,10 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
     // a scalar weight in the spectral variant is a constant (a textured one is refused at scene creation)
     const NestInfo ni = nest_info<NEST>(bsdf, refl.v[0], refl.v[1], refl.v[2]);
     const bool smooth = !GENERAL || bsdf_is_smooth(bsdf);
-    auto chan_of = [&](const DevBsdf &rec, bool child) { return child ? spectral_channels(rec, s.wav) : chan; };
+    auto chan_of = [&](const DevBsdf &rec, bool child) {
+        if constexpr (TAB) return child ? spectral_channels_tab(rec, s.wav, sv) : chan;
+        else return child ? spectral_channels(rec, s.wav) : chan;
+    };
 
     if (smooth) {
         f2 s2; s2.x = pcg_next_f32(s.rng); s2.y = pcg_next_f32(s.rng);
@@ -636,7 +686,7 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
             float mis = (GENERAL && ds.delta) ? 1.0f : mis_weight(ds.pdf, bp);
             Spec4 contrib; bool nz = false;
             Spec4 bv4, spec4;                   // for the probe
-            const Spec4 le4 = emitter_spectrum(sv, e, s.wav, ds.uv);
+            const Spec4 le4 = emitter_spectrum<TAB>(sv, e, s.wav, ds.uv);
 #pragma unroll
             for (int k = 0; k < kWav; ++k) {
                 float le = (GENERAL && ds.delta) ? le4.v[k] * ds.falloff : le4.v[k];
@@ -737,6 +787,7 @@ MTS_DEV void store_result_spectral(const RenderParams &P, const PathStateS &s) {
     P.out_rgba[s.ordinal] = make_float4(xyz.x, xyz.y, xyz.z, (valid || !P.store_xyz) ? alpha : -1.0f);
 }
 
+// (k_bounce_spectra below repeats this round for scenes with tabulated spectra: a change here is made there too)
 template <bool FLAT, bool GENERAL, bool NEST = false>
 __global__ __launch_bounds__(kBlock) void k_bounce_spectral(const RenderParams P) {
     extern __shared__ float4 smem[];
@@ -754,6 +805,57 @@ __global__ __launch_bounds__(kBlock) void k_bounce_spectral(const RenderParams P
         if (i0 + lane < n_in) {
             load_state(P.in, base + i0 + lane, s);
             alive = bounce_step_spectral<FLAT, 0, GENERAL, NEST>(P, lds, s, c);
+            if (!alive) store_result_spectral(P, s);
+        }
+        const uint64_t m = __ballot(alive);
+        if (alive) store_state(P.out, base + n_out + mask_rank(m), s);
+        n_out += (uint32_t) __popcll(m);
+    }
+    uint64_t cursor = P.cursor[wave];
+    const uint64_t end = P.cursor_end[wave];
+    while (n_out < P.target && cursor < end) {
+        uint64_t left = end - cursor;
+        uint32_t n_new = min(64u, P.target - n_out);
+        if ((uint64_t) n_new > left) n_new = (uint32_t) left;
+        if (lane < n_new) {
+            PathStateS s;
+            uint64_t ordinal; uint32_t lp, sj;
+            cursor_sample(P, wave, cursor + lane, ordinal, lp, sj);
+            generate_path_spectral(P, ordinal, lp, sj, s);
+            store_state(P.out, base + n_out + lane, s);
+        }
+        n_out += n_new; cursor += n_new;
+    }
+    uint32_t tot[4] = { c.closest, c.any, c.segments, c.tri_tests };
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (int off = 32; off > 0; off >>= 1) tot[k] += __shfl_xor(tot[k], off);
+    if (lane == 0) {
+        P.count_out[wave] = n_out;
+        P.cursor[wave] = cursor;
+        uint64_t *ws = P.wave_stats + 4u * (size_t) wave;
+        ws[0] += tot[0]; ws[1] += tot[1]; ws[2] += tot[2]; ws[3] += tot[3];
+    }
+}
+// The same round for a scene that binds tabulated / analytic spectra: the general step with the spectrum pool.  A copy, because the
+// round shared through an inlined function assembled k_bounce_spectral differently (scripts/isa_compare.py).
+template <bool FLAT, bool NEST>
+__global__ __launch_bounds__(kBlock) void k_bounce_spectra(const RenderParams P) {
+    extern __shared__ float4 smem[];
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    const uint32_t wave = (blockIdx.x * kBlock + threadIdx.x) >> 6;
+    if (wave >= P.n_waves) return;
+    const uint32_t lane = lane_id();
+    const uint32_t n_in = __builtin_amdgcn_readfirstlane(P.count_in[wave]);
+    const size_t base = (size_t) wave * P.seg_cap;
+    uint32_t n_out = 0;
+    Counters c = { 0u, 0u, 0u, 0u };
+    for (uint32_t i0 = 0; i0 < n_in; i0 += 64u) {
+        PathStateS s;
+        bool alive = false;
+        if (i0 + lane < n_in) {
+            load_state(P.in, base + i0 + lane, s);
+            alive = bounce_step_spectral<FLAT, 0, true, NEST, NoProbeS, true>(P, lds, s, c);
             if (!alive) store_result_spectral(P, s);
         }
         const uint64_t m = __ballot(alive);
@@ -1012,6 +1114,10 @@ MTS_DEV bool step_deferred(const RenderParams &P, const LdsView &lds, PathState 
 template <bool GENERAL, bool FLAT>
 MTS_DEV bool step_deferred(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c, Deferred &df) {
     return bounce_step_spectral<FLAT, FLAT ? 2 : 1, GENERAL>(P, lds, s, c, &df);
+}
+template <bool GENERAL, bool FLAT>
+MTS_DEV bool step_deferred(const RenderParams &P, const LdsView &lds, PathStateT &s, Counters &c, Deferred &df) {
+    return bounce_step_spectral<FLAT, FLAT ? 2 : 1, GENERAL, false, NoProbeS, true>(P, lds, s, c, &df);
 }
 // radiance += nee of an unoccluded shadow ray: the additions drain_shadow_ring / k_trace<any> make on the stored record
 MTS_DEV void add_nee(PathState &s, const float (&nee)[4]) { s.res = mk3(s.res.x + nee[0], s.res.y + nee[1], s.res.z + nee[2]); }
@@ -1321,6 +1427,8 @@ template <bool GENERAL, bool FLAT>
 MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c) { return bounce_step<FLAT, 0, GENERAL>(P, lds, s, c); }
 template <bool GENERAL, bool FLAT>
 MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c) { return bounce_step_spectral<FLAT, false, GENERAL>(P, lds, s, c); }
+template <bool GENERAL, bool FLAT>
+MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathStateT &s, Counters &c) { return bounce_step_spectral<FLAT, 0, GENERAL, false, NoProbeS, true>(P, lds, s, c); }
 
 template <typename State, bool GENERAL, bool FLAT>
 __global__ __launch_bounds__(64) void k_finish(const RenderParams P, uint32_t per) {
@@ -1439,12 +1547,14 @@ hipError_t launch_mega(const RenderParams &p, hipStream_t s) {
     const size_t lds = p.sv.flat ? lds_bytes(p.sv, 64u) : sizeof(StackEntry) * (std::min(p.sv.stack_depth, kFinishLdsDepth) + 1u) * 64u;
     const uint32_t blocks = p.n_waves;
     if (p.sv.flat) {
-        if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_mega<PathStateS, true, true>), dim3(blocks), dim3(64), lds, s, p);
+        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_mega<PathStateT, true, true>), dim3(blocks), dim3(64), lds, s, p);
+        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_mega<PathStateS, true, true>), dim3(blocks), dim3(64), lds, s, p);
         else if (p.spectral) hipLaunchKernelGGL((k_mega<PathStateS, false, true>), dim3(blocks), dim3(64), lds, s, p);
         else if (p.sv.general) hipLaunchKernelGGL((k_mega<PathState, true, true>), dim3(blocks), dim3(64), lds, s, p);
         else hipLaunchKernelGGL((k_mega<PathState, false, true>), dim3(blocks), dim3(64), lds, s, p);
     } else {
-        if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_mega<PathStateS, true, false>), dim3(blocks), dim3(64), lds, s, p);
+        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_mega<PathStateT, true, false>), dim3(blocks), dim3(64), lds, s, p);
+        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_mega<PathStateS, true, false>), dim3(blocks), dim3(64), lds, s, p);
         else if (p.spectral) hipLaunchKernelGGL((k_mega<PathStateS, false, false>), dim3(blocks), dim3(64), lds, s, p);
         else if (p.sv.general) hipLaunchKernelGGL((k_mega<PathState, true, false>), dim3(blocks), dim3(64), lds, s, p);
         else hipLaunchKernelGGL((k_mega<PathState, false, false>), dim3(blocks), dim3(64), lds, s, p);
@@ -1459,12 +1569,14 @@ hipError_t launch_finish(const RenderParams &p, uint64_t alive, hipStream_t s) {
     const uint32_t blocks = (p.n_waves + per - 1u) / per;
     const size_t lds = p.sv.flat ? lds_bytes(p.sv, 64u) : sizeof(StackEntry) * (std::min(p.sv.stack_depth, kFinishLdsDepth) + 1u) * 64u;
     if (p.sv.flat) {
-        if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_finish<PathStateS, true, true>), dim3(blocks), dim3(64), lds, s, p, per);
+        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_finish<PathStateT, true, true>), dim3(blocks), dim3(64), lds, s, p, per);
+        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_finish<PathStateS, true, true>), dim3(blocks), dim3(64), lds, s, p, per);
         else if (p.spectral) hipLaunchKernelGGL((k_finish<PathStateS, false, true>), dim3(blocks), dim3(64), lds, s, p, per);
         else if (p.sv.general) hipLaunchKernelGGL((k_finish<PathState, true, true>), dim3(blocks), dim3(64), lds, s, p, per);
         else hipLaunchKernelGGL((k_finish<PathState, false, true>), dim3(blocks), dim3(64), lds, s, p, per);
     } else {
-        if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_finish<PathStateS, true, false>), dim3(blocks), dim3(64), lds, s, p, per);
+        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_finish<PathStateT, true, false>), dim3(blocks), dim3(64), lds, s, p, per);
+        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_finish<PathStateS, true, false>), dim3(blocks), dim3(64), lds, s, p, per);
         else if (p.spectral) hipLaunchKernelGGL((k_finish<PathStateS, false, false>), dim3(blocks), dim3(64), lds, s, p, per);
         else if (p.sv.general) hipLaunchKernelGGL((k_finish<PathState, true, false>), dim3(blocks), dim3(64), lds, s, p, per);
         else hipLaunchKernelGGL((k_finish<PathState, false, false>), dim3(blocks), dim3(64), lds, s, p, per);
@@ -1693,7 +1805,8 @@ hipError_t launch_split_stage(const RenderParams &p, int stage, hipStream_t s) {
         if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_trace<false, false>), trace_lds_bytes(p.sv))) return e;
         hipLaunchKernelGGL((k_trace<false, false>), dim3(trace_blocks), dim3(kTraceBlock), trace_lds_bytes(p.sv), s, p);
     } else if (stage == 1) {
-        if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
+        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_shade<PathStateT, true, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
+        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
         else if (p.spectral) hipLaunchKernelGGL((k_shade<PathStateS, false, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
         else if (p.sv.general) hipLaunchKernelGGL((k_shade<PathState, true, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
         else hipLaunchKernelGGL((k_shade<PathState, false, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
@@ -1711,7 +1824,8 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
         const uint32_t shade_blocks = p.gather_w > 4u ? (n_launch + p.gather_w - 1u) / p.gather_w : (n_launch * 64u + kBlock - 1) / kBlock;
         p.lds_queue_offset = (uint32_t) (shade_ring_offset(p.sv, kBlock) / 16u);
         const size_t lds = shade_ring_lds_bytes(p.sv, p.spectral != 0, p.gather_w);
-        if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
+        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_shade<PathStateT, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
+        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else if (p.spectral) hipLaunchKernelGGL((k_shade<PathStateS, false, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else if (p.sv.general) hipLaunchKernelGGL((k_shade<PathState, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else hipLaunchKernelGGL((k_shade<PathState, false, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
@@ -1720,7 +1834,8 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
     if (p.split == 2) {       // LDS-resident scene: closest hit + shading fused, shadow rays queued and resolved in dense batches
         const uint32_t shade_blocks = (p.n_waves * 64u + kBlock - 1) / kBlock;
         const size_t lds = bounce_lds_bytes(p.sv);
-        if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
+        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_shade<PathStateT, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
+        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else if (p.spectral) hipLaunchKernelGGL((k_shade<PathStateS, false, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else if (p.sv.general) hipLaunchKernelGGL((k_shade<PathState, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
         else hipLaunchKernelGGL((k_shade<PathState, false, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
@@ -1735,7 +1850,15 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
     }
     uint32_t blocks = (p.n_waves * 64u + kBlock - 1) / kBlock;
     if (p.spectral) {
-        if (p.sv.general == 2u) {
+        if (p.sv.n_spectra) {
+            if (p.sv.general == 2u) {
+                if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectra<true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+                else hipLaunchKernelGGL((k_bounce_spectra<false, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            } else {
+                if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectra<true, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+                else hipLaunchKernelGGL((k_bounce_spectra<false, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            }
+        } else if (p.sv.general == 2u) {
             if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectral<true, true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
             else hipLaunchKernelGGL((k_bounce_spectral<false, true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
         } else if (p.sv.general) {
@@ -3358,6 +3481,18 @@ __global__ __launch_bounds__(kBlock) void k_libm_eval(int fn, uint64_t n, const 
 hipError_t launch_libm_eval(int fn, uint64_t n, const float *x, const float *y, float *out, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_libm_eval, dim3((uint32_t) ((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, fn, n, x, y, out);
+    return hipGetLastError();
+}
+
+// spectrum_eval() on a wavelength stream (mtsamd_spectrum_eval): the function the render kernels call, on a pool of one spectrum
+__global__ __launch_bounds__(kBlock) void k_spectrum_eval(const DevSpectrum *headers, const float *data, uint64_t n, const float *lambda, float *out) {
+    const uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    out[i] = spectrum_eval(SpectrumPool{ headers, data }, 0u, lambda[i]);
+}
+hipError_t launch_spectrum_eval(const DevSpectrum *headers, const float *data, uint64_t n, const float *lambda, float *out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_spectrum_eval, dim3((uint32_t) ((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, headers, data, n, lambda, out);
     return hipGetLastError();
 }
 

@@ -32,6 +32,16 @@ def normalize(e):
         return out
     key = _VALUE_KEY[t]
     value = e.get(key, e.get("radiance"))              # the synthetic scenes call every emitted quantity `radiance`
+    # a spectrum plugin (src/spectra/regular.cpp, irregular.cpp, d65.cpp, blackbody.cpp) as the emitted quantity, or the spectrum a loaded
+    # XML scene carries beside the pre-integrated colour: bound by a spectral scene (then it IS the radiance, without the D65 factor of an
+    # srgb_d65 colour); an RGB scene uses the pre-integrated colour -- a blackbody has none (blackbody.cpp:84-89)
+    from . import spectrum as S
+    carried = e.get("spectra", {})
+    if S.is_spectrum(value):
+        out["spectrum"] = S.parse(value, within_emitter=True)
+        value = S.to_rgb(out["spectrum"], True, key) if out["spectrum"]["kind"] != "blackbody" else None
+    elif carried:
+        out["spectrum"] = carried.get(key, carried.get("radiance"))
     out["radiance"] = _rgb(1.0 if value is None else value)     # Texture::D65(1.f) default
     if t == "point" and e.get("position") is not None:
         if e.get("to_world") is not None:                 # point.cpp:53-57

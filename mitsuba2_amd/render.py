@@ -486,6 +486,50 @@ def srgb_coeff_path(build=True):
     return path
 
 
+def spectrum_descs(spectra, keep):
+    """parsed spectra (mitsuba2_amd.spectrum.parse) -> array of mtsamd_spectrum_desc; the arrays they point to are appended to `keep`"""
+    sp = (L.SpectrumDesc * max(len(spectra), 1))()
+    for i, s in enumerate(spectra):
+        sp[i].type = {"regular": 0, "irregular": 1, "blackbody": 2}[s["kind"]]
+        if s["kind"] == "blackbody":
+            sp[i].temperature = s["temperature"]
+            continue
+        values = _f32(s["values"]).reshape(-1)
+        keep.append(values)
+        sp[i].size, sp[i].values = values.size, values.ctypes.data_as(L.f32p)
+        if s["kind"] == "regular":
+            sp[i].lambda_min, sp[i].lambda_max = s["lambda_min"], s["lambda_max"]
+        else:
+            nodes = _f32(s["wavelengths"]).reshape(-1)
+            keep.append(nodes)
+            sp[i].wavelengths = nodes.ctypes.data_as(L.f32p)
+    return sp
+
+
+def spectrum_eval(spectrum, wavelengths):
+    """Texture::eval of a spectrum plugin dictionary (or a parsed spectrum) at a tensor of wavelengths, on the device function the render
+    kernels call (mtsamd_spectrum_eval)"""
+    from . import spectrum as S
+    spec = S.parse(spectrum) if "kind" not in spectrum else spectrum
+    keep = []
+    sp = spectrum_descs([spec], keep)
+    lam = wavelengths.to(torch.float32).contiguous()
+    out = torch.empty_like(lam)
+    L.check(L.lib().mtsamd_spectrum_eval(sp, lam.numel(), _ptr(lam), _ptr(out), _stream()))
+    return out
+
+
+def spectrum_mean(spectrum):
+    """Texture::mean() of a `regular` / `irregular` spectrum (mtsamd_spectrum_mean; host only)"""
+    from . import spectrum as S
+    spec = S.parse(spectrum) if "kind" not in spectrum else spectrum
+    keep = []
+    sp = spectrum_descs([spec], keep)
+    mean = C.c_float()
+    L.check(L.lib().mtsamd_spectrum_mean(sp, C.byref(mean)))
+    return float(mean.value)
+
+
 # --------------------------------------------------------------------------------------------
 class Scene:
     """src/librender/scene.cpp: shapes + BSDFs + emitters uploaded to one GPU, BVH built by the library."""
@@ -518,9 +562,11 @@ class Scene:
         tex = []                       # bitmap textures (src/textures/bitmap.cpp): reflectance = dict(type="bitmap", data=(H,W,3))
         self._bsdf_texture = {}
         from . import bsdfs as B
+        from . import spectrum as S
         self._bsdf_records = [B.normalize(b) for b in bsdfs]      # plugin defaults / validation (src/bsdfs/*.cpp constructors)
         flat = B.flatten(self._bsdf_records)                      # + the children of blendbsdf / mask records
         bd = (L.BsdfDesc * max(len(flat), 1))()
+        bindings = []                  # (target, index, mtsamd_bsdf_param, parsed spectrum): mtsamd_spectrum_binding
         for i, n in enumerate(flat):
             bd[i].type, bd[i].twosided = n["type"], int(n["twosided"])
             bd[i].nested = (C.c_int32 * 2)(*n.get("nested", [-1, -1]))
@@ -547,6 +593,9 @@ class Scene:
             bd[i].int_ior, bd[i].ext_ior, bd[i].alpha_u, bd[i].alpha_v = n["int_ior"], n["ext_ior"], n["alpha_u"], n["alpha_v"]
             bd[i].distribution, bd[i].sample_visible, bd[i].nonlinear = n["distribution"], int(n["sample_visible"]), int(n["nonlinear"])
             bd[i].uniform_mask = n["uniform_mask"]
+            for param, spec in (n.get("spectra", {}) if variant == "spectral" else {}).items():
+                # tabulated spectra replace the colour (RGB variant: the pre-integrated colour stays)
+                bindings.append((0, i, param, spec if "kind" in spec else S.parse(spec)))
         td = (L.TextureDesc * max(len(tex), 1))()
         for i, (kind, t, spec) in enumerate(tex):
             if kind == "bitmap":
@@ -568,6 +617,12 @@ class Scene:
             ed[i].to_world = (C.c_float * 16)(*n["to_world"].reshape(-1).tolist())
             ed[i].radiance = (C.c_float * 3)(*n["radiance"])
             ed[i].cutoff_angle, ed[i].beam_width = n["cutoff_angle"], n["beam_width"]
+            if n.get("spectrum") is not None:
+                spec = n["spectrum"]
+                if variant == "spectral":
+                    bindings.append((1, i, 0, spec if "kind" in spec else S.parse(spec, within_emitter=True)))
+                elif spec.get("kind") == "blackbody":
+                    raise RuntimeError("blackbody: Not implemented for non-spectral modes")
             if n["type"] == E.TYPE_IDS["envmap"]:          # src/emitters/envmap.cpp: lat-long image (linear RGB), scale, to_world
                 img = _f32(n["data"])
                 if img.ndim != 3 or img.shape[2] != 3:
@@ -581,8 +636,15 @@ class Scene:
             sd.spectral = 1
             sd.rgb2spec_path = srgb_coeff_path().encode()
         handle = C.c_void_p()
-        L.check(lib.mtsamd_scene_create(C.byref(sd), self._device_index, C.byref(handle)))
+        if bindings:
+            sp, bn = spectrum_descs([b[3] for b in bindings], keep), (L.SpectrumBinding * len(bindings))()
+            for i, (target, index, param, _) in enumerate(bindings):
+                bn[i].target, bn[i].index, bn[i].param, bn[i].spectrum = target, index, param, i
+            L.check(lib.mtsamd_scene_create_with_spectra(C.byref(sd), sp, len(bindings), bn, len(bindings), self._device_index, C.byref(handle)))
+        else:
+            L.check(lib.mtsamd_scene_create(C.byref(sd), self._device_index, C.byref(handle)))
         self._handle = handle
+        self._n_spectra = len(bindings)
         self._shape_count = len(meshes)
 
     def __del__(self):

@@ -258,7 +258,7 @@ def _parse_child(el, ctx, node):
         ctx.base_dir = old
         ctx.depth_includes -= 1
         return
-    if tag in _OBJECT_TAGS:
+    if tag in _OBJECT_TAGS or (tag == "spectrum" and "type" in el.attrib):       # <spectrum type="regular|irregular|d65|blackbody">: a nested plugin
         child = _parse_object(el, ctx, node)
         name = el.attrib.get("name")
         if name is not None:
@@ -399,6 +399,29 @@ def _colour(value, what, emitter=False):
     raise XMLError("%s: expected an <rgb> or constant <spectrum> value" % what)
 
 
+def _spectrum_plugin(node):
+    """<spectrum type=...> object -> the plugin dictionary mitsuba2_amd.spectrum.parse takes"""
+    d = {"type": node.type}
+    for k, v in node.props.items():
+        node.queried.add(k)
+        d[k] = v
+    return d
+
+
+def _pairs(v):
+    """a wavelength:value property as the `spectrum` dictionary a spectral scene binds (xml.cpp:1111-1125)"""
+    return {"type": "spectrum", "value": [(float(l), float(x)) for l, x in zip(v[1], v[2])]}
+
+
+def _emitted(ctx, it, key, what):
+    """the emitted quantity of an emitter: (value for the scene dictionary, {key: spectrum} to carry beside it or {})"""
+    v = _resolve(ctx, it.get(key, ("spectrum", 1.0)))
+    if isinstance(v, Node) and v.tag == "spectrum":
+        return _spectrum_plugin(v), {}
+    colour = _colour(v, what, True)
+    return colour, ({key: _pairs(v)} if isinstance(v, tuple) and v[0] == "tabulated" else {})
+
+
 def _texture(ctx, node, base_dir):
     from . import bitmap
     to_uv = node.get("to_uv", np.eye(4, dtype=F32), "transform")
@@ -441,6 +464,8 @@ def _bsdf_plugin_dict(ctx, node, base_dir):
             elif v.tag == "bsdf":
                 d["bsdf_%d" % nested] = _bsdf_plugin_dict(ctx, v, base_dir)
                 nested += 1
+            elif v.tag == "spectrum":
+                d[k] = _spectrum_plugin(v)
             else:
                 raise XMLError('bsdf: unexpected nested object "%s"' % v.tag)
         elif isinstance(v, tuple) and v and v[0] == "rgb":
@@ -448,7 +473,8 @@ def _bsdf_plugin_dict(ctx, node, base_dir):
         elif isinstance(v, tuple) and v and v[0] == "spectrum":
             d[k] = float(v[1])                           # a constant: `uniform` spectrum in the spectral variant
         elif isinstance(v, tuple) and v and v[0] == "tabulated":
-            d[k] = _colour(v, k)
+            d[k] = _colour(v, k)                         # the RGB variants' value; a spectral scene binds the spectrum itself
+            d.setdefault("spectra", {})[k] = _pairs(v)
         else:
             d[k] = v
     for c in node.children:
@@ -507,9 +533,9 @@ def _shape(ctx, node, desc, cache, base_dir):
                 raise XMLError("Only a single Emitter child object can be specified per shape.")
             if it.type != "area":
                 raise XMLError('Emitter plugin "%s" is not supported by this backend (area only)' % it.type)
-            rad = _colour(_resolve(ctx, it.get("radiance", ("spectrum", 1.0))), "area.radiance", True)
+            rad, carried = _emitted(ctx, it, "radiance", "area.radiance")
             it.check_unqueried()
-            desc.scene_dict["emitters"].append(dict(type="area", radiance=rad))
+            desc.scene_dict["emitters"].append(dict(type="area", radiance=rad, **({"spectra": carried} if carried else {})))
             emitter = len(desc.scene_dict["emitters"]) - 1
         else:
             raise XMLError('Tried to add an unsupported object of type "%s" to a shape' % it.tag)
@@ -650,9 +676,9 @@ def _instantiate(ctx, root, base_dir):
             continue                                 # instantiated where referenced
         elif it.tag == "emitter":
             if it.type == "constant":
-                rad = _colour(_resolve(ctx, it.get("radiance", ("spectrum", 1.0))), "constant.radiance", True)
+                rad, carried = _emitted(ctx, it, "radiance", "constant.radiance")
                 it.check_unqueried()
-                desc.scene_dict["emitters"].append(dict(type="constant", radiance=rad))
+                desc.scene_dict["emitters"].append(dict(type="constant", radiance=rad, **({"spectra": carried} if carried else {})))
             elif it.type == "envmap":
                 from . import bitmap
                 fn = it.get("filename", kind="string")
@@ -667,7 +693,10 @@ def _instantiate(ctx, root, base_dir):
                 desc.scene_dict["emitters"].append(entry)
             elif it.type in ("point", "spot", "directional"):       # point.cpp:52-65, spot.cpp:68-91, directional.cpp:43-63
                 key = "irradiance" if it.type == "directional" else "intensity"
-                entry = {"type": it.type, key: _colour(_resolve(ctx, it.get(key, ("spectrum", 1.0))), "%s.%s" % (it.type, key), True)}
+                value, carried = _emitted(ctx, it, key, "%s.%s" % (it.type, key))
+                entry = {"type": it.type, key: value}
+                if carried:
+                    entry["spectra"] = carried
                 if "to_world" in it.props:
                     entry["to_world"] = it.get("to_world", kind="transform")
                 if it.type == "point" and "position" in it.props:
@@ -721,8 +750,6 @@ def parse_file(path, **params):
 def instantiate(desc, device=0, variant="rgb"):
     """SceneDescription -> render.Scene with its sensors and integrator (needs the HIP library and a GPU)."""
     from . import render as R
-    if variant == "spectral" and desc.uses_tabulated_spectra:
-        raise XMLError("wavelength:value spectra are pre-integrated to RGB by this backend: RGB variant only")
     sensors = []
     for s in desc.sensors:
         f = s["film"]
@@ -774,11 +801,32 @@ def _node_from_dict(d, ctx):
                     raise XMLError("'rgb' dictionary should always contain 2 entries ('type' and 'value'), got %u." % len(v))
                 node.set(k, ("rgb", tuple(float(x) for x in v["value"])))
             elif t2 == "spectrum":
-                if len(v) != 2:
-                    raise XMLError("'spectrum' dictionary should always contain 2 entries ('type' and 'value'), got %u." % len(v))
-                if not isinstance(v.get("value"), (int, float)):
-                    raise XMLError("tabulated spectra are not supported by this backend (constant values only)")
-                node.set(k, ("spectrum", float(v["value"])))
+                if len(v) != 2 or ("value" in v) == ("filename" in v):
+                    raise XMLError("'spectrum' dictionary should always contain 2 entries ('type' and 'value' or 'filename'), got %u." % len(v))
+                if isinstance(v.get("value"), (int, float)) and not isinstance(v.get("value"), bool):
+                    node.set(k, ("spectrum", float(v["value"])))
+                else:                                     # [(wavelength, value), ...] or a file of `wavelength value` lines (xml_v.cpp:100-127)
+                    if "filename" in v:
+                        from . import spectrum as S
+                        fn = str(v["filename"])
+                        try:
+                            wl, vals = S.spectrum_from_file(fn if os.path.isabs(fn) else os.path.join(ctx.base_dir, fn))
+                        except RuntimeError as e:
+                            raise XMLError(str(e))
+                    else:
+                        try:
+                            pairs = [(float(l), float(x)) for l, x in v["value"]]
+                        except (TypeError, ValueError):
+                            raise XMLError("'spectrum' dictionary: 'value' is a constant or a list of (wavelength, value) pairs")
+                        wl, vals = [p[0] for p in pairs], [p[1] for p in pairs]
+                    node.set(k, ("tabulated", tuple(wl), tuple(vals)))
+                    ctx.tabulated = True
+            elif t2 in ("regular", "irregular", "d65", "blackbody"):       # a spectrum plugin as a parameter value
+                child = Node("spectrum", t2, v.get("id"))
+                for k2, v2 in v.items():
+                    if k2 not in ("type", "id"):
+                        child.set(k2, v2)
+                node.set(k, child)
             elif t2 == "ref":
                 if node.tag == "scene":
                     raise XMLError("Reference found at the scene level: %s" % k)
