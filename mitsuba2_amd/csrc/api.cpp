@@ -11,6 +11,7 @@
 #include "bvh.h"
 #include "envmap.h"
 #include "kernels.h"
+#include "scene_build.h"
 #include "spectral_upsampling.h"
 #include "cie_data.h"
 
@@ -18,18 +19,16 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
 using namespace mtsamd;
 
 namespace {
-
-thread_local std::string g_last_error;
 
 // Experiment switches (scheduler geometry, BVH leaf size, ...) read from the environment exist only in builds made with
 // -DMTSAMD_EXPERIMENTS (scripts/ab_build.sh); the release library never looks at the process environment.
@@ -38,13 +37,6 @@ static const char *exp_env(const char *name) { return std::getenv(name); }
 #else
 static const char *exp_env(const char *) { return nullptr; }
 #endif
-
-int fail(int code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    g_last_error = buf;
-    return code;
-}
 
 #define HIP_TRY(expr)                                                                                  \
     do {                                                                                               \
@@ -273,37 +265,6 @@ struct Workspace {
 
 } // namespace
 
-// Model parameters of a BSDF -> device record (see DevBsdf in device_bsdf.h), with the constants the reference's
-// constructors derive (plastic.cpp:162-176; fresnel_diffuse_reflectance: fresnel.h:331-358).
-static float fresnel_diffuse_reflectance(float eta) {
-    if (eta < 1.0f) return -1.4399f * (eta * eta) + 0.7099f * eta + 0.6681f + 0.0636f / eta;
-    const float i1 = 1.0f / eta, i2 = i1 * i1, i3 = i2 * i1, i4 = i3 * i1, i5 = i4 * i1;
-    return 0.919317f - 3.4793f * i1 + 6.75335f * i2 - 7.80989f * i3 + 4.98554f * i4 - 1.36881f * i5;
-}
-static void fill_bsdf_model(const mtsamd_bsdf_desc &bd, DevBsdf &d) {
-    d.flags = (bd.twosided ? kBsdfTwoSided : 0u) | (bd.distribution == 1 ? kBsdfGGX : 0u) | (bd.sample_visible ? kBsdfSampleVisible : 0u) |
-              (bd.nonlinear ? kBsdfNonlinear : 0u);
-    if (bd.type == MTSAMD_BSDF_DIFFUSE) d.flags &= kBsdfTwoSided;
-    d.flags |= ((bd.uniform_mask & 1) ? kBsdfUniformRefl : 0u) | ((bd.uniform_mask & 2) ? kBsdfUniformSpec : 0u) |
-               ((bd.uniform_mask & 4) ? kBsdfUniformTrans : 0u);
-    d.sr = bd.specular_reflectance[0]; d.sg = bd.specular_reflectance[1]; d.sb = bd.specular_reflectance[2];
-    d.alpha_u = bd.alpha_u; d.alpha_v = bd.alpha_v;
-    if (bd.type == MTSAMD_BSDF_CONDUCTOR || bd.type == MTSAMD_BSDF_ROUGHCONDUCTOR) {
-        d.er = bd.eta[0]; d.eg = bd.eta[1]; d.eb = bd.eta[2];
-        d.kr = bd.k[0]; d.kg = bd.k[1]; d.kb = bd.k[2];
-    } else if (bd.type == MTSAMD_BSDF_DIELECTRIC || bd.type == MTSAMD_BSDF_ROUGHDIELECTRIC || bd.type == MTSAMD_BSDF_THINDIELECTRIC) {
-        d.er = bd.int_ior / bd.ext_ior;
-        d.kr = bd.specular_transmittance[0]; d.kg = bd.specular_transmittance[1]; d.kb = bd.specular_transmittance[2];
-    } else if (bd.type == MTSAMD_BSDF_PLASTIC || bd.type == MTSAMD_BSDF_ROUGHPLASTIC) {
-        const float eta = bd.int_ior / bd.ext_ior;
-        d.er = eta; d.eg = 1.0f / (eta * eta);
-        d.eb = bd.type == MTSAMD_BSDF_PLASTIC ? fresnel_diffuse_reflectance(1.0f / eta) : 0.0f;     // roughplastic: set by the table kernel
-        const float d_mean = (bd.reflectance[0] + bd.reflectance[1] + bd.reflectance[2]) * (1.0f / 3.0f);
-        const float s_mean = (bd.specular_reflectance[0] + bd.specular_reflectance[1] + bd.specular_reflectance[2]) * (1.0f / 3.0f);
-        d.kr = s_mean / (d_mean + s_mean);
-    }
-}
-
 // quad::gauss_legendre (src/libcore/quad.cpp:7-66, legendre_pd: math.h:127-154): nodes / weights on [-1, 1]
 static void gauss_legendre(int n, float *nodes, float *weights) {
     auto legendre_pd = [](int l, double x, double &lv, double &dv) {
@@ -342,32 +303,6 @@ static void gauss_legendre(int n, float *nodes, float *weights) {
         legendre_pd(n + 1, 0.0, l, d);
         weights[n / 2] = (float) (2.0 / (d * d));
         nodes[n / 2] = 0.0f;
-    }
-}
-
-// Spectral variant: bitmap texels -> model coefficients (bitmap.cpp:116-123) and their Jacobians, 9 floats per texel at 3 * grad_offset
-// of `jac`; returns the sum of srgb_model_mean over the texels (Texture::mean() times their number)
-static double spectral_texels(const Rgb2Spec &model, const float *rgb, size_t n_texels, std::vector<float> &coeffs, std::vector<float> &jac, uint32_t grad_offset) {
-    coeffs.resize(3 * n_texels);
-    if (jac.size() < 3 * (size_t) grad_offset + 9 * n_texels) jac.resize(3 * (size_t) grad_offset + 9 * n_texels, 0.0f);
-    double mean = 0.0;
-    for (size_t i = 0; i < n_texels; ++i) {
-        srgb_model_fetch(model, rgb + 3 * i, coeffs.data() + 3 * i);
-        srgb_model_fetch_jacobian(model, rgb + 3 * i, jac.data() + 3 * (size_t) grad_offset + 9 * i);
-        mean += (double) srgb_model_mean(coeffs.data() + 3 * i);
-    }
-    return mean;
-}
-
-// Spectral variant: the RGBA texels of an envmap -> (model coefficients of the colour scaled to a 50% maximum, scale), in place
-// (envmap.cpp:96-109); black: (0, 0, -inf), evaluates to 0 (srgb.cpp:31-33)
-static void spectral_envmap_texels(const Rgb2Spec &model, float *texels4, size_t n_texels) {
-    for (size_t i = 0; i < n_texels; ++i) {
-        float *px = texels4 + 4 * i;
-        const float sc = std::max(std::max(px[0], px[1]), px[2]) * 2.0f, dn = std::max(1e-8f, sc);
-        float rgb_norm[3] = { px[0] / dn, px[1] / dn, px[2] / dn }, coeff[3];
-        srgb_model_fetch(model, rgb_norm, coeff);
-        px[0] = coeff[0]; px[1] = coeff[1]; px[2] = coeff[2]; px[3] = sc;
     }
 }
 
@@ -413,117 +348,10 @@ static void emitter_jacobian_row(const Rgb2Spec &model, const float rgb[3], floa
     }
 }
 
-// ---- tabulated / analytic spectra (mtsamd_spectrum_desc) ------------------------------------------
-// the checks of ContinuousDistribution::update (distr_1d.h:293-345) and IrregularContinuousDistribution::update (distr_1d.h:561-622), with
-// their messages; *integral (may be null): the trapezoid integral both compute in double
-static int check_spectrum(const mtsamd_spectrum_desc &sp, uint32_t index, double *integral) {
-    if (integral) *integral = 0.0;
-    if (sp.type == MTSAMD_SPECTRUM_BLACKBODY) {
-        if (!(sp.temperature > 0.0f) || !std::isfinite(sp.temperature)) return fail(MTSAMD_ERR_INVALID, "spectrum %u: blackbody needs a positive temperature", index);
-        return MTSAMD_OK;
-    }
-    if (sp.type != MTSAMD_SPECTRUM_REGULAR && sp.type != MTSAMD_SPECTRUM_IRREGULAR) return fail(MTSAMD_ERR_INVALID, "spectrum %u: unknown type %d", index, sp.type);
-    const bool regular = sp.type == MTSAMD_SPECTRUM_REGULAR;
-    const char *cls = regular ? "ContinuousDistribution" : "IrregularContinuousDistribution";
-    if (sp.size < 2) return fail(MTSAMD_ERR_INVALID, "%s: needs at least two entries!", cls);
-    if (!sp.values || (!regular && !sp.wavelengths)) return fail(MTSAMD_ERR_INVALID, "spectrum %u: null array", index);
-    if (regular && !(sp.lambda_min < sp.lambda_max)) return fail(MTSAMD_ERR_INVALID, "ContinuousDistribution: invalid range!");
-    const double interval = regular ? ((double) sp.lambda_max - (double) sp.lambda_min) / (sp.size - 1) : 0.0;
-    double sum = 0.0; bool mass = false;
-    for (uint32_t i = 0; i + 1 < sp.size; ++i) {
-        const double y0 = (double) sp.values[i], y1 = (double) sp.values[i + 1];
-        double dx = interval;
-        if (!regular) {
-            const double x0 = (double) sp.wavelengths[i], x1 = (double) sp.wavelengths[i + 1];
-            if (!(x1 > x0)) return fail(MTSAMD_ERR_INVALID, "IrregularContinuousDistribution: node positions must be strictly increasing!");
-            dx = x1 - x0;
-        }
-        const double value = 0.5 * dx * (y0 + y1);
-        sum += value;
-        if (!(y0 >= 0.0) || !(y1 >= 0.0)) return fail(MTSAMD_ERR_INVALID, "%s: entries must be non-negative!", cls);
-        mass = mass || value > 0.0;
-    }
-    if (!mass) return fail(MTSAMD_ERR_INVALID, "%s: no probability mass found!", cls);
-    if (integral) *integral = sum;
-    return MTSAMD_OK;
-}
-// Texture::mean() of a table: integral / (MTS_WAVELENGTH_MAX - MTS_WAVELENGTH_MIN) (regular.cpp:99-101, irregular.cpp:111-113)
-static float spectrum_table_mean(double integral) { return (float) integral / (830.0f - 360.0f); }
-
-// headers + node / value arrays of a spectrum pool (device_spectral.h); the descs have passed check_spectrum
-static void build_spectrum_pool(const mtsamd_spectrum_desc *spectra, uint32_t n, std::vector<DevSpectrum> &headers, std::vector<float> &data) {
-    headers.assign(n, DevSpectrum{});
-    data.clear();
-    for (uint32_t i = 0; i < n; ++i) {
-        const mtsamd_spectrum_desc &sp = spectra[i];
-        DevSpectrum &h = headers[i];
-        if (sp.type == MTSAMD_SPECTRUM_BLACKBODY) { h.kind = kSpectrumBlackbody; h.temperature = sp.temperature; continue; }
-        h.size = sp.size;
-        if (sp.type == MTSAMD_SPECTRUM_REGULAR) {
-            h.kind = kSpectrumRegular; h.lambda_min = sp.lambda_min; h.lambda_max = sp.lambda_max;
-            const double interval = ((double) sp.lambda_max - (double) sp.lambda_min) / (sp.size - 1);
-            h.inv_interval = (float) (1.0 / interval);
-        } else {
-            h.kind = kSpectrumIrregular; h.lambda_min = sp.wavelengths[0]; h.lambda_max = sp.wavelengths[sp.size - 1];
-            h.nodes = (uint32_t) data.size();
-            data.insert(data.end(), sp.wavelengths, sp.wavelengths + sp.size);
-        }
-        h.values = (uint32_t) data.size();
-        data.insert(data.end(), sp.values, sp.values + sp.size);
-    }
-}
-// which spectrum slot of a record a mtsamd_bsdf_param names, or -1 if a record of this type has no such spectral parameter
-static int bsdf_spectrum_slot(int32_t type, int32_t param) {
-    const bool conductor = type == MTSAMD_BSDF_CONDUCTOR || type == MTSAMD_BSDF_ROUGHCONDUCTOR;
-    const bool dielectric = type == MTSAMD_BSDF_DIELECTRIC || type == MTSAMD_BSDF_ROUGHDIELECTRIC || type == MTSAMD_BSDF_THINDIELECTRIC;
-    const bool plastic = type == MTSAMD_BSDF_PLASTIC || type == MTSAMD_BSDF_ROUGHPLASTIC;
-    switch (param) {
-    case MTSAMD_PARAM_REFLECTANCE: return (type == MTSAMD_BSDF_DIFFUSE || plastic) ? kSpecRefl : -1;
-    case MTSAMD_PARAM_SPECULAR_REFLECTANCE: return (conductor || dielectric || plastic) ? kSpecSpec : -1;
-    case MTSAMD_PARAM_SPECULAR_TRANSMITTANCE: return dielectric ? kSpecTrans : -1;
-    case MTSAMD_PARAM_ETA: return conductor ? kSpecEta : -1;
-    case MTSAMD_PARAM_K: return conductor ? kSpecK : -1;
-    default: return -1;
-    }
-}
-static int check_spectrum_bindings(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
-                                   const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, std::vector<double> &integrals) {
-    if ((n_spectra && !spectra) || (n_bindings && !bindings)) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_create_with_spectra: null argument");
-    if ((n_spectra || n_bindings) && !desc->spectral)
-        return fail(MTSAMD_ERR_UNSUPPORTED, "tabulated spectra need the spectral variant (the RGB variants pre-integrate them on the host, xml.cpp:1126-1143)");
-    if (n_spectra > kMaxSpectra) return fail(MTSAMD_ERR_UNSUPPORTED, "at most %u spectra per scene (got %u)", kMaxSpectra, n_spectra);
-    integrals.assign(n_spectra, 0.0);
-    for (uint32_t i = 0; i < n_spectra; ++i)
-        if (int rc = check_spectrum(spectra[i], i, &integrals[i])) return rc;
-    for (uint32_t i = 0; i < n_bindings; ++i) {
-        const mtsamd_spectrum_binding &b = bindings[i];
-        if (b.spectrum >= n_spectra) return fail(MTSAMD_ERR_INVALID, "binding %u: spectrum index %u out of range", i, b.spectrum);
-        if (b.target == MTSAMD_SPECTRUM_TARGET_BSDF) {
-            if (b.index >= desc->bsdf_count) return fail(MTSAMD_ERR_INVALID, "binding %u: bsdf index %u out of range", i, b.index);
-            if (spectra[b.spectrum].type == MTSAMD_SPECTRUM_BLACKBODY) return fail(MTSAMD_ERR_INVALID, "binding %u: a blackbody spectrum is an emission spectrum, not a BSDF parameter", i);
-            const mtsamd_bsdf_desc &bd = desc->bsdfs[b.index];
-            if (bsdf_spectrum_slot(bd.type, b.param) < 0 || (b.param == MTSAMD_PARAM_REFLECTANCE && bd.texture >= 0))
-                return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: bsdf %u (type %d) takes no spectrum for parameter %d (texture weights, textured reflectances and dielectric IORs are not spectra)", i, b.index, bd.type, b.param);
-        } else if (b.target == MTSAMD_SPECTRUM_TARGET_EMITTER) {
-            if (b.index >= desc->emitter_count) return fail(MTSAMD_ERR_INVALID, "binding %u: emitter index %u out of range", i, b.index);
-            if (desc->emitters[b.index].type == MTSAMD_EMITTER_ENVMAP) return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: an envmap takes no spectrum", i);
-        } else return fail(MTSAMD_ERR_INVALID, "binding %u: unknown target %d", i, b.target);
-    }
-    return MTSAMD_OK;
-}
-
-struct mtsamd_scene {
-    int32_t environment = -1;        // index of the `constant` emitter
-    bool general_bsdfs = false;      // any BSDF other than one-sided `diffuse`: the kernels with the BSDF switch are used
-    bool nested_bsdfs = false;       // blendbsdf / mask: the fused schedule (k_bounce*, k_direct) is the one that carries the nesting code
-    bool non_diffuse_bsdfs = false;  // any BSDF other than `diffuse` (one- or two-sided): what the adjoint path replay cannot differentiate
-    bool delta_emitters = false;     // point / spot / directional emitters: handled by the same general kernels
+// A scene: the host records the setters edit (SceneState, scene_build.h) and everything that lives on the device
+struct mtsamd_scene : SceneState {
     int device = 0;
     int cu_count = 256;
-    BvhOutput bvh;
-    uint32_t n_prims = 0, n_shapes = 0;
-    std::vector<DevBsdf> bsdfs;
-    std::vector<DevEmitter> emitters;
     float4 *d_nodes = nullptr, *d_tris = nullptr;
     uint4 *d_qnodes = nullptr, *d_wnodes = nullptr;
     StackEntry *d_walk_spill = nullptr;
@@ -533,31 +361,134 @@ struct mtsamd_scene {
     float *d_area_pmf = nullptr, *d_area_cdf = nullptr;
     float *d_rough_tables = nullptr;     // roughplastic: 64 floats per BSDF that needs them
     float *d_env_texels = nullptr, *d_env_warp = nullptr; DevEnvmap *d_envmap = nullptr;      // envmap emitter
-    int32_t env_w = 0, env_h = 0;
     float4 *d_flat = nullptr, *d_pairs = nullptr;
-    std::vector<DevTexture> textures;       // device data pointers, owned
-    std::vector<float> spec_mean;           // per BSDF: mean of specular_reflectance
-    std::vector<float> diff_mean;           // spectral variant, per BSDF: Texture::mean() of a constant reflectance
-    Rgb2Spec rgb2spec;                      // spectral variant: the upsampling model, kept for parameter updates
-    // spectral variant: d(model coefficients) / d(rgb) (srgb_model_fetch_jacobian) of every constant reflectance (9 floats per BSDF) and of
-    // every bitmap texel (9 floats per texel, at 3 * grad_offset), recomputed whenever a colour is converted; d_jac = [bsdfs | texels] on
-    // the device (uploaded by mtsamd_render_adjoint_spectral when `jac_dirty`), d_cgrad = its coefficient-gradient scratch (3 floats each)
-    std::vector<float> jac_bsdf, jac_tex;
+    // spectral variant: d_jac = the Jacobians [bsdfs | texels] (jac_bsdf, jac_tex; uploaded by mtsamd_render_adjoint_spectral when `jac_dirty`),
+    // d_cgrad = its coefficient-gradient scratch (3 floats each); d_ejac = the table of mtsamd_render_adjoint_spectral_emitters, 12 floats per
+    // colour for [emitters | envmap texels] (emitter_jacobian_row), rebuilt when `ejac_dirty`; d_egrad = its 4-float (coefficient, scale) rows
     float *d_jac = nullptr, *d_cgrad = nullptr;
-    bool jac_dirty = true;
-    // spectral variant, emitter colours: the RGB texels of the envmap as the scene holds them (the device keeps coefficients), and the
-    // table of mtsamd_render_adjoint_spectral_emitters, 12 floats per colour for [emitters | envmap texels] (emitter_jacobian_row), rebuilt
-    // when `ejac_dirty`; d_egrad = its 4-float (coefficient, scale) gradient rows
-    std::vector<float> env_rgb;
     float *d_ejac = nullptr, *d_egrad = nullptr;
-    bool ejac_dirty = true;
-    DevTexture *d_textures = nullptr;
+    DevTexture *d_textures = nullptr;       // the table `textures`, whose `data` are device pointers owned by the scene
     SceneView view{};
-    bool spectral = false;
     Workspace ws;
     std::atomic<int> cancel{ 0 };
     uint64_t aov_keep_limit = 1ull << 30;      // mtsamd_scene_set_aov_keep_limit
 };
+
+namespace {
+
+struct SceneDestroyer { void operator()(mtsamd_scene *s) const { mtsamd_scene_destroy(s); } };
+
+BuildOptions build_options() {       // the shipped values, or what an experiment build finds in the environment
+    BuildOptions o;
+    if (const char *e = exp_env("MTSAMD_BVH_LEAF")) o.max_leaf = (uint32_t) std::min(15, std::max(1, atoi(e)));
+    if (const char *e = exp_env("MTSAMD_BVH_BINS")) o.bvh.bins = atoi(e);
+    if (const char *e = exp_env("MTSAMD_BVH_ICOST")) o.bvh.intersect_cost = atof(e);
+    if (const char *e = exp_env("MTSAMD_BVH_SWEEP")) o.bvh.sweep_below = (uint32_t) std::max(0, atoi(e));
+    if (const char *e = exp_env("MTSAMD_BVH_ORDER")) o.bvh.dfs_order = e[0] == 'd';
+    if (const char *e = exp_env("MTSAMD_FLAT_MAX")) o.flat_max = std::min<uint32_t>(kFlatMaxPrims, (uint32_t) std::strtoul(e, nullptr, 10));
+    return o;
+}
+
+// Everything build_host_scene made goes to the device; the scene owns every buffer from the moment it is allocated.
+int upload_scene(mtsamd_scene *s, HostScene &hs) {
+    for (size_t t = 0; t < s->textures.size(); ++t) {
+        DevTexture &dt = s->textures[t];
+        if (dt.kind != 0) continue;
+        const size_t bytes = sizeof(float) * 3 * (size_t) dt.w * dt.h;
+        if (hipMalloc((void **) &dt.data, bytes) != hipSuccess || hipMemcpy((void *) dt.data, hs.tex_src[t], bytes, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(MTSAMD_ERR_NOMEM, "texture %u: upload failed", (uint32_t) t);
+    }
+    if (s->spectral) {
+        float tx[95], ty[95], tz[95], td[95];
+        for (int i = 0; i < 95; ++i) { tx[i] = (float) kCie_x[i]; ty[i] = (float) kCie_y[i]; tz[i] = (float) kCie_z[i]; td[i] = (float) kCie_d65[i]; }
+        if (upload_spectral_tables(tx, ty, tz, td) != hipSuccess) return fail(MTSAMD_ERR_DEVICE, "spectral table upload failed");
+    }
+    const BvhOutput &bvh = s->bvh;
+    std::vector<float4> nodes(4 * (size_t) bvh.n_nodes), tris(3 * (size_t) bvh.n_slots);
+    std::memcpy(nodes.data(), bvh.nodes.data(), bvh.nodes.size() * sizeof(float));
+    std::vector<uint4> qnodes(2 * (size_t) bvh.n_nodes);
+    std::memcpy(qnodes.data(), bvh.qnodes.data(), bvh.qnodes.size() * sizeof(uint32_t));
+    std::vector<uint4> wnodes(4 * (size_t) bvh.n_wnodes);
+    std::memcpy(wnodes.data(), (MTS_NODE_P15 ? bvh.wnodes_p : (MTS_NODE_F16 ? bvh.wnodes_h : bvh.wnodes)).data(), bvh.wnodes.size() * sizeof(uint32_t));
+    std::memcpy(tris.data(), bvh.tris.data(), bvh.tris.size() * sizeof(float));
+    int rc = 0;
+    if ((rc = upload(&s->d_textures, s->textures)) || (rc = upload(&s->d_flat, hs.flat_recs)) || (rc = upload(&s->d_pairs, hs.pair_recs)) ||
+        (rc = upload(&s->d_nodes, nodes)) || (rc = upload(&s->d_qnodes, qnodes)) || (rc = upload(&s->d_wnodes, wnodes)) || (rc = upload(&s->d_tris, tris)) ||
+        (rc = upload(&s->d_tri_pos, hs.tri_pos)) || (rc = upload(&s->d_tri_nrm, hs.tri_nrm)) || (rc = upload(&s->d_tri_uv, hs.tri_uv)) ||
+        (rc = upload(&s->d_prim_shape, hs.prim_shape)) || (rc = upload(&s->d_shapes, hs.shapes)) || (rc = upload(&s->d_bsdfs, hs.bsdf_block)) ||
+        (rc = upload(&s->d_emitters, s->emitters)) || (rc = upload(&s->d_area_pmf, hs.area_pmf)) || (rc = upload(&s->d_area_cdf, hs.area_cdf)))
+        return rc;
+    if (hs.has_envmap) {
+        if ((rc = upload(&s->d_env_texels, hs.env.texels)) || (rc = upload(&s->d_env_warp, hs.env.warp))) return rc;
+        std::vector<DevEnvmap> one(1, hs.dev_env);
+        one[0].data = reinterpret_cast<const float4 *>(s->d_env_texels); one[0].warp = s->d_env_warp;
+        if ((rc = upload(&s->d_envmap, one))) return rc;
+    }
+    return MTSAMD_OK;
+}
+
+// roughplastic: transmittance tables and internal reflectance are integrated on the device (roughplastic.cpp:380-399)
+int roughplastic_tables(mtsamd_scene *s) {
+    std::vector<uint32_t> rough;
+    for (uint32_t b = 0; b < (uint32_t) s->bsdfs.size(); ++b) if (s->bsdfs[b].type == kBsdfRoughPlastic) rough.push_back(b);
+    if (rough.empty()) return MTSAMD_OK;
+    float *d_gl = nullptr;
+    if (hipMalloc((void **) &s->d_rough_tables, rough.size() * kRoughTableRes * sizeof(float)) != hipSuccess ||
+        hipMalloc((void **) &d_gl, 512 * sizeof(float)) != hipSuccess)
+        return fail(MTSAMD_ERR_NOMEM, "roughplastic tables: allocation failed");
+    hipError_t err = hipSuccess;
+    for (size_t k = 0; k < rough.size() && err == hipSuccess; ++k) {
+        const float eta = s->bsdfs[rough[k]].er;
+        const int res_t = eta > 1.0f ? 32 : 128, res_r = (1.0f / eta) > 1.0f ? 32 : 128;      // microfacet.h:476-478,520-522
+        float gl[512] = {};
+        gauss_legendre(res_t, gl, gl + 128);
+        gauss_legendre(res_r, gl + 256, gl + 384);
+        err = hipMemcpy(d_gl, gl, sizeof(gl), hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = launch_roughplastic_tables(s->d_bsdfs, rough[k], s->d_rough_tables + k * kRoughTableRes, d_gl, res_t, res_r, nullptr);
+        if (err == hipSuccess) err = hipDeviceSynchronize();
+    }
+    if (err == hipSuccess) err = hipMemcpy(s->bsdfs.data(), s->d_bsdfs, s->bsdfs.size() * sizeof(DevBsdf), hipMemcpyDeviceToHost);
+    (void) hipFree(d_gl);
+    if (err != hipSuccess) return fail(MTSAMD_ERR_DEVICE, "roughplastic tables: %s", hipGetErrorString(err));
+    return MTSAMD_OK;
+}
+
+int fill_scene_view(mtsamd_scene *s, const HostScene &hs) {
+    SceneView &v = s->view;
+    v.nodes = s->d_nodes; v.qnodes = s->d_qnodes; v.wnodes = s->d_wnodes; v.wroot = s->bvh.wroot; v.n_wnodes = s->bvh.n_wnodes; v.tris = s->d_tris; v.root = s->bvh.root;
+    for (int k = 0; k < 3; ++k) { v.q_lo[k] = s->bvh.q_lo[k]; v.q_step[k] = s->bvh.q_step[k]; v.q_inv_step[k] = 1.0f / s->bvh.q_step[k]; }
+    v.n_nodes = s->bvh.n_nodes; v.n_slots = s->bvh.n_slots; v.n_prims = s->n_prims;
+    // LDS residency: flat scenes keep everything in LDS (flat_recs).  For hierarchy scenes staging the
+    // top of the tree (nodes are stored in BFS order) was measured to LOSE: 384 staged nodes 2.5-3.2 Gray/s vs none
+    // 3.8-4.8 Gray/s on a 261 k-triangle mesh -- the 24 KB cost occupancy and the LDS/global select compiles to
+    // generic (flat) loads, while the top levels stay L1/L2-resident anyway.  Only the traversal stack lives in LDS.
+    v.lds_nodes = 0; v.lds_slots = 0;      // nodes and triangle slots are always read through L1/L2
+    // BVH2: one deferred subtree per level; BVH4: up to three
+    v.stack_depth = MTS_BVH4 ? 3u * s->bvh.wdepth + 2u : std::max<uint32_t>(s->bvh.depth, 2);
+    // standalone ray streams: 8 persistent workgroups per CU, the first 12 (BVH2: 16) stack entries of a lane in LDS
+    v.walk_lds_depth = std::min<uint32_t>(v.stack_depth, MTS_BVH4 ? 8u : 16u);      // 16 KB per workgroup: 8 workgroups (k_ray_walk: 8 waves per SIMD) per CU
+    v.walk_blocks = 8u * (uint32_t) s->cu_count;
+    if (!hs.flat && v.stack_depth > v.walk_lds_depth) {
+        const size_t entries = (size_t) v.walk_blocks * (v.stack_depth - v.walk_lds_depth) * 256u;
+        if (ws_alloc((void **) &s->d_walk_spill, entries * sizeof(StackEntry))) return fail(MTSAMD_ERR_NOMEM, "traversal spill area");
+    }
+    v.walk_spill = s->d_walk_spill;
+    v.tri_pos = s->d_tri_pos; v.tri_nrm = hs.tri_nrm.empty() ? nullptr : s->d_tri_nrm; v.tri_uv = hs.tri_uv.empty() ? nullptr : s->d_tri_uv;
+    v.prim_shape = s->d_prim_shape; v.shapes = s->d_shapes; v.bsdfs = s->d_bsdfs;
+    v.emitters = s->d_emitters; v.n_emitters = (uint32_t) s->emitters.size();
+    v.env_emitter = s->environment; v.envmap = s->d_envmap;
+    v.area_pmf = s->d_area_pmf; v.area_cdf = s->d_area_cdf;
+    v.n_shapes = s->n_shapes; v.n_bsdfs = (uint32_t) s->bsdfs.size();
+    v.textures = s->d_textures; v.n_textures = (uint32_t) s->textures.size();
+    v.flat_recs = s->d_flat; v.flat = hs.flat ? 1u : 0u;
+    v.general = s->nested_bsdfs ? 2u : (s->general_bsdfs || s->delta_emitters || s->environment >= 0) ? 1u : 0u;       // the diffuse / area-light fast path (kernels.hip) handles none of these
+    v.flat_pairs = s->d_pairs; v.n_pairs = hs.n_pairs; v.n_clusters = hs.n_clusters;
+    v.n_spectra = hs.n_spectra;
+    if (bounce_lds_bytes(v) > 150 * 1024) return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", v.stack_depth);
+    return MTSAMD_OK;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -565,7 +496,7 @@ int mtsamd_abi_version(void) { return MTSAMD_ABI_VERSION; }
 // MTS_EXPORT_PLUGIN (include/mitsuba/core/class.h:205-211): what PluginManager reads after dlopen (src/libcore/plugin.cpp:19-31)
 const char *plugin_name(void) { return "path_amd"; }
 const char *plugin_descr(void) { return "Wavefront path tracer for AMD MI355X (gfx950)"; }
-const char *mtsamd_last_error(void) { return g_last_error.c_str(); }
+const char *mtsamd_last_error(void) { return last_error(); }
 
 int mtsamd_device_count(void) {
     int n = 0;
@@ -595,562 +526,22 @@ int mtsamd_scene_create_with_spectra(const mtsamd_scene_desc *desc, const mtsamd
                                      const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, int device, mtsamd_scene **out) {
     if (!desc || !out) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_create: null argument");
     *out = nullptr;
-    std::vector<double> spectrum_integrals;      // host-only checks first: they need no device
-    if (int rc = check_spectrum_bindings(desc, spectra, n_spectra, bindings, n_bindings, spectrum_integrals)) return rc;
-    // an empty scene is valid (it renders to zeros: scenes.py:262-267 of the reference's integrator tests)
-    if (desc->mesh_count > 0 && !desc->meshes) return fail(MTSAMD_ERR_INVALID, "scene has no shapes");
-    if (desc->mesh_count > 0 && (desc->bsdf_count == 0 || !desc->bsdfs)) return fail(MTSAMD_ERR_INVALID, "scene has no BSDFs");
+    HostScene hs;       // everything the host can check and compute comes first: it needs no device
+    if (int rc = build_host_scene(desc, spectra, n_spectra, bindings, n_bindings, build_options(), hs)) return rc;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(MTSAMD_ERR_INVALID, "invalid device index %d (have %d)", device, ndev);
     HIP_TRY(hipSetDevice(device));
 
-    // ---- validate + flatten the meshes into one global primitive list ----------------------
-    uint64_t total = 0;
-    bool any_nrm = false, any_uv = false;
-    std::vector<int32_t> emitter_shape(desc->emitter_count, -1);
-    for (uint32_t i = 0; i < desc->mesh_count; ++i) {
-        const mtsamd_mesh_desc &m = desc->meshes[i];
-        if (!m.positions || !m.faces || m.face_count == 0 || m.vertex_count == 0)
-            return fail(MTSAMD_ERR_INVALID, "mesh %u: empty mesh", i);
-        if (m.bsdf < 0 || (uint32_t) m.bsdf >= desc->bsdf_count) return fail(MTSAMD_ERR_INVALID, "mesh %u: invalid bsdf index %d", i, m.bsdf);
-        if (m.emitter >= (int32_t) desc->emitter_count) return fail(MTSAMD_ERR_INVALID, "mesh %u: invalid emitter index %d", i, m.emitter);
-        if (m.emitter >= 0) {
-            // "An area emitter can be only be attached to a single shape." (area.cpp:64-66)
-            if (emitter_shape[m.emitter] >= 0) return fail(MTSAMD_ERR_INVALID, "An area emitter can be only be attached to a single shape.");
-            emitter_shape[m.emitter] = (int32_t) i;
-        }
-        for (uint64_t k = 0; k < 3ull * m.face_count; ++k)
-            if (m.faces[k] >= m.vertex_count) return fail(MTSAMD_ERR_INVALID, "mesh %u: face index out of range", i);
-        total += m.face_count;
-        any_nrm |= m.normals != nullptr; any_uv |= m.texcoords != nullptr;
-    }
-    int32_t environment = -1;
-    for (uint32_t e = 0; e < desc->emitter_count; ++e) {
-        const int32_t et = desc->emitters[e].type;
-        if (et == MTSAMD_EMITTER_CONSTANT || et == MTSAMD_EMITTER_ENVMAP) {
-            if (emitter_shape[e] >= 0) return fail(MTSAMD_ERR_INVALID, "emitter %u: an environment emitter cannot be attached to a shape", e);
-            if (environment >= 0) return fail(MTSAMD_ERR_INVALID, "Only one environment emitter can be specified per scene.");      // scene.cpp:45-46
-            if (et == MTSAMD_EMITTER_ENVMAP && (!desc->emitters[e].envmap_data || desc->emitters[e].envmap_width < 2 || desc->emitters[e].envmap_height < 2))
-                return fail(MTSAMD_ERR_INVALID, "emitter %u: the environment map must be at least 2x2 pixels in size", e);
-            environment = (int32_t) e;
-            continue;
-        }
-        if (et == MTSAMD_EMITTER_POINT || et == MTSAMD_EMITTER_SPOT || et == MTSAMD_EMITTER_DIRECTIONAL) {
-            if (emitter_shape[e] >= 0) return fail(MTSAMD_ERR_INVALID, "emitter %u: a point / spot / directional emitter cannot be attached to a shape", e);
-            if (et == MTSAMD_EMITTER_SPOT && !(desc->emitters[e].cutoff_angle >= desc->emitters[e].beam_width))
-                return fail(MTSAMD_ERR_INVALID, "emitter %u: spot: cutoff_angle must not be smaller than beam_width", e);      // spot.cpp:89
-            continue;
-        }
-        if (et != MTSAMD_EMITTER_AREA) return fail(MTSAMD_ERR_UNSUPPORTED, "emitter %u: unknown emitter type %d", e, et);
-        if (emitter_shape[e] < 0) return fail(MTSAMD_ERR_INVALID, "emitter %u is not attached to a shape", e);
-    }
-    for (uint32_t b = 0; b < desc->bsdf_count; ++b) {
-        const mtsamd_bsdf_desc &bd = desc->bsdfs[b];
-        if (bd.type < MTSAMD_BSDF_DIFFUSE || bd.type > MTSAMD_BSDF_MASK) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: unknown BSDF type %d", b, bd.type);
-        auto bound = [&](int32_t param) {       // the parameter holds a tabulated spectrum: its value in the description is ignored
-            for (uint32_t i = 0; i < n_bindings; ++i)
-                if (bindings[i].target == MTSAMD_SPECTRUM_TARGET_BSDF && bindings[i].index == b && bindings[i].param == param) return true;
-            return false;
-        };
-        if (desc->spectral && (bd.type == MTSAMD_BSDF_CONDUCTOR || bd.type == MTSAMD_BSDF_ROUGHCONDUCTOR) &&
-            ((!bound(MTSAMD_PARAM_ETA) && (bd.eta[0] != bd.eta[1] || bd.eta[0] != bd.eta[2])) || (!bound(MTSAMD_PARAM_K) && (bd.k[0] != bd.k[1] || bd.k[0] != bd.k[2]))))
-            return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: the spectral variant needs uniform (constant) eta and k spectra, or tabulated ones (mtsamd_scene_create_with_spectra)", b);
-        if (bd.texture >= 0 && bd.type != MTSAMD_BSDF_DIFFUSE && bd.type != MTSAMD_BSDF_PLASTIC && bd.type != MTSAMD_BSDF_ROUGHPLASTIC &&
-            bd.type != MTSAMD_BSDF_BLEND && bd.type != MTSAMD_BSDF_MASK)
-            return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: textures are implemented for diffuse.reflectance and (rough)plastic.diffuse_reflectance only", b);
-        if (bd.type == MTSAMD_BSDF_ROUGHPLASTIC && (bd.int_ior == bd.ext_ior || bd.alpha_u != bd.alpha_v))
-            return fail(MTSAMD_ERR_INVALID, bd.int_ior == bd.ext_ior ? "The interior and exterior indices of refraction must be positive and differ!"
-                                                                      : "The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!");
-        if (bd.type == MTSAMD_BSDF_ROUGHDIELECTRIC && (bd.int_ior < 0.0f || bd.ext_ior < 0.0f || bd.int_ior == bd.ext_ior))
-            return fail(MTSAMD_ERR_INVALID, "The interior and exterior indices of refraction must be positive and differ!");      // roughdielectric.cpp:153-155
-        if ((bd.type == MTSAMD_BSDF_DIELECTRIC || bd.type == MTSAMD_BSDF_PLASTIC || bd.type == MTSAMD_BSDF_ROUGHPLASTIC || bd.type == MTSAMD_BSDF_ROUGHDIELECTRIC ||
-             bd.type == MTSAMD_BSDF_THINDIELECTRIC) &&
-            (bd.int_ior < 0.0f || bd.ext_ior < 0.0f || bd.ext_ior == 0.0f))
-            return fail(MTSAMD_ERR_INVALID, "The interior and exterior indices of refraction must be positive!");      // dielectric.cpp:183-185
-        if ((bd.type == MTSAMD_BSDF_DIELECTRIC || bd.type == MTSAMD_BSDF_ROUGHDIELECTRIC || bd.type == MTSAMD_BSDF_THINDIELECTRIC) && bd.twosided)
-            return fail(MTSAMD_ERR_INVALID, "Only materials without a transmission component can be nested!");          // twosided.cpp:90-91
-        if (desc->bsdfs[b].texture >= (int32_t) desc->texture_count) return fail(MTSAMD_ERR_INVALID, "bsdf %u: invalid texture index %d", b, desc->bsdfs[b].texture);
-    }
-    for (uint32_t t = 0; t < desc->texture_count; ++t) {
-        if (!desc->textures) return fail(MTSAMD_ERR_INVALID, "null texture table");
-        const mtsamd_texture_desc &td = desc->textures[t];
-        if (td.kind != 0 && td.kind != 1) return fail(MTSAMD_ERR_UNSUPPORTED, "texture %u: unknown texture kind %d", t, td.kind);
-        if (td.kind == 0 && (!td.data || td.width < 2 || td.height < 2))
-            return fail(MTSAMD_ERR_INVALID, "texture %u: image must be at least 2x2 pixels in size", t);      // bitmap.cpp:101-107
-    }
-    if (total >= (1ull << 27)) return fail(MTSAMD_ERR_UNSUPPORTED, "too many primitives (%llu)", (unsigned long long) total);
-
-    mtsamd_scene *s = new mtsamd_scene();
+    std::unique_ptr<mtsamd_scene, SceneDestroyer> s(new mtsamd_scene());       // an error return below frees whatever was uploaded
     s->device = device;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->cu_count = prop.multiProcessorCount;
-    s->n_prims = (uint32_t) total; s->n_shapes = desc->mesh_count;
-
-    std::vector<float> tri_pos(9 * total), tri_nrm(any_nrm ? 9 * total : 0), tri_uv(any_uv ? 6 * total : 0);
-    std::vector<uint32_t> prim_shape(total);
-    std::vector<DevShape> shapes(desc->mesh_count);
-    std::vector<float> area_pmf(total, 0.0f), area_cdf(total, 0.0f);
-    s->emitters.resize(desc->emitter_count);
-    s->environment = environment;
-    uint32_t off = 0;
-    for (uint32_t i = 0; i < desc->mesh_count; ++i) {
-        const mtsamd_mesh_desc &m = desc->meshes[i];
-        shapes[i].bsdf = m.bsdf; shapes[i].emitter = m.emitter; shapes[i].first_prim = off;
-        shapes[i].flags = (m.normals ? kShapeHasNormals : 0u) | (m.texcoords ? kShapeHasUV : 0u);
-        for (uint32_t f = 0; f < m.face_count; ++f) {
-            uint32_t gp = off + f;
-            prim_shape[gp] = i;
-            for (int j = 0; j < 3; ++j) {
-                uint32_t vi = m.faces[3 * f + j];
-                for (int k = 0; k < 3; ++k) tri_pos[9 * (size_t) gp + 3 * j + k] = m.positions[3 * (size_t) vi + k];
-                if (m.normals) for (int k = 0; k < 3; ++k) tri_nrm[9 * (size_t) gp + 3 * j + k] = m.normals[3 * (size_t) vi + k];
-                if (m.texcoords) for (int k = 0; k < 2; ++k) tri_uv[6 * (size_t) gp + 2 * j + k] = m.texcoords[2 * (size_t) vi + k];
-            }
-        }
-        if (m.emitter >= 0) {
-            // Mesh::area_distr_build (mesh.cpp:284-307) + DiscreteDistribution::update (distr_1d.h:49-88)
-            double sum = 0.0; uint32_t lo = 0xffffffffu, hi = 0xffffffffu;
-            for (uint32_t f = 0; f < m.face_count; ++f) {
-                const float *tp = &tri_pos[9 * (size_t) (off + f)];
-                float e1[3] = { tp[3] - tp[0], tp[4] - tp[1], tp[5] - tp[2] }, e2[3] = { tp[6] - tp[0], tp[7] - tp[1], tp[8] - tp[2] };
-                float cx = std::fma(e1[1], e2[2], -(e1[2] * e2[1])), cy = std::fma(e1[2], e2[0], -(e1[0] * e2[2])),
-                      cz = std::fma(e1[0], e2[1], -(e1[1] * e2[0]));
-                float area = 0.5f * std::sqrt(std::fma(cz, cz, std::fma(cy, cy, cx * cx)));
-                area_pmf[off + f] = area;
-                sum += (double) area;
-                area_cdf[off + f] = (float) sum;
-                if (area > 0.0f) { if (lo == 0xffffffffu) lo = f; hi = f; }
-            }
-            if (lo == 0xffffffffu) { delete s; return fail(MTSAMD_ERR_INVALID, "DiscreteDistribution: no probability mass found!"); }
-            DevEmitter &e = s->emitters[m.emitter];
-            std::memset(&e, 0, sizeof(e));
-            const mtsamd_emitter_desc &ed = desc->emitters[m.emitter];
-            e.r = ed.radiance[0]; e.g = ed.radiance[1]; e.b = ed.radiance[2];
-            e.shape = i; e.first_prim = off; e.n_prims = m.face_count;
-            e.area_sum = (float) sum; e.area_norm = (float) (1.0 / sum);
-            e.valid_lo = lo; e.valid_hi = hi;
-        }
-        off += m.face_count;
-    }
-    // delta emitters (point.cpp:52-65, spot.cpp:68-91, directional.cpp:43-63)
-    for (uint32_t ei = 0; ei < desc->emitter_count; ++ei) {
-        const mtsamd_emitter_desc &ed = desc->emitters[ei];
-        if (ed.type != MTSAMD_EMITTER_POINT && ed.type != MTSAMD_EMITTER_SPOT && ed.type != MTSAMD_EMITTER_DIRECTIONAL) continue;
-        DevEmitter &e = s->emitters[ei];
-        std::memset(&e, 0, sizeof(e));
-        s->delta_emitters = true;
-        e.r = ed.radiance[0]; e.g = ed.radiance[1]; e.b = ed.radiance[2];
-        e.shape = 0xffffffffu; e.pad0 = (uint32_t) ed.type;
-        const float *m = ed.to_world;
-        e.cx = m[3]; e.cy = m[7]; e.cz = m[11];
-        if (ed.type == MTSAMD_EMITTER_DIRECTIONAL) {             // d = to_world * (0, 0, 1)
-            e.aux[0] = m[2]; e.aux[1] = m[6]; e.aux[2] = m[10];
-        } else if (ed.type == MTSAMD_EMITTER_SPOT) {
-            const double a = m[0], b = m[1], c = m[2], d2 = m[4], e2 = m[5], f = m[6], g = m[8], h2 = m[9], i2 = m[10];
-            const double det = a * (e2 * i2 - f * h2) - b * (d2 * i2 - f * g) + c * (d2 * h2 - e2 * g);
-            if (det == 0.0) { delete s; return fail(MTSAMD_ERR_INVALID, "emitter %u: singular to_world transformation", ei); }
-            const double inv[9] = { (e2 * i2 - f * h2) / det, (c * h2 - b * i2) / det, (b * f - c * e2) / det,
-                                    (f * g - d2 * i2) / det, (a * i2 - c * g) / det, (c * d2 - a * f) / det,
-                                    (d2 * h2 - e2 * g) / det, (b * g - a * h2) / det, (a * e2 - b * d2) / det };
-            for (int k = 0; k < 9; ++k) e.aux[k] = (float) inv[k];
-            const float cutoff = ed.cutoff_angle * (kPi / 180.0f), beam = ed.beam_width * (kPi / 180.0f);
-            e.aux[9] = cutoff; e.aux[10] = std::cos(cutoff); e.aux[11] = std::cos(beam); e.aux[12] = 1.0f / (cutoff - beam);
-        }
-    }
-    // spectral variant: RGB -> spectrum coefficients on the host (srgb.cpp:31-41, srgb_d65.cpp:31-46)
-    Rgb2Spec &model = s->rgb2spec;
-    if (desc->spectral) {
-        if (!desc->rgb2spec_path || !rgb2spec_load(desc->rgb2spec_path, model)) {
-            delete s;
-            return fail(MTSAMD_ERR_INVALID, "Could not load sRGB-to-spectrum upsampling model ('%s'); build it with mtsamd_rgb2spec_build",
-                        desc->rgb2spec_path ? desc->rgb2spec_path : "(null)");
-        }
-        s->spectral = true;
-        for (uint32_t e = 0; e < desc->emitter_count; ++e) {
-            const float *c = desc->emitters[e].radiance;
-            float color[3] = { c[0], c[1], c[2] };
-            float scale = std::max(std::max(color[0], color[1]), color[2]) * 2.0f;
-            if (scale != 0.0f) { float r = 1.0f / scale; for (float &v : color) v *= r; }
-            float coeff[3];
-            srgb_model_fetch(model, color, coeff);
-            float d65_scale = 1.0f * scale;
-            d65_scale *= 1.0f / 10568.0f;                      // d65.cpp:44-50
-            DevEmitter &d = s->emitters[e];
-            d.c0 = coeff[0]; d.c1 = coeff[1]; d.c2 = coeff[2]; d.d65_scale = d65_scale;
-        }
-    }
-    s->bsdfs.resize(desc->bsdf_count);
-    std::vector<float> spec_mean(desc->bsdf_count, 0.0f);          // Texture::mean() of specular_reflectance (plastic lobe weights)
-    for (uint32_t b = 0; b < desc->bsdf_count; ++b) {
-        DevBsdf &d = s->bsdfs[b];
-        spec_mean[b] = (desc->bsdfs[b].specular_reflectance[0] + desc->bsdfs[b].specular_reflectance[1] + desc->bsdfs[b].specular_reflectance[2]) * (1.0f / 3.0f);
-        std::memset(&d, 0, sizeof(d));
-        d.r = desc->bsdfs[b].reflectance[0]; d.g = desc->bsdfs[b].reflectance[1]; d.b = desc->bsdfs[b].reflectance[2];
-        d.type = desc->bsdfs[b].type; d.texture = desc->bsdfs[b].texture < 0 ? -1 : desc->bsdfs[b].texture;
-        fill_bsdf_model(desc->bsdfs[b], d);
-        if (d.type != kBsdfDiffuse || (d.flags & kBsdfTwoSided)) s->general_bsdfs = true;
-        if (d.type != kBsdfDiffuse) s->non_diffuse_bsdfs = true;
-        if (d.type == kBsdfBlend || d.type == kBsdfMask) {
-            s->nested_bsdfs = true;
-            // blendbsdf.cpp:57-79 / mask.cpp:67-91 over plain records of this table (one level of nesting)
-            const mtsamd_bsdf_desc &bd = desc->bsdfs[b];
-            const int n_child = d.type == kBsdfBlend ? 2 : 1;
-            bool smooth = false;
-            for (int k = 0; k < n_child; ++k) {
-                const int32_t c = bd.nested[k];
-                if (c < 0 || (uint32_t) c >= desc->bsdf_count || desc->bsdfs[c].type < MTSAMD_BSDF_DIFFUSE || desc->bsdfs[c].type > MTSAMD_BSDF_THINDIELECTRIC) {
-                    delete s;
-                    return fail(MTSAMD_ERR_INVALID, "bsdf %u: nested[%d] must index a plain BSDF record", b, k);
-                }
-                if (desc->spectral && desc->bsdfs[c].texture >= 0) {
-                    delete s;
-                    return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: textured children of a blendbsdf / mask are implemented for the RGB variant only", b);
-                }
-                const int ct = desc->bsdfs[c].type;
-                smooth = smooth || ct == kBsdfDiffuse || ct == kBsdfRoughConductor || ct == kBsdfPlastic || ct == kBsdfRoughPlastic || ct == kBsdfRoughDielectric;
-            }
-            if (d.type == kBsdfMask && bd.twosided) { delete s; return fail(MTSAMD_ERR_INVALID, "Only materials without a transmission component can be nested!"); }
-            if (desc->spectral && d.texture >= 0) {
-                delete s;
-                return fail(MTSAMD_ERR_UNSUPPORTED, "eval_1(): a bitmap / checkerboard weight is converted into spectra in the spectral variant (bitmap.cpp:218-222); use a constant");
-            }
-            d.nested0 = (uint32_t) bd.nested[0]; d.nested1 = (uint32_t) (n_child == 2 ? bd.nested[1] : bd.nested[0]);
-            d.flags = (bd.twosided ? kBsdfTwoSided : 0u) | kBsdfUniformRefl | (smooth ? kBsdfNestSmooth : 0u) |
-                      ((d.texture >= 0 && desc->textures[d.texture].kind == 0) ? kBsdfWeightLum : 0u);
-        }
-        if (desc->spectral) {
-            // every colour-valued parameter is a `uniform` constant or an `srgb` texture: range check + coefficient fetch
-            // (srgb.cpp:31-41); Texture::mean() of either kind feeds the plastic lobe-selection weight (plastic.cpp:170-175)
-            const mtsamd_bsdf_desc &bd = desc->bsdfs[b];
-            const float *vals[3] = { bd.reflectance, bd.specular_reflectance, bd.specular_transmittance };
-            float *coeffs[3] = { &d.c0, &d.sc0, &d.tc0 };
-            float means[3] = { 0.0f, 0.0f, 0.0f };
-            for (int p = 0; p < 3; ++p) {
-                if (d.type == kBsdfBlend || d.type == kBsdfMask) break;   // the weight is a scalar; the children are records of their own
-                if (p == 0 && d.texture >= 0) continue;               // textured: coefficients per texel, mean from the texture (below)
-                if (bd.uniform_mask & (1 << p)) { means[p] = vals[p][0]; continue; }
-                bool tabulated = false;               // a bound spectrum (below) replaces the colour: no range check, no coefficients
-                for (uint32_t i = 0; i < n_bindings; ++i)
-                    tabulated = tabulated || (bindings[i].target == MTSAMD_SPECTRUM_TARGET_BSDF && bindings[i].index == b &&
-                                              bsdf_spectrum_slot(bd.type, bindings[i].param) == p);
-                if (tabulated) continue;
-                const float *c = vals[p];
-                if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] > 1 || c[1] > 1 || c[2] > 1) {
-                    delete s;
-                    return fail(MTSAMD_ERR_INVALID, "Invalid RGB reflectance value [%g, %g, %g], must be in the range [0, 1]!", c[0], c[1], c[2]);
-                }
-                float coeff[3];
-                srgb_model_fetch(model, c, coeff);
-                coeffs[p][0] = coeff[0]; coeffs[p][1] = coeff[1]; coeffs[p][2] = coeff[2];
-                means[p] = srgb_model_mean(coeff);
-                if (p == 0) {
-                    s->jac_bsdf.resize(9 * (size_t) desc->bsdf_count, 0.0f);
-                    srgb_model_fetch_jacobian(model, c, s->jac_bsdf.data() + 9 * (size_t) b);
-                }
-            }
-            if (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic) d.kr = means[1] / (means[0] + means[1]);
-            spec_mean[b] = means[1];
-            s->diff_mean.resize(desc->bsdf_count, 0.0f);
-            s->diff_mean[b] = means[0];
-        }
-    }
-    // bound spectra replace the colour / constant of their parameter; Texture::mean() of the two reflectances feeds the plastic lobe weights
-    for (uint32_t i = 0; i < n_bindings; ++i) {
-        const mtsamd_spectrum_binding &bn = bindings[i];
-        if (bn.target != MTSAMD_SPECTRUM_TARGET_BSDF) continue;
-        DevBsdf &d = s->bsdfs[bn.index];
-        const int slot = bsdf_spectrum_slot(desc->bsdfs[bn.index].type, bn.param);
-        uint32_t &word = slot < 3 ? d.spectra0 : d.spectra1;
-        const int shift = 10 * (slot < 3 ? slot : slot - 3);
-        word = (word & ~(1023u << shift)) | ((bn.spectrum + 1u) << shift);
-        const float mean = spectrum_table_mean(spectrum_integrals[bn.spectrum]);
-        if (slot == kSpecRefl) s->diff_mean[bn.index] = mean;
-        if (slot == kSpecSpec) spec_mean[bn.index] = mean;
-        if (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic) d.kr = spec_mean[bn.index] / (s->diff_mean[bn.index] + spec_mean[bn.index]);
-    }
-    if (n_spectra) s->general_bsdfs = true;       // the spectrum pool is read by the general step
-
-    for (uint32_t t = 0; t < desc->texture_count; ++t) {
-        const mtsamd_texture_desc &td = desc->textures[t];
-        DevTexture dt{};
-        dt.kind = (uint32_t) td.kind;
-        dt.w = td.kind == 0 ? td.width : 0; dt.h = td.kind == 0 ? td.height : 0;
-        dt.grad_offset = s->textures.empty() ? 0u : s->textures.back().grad_offset + 3u * (uint32_t) s->textures.back().w * (uint32_t) s->textures.back().h;
-        bool ident = true;
-        for (int k = 0; k < 6; ++k) { dt.uvm[k] = td.to_uv[k]; ident = ident && td.to_uv[k] == 0.0f; }
-        if (ident) { dt.uvm[0] = 1.0f; dt.uvm[4] = 1.0f; }
-        for (int k = 0; k < 3; ++k) { dt.c0[k] = td.color0[k]; dt.c1[k] = td.color1[k]; }
-        if (td.kind == 1) {
-            // Texture::mean(): mean of the two colours' means (checkerboard.cpp:88-90, srgb.cpp:52-57); spectral variant: `srgb`
-            // spectra with the constructor's range check (srgb.cpp:34-35)
-            if (desc->spectral) {
-                for (int k = 0; k < 3; ++k)
-                    if (td.color0[k] < 0 || td.color0[k] > 1 || td.color1[k] < 0 || td.color1[k] > 1) {
-                        mtsamd_scene_destroy(s);
-                        return fail(MTSAMD_ERR_INVALID, "Invalid RGB reflectance value in checkerboard texture %u, must be in the range [0, 1]!", t);
-                    }
-                srgb_model_fetch(model, td.color0, dt.c0);
-                srgb_model_fetch(model, td.color1, dt.c1);
-                dt.mean = 0.5f * (srgb_model_mean(dt.c0) + srgb_model_mean(dt.c1));
-            } else {
-                dt.mean = 0.5f * ((td.color0[0] + td.color0[1] + td.color0[2]) * (1.0f / 3.0f) + (td.color1[0] + td.color1[1] + td.color1[2]) * (1.0f / 3.0f));
-            }
-            s->textures.push_back(dt);
-            continue;
-        }
-        size_t bytes = sizeof(float) * 3 * (size_t) td.width * td.height;
-        float *ptr = nullptr;
-        // Texture::mean(): mean luminance (bitmap.cpp:124-136); spectral variant: texels become model coefficients, mean of
-        // srgb_model_mean (bitmap.cpp:116-123)
-        const size_t n_texels = (size_t) td.width * td.height;
-        std::vector<float> coeffs;
-        const float *src = td.data;
-        double mean = 0.0;
-        if (desc->spectral) {
-            mean = spectral_texels(model, td.data, n_texels, coeffs, s->jac_tex, dt.grad_offset);
-            src = coeffs.data();
-        } else {
-            for (size_t i = 0; i < n_texels; ++i) {
-                const float *p = td.data + 3 * i;
-                mean += (double) (p[0] * 0.212671f + p[1] * 0.715160f + p[2] * 0.072169f);
-            }
-        }
-        dt.mean = (float) (mean / (double) n_texels);
-        if (hipMalloc((void **) &ptr, bytes) != hipSuccess || hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            mtsamd_scene_destroy(s);
-            return fail(MTSAMD_ERR_NOMEM, "texture %u: upload failed", t);
-        }
-        dt.data = ptr;
-        s->textures.push_back(dt);
-    }
-    // plastic.cpp:170-175: specular sampling weight from Texture::mean() of both reflectances
-    s->spec_mean = spec_mean;
-    for (uint32_t b = 0; b < desc->bsdf_count; ++b) {
-        DevBsdf &d = s->bsdfs[b];
-        if (d.texture >= 0 && (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic)) d.kr = spec_mean[b] / (s->textures[d.texture].mean + spec_mean[b]);
-    }
-
-    if (desc->spectral) {
-        float tx[95], ty[95], tz[95], td[95];
-        for (int i = 0; i < 95; ++i) { tx[i] = (float) kCie_x[i]; ty[i] = (float) kCie_y[i]; tz[i] = (float) kCie_z[i]; td[i] = (float) kCie_d65[i]; }
-        if (upload_spectral_tables(tx, ty, tz, td) != hipSuccess) { mtsamd_scene_destroy(s); return fail(MTSAMD_ERR_DEVICE, "spectral table upload failed"); }
-    }
-
-    // ---- accelerator -------------------------------------------------------------------------
-    uint32_t max_leaf = 4;
-    if (const char *e = exp_env("MTSAMD_BVH_LEAF")) max_leaf = (uint32_t) std::min(15, std::max(1, atoi(e)));      // experiment switch
-    BvhOptions bopt;
-    if (const char *e = exp_env("MTSAMD_BVH_BINS")) bopt.bins = atoi(e);                      // experiment switches
-    if (const char *e = exp_env("MTSAMD_BVH_ICOST")) bopt.intersect_cost = atof(e);
-    if (const char *e = exp_env("MTSAMD_BVH_SWEEP")) bopt.sweep_below = (uint32_t) std::max(0, atoi(e));
-    if (const char *e = exp_env("MTSAMD_BVH_ORDER")) bopt.dfs_order = e[0] == 'd';
-    if (s->n_prims > 0) build_bvh(tri_pos.data(), s->n_prims, max_leaf, s->bvh, &bopt);
-    else { s->bvh = BvhOutput{}; s->bvh.root = s->bvh.wroot = 0x80000000u; s->bvh.wdepth = 1; }       // a leaf with no triangles (BVH2 and BVH4 root: without wroot the walks of the split pipeline started at node 0 of an empty node array)
-    if (s->environment >= 0) {       // ConstantBackgroundEmitter::set_scene (constant.cpp:47-51): bounding sphere of Scene::bbox()
-        DevEmitter &e = s->emitters[s->environment];
-        const float sc[4] = { e.c0, e.c1, e.c2, e.d65_scale };            // spectral variant: filled above
-        std::memset(&e, 0, sizeof(e));
-        e.c0 = sc[0]; e.c1 = sc[1]; e.c2 = sc[2]; e.d65_scale = sc[3];
-        const mtsamd_emitter_desc &ed = desc->emitters[s->environment];
-        e.r = ed.radiance[0]; e.g = ed.radiance[1]; e.b = ed.radiance[2];
-        e.shape = 0xffffffffu; e.pad0 = ed.type == MTSAMD_EMITTER_ENVMAP ? kEmitterEnvmap : kEmitterConstant;
-        const float *bb = s->bvh.bbox;
-        e.cx = (bb[3] + bb[0]) * 0.5f; e.cy = (bb[4] + bb[1]) * 0.5f; e.cz = (bb[5] + bb[2]) * 0.5f;
-        const float dx = e.cx - bb[3], dy = e.cy - bb[4], dz = e.cz - bb[5];
-        const float r = std::sqrt(std::fma(dz, dz, std::fma(dy, dy, dx * dx)));
-        e.radius = std::max(kRayEpsilon, r * (1.0f + kRayEpsilon));
-    }
-
-    for (DevEmitter &e : s->emitters) {           // DirectionalEmitter::set_scene (directional.cpp:65-70)
-        if (e.pad0 != kEmitterDirectional) continue;
-        const float *bb = s->bvh.bbox;
-        const float cx = (bb[3] + bb[0]) * 0.5f, cy = (bb[4] + bb[1]) * 0.5f, cz = (bb[5] + bb[2]) * 0.5f;
-        const float dx = cx - bb[3], dy = cy - bb[4], dz = cz - bb[5];
-        const float r = std::sqrt(std::fma(dz, dz, std::fma(dy, dy, dx * dx)));
-        e.radius = std::max(kRayEpsilon, r * (1.0f + kRayEpsilon));
-    }
-
-    for (uint32_t i = 0; i < n_bindings; ++i)       // a tabulated radiance is the radiance itself (no D65 factor)
-        if (bindings[i].target == MTSAMD_SPECTRUM_TARGET_EMITTER) s->emitters[bindings[i].index].spectrum = bindings[i].spectrum + 1u;
-
-    std::vector<float4> nodes(4 * (size_t) s->bvh.n_nodes), tris(3 * (size_t) s->bvh.n_slots);
-    std::memcpy(nodes.data(), s->bvh.nodes.data(), s->bvh.nodes.size() * sizeof(float));
-    std::vector<uint4> qnodes(2 * (size_t) s->bvh.n_nodes);
-    std::memcpy(qnodes.data(), s->bvh.qnodes.data(), s->bvh.qnodes.size() * sizeof(uint32_t));
-    std::vector<uint4> wnodes(4 * (size_t) s->bvh.n_wnodes);
-    std::memcpy(wnodes.data(), (MTS_NODE_P15 ? s->bvh.wnodes_p : (MTS_NODE_F16 ? s->bvh.wnodes_h : s->bvh.wnodes)).data(), s->bvh.wnodes.size() * sizeof(uint32_t));
-    std::memcpy(tris.data(), s->bvh.tris.data(), s->bvh.tris.size() * sizeof(float));
-    // flat scenes: 64-byte records in primitive order (device_scene.h)
-    uint32_t flat_max = kFlatMaxPrims;
-    if (const char *e = exp_env("MTSAMD_FLAT_MAX")) flat_max = std::min<uint32_t>(kFlatMaxPrims, (uint32_t) std::strtoul(e, nullptr, 10));   // experiment switch
-    const bool flat = s->n_prims <= flat_max;
-    std::vector<float4> flat_recs(flat ? 4 * (size_t) s->n_prims : 0);
-    for (uint32_t gp = 0; flat && gp < s->n_prims; ++gp) {
-        const float *tp = &tri_pos[9 * (size_t) gp];
-        uint32_t sh = prim_shape[gp]; float shf; std::memcpy(&shf, &sh, 4);
-        flat_recs[4 * gp + 0] = make_float4(tp[0], tp[1], tp[2], tp[3] - tp[0]);
-        flat_recs[4 * gp + 1] = make_float4(tp[4] - tp[1], tp[5] - tp[2], tp[6] - tp[0], tp[7] - tp[1]);
-        flat_recs[4 * gp + 2] = make_float4(tp[8] - tp[2], tp[3], tp[4], tp[5]);
-        flat_recs[4 * gp + 3] = make_float4(tp[6], tp[7], tp[8], shf);
-    }
-    const uint32_t n_pairs = flat ? (s->n_prims + 1) / 2 : 0;
-    std::vector<float4> pair_recs(5 * (size_t) n_pairs, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (uint32_t k = 0; k < n_pairs; ++k) {
-        float a[9] = { 0 }, b[9] = { 0 };       // p0, e1, e2 of primitives 2k and 2k+1 (zero = never hit)
-        for (int which = 0; which < 2; ++which) {
-            uint32_t gp = 2 * k + which;
-            if (gp >= s->n_prims) continue;
-            const float *tp = &tri_pos[9 * (size_t) gp];
-            float *r = which ? b : a;
-            r[0] = tp[0]; r[1] = tp[1]; r[2] = tp[2];
-            r[3] = tp[3] - tp[0]; r[4] = tp[4] - tp[1]; r[5] = tp[5] - tp[2];
-            r[6] = tp[6] - tp[0]; r[7] = tp[7] - tp[1]; r[8] = tp[8] - tp[2];
-        }
-        pair_recs[5 * k + 0] = make_float4(a[0], b[0], a[1], b[1]);
-        pair_recs[5 * k + 1] = make_float4(a[2], b[2], a[3], b[3]);
-        pair_recs[5 * k + 2] = make_float4(a[4], b[4], a[5], b[5]);
-        pair_recs[5 * k + 3] = make_float4(a[6], b[6], a[7], b[7]);
-        pair_recs[5 * k + 4] = make_float4(a[8], b[8], 0.0f, 0.0f);
-    }
-    // clusters of consecutive pairs that belong to one shape, with their bounding box padded by 1e-4 of the scene's extent (the box
-    // test of coherent waves only culls; device_scene.h, traverse_flat_clustered).  Appended to the pair records.
-    uint32_t n_clusters = 0;
-    if (flat && n_pairs > 0) {
-        float ext = 0.0f;
-        for (uint32_t gp = 0; gp < s->n_prims; ++gp) for (int q = 0; q < 9; ++q) ext = std::max(ext, std::fabs(tri_pos[9 * (size_t) gp + q]));
-        const float pad = 1e-4f * std::max(ext, 1e-3f);
-        uint32_t k0 = 0;
-        while (k0 < n_pairs) {
-            uint32_t k1 = k0 + 1;
-            while (k1 < n_pairs && prim_shape[2 * k1] == prim_shape[2 * k0]) ++k1;
-            float lo[3] = { 3e38f, 3e38f, 3e38f }, hi[3] = { -3e38f, -3e38f, -3e38f };
-            for (uint32_t gp = 2 * k0; gp < std::min(2 * k1, s->n_prims); ++gp)
-                for (int vtx = 0; vtx < 3; ++vtx) for (int a = 0; a < 3; ++a) {
-                    lo[a] = std::min(lo[a], tri_pos[9 * (size_t) gp + 3 * vtx + a]); hi[a] = std::max(hi[a], tri_pos[9 * (size_t) gp + 3 * vtx + a]);
-                }
-            const uint32_t cnt = k1 - k0; float cntf; std::memcpy(&cntf, &cnt, 4);
-            pair_recs.push_back(make_float4(lo[0] - pad, lo[1] - pad, lo[2] - pad, cntf));
-            pair_recs.push_back(make_float4(hi[0] + pad, hi[1] + pad, hi[2] + pad, 0.0f));
-            ++n_clusters; k0 = k1;
-        }
-    }
-    // the BSDF records, and behind them the spectrum pool: headers, then node / value arrays (spectrum_pool() in kernels.hip)
-    std::vector<DevBsdf> bsdf_block = s->bsdfs;
-    if (n_spectra) {
-        std::vector<DevSpectrum> headers; std::vector<float> data;
-        build_spectrum_pool(spectra, n_spectra, headers, data);
-        const size_t bytes = headers.size() * sizeof(DevSpectrum) + data.size() * sizeof(float);
-        bsdf_block.resize(s->bsdfs.size() + (bytes + sizeof(DevBsdf) - 1) / sizeof(DevBsdf));
-        char *dst = reinterpret_cast<char *>(bsdf_block.data() + s->bsdfs.size());
-        std::memset(dst, 0, (bsdf_block.size() - s->bsdfs.size()) * sizeof(DevBsdf));
-        std::memcpy(dst, headers.data(), headers.size() * sizeof(DevSpectrum));
-        if (!data.empty()) std::memcpy(dst + headers.size() * sizeof(DevSpectrum), data.data(), data.size() * sizeof(float));
-    }
-    int rc = 0;
-    if ((rc = upload(&s->d_textures, s->textures)) || (rc = upload(&s->d_flat, flat_recs)) || (rc = upload(&s->d_pairs, pair_recs)) || (rc = upload(&s->d_nodes, nodes)) || (rc = upload(&s->d_qnodes, qnodes)) || (rc = upload(&s->d_wnodes, wnodes)) || (rc = upload(&s->d_tris, tris)) || (rc = upload(&s->d_tri_pos, tri_pos)) ||
-        (rc = upload(&s->d_tri_nrm, tri_nrm)) || (rc = upload(&s->d_tri_uv, tri_uv)) || (rc = upload(&s->d_prim_shape, prim_shape)) ||
-        (rc = upload(&s->d_shapes, shapes)) || (rc = upload(&s->d_bsdfs, bsdf_block)) || (rc = upload(&s->d_emitters, s->emitters)) ||
-        (rc = upload(&s->d_area_pmf, area_pmf)) || (rc = upload(&s->d_area_cdf, area_cdf))) {
-        mtsamd_scene_destroy(s);
-        return rc;
-    }
-    // envmap emitter: texels + sampling hierarchy (envmap.cpp:66-125, distr_2d.h:200-312)
-    if (s->environment >= 0 && desc->emitters[s->environment].type == MTSAMD_EMITTER_ENVMAP) {
-        const mtsamd_emitter_desc &ed = desc->emitters[s->environment];
-        EnvmapHost eh;
-        if (!build_envmap(ed.envmap_data, ed.envmap_width, ed.envmap_height, eh) || eh.lv_offset.size() > (size_t) kEnvMaxLevels) {
-            mtsamd_scene_destroy(s);
-            return fail(MTSAMD_ERR_INVALID, "envmap: unsupported image size %d x %d", ed.envmap_width, ed.envmap_height);
-        }
-        if (desc->spectral) {
-            // envmap.cpp:96-109: every texel becomes (model coefficients of the colour scaled to a 50% maximum, scale); the
-            // sampling hierarchy stays the one built from the RGB luminance
-            s->env_rgb.assign(ed.envmap_data, ed.envmap_data + 3 * (size_t) ed.envmap_width * ed.envmap_height);
-            spectral_envmap_texels(model, eh.texels.data(), eh.texels.size() / 4);
-        }
-        DevEnvmap de{};
-        std::vector<DevEnvmap> one(1);
-        if ((rc = upload(&s->d_env_texels, eh.texels)) || (rc = upload(&s->d_env_warp, eh.warp))) { mtsamd_scene_destroy(s); return rc; }
-        de.data = reinterpret_cast<const float4 *>(s->d_env_texels); de.warp = s->d_env_warp;
-        s->env_w = ed.envmap_width; s->env_h = ed.envmap_height;
-        de.w = ed.envmap_width; de.h = ed.envmap_height; de.n_levels = (int32_t) eh.lv_offset.size(); de.scale = ed.envmap_scale;
-        for (size_t k = 0; k < eh.lv_offset.size(); ++k) { de.lv_offset[k] = eh.lv_offset[k]; de.lv_width[k] = eh.lv_width[k]; }
-        for (int k = 0; k < 2; ++k) { de.patch_size[k] = eh.patch_size[k]; de.inv_patch_size[k] = eh.inv_patch_size[k]; de.max_patch_index[k] = eh.max_patch_index[k]; }
-        const float *m = ed.to_world;
-        const double a = m[0], b = m[1], c = m[2], d2 = m[4], e2 = m[5], f = m[6], g = m[8], h2 = m[9], i2 = m[10];
-        const float lin[9] = { m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10] };
-        const double det = a * (e2 * i2 - f * h2) - b * (d2 * i2 - f * g) + c * (d2 * h2 - e2 * g);
-        if (det == 0.0) { mtsamd_scene_destroy(s); return fail(MTSAMD_ERR_INVALID, "envmap: singular to_world transformation"); }
-        const double inv[9] = { (e2 * i2 - f * h2) / det, (c * h2 - b * i2) / det, (b * f - c * e2) / det,
-                                (f * g - d2 * i2) / det, (a * i2 - c * g) / det, (c * d2 - a * f) / det,
-                                (d2 * h2 - e2 * g) / det, (b * g - a * h2) / det, (a * e2 - b * d2) / det };
-        for (int k = 0; k < 9; ++k) { de.to_world[k] = lin[k]; de.to_local[k] = (float) inv[k]; }
-        one[0] = de;
-        if ((rc = upload(&s->d_envmap, one))) { mtsamd_scene_destroy(s); return rc; }
-    }
-    // roughplastic: transmittance tables and internal reflectance are integrated on the device (roughplastic.cpp:380-399)
-    {
-        std::vector<uint32_t> rough;
-        for (uint32_t b = 0; b < (uint32_t) s->bsdfs.size(); ++b) if (s->bsdfs[b].type == kBsdfRoughPlastic) rough.push_back(b);
-        if (!rough.empty()) {
-            float *d_gl = nullptr;
-            if (hipMalloc((void **) &s->d_rough_tables, rough.size() * kRoughTableRes * sizeof(float)) != hipSuccess ||
-                hipMalloc((void **) &d_gl, 512 * sizeof(float)) != hipSuccess) {
-                mtsamd_scene_destroy(s);
-                return fail(MTSAMD_ERR_NOMEM, "roughplastic tables: allocation failed");
-            }
-            hipError_t err = hipSuccess;
-            for (size_t k = 0; k < rough.size() && err == hipSuccess; ++k) {
-                const float eta = s->bsdfs[rough[k]].er;
-                const int res_t = eta > 1.0f ? 32 : 128, res_r = (1.0f / eta) > 1.0f ? 32 : 128;      // microfacet.h:476-478,520-522
-                float gl[512] = {};
-                gauss_legendre(res_t, gl, gl + 128);
-                gauss_legendre(res_r, gl + 256, gl + 384);
-                err = hipMemcpy(d_gl, gl, sizeof(gl), hipMemcpyHostToDevice);
-                if (err == hipSuccess) err = launch_roughplastic_tables(s->d_bsdfs, rough[k], s->d_rough_tables + k * kRoughTableRes, d_gl, res_t, res_r, nullptr);
-                if (err == hipSuccess) err = hipDeviceSynchronize();
-            }
-            if (err == hipSuccess) err = hipMemcpy(s->bsdfs.data(), s->d_bsdfs, s->bsdfs.size() * sizeof(DevBsdf), hipMemcpyDeviceToHost);
-            (void) hipFree(d_gl);
-            if (err != hipSuccess) { mtsamd_scene_destroy(s); return fail(MTSAMD_ERR_DEVICE, "roughplastic tables: %s", hipGetErrorString(err)); }
-        }
-    }
-    SceneView &v = s->view;
-    v.nodes = s->d_nodes; v.qnodes = s->d_qnodes; v.wnodes = s->d_wnodes; v.wroot = s->bvh.wroot; v.n_wnodes = s->bvh.n_wnodes; v.tris = s->d_tris; v.root = s->bvh.root;
-    for (int k = 0; k < 3; ++k) { v.q_lo[k] = s->bvh.q_lo[k]; v.q_step[k] = s->bvh.q_step[k]; v.q_inv_step[k] = 1.0f / s->bvh.q_step[k]; }
-    v.n_nodes = s->bvh.n_nodes; v.n_slots = s->bvh.n_slots; v.n_prims = s->n_prims;
-    // LDS residency: flat scenes keep everything in LDS (see flat_recs below).  For hierarchy scenes staging the
-    // top of the tree (nodes are stored in BFS order) was measured to LOSE: 384 staged nodes 2.5-3.2 Gray/s vs none
-    // 3.8-4.8 Gray/s on a 261 k-triangle mesh -- the 24 KB cost occupancy and the LDS/global select compiles to
-    // generic (flat) loads, while the top levels stay L1/L2-resident anyway.  Only the traversal stack lives in LDS.
-    v.lds_nodes = 0; v.lds_slots = 0;      // nodes and triangle slots are always read through L1/L2
-    // BVH2: one deferred subtree per level; BVH4: up to three
-    v.stack_depth = MTS_BVH4 ? 3u * s->bvh.wdepth + 2u : std::max<uint32_t>(s->bvh.depth, 2);
-    // standalone ray streams: 8 persistent workgroups per CU, the first 12 (BVH2: 16) stack entries of a lane in LDS
-    v.walk_lds_depth = std::min<uint32_t>(v.stack_depth, MTS_BVH4 ? 8u : 16u);      // 16 KB per workgroup: 8 workgroups (k_ray_walk: 8 waves per SIMD) per CU
-    v.walk_blocks = 8u * (uint32_t) s->cu_count;
-    if (!flat && v.stack_depth > v.walk_lds_depth) {
-        const size_t entries = (size_t) v.walk_blocks * (v.stack_depth - v.walk_lds_depth) * 256u;
-        if (ws_alloc((void **) &s->d_walk_spill, entries * sizeof(StackEntry))) { mtsamd_scene_destroy(s); return fail(MTSAMD_ERR_NOMEM, "traversal spill area"); }
-    }
-    v.walk_spill = s->d_walk_spill;
-    v.tri_pos = s->d_tri_pos; v.tri_nrm = any_nrm ? s->d_tri_nrm : nullptr; v.tri_uv = any_uv ? s->d_tri_uv : nullptr;
-    v.prim_shape = s->d_prim_shape; v.shapes = s->d_shapes; v.bsdfs = s->d_bsdfs;
-    v.emitters = s->d_emitters; v.n_emitters = desc->emitter_count;
-    v.env_emitter = s->environment; v.envmap = s->d_envmap;
-    v.area_pmf = s->d_area_pmf; v.area_cdf = s->d_area_cdf;
-    v.n_shapes = desc->mesh_count; v.n_bsdfs = desc->bsdf_count;
-    v.textures = s->d_textures; v.n_textures = desc->texture_count;
-    v.flat_recs = s->d_flat; v.flat = flat ? 1u : 0u;
-    v.general = s->nested_bsdfs ? 2u : (s->general_bsdfs || s->delta_emitters || s->environment >= 0) ? 1u : 0u;       // the diffuse / area-light fast path (kernels.hip) handles none of these
-    v.flat_pairs = s->d_pairs; v.n_pairs = n_pairs; v.n_clusters = n_clusters;
-    v.n_spectra = n_spectra;
-    if (bounce_lds_bytes(v) > 150 * 1024) {
-        mtsamd_scene_destroy(s);
-        return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", v.stack_depth);
-    }
-    *out = s;
+    static_cast<SceneState &>(*s) = std::move(hs.state);
+    if (int rc = upload_scene(s.get(), hs)) return rc;
+    if (int rc = roughplastic_tables(s.get())) return rc;
+    if (int rc = fill_scene_view(s.get(), hs)) return rc;
+    *out = s.release();
     return MTSAMD_OK;
 }
 
@@ -1167,48 +558,17 @@ int mtsamd_scene_info(const mtsamd_scene *s, uint32_t *out6) {
     return MTSAMD_OK;
 }
 
-// Spectral variant: a colour-valued BSDF parameter (p = 0 reflectance, 1 specular_reflectance, 2 specular_transmittance) is an `srgb`
-// spectrum -- range check, model coefficients, mean for the plastic lobe weights, exactly as mtsamd_scene_create does it
-// (srgb.cpp:31-41, plastic.cpp:170-175).  Parameters given as `uniform` spectra and textured reflectances are not settable this way.
-static int spectral_set_colour(mtsamd_scene *s, uint32_t bsdf, int p, const float *rgb) {
-    DevBsdf &d = s->bsdfs[bsdf];
-    if (bsdf_spectrum(d, p)) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: this parameter holds a tabulated spectrum; only srgb colours can be set in the spectral variant", bsdf);
-    const uint32_t uniform_flag = p == 0 ? kBsdfUniformRefl : (p == 1 ? kBsdfUniformSpec : kBsdfUniformTrans);
-    if (d.type == kBsdfBlend || d.type == kBsdfMask || (d.flags & uniform_flag) || (p == 0 && d.texture >= 0))
-        return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: this parameter is a uniform spectrum, a texture or a nesting weight; only srgb colours can be set in the spectral variant", bsdf);
-    if (rgb[0] < 0 || rgb[1] < 0 || rgb[2] < 0 || rgb[0] > 1 || rgb[1] > 1 || rgb[2] > 1)
-        return fail(MTSAMD_ERR_INVALID, "Invalid RGB reflectance value [%g, %g, %g], must be in the range [0, 1]!", rgb[0], rgb[1], rgb[2]);
-    float coeff[3];
-    srgb_model_fetch(s->rgb2spec, rgb, coeff);
-    float *dst = p == 0 ? &d.c0 : (p == 1 ? &d.sc0 : &d.tc0);
-    dst[0] = coeff[0]; dst[1] = coeff[1]; dst[2] = coeff[2];
-    if (p == 0) {
-        d.r = rgb[0]; d.g = rgb[1]; d.b = rgb[2]; s->diff_mean[bsdf] = srgb_model_mean(coeff);
-        s->jac_bsdf.resize(9 * s->bsdfs.size(), 0.0f);
-        srgb_model_fetch_jacobian(s->rgb2spec, rgb, s->jac_bsdf.data() + 9 * (size_t) bsdf);
-        s->jac_dirty = true;
-    }
-    if (p == 1) { d.sr = rgb[0]; d.sg = rgb[1]; d.sb = rgb[2]; s->spec_mean[bsdf] = srgb_model_mean(coeff); }
-    if (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic) {
-        const float d_mean = d.texture >= 0 ? s->textures[d.texture].mean : s->diff_mean[bsdf];
-        d.kr = s->spec_mean[bsdf] / (d_mean + s->spec_mean[bsdf]);
-    }
-    HIP_TRY(hipMemcpy(s->d_bsdfs + bsdf, &d, sizeof(DevBsdf), hipMemcpyHostToDevice));
+// The setters: the host half (scene_build.h) edits the records, then the records it names are pushed to the device.
+static int push_bsdf(mtsamd_scene *s, uint32_t bsdf) {
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(s->d_bsdfs + bsdf, &s->bsdfs[bsdf], sizeof(DevBsdf), hipMemcpyHostToDevice));
     return MTSAMD_OK;
 }
 
 int mtsamd_scene_set_bsdf_reflectance(mtsamd_scene *s, uint32_t bsdf, const float *rgb) {
     if (!s || !rgb || bsdf >= s->bsdfs.size()) return fail(MTSAMD_ERR_INVALID, "invalid bsdf index");
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->spectral) return spectral_set_colour(s, bsdf, 0, rgb);
-    s->bsdfs[bsdf].r = rgb[0]; s->bsdfs[bsdf].g = rgb[1]; s->bsdfs[bsdf].b = rgb[2];
-    if (s->bsdfs[bsdf].type == kBsdfPlastic || s->bsdfs[bsdf].type == kBsdfRoughPlastic) {       // parameters_changed(): specular sampling weight (plastic.cpp:170-175)
-        DevBsdf &d = s->bsdfs[bsdf];
-        const float d_mean = d.texture >= 0 ? s->textures[d.texture].mean : (d.r + d.g + d.b) * (1.0f / 3.0f), s_mean = (d.sr + d.sg + d.sb) * (1.0f / 3.0f);
-        d.kr = s_mean / (d_mean + s_mean);
-    }
-    HIP_TRY(hipMemcpy(s->d_bsdfs + bsdf, &s->bsdfs[bsdf], sizeof(DevBsdf), hipMemcpyHostToDevice));
-    return MTSAMD_OK;
+    if (int rc = set_bsdf_reflectance(*s, bsdf, rgb)) return rc;
+    return push_bsdf(s, bsdf);
 }
 
 int mtsamd_scene_roughplastic_tables(const mtsamd_scene *s, uint32_t bsdf, float *out65) {
@@ -1226,61 +586,26 @@ int mtsamd_scene_update_texture(mtsamd_scene *s, uint32_t texture, const float *
     HIP_TRY(hipSetDevice(s->device));
     const DevTexture &t = s->textures[texture];
     if (t.kind != 0) return fail(MTSAMD_ERR_INVALID, "texture %u is not a bitmap", texture);
-    if (s->spectral) {       // the texels hold model coefficients: converted on the host as mtsamd_scene_create does, after the clamp of an srgb colour
-        const size_t n_texels = (size_t) t.w * t.h;
-        std::vector<float> host(3 * n_texels), coeffs;
-        HIP_TRY(hipStreamSynchronize((hipStream_t) stream));          // whatever writes `rgb`, and the renders that read the old texels
-        HIP_TRY(hipMemcpy(host.data(), rgb, host.size() * sizeof(float), hipMemcpyDefault));
-        for (float &v : host) v = std::max(std::min(v, 1.0f), 0.0f);
-        const double mean = spectral_texels(s->rgb2spec, host.data(), n_texels, coeffs, s->jac_tex, t.grad_offset);
-        s->jac_dirty = true;
-        HIP_TRY(hipMemcpy((void *) t.data, coeffs.data(), coeffs.size() * sizeof(float), hipMemcpyHostToDevice));
-        s->textures[texture].mean = (float) (mean / (double) n_texels);
-        for (size_t b = 0; b < s->bsdfs.size(); ++b) {       // parameters_changed(): the plastic lobe weights read the mean
-            DevBsdf &d = s->bsdfs[b];
-            if (d.texture != (int32_t) texture || (d.type != kBsdfPlastic && d.type != kBsdfRoughPlastic)) continue;
-            d.kr = s->spec_mean[b] / (s->textures[texture].mean + s->spec_mean[b]);
-            HIP_TRY(hipMemcpy(s->d_bsdfs + b, &d, sizeof(DevBsdf), hipMemcpyHostToDevice));
-        }
-        return MTSAMD_OK;
+    const size_t bytes = sizeof(float) * 3 * (size_t) t.w * t.h;
+    if (!s->spectral) {
+        HIP_TRY(hipMemcpyAsync((void *) t.data, rgb, bytes, hipMemcpyDefault, (hipStream_t) stream));
+        if (!texture_feeds_lobe_weight(*s, texture)) return MTSAMD_OK;       // only plastic lobe weights read the mean
     }
-    HIP_TRY(hipMemcpyAsync((void *) t.data, rgb, sizeof(float) * 3 * (size_t) t.w * t.h, hipMemcpyDefault, (hipStream_t) stream));
-    // parameters_changed() (bitmap.cpp:308-322): the mean follows the data; only plastic lobe weights read it
-    bool used = false;
-    for (const DevBsdf &b : s->bsdfs) used = used || (b.texture == (int32_t) texture && (b.type == kBsdfPlastic || b.type == kBsdfRoughPlastic));
-    if (used) {
-        std::vector<float> host(3 * (size_t) t.w * t.h);
-        HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
-        HIP_TRY(hipMemcpy(host.data(), t.data, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        double mean = 0.0;
-        for (size_t i = 0; i < host.size() / 3; ++i) mean += (double) (host[3 * i] * 0.212671f + host[3 * i + 1] * 0.715160f + host[3 * i + 2] * 0.072169f);
-        s->textures[texture].mean = (float) (mean / (double) (host.size() / 3));
-        for (size_t b = 0; b < s->bsdfs.size(); ++b) {
-            DevBsdf &d = s->bsdfs[b];
-            if (d.texture != (int32_t) texture || (d.type != kBsdfPlastic && d.type != kBsdfRoughPlastic)) continue;
-            d.kr = s->spec_mean[b] / (s->textures[texture].mean + s->spec_mean[b]);
-            HIP_TRY(hipMemcpy(s->d_bsdfs + b, &d, sizeof(DevBsdf), hipMemcpyHostToDevice));
-        }
-    }
+    // the host half needs the texels: the spectral variant converts them (the device holds model coefficients), the RGB one takes their mean
+    std::vector<float> host(bytes / sizeof(float)), coeffs;
+    HIP_TRY(hipStreamSynchronize((hipStream_t) stream));          // whatever writes `rgb`, and the renders that read the old texels
+    HIP_TRY(hipMemcpy(host.data(), rgb, bytes, hipMemcpyDefault));
+    std::vector<uint32_t> changed;
+    set_texture_texels(*s, texture, host.data(), coeffs, changed);
+    if (s->spectral) HIP_TRY(hipMemcpy((void *) t.data, coeffs.data(), coeffs.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (uint32_t b : changed) HIP_TRY(hipMemcpy(s->d_bsdfs + b, &s->bsdfs[b], sizeof(DevBsdf), hipMemcpyHostToDevice));
     return MTSAMD_OK;
 }
 
 int mtsamd_scene_set_emitter_radiance(mtsamd_scene *s, uint32_t emitter, const float *rgb) {
     if (!s || !rgb || emitter >= s->emitters.size()) return fail(MTSAMD_ERR_INVALID, "invalid emitter index");
-    if (s->emitters[emitter].spectrum) return fail(MTSAMD_ERR_UNSUPPORTED, "emitter %u: its radiance holds a tabulated spectrum; only srgb_d65 colours can be set", emitter);
+    if (int rc = set_emitter_radiance(*s, emitter, rgb)) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    s->emitters[emitter].r = rgb[0]; s->emitters[emitter].g = rgb[1]; s->emitters[emitter].b = rgb[2];
-    if (s->spectral) {       // srgb_d65 spectrum: normalised colour -> coefficients, the scale rides on the D65 curve (srgb_d65.cpp:31-46)
-        float color[3] = { rgb[0], rgb[1], rgb[2] }, coeff[3];
-        const float scale = std::max(std::max(color[0], color[1]), color[2]) * 2.0f;
-        if (scale != 0.0f) { const float r = 1.0f / scale; for (float &v : color) v *= r; }
-        srgb_model_fetch(s->rgb2spec, color, coeff);
-        float d65_scale = 1.0f * scale;
-        d65_scale *= 1.0f / 10568.0f;                      // d65.cpp:44-50
-        DevEmitter &d = s->emitters[emitter];
-        d.c0 = coeff[0]; d.c1 = coeff[1]; d.c2 = coeff[2]; d.d65_scale = d65_scale;
-        s->ejac_dirty = true;
-    }
     HIP_TRY(hipMemcpy(s->d_emitters + emitter, &s->emitters[emitter], sizeof(DevEmitter), hipMemcpyHostToDevice));
     return MTSAMD_OK;
 }
@@ -2273,60 +1598,10 @@ int mtsamd_render_adjoint(mtsamd_scene *s, const mtsamd_render_desc *d, const fl
     return MTSAMD_OK;
 }
 
-// One scalar parameter of a BSDF record: which float(s) of DevBsdf it is.  ok = false: the model has no such (differentiable) parameter.
-static bool bsdf_param_fields(const DevBsdf &b, int32_t kind, int32_t comp, float DevBsdf::*&f0, float DevBsdf::*&f1) {
-    static float DevBsdf::*const refl[3] = { &DevBsdf::r, &DevBsdf::g, &DevBsdf::b }, DevBsdf::*const spec[3] = { &DevBsdf::sr, &DevBsdf::sg, &DevBsdf::sb },
-                 DevBsdf::*const eta[3] = { &DevBsdf::er, &DevBsdf::eg, &DevBsdf::eb }, DevBsdf::*const kk[3] = { &DevBsdf::kr, &DevBsdf::kg, &DevBsdf::kb };
-    f1 = nullptr;
-    if (comp < 0 || comp > 2 || b.type >= kBsdfBlend) return false;
-    const bool conductor = b.type == kBsdfConductor || b.type == kBsdfRoughConductor;
-    const bool dielectric = b.type == kBsdfDielectric || b.type == kBsdfRoughDielectric || b.type == kBsdfThinDielectric;
-    switch (kind) {
-    case MTSAMD_PARAM_REFLECTANCE:        // diffuse.reflectance, (rough)plastic.diffuse_reflectance -- constants only
-        if (b.texture >= 0 || !(b.type == kBsdfDiffuse || b.type == kBsdfPlastic || b.type == kBsdfRoughPlastic)) return false;
-        f0 = refl[comp]; return true;
-    case MTSAMD_PARAM_SPECULAR_REFLECTANCE:
-        if (b.type == kBsdfDiffuse) return false;
-        f0 = spec[comp]; return true;
-    case MTSAMD_PARAM_SPECULAR_TRANSMITTANCE:
-        if (!dielectric) return false;
-        f0 = kk[comp]; return true;
-    case MTSAMD_PARAM_ETA: if (!conductor) return false; f0 = eta[comp]; return true;
-    case MTSAMD_PARAM_K: if (!conductor) return false; f0 = kk[comp]; return true;
-    case MTSAMD_PARAM_ALPHA:              // isotropic roughness; roughplastic's alpha also shapes its transmittance tables: not offered
-        if (!(b.type == kBsdfRoughConductor || b.type == kBsdfRoughDielectric) || b.alpha_u != b.alpha_v || comp != 0) return false;
-        f0 = &DevBsdf::alpha_u; f1 = &DevBsdf::alpha_v; return true;
-    default: return false;
-    }
-}
-
 int mtsamd_scene_set_bsdf_param(mtsamd_scene *s, uint32_t bsdf, int32_t kind, const float *value3) {
     if (!s || !value3 || bsdf >= s->bsdfs.size()) return fail(MTSAMD_ERR_INVALID, "invalid bsdf index");
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->spectral) {       // colours become srgb spectra; eta / k must stay uniform spectra (one value); alpha is a plain number
-        if (kind == MTSAMD_PARAM_REFLECTANCE || kind == MTSAMD_PARAM_SPECULAR_REFLECTANCE || kind == MTSAMD_PARAM_SPECULAR_TRANSMITTANCE) {
-            float DevBsdf::*f0, DevBsdf::*f1;
-            if (!bsdf_param_fields(s->bsdfs[bsdf], kind, 0, f0, f1)) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u (type %d) has no settable parameter of kind %d", bsdf, s->bsdfs[bsdf].type, kind);
-            return spectral_set_colour(s, bsdf, kind == MTSAMD_PARAM_REFLECTANCE ? 0 : (kind == MTSAMD_PARAM_SPECULAR_REFLECTANCE ? 1 : 2), value3);
-        }
-        if ((kind == MTSAMD_PARAM_ETA || kind == MTSAMD_PARAM_K) && bsdf_spectrum(s->bsdfs[bsdf], kind == MTSAMD_PARAM_ETA ? kSpecEta : kSpecK))
-            return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: this parameter holds a tabulated spectrum and cannot be set to a constant", bsdf);
-        if ((kind == MTSAMD_PARAM_ETA || kind == MTSAMD_PARAM_K) && !(value3[0] == value3[1] && value3[1] == value3[2]))
-            return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: the spectral variant needs uniform (constant) eta and k spectra", bsdf);
-    }
-    DevBsdf &d = s->bsdfs[bsdf];
-    for (int c = 0; c < (kind == MTSAMD_PARAM_ALPHA ? 1 : 3); ++c) {
-        float DevBsdf::*f0, DevBsdf::*f1;
-        if (!bsdf_param_fields(d, kind, c, f0, f1)) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u (type %d) has no settable parameter of kind %d", bsdf, d.type, kind);
-        d.*f0 = value3[c];
-        if (f1) d.*f1 = value3[c];
-    }
-    if (!s->spectral && (d.type == kBsdfPlastic || d.type == kBsdfRoughPlastic)) {       // parameters_changed(): specular sampling weight (plastic.cpp:170-175; spectral: spectral_set_colour)
-        const float d_mean = d.texture >= 0 ? s->textures[d.texture].mean : (d.r + d.g + d.b) * (1.0f / 3.0f), s_mean = (d.sr + d.sg + d.sb) * (1.0f / 3.0f);
-        d.kr = s_mean / (d_mean + s_mean);
-    }
-    HIP_TRY(hipMemcpy(s->d_bsdfs + bsdf, &d, sizeof(DevBsdf), hipMemcpyHostToDevice));
-    return MTSAMD_OK;
+    if (int rc = set_bsdf_param(*s, bsdf, kind, value3)) return rc;
+    return push_bsdf(s, bsdf);
 }
 
 int mtsamd_render_adjoint_param(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, uint32_t bsdf, int32_t kind,
@@ -2469,12 +1744,7 @@ int mtsamd_scene_update_envmap(mtsamd_scene *s, const float *rgb, int32_t rebuil
     if (s->environment < 0 || !s->d_envmap) return fail(MTSAMD_ERR_UNSUPPORTED, "the scene has no envmap emitter");
     HIP_TRY(hipSetDevice(s->device));
     EnvmapHost eh;
-    if (!build_envmap(rgb, s->env_w, s->env_h, eh)) return fail(MTSAMD_ERR_INVALID, "envmap: unsupported image size");
-    if (s->spectral) {       // the texels hold (model coefficients, scale), converted as mtsamd_scene_create converts them; the hierarchy stays RGB
-        s->env_rgb.assign(rgb, rgb + 3 * (size_t) s->env_w * s->env_h);
-        spectral_envmap_texels(s->rgb2spec, eh.texels.data(), eh.texels.size() / 4);
-        s->ejac_dirty = true;
-    }
+    if (int rc = set_envmap_texels(*s, rgb, eh)) return rc;
     HIP_TRY(hipDeviceSynchronize());           // renders in flight read the old texels
     HIP_TRY(hipMemcpy(s->d_env_texels, eh.texels.data(), eh.texels.size() * sizeof(float), hipMemcpyHostToDevice));
     if (rebuild_distribution) HIP_TRY(hipMemcpy(s->d_env_warp, eh.warp.data(), eh.warp.size() * sizeof(float), hipMemcpyHostToDevice));

@@ -1,0 +1,113 @@
+// scene_build.h -- host-only scene ingestion: everything mtsamd_scene_create computes before the first byte goes to the device, and the
+// host half of every parameter setter.  Nothing declared here calls the HIP runtime (kernels.h is included for the record types), so the
+// whole path runs -- and is tested -- on a machine without a GPU (tests/test_scene_build_cpu.py); api.cpp uploads what it produces.
+#pragma once
+#include "../../include/mtsamd.h"
+#include "bvh.h"
+#include "envmap.h"
+#include "kernels.h"
+#include "spectral_upsampling.h"
+
+#include <cstdint>
+#include <vector>
+
+namespace mtsamd {
+
+// the thread's last error (mtsamd_last_error): fail() formats and stores the text and returns `code`
+int fail(int code, const char *fmt, ...);
+const char *last_error();
+
+// ---- one function per conversion, shared by creation and by every setter ---------------------------------------------------
+inline float rgb_mean(const float c[3]) { return (c[0] + c[1] + c[2]) * (1.0f / 3.0f); }       // Texture::mean() of a constant colour
+// plastic.cpp:170-175: specular sampling weight from Texture::mean() of the diffuse and the specular reflectance
+inline float plastic_lobe_weight(float d_mean, float s_mean) { return s_mean / (d_mean + s_mean); }
+inline bool srgb_in_range(const float c[3]) { return !(c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] > 1 || c[1] > 1 || c[2] > 1); }
+// `srgb` spectrum of a reflectance colour (srgb.cpp:31-41): range check with the constructor's message, model coefficients, their mean
+// and -- jac9 not null -- d coeff / d rgb
+int srgb_colour(const Rgb2Spec &model, const float rgb[3], float coeff[3], float *mean, float *jac9);
+// `srgb_d65` spectrum of an emitter colour (srgb_d65.cpp:31-46, d65.cpp:44-50): coefficients of the normalised colour and d65_scale
+void srgb_d65_colour(const Rgb2Spec &model, const float rgb[3], DevEmitter &e);
+float bitmap_luminance_mean(const float *rgb, size_t n_texels);              // Texture::mean() of an RGB bitmap (bitmap.cpp:124-136)
+bool invert_linear3(const float to_world[16], float inv[9]);                 // inverse of the upper 3x3, in double; false: singular
+void bounding_sphere(const float bbox[6], float centre[3], float *radius);  // of Scene::bbox() (constant.cpp:47-51, directional.cpp:65-70)
+
+// ---- tabulated / analytic spectra -------------------------------------------------------------------------------------------
+int check_spectrum(const mtsamd_spectrum_desc &sp, uint32_t index, double *integral);
+float spectrum_table_mean(double integral);
+void build_spectrum_pool(const mtsamd_spectrum_desc *spectra, uint32_t n, std::vector<DevSpectrum> &headers, std::vector<float> &data);
+
+// What stays on the host for the life of a scene (mtsamd_scene embeds it): the records the setters edit and the queries read.
+struct SceneState {
+    int32_t environment = -1;        // index of the `constant` / `envmap` emitter
+    bool general_bsdfs = false;      // any BSDF other than one-sided `diffuse`: the kernels with the BSDF switch are used
+    bool nested_bsdfs = false;       // blendbsdf / mask: the fused schedule (k_bounce*, k_direct) is the one that carries the nesting code
+    bool non_diffuse_bsdfs = false;  // any BSDF other than `diffuse` (one- or two-sided): what the adjoint path replay cannot differentiate
+    bool delta_emitters = false;     // point / spot / directional emitters: handled by the same general kernels
+    bool spectral = false;
+    BvhOutput bvh;
+    uint32_t n_prims = 0, n_shapes = 0;
+    std::vector<DevBsdf> bsdfs;
+    std::vector<DevEmitter> emitters;
+    std::vector<DevTexture> textures;       // `data`: null until api.cpp uploads the texels (device pointers, owned by the scene)
+    std::vector<float> spec_mean;           // per BSDF: mean of specular_reflectance
+    std::vector<float> diff_mean;           // spectral variant, per BSDF: Texture::mean() of a constant reflectance
+    Rgb2Spec rgb2spec;                      // spectral variant: the upsampling model, kept for parameter updates
+    // spectral variant: d(model coefficients) / d(rgb) (srgb_model_fetch_jacobian) of every constant reflectance (9 floats per BSDF) and of
+    // every bitmap texel (9 floats per texel, at 3 * grad_offset), recomputed whenever a colour is converted; `jac_dirty`: the device copy
+    // (mtsamd_render_adjoint_spectral) is stale
+    std::vector<float> jac_bsdf, jac_tex;
+    bool jac_dirty = true;
+    // spectral variant, emitter colours: the RGB texels of the envmap as the scene holds them (the device keeps coefficients); `ejac_dirty`:
+    // the table of mtsamd_render_adjoint_spectral_emitters is stale
+    std::vector<float> env_rgb;
+    bool ejac_dirty = true;
+    int32_t env_w = 0, env_h = 0;           // envmap emitter: its size (0: none)
+};
+
+// builder knobs: the shipped values; experiment builds (-DMTSAMD_EXPERIMENTS) fill them from the environment in api.cpp
+struct BuildOptions {
+    uint32_t max_leaf = 4;
+    BvhOptions bvh;
+    uint32_t flat_max = kFlatMaxPrims;
+};
+
+// Everything creation computes on the host.  `state` outlives creation; the rest is uploaded and dropped.
+struct HostScene {
+    SceneState state;
+    std::vector<float> tri_pos, tri_nrm, tri_uv;       // 9 / 9 / 6 floats per primitive (normals, uvs: empty if no mesh has them)
+    std::vector<uint32_t> prim_shape;
+    std::vector<DevShape> shapes;
+    std::vector<float> area_pmf, area_cdf;
+    std::vector<DevBsdf> bsdf_block;                    // state.bsdfs, and behind them the spectrum pool (spectrum_pool() in kernels.hip)
+    uint32_t n_spectra = 0;
+    // texels of bitmap t as they are uploaded: tex_src[t] points into the description (RGB variant) or into tex_coeffs[t] (spectral
+    // variant: model coefficients); null for a checkerboard
+    std::vector<const float *> tex_src;
+    std::vector<std::vector<float>> tex_coeffs;
+    bool flat = false;                                  // n_prims <= flat_max: the scene lives in LDS
+    std::vector<float4> flat_recs, pair_recs;           // pair_recs: 5 per pair, then 2 per cluster
+    uint32_t n_pairs = 0, n_clusters = 0;
+    bool has_envmap = false;
+    EnvmapHost env;                                     // texels (spectral variant: coefficients + scale) and sampling hierarchy
+    DevEnvmap dev_env{};                                // all fields but the two device pointers
+};
+
+// Returns the ABI error code; the error text is set exactly as mtsamd_scene_create sets it.
+int build_host_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
+                     const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, const BuildOptions &options, HostScene &hs);
+
+// ---- host half of the setters: they edit `st` and name what the device copy now lacks ------------------------------------------
+// One scalar parameter of a BSDF record: which float(s) of DevBsdf it is.  false: the model has no such (differentiable) parameter.
+bool bsdf_param_fields(const DevBsdf &b, int32_t kind, int32_t comp, float DevBsdf::*&f0, float DevBsdf::*&f1);
+// these three change record `bsdf` / `emitter` only (valid indices) and the Jacobians behind jac_dirty / ejac_dirty
+int set_bsdf_reflectance(SceneState &st, uint32_t bsdf, const float *rgb);
+int set_bsdf_param(SceneState &st, uint32_t bsdf, int32_t kind, const float *value3);
+int set_emitter_radiance(SceneState &st, uint32_t emitter, const float *rgb);
+bool texture_feeds_lobe_weight(const SceneState &st, uint32_t texture);      // some (rough)plastic reads its mean
+// New texels of bitmap `texture` (host copy, w * h * 3).  Spectral variant: clamps them to [0, 1] in place and returns their model
+// coefficients in `coeffs` (what the device holds).  Either variant: updates the mean and lists the BSDF records whose lobe weight moved.
+void set_texture_texels(SceneState &st, uint32_t texture, float *rgb, std::vector<float> &coeffs, std::vector<uint32_t> &changed_bsdfs);
+// New texels of the envmap: `eh` receives the texel table (spectral variant: coefficients + scale) and the hierarchy to push
+int set_envmap_texels(SceneState &st, const float *rgb, EnvmapHost &eh);
+
+} // namespace mtsamd
