@@ -1,5 +1,7 @@
 // api.cpp -- host side of libmtsamd: scene upload, BVH build, emitter tables, sensor/film setup,
-// the wavefront scheduler and the C ABI declared in include/mtsamd.h.
+// the wavefront scheduler and the C ABI declared in include/mtsamd.h.  The two host-only halves live beside it: scene_build.{h,cpp}
+// computes what is uploaded, schedule.{h,cpp} plans jobs, passes, the pool drain and the film passes; this file carries them out on
+// the device (allocations, streams, events, copies, launches).
 //
 // Reference call stack this replaces:
 //   Scene::Scene -> accel_init -> ShapeKDTree::build          src/librender/scene.cpp:22-98
@@ -12,6 +14,7 @@
 #include "envmap.h"
 #include "kernels.h"
 #include "scene_build.h"
+#include "schedule.h"
 #include "spectral_upsampling.h"
 #include "cie_data.h"
 
@@ -187,6 +190,23 @@ static int ws_alloc(void **p, size_t bytes) {
     HIP_TRY(hipMemset(*p, 0, bytes));
     return 0;
 }
+// A workspace buffer that only grows: it holds `have` elements; if `need` are more, it is freed and allocated anew (zeroed).
+template <typename T, typename N> static int grow(T *&p, N &have, size_t need) {
+    if (have >= need) return 0;
+    (void) hipFree(p); p = nullptr; have = 0;
+    if (int rc = ws_alloc((void **) &p, need * sizeof(T))) return rc;
+    have = (N) need;
+    return 0;
+}
+// ... two buffers of `have` elements each: both are freed before either is allocated anew, and `have` counts once both are there
+template <typename A, typename B, typename N> static int grow(A *&a, B *&b, N &have, size_t need) {
+    if (have >= need) return 0;
+    (void) hipFree(a); (void) hipFree(b); a = nullptr; b = nullptr; have = 0;
+    if (int rc = ws_alloc((void **) &a, need * sizeof(A))) return rc;
+    if (int rc = ws_alloc((void **) &b, need * sizeof(B))) return rc;
+    have = (N) need;
+    return 0;
+}
 
 struct Workspace {
     uint32_t n_waves = 0, seg_cap = 0;
@@ -199,7 +219,7 @@ struct Workspace {
     float4 *out_rgba = nullptr; float2 *out_pos = nullptr;
     float4 *out_rgba2 = nullptr; float2 *out_pos2 = nullptr; uint64_t pass_cap2 = 0;      // second sample stream: pass k + 1 is traced while pass k is splatted
     hipStream_t film_stream = nullptr; hipEvent_t film_done[2] = {};
-    float *moment_film = nullptr; uint64_t moment_pixels = 0;     // moment integrator: two scratch 5-channel films
+    float *moment_film = nullptr; uint64_t moment_floats = 0;     // moment integrator: two scratch 5-channel films
     float4 *aov_stream = nullptr; uint64_t aov_stream_slots = 0;  // aov integrator: channel groups of a pass (+ the nested stream's second colour space)
     float *aov_film = nullptr; uint64_t aov_film_floats = 0;      // ... and its scratch 5-channel films
     float4 *aov_keep = nullptr;                                   // ... and, during a render of several passes, the streams + positions of all of them
@@ -230,7 +250,7 @@ struct Workspace {
         (void) hipFree(cursor); (void) hipFree(cursor_end); (void) hipFree(wave_stats);
         (void) hipFree(count_shadow); count_shadow = nullptr;
         (void) hipFree(trace_spill); trace_spill = nullptr; trace_spill_words = 0;
-        (void) hipFree(moment_film); moment_film = nullptr; moment_pixels = 0;
+        (void) hipFree(moment_film); moment_film = nullptr; moment_floats = 0;
         (void) hipFree(aov_stream); aov_stream = nullptr; aov_stream_slots = 0;
         (void) hipFree(aov_film); aov_film = nullptr; aov_film_floats = 0;
         (void) hipFree(aov_keep); aov_keep = nullptr;
@@ -387,6 +407,18 @@ BuildOptions build_options() {       // the shipped values, or what an experimen
     if (const char *e = exp_env("MTSAMD_BVH_ORDER")) o.bvh.dfs_order = e[0] == 'd';
     if (const char *e = exp_env("MTSAMD_FLAT_MAX")) o.flat_max = std::min<uint32_t>(kFlatMaxPrims, (uint32_t) std::strtoul(e, nullptr, 10));
     return o;
+}
+
+ScheduleSwitches schedule_switches() {       // nothing set, or what an experiment build finds in the environment
+    ScheduleSwitches sw;
+    if (const char *e = exp_env("MTSAMD_CHUNKS_PER_WAVE")) sw.chunks_per_wave = (uint32_t) std::min(64, std::max(1, atoi(e)));
+    if (const char *e = exp_env("MTSAMD_CHAINS")) sw.chains = (uint32_t) std::min<int>(kMaxChains, std::max(1, atoi(e)));
+    sw.one_chain = exp_env("MTSAMD_ONE_CHAIN") != nullptr;
+    if (const char *e = exp_env("MTSAMD_STREAMS")) sw.streams = (uint32_t) std::min(4, std::max(1, atoi(e)));
+    sw.no_gather = exp_env("MTSAMD_NO_GATHER") != nullptr;
+    sw.mega = exp_env("MTSAMD_MEGA") != nullptr;
+    if (const char *e = exp_env("MTSAMD_WAVES_PER_CU")) sw.waves_per_cu = (uint32_t) std::max(1, atoi(e));
+    return sw;
 }
 
 // Everything build_host_scene made goes to the device; the scene owns every buffer from the moment it is allocated.
@@ -732,13 +764,12 @@ namespace {
 struct Job {
     mtsamd_scene *s; const mtsamd_render_desc *d; hipStream_t stream;
     CameraView cam; FilterView filter;
-    uint32_t n_waves, target; uint64_t pass_cap;
+    JobShape shape; uint64_t pass_cap;       // the plan of the job (schedule.h) and the samples a pass holds
     uint64_t iterations = 0;
     double bounce_ms = 0.0, film_ms = 0.0;
     RowMap rows{};
     int store_xyz = 1;
     uint32_t plane_pix0 = 0, plane_pixels = 0;
-    bool split = false, shadow_queue = false, shadow_ring = false;
     double stage_ms[3] = { 0.0, 0.0, 0.0 }; uint64_t stage_launches[3] = { 0, 0, 0 };      // desc->profile: k_trace<closest>, k_shade, k_trace<any>
     uint64_t passes = 0;
     int buf = 0;                 // sample stream buffer this pass writes
@@ -749,130 +780,50 @@ struct Job {
     }
 };
 
-// Traces the local sample ordinals [first, first+n) of this render's rows to completion; results land in
-// ws.out_rgba / out_pos (slot = ordinal - first).
-int trace_pass(Job &j, uint64_t first, uint64_t n) {
+// The timed bracket of a pass: `body` issues the pass on j.stream between two events; once the second has completed, the time between
+// them is added to bounce_ms.  A body that fails or stops (rc != 0) leaves the bracket open.
+extern "C++" template <typename F> int timed(Job &j, F &&body) {       // (a template inside the file's extern "C" block)
     Workspace &w = j.s->ws;
-    const uint32_t nw = j.n_waves;
-    const uint64_t spp = (uint64_t) j.d->sample_count;
-    // the pass's samples are dealt to the scheduling waves in chunks, round-robin (kernels.hip, cursor_sample): wave k owns the
-    // chunks k, k + nw, ...; its cursor counts the samples of its own it has generated.  64-sample chunks for LDS-resident scenes
-    // hierarchy scenes: four chunks of consecutive pixels per scheduling wave (a wave's 256 slots still hold neighbouring pixels, but
-    // every wave sees four regions of the film, which evens out when the waves run dry: 1 / 4 / 16 / 64 chunks: 0 / +2.1 / +2.3 / +1.3 %
-    // on the 261 k-triangle mesh at 1024 spp; 64-sample chunks as on flat scenes cost 5 %), at least 256 samples each
-    uint64_t cpw = 4;
-    if (const char *e = exp_env("MTSAMD_CHUNKS_PER_WAVE")) cpw = (uint64_t) std::min(64, std::max(1, atoi(e)));      // experiment switch
-    const uint64_t chunk = j.s->view.flat ? 64u : std::max<uint64_t>({ (n + nw * cpw - 1) / (nw * cpw), std::min<uint64_t>(256u, (n + nw - 1) / nw), 1u });
-    const uint64_t n_chunks = (n + chunk - 1u) / chunk, last_size = n - (n_chunks - 1u) * chunk;
-    // hierarchy scenes run several launch chains over parts of the scheduling waves: their chunks alternate (kernels.h, chunk_owner)
-    uint32_t n_chains = 1;
-    if (!j.s->view.flat && j.split && nw >= 256u) n_chains = kTraceChains;
-    if (const char *e = exp_env("MTSAMD_CHAINS")) n_chains = (uint32_t) std::min<int>(kMaxChains, std::max(1, atoi(e)));      // experiment switch
-    if (exp_env("MTSAMD_ONE_CHAIN")) n_chains = 1;
-    while (n_chains > 1 && nw / n_chains < 2u * kChainAlign) --n_chains;
-    for (uint32_t k = 0; k < nw; ++k) {
-        const uint64_t c0 = chunk_owner(k, nw, n_chains);      // this wave owns the chunks c0, c0 + nw, ...
-        const uint64_t mine = c0 < n_chunks ? (n_chunks - 1u - c0) / nw + 1u : 0u;
-        uint64_t samples = mine * chunk;
-        if (mine && (n_chunks - 1u) % nw == c0) samples -= chunk - last_size;       // the last, partial chunk of the pass
-        w.h_cursor[k] = 0; w.h_cursor[nw + k] = samples;
-    }
-    if (n >= (1ull << 31)) return fail(MTSAMD_ERR_INVALID, "a pass holds fewer than 2^31 samples");
-    HIP_TRY(hipMemcpyAsync(w.cursor, w.h_cursor, nw * sizeof(uint64_t), hipMemcpyHostToDevice, j.stream));
-    HIP_TRY(hipMemcpyAsync(w.cursor_end, w.h_cursor + nw, nw * sizeof(uint64_t), hipMemcpyHostToDevice, j.stream));
-    HIP_TRY(hipMemsetAsync(w.count[0], 0, 2 * (size_t) nw * sizeof(uint32_t), j.stream));
-    HIP_TRY(hipMemsetAsync(w.count[1], 0, 2 * (size_t) nw * sizeof(uint32_t), j.stream));
-
-    RenderParams p{};
-    p.sv = j.s->view; p.cam = j.cam;
-    if (p.cam.aperture_radius > 0.0f) p.sv.general = std::max(p.sv.general, 1u);      // thin lens: aperture sampling lives in the general kernels
-    p.cursor = w.cursor; p.cursor_end = w.cursor_end; p.wave_stats = w.wave_stats;
-    p.out_rgba = j.buf ? w.out_rgba2 : w.out_rgba; p.out_pos = j.buf ? w.out_pos2 : w.out_pos;
-    p.count_shadow = w.count_shadow;
-    p.first_ordinal = first; p.first_pix = (uint32_t) (first / spp); p.first_rem = (uint32_t) (first % spp);
-    p.chunk = (uint32_t) chunk; p.base_seed = j.d->seed;
-    p.n_chains = n_chains;
-    p.rows = j.rows; p.store_xyz = j.store_xyz;
-    p.plane_pix0 = j.plane_pix0; p.plane_pixels = j.plane_pixels;
-    p.n_waves = nw; p.seg_cap = w.seg_cap; p.target = j.target;
-    p.spp = j.d->sample_count; p.crop_x = j.d->crop_x; p.crop_y = j.d->crop_y; p.crop_w = j.d->crop_width; p.crop_h = j.d->crop_height;
-    p.max_depth = j.d->max_depth; p.rr_depth = j.d->rr_depth;
-    p.spectral = j.s->spectral ? 1 : 0;
-    p.split = j.shadow_ring ? 3 : (j.shadow_queue ? 2 : (j.split ? 1 : 0));
-    if (p.split == 1) {       // k_trace: short per-lane stack in LDS, deep entries in a global spill area
-        const size_t words = trace_spill_words(p.sv, nw);
-        if (words > w.trace_spill_words) {
-            (void) hipFree(w.trace_spill); w.trace_spill = nullptr; w.trace_spill_words = 0;
-            if (int rc = ws_alloc((void **) &w.trace_spill, std::max<size_t>(words, 1) * sizeof(uint32_t))) return rc;
-            w.trace_spill_words = words;
-        }
-        p.trace_lds_depth = trace_lds_depth(p.sv); p.trace_top_nodes = trace_top_nodes(p.sv); p.trace_spill = w.trace_spill;
-    }
-    p.integrator = j.d->integrator; p.emitter_samples = j.d->emitter_samples; p.bsdf_samples = j.d->bsdf_samples;
-    p.hide_emitters = j.d->hide_emitters;
-    if (j.d->integrator != 0) {          // direct / depth: one launch finishes the whole pass
-        HIP_TRY(hipEventRecord(w.tev[0], j.stream));
-        HIP_TRY(launch_direct(p, n, j.stream));
-        HIP_TRY(hipEventRecord(w.tev[1], j.stream));
-        HIP_TRY(hipEventSynchronize(w.tev[1]));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, w.tev[0], w.tev[1]));
-        j.bounce_ms += ms; j.iterations += 1;
-        return 0;
-    }
-
-    // Small passes of the automatic schedule: one launch of persistent lanes instead of launch rounds (kernels.hip, k_mega).  At most a
-    // few samples per lane the launch count, not the kernel, sets the time: differentiable cbox 256^2 @ 1 spp, forward render
-    // 0.33 ms of launch rounds.  LDS-resident scenes up to 2^19 samples, hierarchy scenes (where the wavefront kernels win sooner) 2^17.
-    const uint64_t small_pass = j.s->view.flat ? (1ull << 19) : (1ull << 17);
-    if (((j.d->pipeline == 0 && n <= small_pass) || exp_env("MTSAMD_MEGA")) && (p.split == 1 || p.split == 3) && !j.s->nested_bsdfs) {
-        HIP_TRY(hipEventRecord(w.tev[0], j.stream));
-        HIP_TRY(launch_mega(p, j.stream));
-        HIP_TRY(hipEventRecord(w.tev[1], j.stream));
-        HIP_TRY(hipEventSynchronize(w.tev[1]));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, w.tev[0], w.tev[1]));
-        j.bounce_ms += ms; j.iterations += 1;
-        return 0;
-    }
-    // the sample cursors cannot run dry before this many launches
-    const uint64_t min_iters = (n + (uint64_t) nw * j.target - 1) / ((uint64_t) nw * j.target);
-    uint64_t it = 0;
-    int cur = 0;
-    // Termination test without stalling the device: every `stride` launches the per-wave path counts are copied to
-    // pinned memory; the copy issued at the previous checkpoint (long complete) is inspected before issuing a new one.
-    // While samples are left to generate a checkpoint every fourth launch round does; once the cursors are dry the pool only shrinks,
-    // the rounds get short and every round is checked (against the counts of the round before), so that k_finish takes over as soon
-    // as the pool is small enough
-    uint64_t stride = 4, next_check = 0;
-    int pending = -1, slot = 0;
     HIP_TRY(hipEventRecord(w.tev[0], j.stream));
-    uint32_t n_parts = 2;
-    if (const char *e = exp_env("MTSAMD_STREAMS")) n_parts = (uint32_t) std::min(4, std::max(1, atoi(e)));      // experiment switch
-    if (p.split != 3 || nw < 256u) n_parts = 1;
-    uint32_t part_lo[5] = { 0, nw, nw, nw, nw };
-    for (uint32_t k = 1; k < n_parts; ++k) part_lo[k] = (uint32_t) (((uint64_t) nw * k / n_parts + 3u) & ~3ull);
-    part_lo[n_parts] = nw;
-    // Pool drain of LDS-resident scenes: once every cursor is dry, a workgroup gathers the paths of gather_w consecutive scheduling
-    // waves at the front of the group (k_shade).  gather_w grows by powers of four as the pool empties -- decided on the counts read
-    // back every `stride` launches; they are upper bounds, counts only shrink from then on -- and its groups lie inside one part.
-    // pool size below which k_finish ends the pass (0: never).  Hierarchy scenes: measured flat between 2^20 and 2^24 (the fused kernel
-    // keeps up with the launch rounds of the split pipeline once they are no longer full): 2^22; LDS-resident scenes, whose drain is
-    // already compacted by the gathering below: 2^18
-    uint64_t finish_at = p.split == 1 ? (1ull << 22) : (p.split == 3 ? (1ull << 18) : 0ull);
-    if (j.d->finish_kernel == 1) finish_at = 0;                      // never (tests: the launch rounds run the pool dry)
-    else if (j.d->finish_kernel == 2) finish_at = 1ull << 40;       // as soon as the cursors are dry
-    if (j.s->nested_bsdfs) finish_at = 0;                            // blendbsdf / mask: only the fused kernels carry the nesting code
-    bool finish = false;
-    uint64_t finish_alive = 0;
-    uint32_t gather_max = 4u, gather_w = 4u;
-    if (p.split == 3 && !exp_env("MTSAMD_NO_GATHER")) {
-        gather_max = 1024u;
-        for (uint32_t k = 0; k <= n_parts; ++k) while (gather_max > 4u && part_lo[k] % gather_max) gather_max >>= 2;
+    if (int rc = body()) return rc;
+    HIP_TRY(hipEventRecord(w.tev[1], j.stream));
+    HIP_TRY(hipEventSynchronize(w.tev[1]));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, w.tev[0], w.tev[1]));
+    j.bounce_ms += ms;
+    return 0;
+}
+
+// desc->profile: begin / end timing events around the launches of the split pipeline, each on the stream of its launch
+struct StageProfile {
+    Workspace &w;
+    bool on;
+    struct Rec { int stage; size_t e0; };
+    std::vector<Rec> recs;
+    size_t used = 0;
+    hipError_t err = hipSuccess;
+    size_t mark(hipStream_t st) {
+        if (used == w.prof_ev.size()) {
+            hipEvent_t e = nullptr;
+            const hipError_t rc = hipEventCreate(&e);
+            if (rc != hipSuccess) { err = rc; return 0; }
+            w.prof_ev.push_back(e);
+        }
+        const hipError_t rc = hipEventRecord(w.prof_ev[used], st);
+        if (rc != hipSuccess) err = rc;
+        return used++;
     }
-    const uint32_t split_parts = p.split == 1 ? n_chains : 1u;
-    uint32_t split_lo[kMaxChains + 1];
-    for (uint32_t k = 0; k <= kMaxChains; ++k) split_lo[k] = chain_first(k, nw, split_parts);      // multiples of the k_trace group size
+};
+
+// The launch rounds of a pass: every round advances each path of the pool by one segment, over the wave ranges and streams the plan
+// names, until the drain state (schedule.h) finds the pool empty or hands what is left to k_finish.  1: the timeout stopped the pass.
+int launch_rounds(Job &j, RenderParams &p, const PassPlan &plan, StageProfile &prof) {
+    Workspace &w = j.s->ws;
+    const uint32_t nw = j.shape.n_waves, n_parts = plan.n_parts, split_parts = plan.split_parts;
+    Drain drain(j.shape, plan);
+    uint64_t it = 0;
+    int cur = 0, pending = -1, slot = 0;
+    bool finish = false;
     auto chain_main = [&](uint32_t k) { return k == 0 ? j.stream : w.chain_main[k]; };
     if (split_parts > 1) {       // the other chains start after the cursors and counts are in place
         HIP_TRY(hipEventRecord(w.part_ev[2], j.stream));
@@ -885,22 +836,11 @@ int trace_pass(Job &j, uint64_t first, uint64_t n) {
         }
         return 0;
     };
-    // desc->profile: begin / end timing events around the launches of the split pipeline, each on the stream of its launch
-    const bool prof = j.d->profile != 0 && p.split == 1;
-    struct ProfRec { int stage; size_t e0; };
-    std::vector<ProfRec> prof_recs;
-    size_t prof_used = 0;
-    hipError_t prof_err = hipSuccess;
-    auto prof_mark = [&](hipStream_t st) -> size_t {
-        if (prof_used == w.prof_ev.size()) {
-            hipEvent_t e = nullptr;
-            const hipError_t rc = hipEventCreate(&e);
-            if (rc != hipSuccess) { prof_err = rc; return 0; }
-            w.prof_ev.push_back(e);
-        }
-        const hipError_t rc = hipEventRecord(w.prof_ev[prof_used], st);
-        if (rc != hipSuccess) prof_err = rc;
-        return prof_used++;
+    auto split_stage = [&](const RenderParams &h, int stage, hipStream_t st) -> int {
+        const size_t pe = prof.on ? prof.mark(st) : 0;
+        HIP_TRY(launch_split_stage(h, stage, st));
+        if (prof.on) { prof.mark(st); prof.recs.push_back({ stage, pe }); }
+        return 0;
     };
     auto sync_all = [&]() {
         (void) hipStreamSynchronize(j.stream);
@@ -939,36 +879,29 @@ int trace_pass(Job &j, uint64_t first, uint64_t n) {
             // it.  The scheduling waves are independent, so two such chains (halves of the waves) run side by side.
             for (uint32_t k = 0; k < split_parts; ++k) {
                 RenderParams h = p;
-                h.wave_first = split_lo[k]; h.wave_last = split_lo[k + 1];
+                h.wave_first = plan.split_lo[k]; h.wave_last = plan.split_lo[k + 1];
                 hipStream_t s_main = chain_main(k), s_any = w.chain_any[k];
                 hipEvent_t e_shade = w.chain_ev[2 * k], e_any = w.chain_ev[2 * k + 1];
-                size_t pe = 0;
-                if (prof) pe = prof_mark(s_main);
-                HIP_TRY(launch_split_stage(h, 0, s_main));
-                if (prof) { prof_mark(s_main); prof_recs.push_back({ 0, pe }); }
+                if (int rc = split_stage(h, 0, s_main)) return rc;
                 if (it > 0) HIP_TRY(hipStreamWaitEvent(s_main, e_any, 0));
-                if (prof) pe = prof_mark(s_main);
-                HIP_TRY(launch_split_stage(h, 1, s_main));
-                if (prof) { prof_mark(s_main); prof_recs.push_back({ 1, pe }); }
+                if (int rc = split_stage(h, 1, s_main)) return rc;
                 HIP_TRY(hipEventRecord(e_shade, s_main));
                 HIP_TRY(hipStreamWaitEvent(s_any, e_shade, 0));
-                if (prof) pe = prof_mark(s_any);
-                HIP_TRY(launch_split_stage(h, 2, s_any));
-                if (prof) { prof_mark(s_any); prof_recs.push_back({ 2, pe }); }
+                if (int rc = split_stage(h, 2, s_any)) return rc;
                 HIP_TRY(hipEventRecord(e_any, s_any));
-                HIP_TRY(prof_err);
+                HIP_TRY(prof.err);
             }
         } else if (p.split == 3 && n_parts > 1) {
             // the scheduling waves are independent of each other: part-size launches on their own streams advance in their own
             // rhythm and fill each other's launch tails
             RenderParams h = p;
-            h.gather_w = gather_w;
+            h.gather_w = drain.gather_w;
             for (uint32_t k = 0; k < n_parts; ++k) {
-                h.wave_first = part_lo[k]; h.wave_last = part_lo[k + 1];
+                h.wave_first = plan.part_lo[k]; h.wave_last = plan.part_lo[k + 1];
                 HIP_TRY(launch_bounce(h, k == 0 ? j.stream : w.part_stream[k - 1]));
             }
         } else {
-            p.gather_w = gather_w;
+            p.gather_w = drain.gather_w;
             HIP_TRY(launch_bounce(p, j.stream));
         }
         cur ^= 1; ++it;
@@ -982,43 +915,28 @@ int trace_pass(Job &j, uint64_t first, uint64_t n) {
             static thread_local std::chrono::steady_clock::time_point t_prev;
             const auto t_now = std::chrono::steady_clock::now();
             fprintf(stderr, "iter %llu alive %llu waves_with_paths %llu dt_us %.0f gather_w %u\n", (unsigned long long) it, (unsigned long long) alive,
-                    (unsigned long long) busy_waves, it > 1 ? std::chrono::duration<double, std::micro>(t_now - t_prev).count() : 0.0, gather_w);
+                    (unsigned long long) busy_waves, it > 1 ? std::chrono::duration<double, std::micro>(t_now - t_prev).count() : 0.0, drain.gather_w);
             t_prev = std::chrono::steady_clock::now();
         }
-        if (it >= min_iters && it >= next_check) {
-            next_check = it + stride;
+        if (drain.due(it)) {
             if (pending >= 0) {
                 HIP_TRY(hipEventSynchronize(w.ev[pending]));
-                uint64_t alive = 0;
-                const uint32_t *hc = w.h_counts + (size_t) pending * nw;
-                for (uint32_t k = 0; k < nw; ++k) alive += hc[k];
-                if (alive == 0) break;
-                bool dry = false;
                 const uint64_t *hcur = w.h_cursor_rb + (size_t) pending * nw;
-                if (gather_w < gather_max || finish_at) {
-                    dry = true;
-                    for (uint32_t k = 0; k < nw && dry; ++k) dry = hcur[k] >= w.h_cursor[nw + k];
-                }
-                // every sample has been generated and few paths are left (the counts are a few launches old: an upper bound): one
-                // k_finish launch instead of the dozens of near-empty launch rounds the deepest paths would still need
-                if (dry && alive <= finish_at) { finish = true; finish_alive = alive; break; }
-                if (dry && finish_at) { stride = 1; next_check = it + 1; }
-                if (gather_w < gather_max) {
-                    if (exp_env("MTSAMD_TRACE_ITERS")) {
-                        uint32_t wet = 0, first_wet = 0;
-                        for (uint32_t k = 0; k < nw; ++k) if (hcur[k] < w.h_cursor[nw + k]) { if (!wet) first_wet = k; ++wet; }
-                        fprintf(stderr, "check at it %llu: alive %llu wet %u first_wet %u cur %llu end %llu\n", (unsigned long long) it, (unsigned long long) alive, wet, first_wet,
-                                (unsigned long long) hcur[first_wet], (unsigned long long) w.h_cursor[nw + first_wet]);
-                    }
-                    // a workgroup may take up to eight segments' worth of paths on average (the counts are a few launches old: an
-                    // upper bound); a fuller group just takes longer, its survivors spill into the group's next waves
-                    while (dry && gather_w < gather_max && alive * (uint64_t) (4u * gather_w) <= 8ull * w.seg_cap * (uint64_t) nw) gather_w *= 4u;
+                const bool may_gather = drain.gather_w < plan.gather_max;
+                const Drain::Verdict v = drain.inspect(it, w.h_counts + (size_t) pending * nw, hcur, w.h_cursor + nw);
+                if (v == Drain::Done) break;
+                if (v == Drain::Finish) { finish = true; break; }
+                if (may_gather && exp_env("MTSAMD_TRACE_ITERS")) {
+                    uint32_t wet = 0, first_wet = 0;
+                    for (uint32_t k = 0; k < nw; ++k) if (hcur[k] < w.h_cursor[nw + k]) { if (!wet) first_wet = k; ++wet; }
+                    fprintf(stderr, "check at it %llu: alive %llu wet %u first_wet %u cur %llu end %llu\n", (unsigned long long) it, (unsigned long long) drain.alive, wet, first_wet,
+                            (unsigned long long) hcur[first_wet], (unsigned long long) w.h_cursor[nw + first_wet]);
                 }
             }
             if (n_parts > 1) { if (int rc = join_parts()) return rc; }
             if (split_parts > 1) { if (int rc = join_chains()) return rc; }      // the counts of the other chains are written by their k_shade
             HIP_TRY(hipMemcpyAsync(w.h_counts + (size_t) slot * nw, w.count[cur], nw * sizeof(uint32_t), hipMemcpyDeviceToHost, j.stream));
-            if (gather_w < gather_max || finish_at) HIP_TRY(hipMemcpyAsync(w.h_cursor_rb + (size_t) slot * nw, w.cursor, nw * sizeof(uint64_t), hipMemcpyDeviceToHost, j.stream));
+            if (drain.reads_cursors()) HIP_TRY(hipMemcpyAsync(w.h_cursor_rb + (size_t) slot * nw, w.cursor, nw * sizeof(uint64_t), hipMemcpyDeviceToHost, j.stream));
             HIP_TRY(hipEventRecord(w.ev[slot], j.stream));
             pending = slot; slot ^= 1;
         }
@@ -1033,16 +951,53 @@ int trace_pass(Job &j, uint64_t first, uint64_t n) {
         RenderParams h = p;
         h.in = w.pool[cur]; h.out = w.pool[cur ^ 1];
         h.count_in = w.count[cur]; h.count_out = w.count[cur ^ 1];
-        HIP_TRY(launch_finish(h, finish_alive, j.stream));
+        HIP_TRY(launch_finish(h, drain.alive, j.stream));
         ++it;
     }
-    HIP_TRY(hipEventRecord(w.tev[1], j.stream));
-    HIP_TRY(hipEventSynchronize(w.tev[1]));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, w.tev[0], w.tev[1]));
-    j.bounce_ms += ms;
     j.iterations += it;
-    for (const ProfRec &r : prof_recs) {        // every stream has been joined into j.stream: all events are complete
+    return 0;
+}
+
+// Traces the local sample ordinals [first, first+n) of this render's rows to completion; results land in
+// ws.out_rgba / out_pos (slot = ordinal - first).
+int trace_pass(Job &j, uint64_t first, uint64_t n) {
+    Workspace &w = j.s->ws;
+    const uint32_t nw = j.shape.n_waves;
+    PassPlan plan;
+    if (int rc = plan_pass(j.shape, first, n, j.d->finish_kernel, j.d->pipeline, w.h_cursor + nw, plan)) return rc;
+    std::fill(w.h_cursor, w.h_cursor + nw, 0);
+    HIP_TRY(hipMemcpyAsync(w.cursor, w.h_cursor, nw * sizeof(uint64_t), hipMemcpyHostToDevice, j.stream));
+    HIP_TRY(hipMemcpyAsync(w.cursor_end, w.h_cursor + nw, nw * sizeof(uint64_t), hipMemcpyHostToDevice, j.stream));
+    HIP_TRY(hipMemsetAsync(w.count[0], 0, 2 * (size_t) nw * sizeof(uint32_t), j.stream));
+    HIP_TRY(hipMemsetAsync(w.count[1], 0, 2 * (size_t) nw * sizeof(uint32_t), j.stream));
+
+    RenderParams p{};
+    p.sv = j.s->view; p.cam = j.cam;
+    if (p.cam.aperture_radius > 0.0f) p.sv.general = std::max(p.sv.general, 1u);      // thin lens: aperture sampling lives in the general kernels
+    p.cursor = w.cursor; p.cursor_end = w.cursor_end; p.wave_stats = w.wave_stats;
+    p.out_rgba = j.buf ? w.out_rgba2 : w.out_rgba; p.out_pos = j.buf ? w.out_pos2 : w.out_pos;
+    p.count_shadow = w.count_shadow;
+    p.first_ordinal = first; p.first_pix = plan.first_pix; p.first_rem = plan.first_rem;
+    p.chunk = plan.chunk; p.base_seed = j.d->seed;
+    p.n_chains = plan.n_chains;
+    p.rows = j.rows; p.store_xyz = j.store_xyz;
+    p.plane_pix0 = j.plane_pix0; p.plane_pixels = j.plane_pixels;
+    p.n_waves = nw; p.seg_cap = w.seg_cap; p.target = j.shape.target;
+    p.spp = j.d->sample_count; p.crop_x = j.d->crop_x; p.crop_y = j.d->crop_y; p.crop_w = j.d->crop_width; p.crop_h = j.d->crop_height;
+    p.max_depth = j.d->max_depth; p.rr_depth = j.d->rr_depth;
+    p.spectral = j.s->spectral ? 1 : 0;
+    p.split = plan.split;
+    if (p.split == 1) {       // k_trace: short per-lane stack in LDS, deep entries in a global spill area
+        if (int rc = grow(w.trace_spill, w.trace_spill_words, trace_spill_words(p.sv, nw))) return rc;
+        p.trace_lds_depth = trace_lds_depth(p.sv); p.trace_top_nodes = trace_top_nodes(p.sv); p.trace_spill = w.trace_spill;
+    }
+    p.integrator = j.d->integrator; p.emitter_samples = j.d->emitter_samples; p.bsdf_samples = j.d->bsdf_samples;
+    p.hide_emitters = j.d->hide_emitters;
+    if (plan.mode == PassMode::Direct) return timed(j, [&]() -> int { HIP_TRY(launch_direct(p, n, j.stream)); j.iterations += 1; return 0; });
+    if (plan.mode == PassMode::Mega) return timed(j, [&]() -> int { HIP_TRY(launch_mega(p, j.stream)); j.iterations += 1; return 0; });
+    StageProfile prof{ w, j.d->profile != 0 && p.split == 1 };
+    if (int rc = timed(j, [&] { return launch_rounds(j, p, plan, prof); })) return rc;
+    for (const StageProfile::Rec &r : prof.recs) {        // every stream has been joined into j.stream: all events are complete
         float sm = 0.0f;
         HIP_TRY(hipEventElapsedTime(&sm, w.prof_ev[r.e0], w.prof_ev[r.e0 + 1]));
         j.stage_ms[r.stage] += sm; j.stage_launches[r.stage] += 1;
@@ -1054,54 +1009,16 @@ int setup_job(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, hipStream_t 
     j.s = s; j.d = d; j.stream = stream;
     if (int rc = make_camera(*d, j.cam)) return rc;
     if (int rc = make_filter(d->rfilter, d->rfilter_param, d->rfilter_param2, d->rfilter_analytic, j.filter)) return rc;
-    // One pass holds up to 2^30 camera samples (24 GiB of sample stream; a second buffer of that size lets the film splat of a pass run
-    // beside the tracing of the next): every pass ends with a drain phase in which the pool empties, so fewer, larger passes waste
-    // less (cbox 1024^2 @ 256 spp: 4 passes of 2^26 -> 1 pass: +7 %).
-    uint64_t pass_limit = 1ull << 30;
-    if (d->max_pass_log2 > 0) pass_limit = 1ull << std::min(30, std::max(10, d->max_pass_log2));
-    // samples_per_pass (integrator.cpp:59-66): a pass holds at most that many samples of every pixel of the crop window -- it bounds the
-    // memory of a pass and is where a timeout / cancel can stop; the image does not depend on it (per-sample RNG streams)
-    if (d->samples_per_pass > 0)
-        pass_limit = std::min<uint64_t>(pass_limit, std::max<uint64_t>((uint64_t) d->crop_width * d->crop_height * (uint64_t) d->samples_per_pass,
-                                                                        (uint64_t) d->crop_width * (uint64_t) d->sample_count));
-    // pipeline 0: one kernel with the in-kernel shadow ring (4) for LDS-resident (flat) scenes, split kernels (2) for hierarchy
-    // scenes; 1 / 2 / 3 / 4 force one schedule
-    if (s->spectral && d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the direct and depth integrators are implemented for the RGB variant only");
-    j.split = d->integrator == 0 && (d->pipeline == 2 || (d->pipeline == 0 && !s->view.flat));
-    j.shadow_queue = d->integrator == 0 && s->view.flat && d->pipeline == 3;
-    j.shadow_ring = d->integrator == 0 && s->view.flat && (d->pipeline == 4 || d->pipeline == 0);
-    // scenes with a blendbsdf / mask run the fused schedule whatever was asked for: only its kernels carry the nesting code (inside the
-    // kernels of the other schedules, capped at 128 VGPRs, it cost every general scene up to 20 %)
-    if (s->nested_bsdfs) j.split = j.shadow_queue = j.shadow_ring = false;
-    if ((d->pipeline == 3 || d->pipeline == 4) && !s->view.flat) return fail(MTSAMD_ERR_INVALID, "pipelines 3 and 4 (queued shadow rays) apply to LDS-resident scenes only");
-    // Paths in flight.  A launch advances every in-flight path by one segment and ends with a tail in which the CUs run
-    // dry one by one; the tails (and, for the split pipeline, the gaps between its three launches) only amortise over large
-    // launches.  Measured on MI355X -- fused kernel, cbox 1024^2 @ 256 spp, scheduling waves per CU x slots per wave:
-    // 16 x 256 -> 1753, 48 x 256 -> 1953, 72 x 512 -> 2366, 104 x 512 -> 2459, 208 x 1024 -> 2507 Msample/s (power-of-two
-    // wave counts alias in the memory channels: 64 x 256 is slower than 72 x 256); split pipeline, 261 k-triangle mesh:
-    // 16 / 64 / 128 / 208 waves per CU x 256 slots -> 705 / 1162 / 1339 / 1407 Msample/s; shadow-ring kernel (schedule 4), cbox:
-    // 72 x 512 -> 2453, 104 x 512 -> 2554, 144 x 512 -> 2576, 208 x 512 -> 2629, 104 x 1024 -> 2598 Msample/s.  Split pipeline
-    // after this round's traversal work (two-stream overlap included): 104 / 156 / 208 / 312 / 416 / 624 waves per CU x 256 slots
-    // -> 1747 / 1890 / 1946 / 2075 / 2118 / 2142 Msample/s.
-    j.target = d->paths_per_wave > 0 ? (uint32_t) d->paths_per_wave : (j.split ? 256u : 512u);
-    j.target = std::min<uint32_t>(std::max<uint32_t>(j.target, 64u), 4096u);
-    {   // no more scheduling waves than the pass can fill
-        const uint64_t want = (std::min<uint64_t>(max_pass, pass_limit) + j.target - 1) / j.target;
-        const uint64_t lo = (uint64_t) s->cu_count * 16u, hi = (uint64_t) s->cu_count * (j.split ? 416u : (j.shadow_ring ? 208u : 104u));
-        j.n_waves = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(want, lo), hi);
-    }
-    if (const char *e = exp_env("MTSAMD_WAVES_PER_CU")) j.n_waves = (uint32_t) s->cu_count * (uint32_t) std::max(1, atoi(e));    // experiment switch
-    // segments hold a multiple of 64 slots: k_shade deals whole 64-path chunks of a workgroup's list to its waves.
-    // The sample stream of a 2^30-sample pass is 24 GiB (twice that with the overlap buffer of multi-pass renders): when the device
-    // cannot provide it -- other scenes, the caller's own tensors -- the pass is halved until the workspace fits.
-    for (;;) {
-        j.pass_cap = std::max<uint64_t>(std::min<uint64_t>(max_pass, pass_limit), 1);
-        const int rc = ensure_workspace(s, j.n_waves, (j.target + 63u) & ~63u, j.pass_cap, j.split || j.shadow_queue);
-        if (rc == MTSAMD_ERR_NOMEM && pass_limit > (1ull << 22) && max_pass > (1ull << 22)) { pass_limit = std::min(pass_limit, max_pass) >> 1; continue; }
+    const SceneFacts facts{ s->view.flat != 0, s->nested_bsdfs, s->spectral, (uint32_t) s->cu_count };
+    if (int rc = plan_job(facts, *d, max_pass, schedule_switches(), j.shape)) return rc;
+    for (;;) {       // the pass is halved until its workspace fits the device
+        j.pass_cap = pass_capacity(j.shape, max_pass);
+        const int rc = ensure_workspace(s, j.shape.n_waves, j.shape.seg_cap, j.pass_cap, j.shape.split_pools());
+        if (rc == MTSAMD_ERR_NOMEM && halve_pass(j.shape, max_pass)) continue;
         if (rc) return rc;
         break;
     }
-    HIP_TRY(hipMemsetAsync(s->ws.wave_stats, 0, 4 * (size_t) j.n_waves * sizeof(uint64_t), stream));
+    HIP_TRY(hipMemsetAsync(s->ws.wave_stats, 0, 4 * (size_t) j.shape.n_waves * sizeof(uint64_t), stream));
     s->cancel.store(0);
     j.t_start = std::chrono::steady_clock::now();
     return 0;
@@ -1109,11 +1026,11 @@ int setup_job(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, hipStream_t 
 
 int collect_stats(Job &j, uint64_t samples, uint64_t *stats_host) {
     if (!stats_host) return 0;
-    std::vector<uint64_t> ws(4 * (size_t) j.n_waves);
+    std::vector<uint64_t> ws(4 * (size_t) j.shape.n_waves);
     HIP_TRY(hipMemcpyAsync(ws.data(), j.s->ws.wave_stats, ws.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, j.stream));
     HIP_TRY(hipStreamSynchronize(j.stream));
     uint64_t tot[4] = { 0, 0, 0, 0 };
-    for (uint32_t k = 0; k < j.n_waves; ++k) for (int q = 0; q < 4; ++q) tot[q] += ws[4 * (size_t) k + q];
+    for (uint32_t k = 0; k < j.shape.n_waves; ++k) for (int q = 0; q < 4; ++q) tot[q] += ws[4 * (size_t) k + q];
     stats_host[0] = tot[0]; stats_host[1] = tot[1]; stats_host[2] = samples; stats_host[3] = j.iterations; stats_host[4] = tot[2];
     stats_host[5] = (uint64_t) (j.bounce_ms * 1e6); stats_host[6] = (uint64_t) (j.film_ms * 1e6); stats_host[7] = tot[3];
     stats_host[8] = (uint64_t) (j.stage_ms[0] * 1e6); stats_host[9] = j.stage_launches[0];
@@ -1123,6 +1040,9 @@ int collect_stats(Job &j, uint64_t samples, uint64_t *stats_host) {
     return 0;
 }
 } // namespace
+
+// tiled film splat: room for the scratch tiles of a pass (film_partial_floats)
+static int ensure_film_partials(Workspace &w, size_t need) { return grow(w.film_partials, w.film_partial_floats, need); }
 
 // Film rows owned by this call (include/mtsamd.h: row_begin/row_end window, or interleaved tiles).
 static int make_rows(const mtsamd_render_desc *d, RowMap &m) {
@@ -1157,17 +1077,10 @@ int mtsamd_render(mtsamd_scene *s, const mtsamd_render_desc *d, float *film, uin
     j.rows = rows; j.store_xyz = d->film_rgb ? 2 : 1;
     const int R = (int) std::ceil(j.filter.radius);
     // passes hold whole local rows so that the sample stream can be stored as one plane per sample number
-    if (per_row > j.pass_cap) return fail(MTSAMD_ERR_UNSUPPORTED, "one film row (%llu samples) exceeds the pass capacity", (unsigned long long) per_row);
-    // Passes hold whole local rows.  The film kernel cuts a pass into source tiles of tile_h <= 16 local rows that must be contiguous
-    // on the film: with a partitioned film (interleaved row tiles) tile_h divides the partition's tile height and passes start on
-    // multiples of tile_h.
-    uint64_t rows_per_pass = std::max<uint64_t>(1, j.pass_cap / per_row);
-    int32_t film_tile_h = 16;
-    if (rows.count > 1) {
-        while (rows.tile_rows % film_tile_h) film_tile_h >>= 1;
-        if (rows_per_pass >= (uint64_t) film_tile_h) rows_per_pass -= rows_per_pass % (uint64_t) film_tile_h;
-        else { while (rows_per_pass & (rows_per_pass - 1)) rows_per_pass &= rows_per_pass - 1; film_tile_h = (int32_t) rows_per_pass; }
-    }
+    FilmPasses fp;
+    if (int rc = plan_film_passes(rows, j.pass_cap, per_row, fp)) return rc;
+    const uint64_t rows_per_pass = fp.rows_per_pass;
+    const int32_t film_tile_h = fp.tile_h;
     const bool tiled = film_tiles_supported(j.filter);
     // moment integrator: the sample stream is splatted twice (values, then squared values) into two scratch films
     float *film_target = film, *film_sq = nullptr;
@@ -1175,31 +1088,21 @@ int mtsamd_render(mtsamd_scene *s, const mtsamd_render_desc *d, float *film, uin
     if (d->moment) {
         if (d->film_rgb) return fail(MTSAMD_ERR_UNSUPPORTED, "the moment integrator writes XYZ channels (film_rgb must be 0)");
         Workspace &w = s->ws;
-        if (w.moment_pixels < n_pixels) {
-            (void) hipFree(w.moment_film); w.moment_film = nullptr; w.moment_pixels = 0;
-            if (int rc = ws_alloc((void **) &w.moment_film, 2 * 5 * n_pixels * sizeof(float))) return rc;
-            w.moment_pixels = n_pixels;
-        }
+        if (int rc = grow(w.moment_film, w.moment_floats, 2 * 5 * n_pixels)) return rc;
         HIP_TRY(hipMemsetAsync(w.moment_film, 0, 2 * 5 * n_pixels * sizeof(float), stream));
         film_target = w.moment_film; film_sq = w.moment_film + 5 * n_pixels;
     }
     // Several passes: the film splat of pass k runs on its own stream while pass k + 1 is traced into the other sample stream buffer.
     Workspace &ws = s->ws;
-    const uint64_t n_passes = ((uint64_t) rows.local_rows + rows_per_pass - 1) / rows_per_pass;
-    bool overlap = n_passes > 1;
+    bool overlap = fp.n_passes > 1;
     hipStream_t fstream = stream;
     if (overlap) {
         const uint64_t cap2 = std::min<uint64_t>(rows_per_pass * per_row, j.pass_cap);
-        if (ws.pass_cap2 < cap2) {
-            (void) hipFree(ws.out_rgba2); (void) hipFree(ws.out_pos2); ws.out_rgba2 = nullptr; ws.out_pos2 = nullptr; ws.pass_cap2 = 0;
-            const int rc = ws_alloc((void **) &ws.out_rgba2, cap2 * sizeof(float4));
-            const int rc2 = rc ? rc : ws_alloc((void **) &ws.out_pos2, cap2 * sizeof(float2));
-            if (rc2 == MTSAMD_ERR_NOMEM) {          // no room for the second sample stream: the splat of a pass runs before the next pass
-                (void) hipFree(ws.out_rgba2); (void) hipFree(ws.out_pos2); ws.out_rgba2 = nullptr; ws.out_pos2 = nullptr;
-                overlap = false;
-            } else if (rc2) return rc2;
-            else ws.pass_cap2 = cap2;
-        }
+        const int rc = grow(ws.out_rgba2, ws.out_pos2, ws.pass_cap2, cap2);
+        if (rc == MTSAMD_ERR_NOMEM) {          // no room for the second sample stream: the splat of a pass runs before the next pass
+            (void) hipFree(ws.out_rgba2); (void) hipFree(ws.out_pos2); ws.out_rgba2 = nullptr; ws.out_pos2 = nullptr;
+            overlap = false;
+        } else if (rc) return rc;
     }
     if (overlap) {
         if (!ws.film_stream) HIP_TRY(hipStreamCreateWithFlags(&ws.film_stream, hipStreamNonBlocking));
@@ -1217,11 +1120,7 @@ int mtsamd_render(mtsamd_scene *s, const mtsamd_render_desc *d, float *film, uin
         size_t need = film_partial_floats(f);
         const uint64_t last_rows = (uint64_t) rows.local_rows % rows_per_pass;      // a shorter last pass has fewer tiles but more sample runs
         if (last_rows) { f.pass_rows = (int32_t) last_rows; film_tile_grid(f); need = std::max(need, film_partial_floats(f)); }
-        if (need > ws.film_partial_floats) {
-            (void) hipFree(ws.film_partials); ws.film_partials = nullptr; ws.film_partial_floats = 0;
-            if (int rc = ws_alloc((void **) &ws.film_partials, need * sizeof(float))) return rc;
-            ws.film_partial_floats = need;
-        }
+        if (int rc = ensure_film_partials(ws, need)) return rc;
     }
     std::vector<std::pair<hipEvent_t, hipEvent_t>> film_ev;      // timing of the splats on their stream
     int rc_loop = 0;
@@ -1247,15 +1146,7 @@ int mtsamd_render(mtsamd_scene *s, const mtsamd_render_desc *d, float *film, uin
         f.first_ordinal = a; f.n_samples = n; f.spp = d->sample_count; f.rows = rows;
         f.plane_pix0 = j.plane_pix0; f.plane_pixels = j.plane_pixels;
         f.crop_x = d->crop_x; f.crop_y = d->crop_y; f.crop_w = d->crop_width; f.crop_h = d->crop_height;
-        const int32_t l0 = (int32_t) lr0, l1 = (int32_t) (lr0 + nrows - 1);
-        int32_t g0, g1;
-        if (rows.count <= 1) { g0 = rows.row0 + l0; g1 = rows.row0 + l1; }
-        else {   // global rows are monotone in the local row index
-            int32_t t0 = l0 / rows.tile_rows, t1 = l1 / rows.tile_rows;
-            g0 = (t0 * rows.count + rows.part) * rows.tile_rows + (l0 - t0 * rows.tile_rows);
-            g1 = (t1 * rows.count + rows.part) * rows.tile_rows + (l1 - t1 * rows.tile_rows);
-        }
-        f.row0 = std::max<int32_t>(0, g0 - R); f.row1 = std::min<int32_t>(d->crop_height, g1 + R + 1);
+        film_row_window(rows, lr0, nrows, R, d->crop_height, f.row0, f.row1);
         if (tiled) {
             f.pass_lr0 = (int32_t) lr0; f.pass_rows = (int32_t) nrows; f.tile_h = film_tile_h;
             film_tile_grid(f);
@@ -1328,14 +1219,9 @@ static int setup_aov_job(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, h
     for (;;) {
         if (int rc = setup_job(j, s, d, stream, max_pass)) return rc;
         Workspace &w = s->ws;
-        const uint64_t slots = j.pass_cap * n_streams;
-        if (w.aov_stream_slots >= slots) return 0;
-        (void) hipFree(w.aov_stream); w.aov_stream = nullptr; w.aov_stream_slots = 0;
-        const int rc = ws_alloc((void **) &w.aov_stream, slots * sizeof(float4));
+        const int rc = grow(w.aov_stream, w.aov_stream_slots, j.pass_cap * n_streams);
         if (rc == MTSAMD_ERR_NOMEM && j.pass_cap > (1ull << 22)) { max_pass = j.pass_cap >> 1; continue; }
-        if (rc) return rc;
-        w.aov_stream_slots = slots;
-        return 0;
+        return rc;
     }
 }
 
@@ -1343,7 +1229,7 @@ static int setup_aov_job(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, h
 static void aov_render_params(const Job &j, RenderParams &p) {
     p = RenderParams{};
     p.sv = j.s->view; p.cam = j.cam;
-    p.wave_stats = j.s->ws.wave_stats; p.n_waves = j.n_waves;
+    p.wave_stats = j.s->ws.wave_stats; p.n_waves = j.shape.n_waves;
     p.out_pos = j.s->ws.out_pos;          // the values the nested integrator's sample wrote there, or the only copy
     p.base_seed = j.d->seed; p.rows = j.rows;
     p.spp = j.d->sample_count; p.crop_x = j.d->crop_x; p.crop_y = j.d->crop_y; p.crop_w = j.d->crop_width; p.crop_h = j.d->crop_height;
@@ -1375,25 +1261,16 @@ int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32
     j.rows = rows; j.store_xyz = s->spectral ? 1 : 2;
     const int mode = !nested ? 0 : (s->spectral ? 2 : 1);
     const int R = (int) std::ceil(j.filter.radius);
-    if (per_row > j.pass_cap) return fail(MTSAMD_ERR_UNSUPPORTED, "one film row (%llu samples) exceeds the pass capacity", (unsigned long long) per_row);
     // passes hold whole local rows, cut into source tiles for the film kernel as in mtsamd_render
-    uint64_t rows_per_pass = std::max<uint64_t>(1, j.pass_cap / per_row);
-    int32_t film_tile_h = 16;
-    if (rows.count > 1) while (rows.tile_rows % film_tile_h) film_tile_h >>= 1;
-    const int32_t tile_h_one = film_tile_h;          // source tile height of a one-pass render
-    if (rows.count > 1) {
-        if (rows_per_pass >= (uint64_t) film_tile_h) rows_per_pass -= rows_per_pass % (uint64_t) film_tile_h;
-        else { while (rows_per_pass & (rows_per_pass - 1)) rows_per_pass &= rows_per_pass - 1; film_tile_h = (int32_t) rows_per_pass; }
-    }
+    FilmPasses fp;
+    if (int rc = plan_film_passes(rows, j.pass_cap, per_row, fp)) return rc;
+    const uint64_t rows_per_pass = fp.rows_per_pass, n_passes = fp.n_passes;
+    const int32_t film_tile_h = fp.tile_h, tile_h_one = fp.tile_h_one;
     const bool tiled = film_tiles_supported(j.filter);
     Workspace &ws = s->ws;
     const uint64_t n_pixels = (uint64_t) d->crop_width * (uint64_t) d->crop_height;
     // one scratch 5-channel film per stream: X,Y,Z,A,W | the channel groups | R,G,B,A (k_aov_pack interleaves them)
-    if (ws.aov_film_floats < n_films * 5 * n_pixels) {
-        (void) hipFree(ws.aov_film); ws.aov_film = nullptr; ws.aov_film_floats = 0;
-        if (int rc = ws_alloc((void **) &ws.aov_film, n_films * 5 * n_pixels * sizeof(float))) return rc;
-        ws.aov_film_floats = n_films * 5 * n_pixels;
-    }
+    if (int rc = grow(ws.aov_film, ws.aov_film_floats, n_films * 5 * n_pixels)) return rc;
     HIP_TRY(hipMemsetAsync(ws.aov_film, 0, n_films * 5 * n_pixels * sizeof(float), stream));
     // A film splatted pass by pass is not the film of one pass bit for bit: the film kernels sum per source tile of a pass, so rows
     // reached from two passes are added in another order (tests/test_gpu_lifecycle.py accepts that for mtsamd_render).  A render of
@@ -1403,7 +1280,6 @@ int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32
     // lives for this call only.  Whether it is used follows from the description and the limit alone, never from the memory that happens
     // to be free: if the device cannot provide it the call fails.  Above the limit each pass is splatted before the next is traced, as
     // mtsamd_render does.
-    const uint64_t n_passes = ((uint64_t) rows.local_rows + rows_per_pass - 1) / rows_per_pass;
     const uint32_t n_kept = n_groups + (nested ? 2u : 1u);          // groups, second colour space, the nested stream
     const uint64_t keep_slots = total * n_kept + total / 2 + 1;
     const bool retain = n_passes > 1 && total <= (1ull << 30) && keep_slots * sizeof(float4) <= s->aov_keep_limit;
@@ -1413,12 +1289,7 @@ int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32
             FilmParams f{};
             f.crop_w = d->crop_width; f.pass_rows = rows.local_rows; f.tile_h = tile_h_one; f.spp = d->sample_count;
             film_tile_grid(f);
-            const size_t need = film_partial_floats(f);
-            if (need > ws.film_partial_floats) {
-                (void) hipFree(ws.film_partials); ws.film_partials = nullptr; ws.film_partial_floats = 0;
-                if (int rc = ws_alloc((void **) &ws.film_partials, need * sizeof(float))) return rc;
-                ws.film_partial_floats = need;
-            }
+            if (int rc = ensure_film_partials(ws, film_partial_floats(f))) return rc;
         }
         (void) hipFree(ws.aov_keep); ws.aov_keep = nullptr;
         if (int rc = ws_alloc((void **) &ws.aov_keep, keep_slots * sizeof(float4))) return rc;
@@ -1438,25 +1309,13 @@ int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32
         f.first_ordinal = lr0 * per_row; f.n_samples = nrows * per_row; f.spp = d->sample_count; f.rows = rows;
         f.plane_pix0 = (uint32_t) (lr0 * (uint64_t) d->crop_width); f.plane_pixels = 0u;
         f.crop_x = d->crop_x; f.crop_y = d->crop_y; f.crop_w = d->crop_width; f.crop_h = d->crop_height;
-        const int32_t l0 = (int32_t) lr0, l1 = (int32_t) (lr0 + nrows - 1);
-        int32_t g0, g1;
-        if (rows.count <= 1) { g0 = rows.row0 + l0; g1 = rows.row0 + l1; }
-        else {   // global rows are monotone in the local row index
-            int32_t t0 = l0 / rows.tile_rows, t1 = l1 / rows.tile_rows;
-            g0 = (t0 * rows.count + rows.part) * rows.tile_rows + (l0 - t0 * rows.tile_rows);
-            g1 = (t1 * rows.count + rows.part) * rows.tile_rows + (l1 - t1 * rows.tile_rows);
-        }
-        f.row0 = std::max<int32_t>(0, g0 - R); f.row1 = std::min<int32_t>(d->crop_height, g1 + R + 1);
+        film_row_window(rows, lr0, nrows, R, d->crop_height, f.row0, f.row1);
         if (tiled) {
             f.pass_lr0 = (int32_t) lr0; f.pass_rows = (int32_t) nrows; f.tile_h = tile_h;
             film_tile_grid(f);
             const size_t need = film_partial_floats(f);
-            if (need > ws.film_partial_floats) {
-                HIP_TRY(hipStreamSynchronize(stream));               // an earlier splat may still read the scratch tiles
-                (void) hipFree(ws.film_partials); ws.film_partials = nullptr; ws.film_partial_floats = 0;
-                if (int rc = ws_alloc((void **) &ws.film_partials, need * sizeof(float))) return rc;
-                ws.film_partial_floats = need;
-            }
+            if (need > ws.film_partial_floats) HIP_TRY(hipStreamSynchronize(stream));               // an earlier splat may still read the scratch tiles
+            if (int rc = ensure_film_partials(ws, need)) return rc;
             f.partials = ws.film_partials;
         }
         while (ws.film_ev.size() < 2 * (film_events + 1)) {

@@ -26,7 +26,7 @@ struct PoolView {
 // Film rows owned by one render call.  count <= 1: the contiguous window [row0, row0 + local_rows);
 // count > 1: the film is cut into tiles of tile_rows rows dealt round-robin, this call owns tiles t % count == part.
 struct RowMap { int32_t row0, local_rows, tile_rows, part, count; };
-MTS_DEV int32_t row_to_global(const RowMap &m, int32_t lr) {
+__host__ __device__ __forceinline__ int32_t row_to_global(const RowMap &m, int32_t lr) {
     if (m.count <= 1) return m.row0 + lr;
     int32_t t = lr / m.tile_rows;
     return (t * m.count + m.part) * m.tile_rows + (lr - t * m.tile_rows);

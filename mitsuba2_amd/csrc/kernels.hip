@@ -1543,22 +1543,25 @@ __global__ __launch_bounds__(64) void k_mega(const RenderParams P) {
     }
 }
 
+// Host side: the variant of a path kernel a launch needs.  `f` is called with the state type (tabulated spectra / spectral / RGB) as a
+// VariantState tag and with GENERAL (the BSDF switch is compiled in) as a std::bool_constant; with_flag does the same for one bool.
+template <typename S> struct VariantState { using type = S; };
+template <typename F> static void with_variant(const RenderParams &p, F &&f) {
+    if (p.spectral && p.sv.n_spectra) f(VariantState<PathStateT>{}, std::true_type{});
+    else if (p.spectral && p.sv.general) f(VariantState<PathStateS>{}, std::true_type{});
+    else if (p.spectral) f(VariantState<PathStateS>{}, std::false_type{});
+    else if (p.sv.general) f(VariantState<PathState>{}, std::true_type{});
+    else f(VariantState<PathState>{}, std::false_type{});
+}
+template <typename F> static void with_flag(bool v, F &&f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+#define MTS_VARIANT(st, general) typename decltype(st)::type, decltype(general)::value
+
 hipError_t launch_mega(const RenderParams &p, hipStream_t s) {
     const size_t lds = p.sv.flat ? lds_bytes(p.sv, 64u) : sizeof(StackEntry) * (std::min(p.sv.stack_depth, kFinishLdsDepth) + 1u) * 64u;
     const uint32_t blocks = p.n_waves;
-    if (p.sv.flat) {
-        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_mega<PathStateT, true, true>), dim3(blocks), dim3(64), lds, s, p);
-        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_mega<PathStateS, true, true>), dim3(blocks), dim3(64), lds, s, p);
-        else if (p.spectral) hipLaunchKernelGGL((k_mega<PathStateS, false, true>), dim3(blocks), dim3(64), lds, s, p);
-        else if (p.sv.general) hipLaunchKernelGGL((k_mega<PathState, true, true>), dim3(blocks), dim3(64), lds, s, p);
-        else hipLaunchKernelGGL((k_mega<PathState, false, true>), dim3(blocks), dim3(64), lds, s, p);
-    } else {
-        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_mega<PathStateT, true, false>), dim3(blocks), dim3(64), lds, s, p);
-        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_mega<PathStateS, true, false>), dim3(blocks), dim3(64), lds, s, p);
-        else if (p.spectral) hipLaunchKernelGGL((k_mega<PathStateS, false, false>), dim3(blocks), dim3(64), lds, s, p);
-        else if (p.sv.general) hipLaunchKernelGGL((k_mega<PathState, true, false>), dim3(blocks), dim3(64), lds, s, p);
-        else hipLaunchKernelGGL((k_mega<PathState, false, false>), dim3(blocks), dim3(64), lds, s, p);
-    }
+    with_flag(p.sv.flat != 0u, [&](auto flat) {
+        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_mega<MTS_VARIANT(st, general), decltype(flat)::value>), dim3(blocks), dim3(64), lds, s, p); });
+    });
     return hipGetLastError();
 }
 
@@ -1568,19 +1571,9 @@ hipError_t launch_finish(const RenderParams &p, uint64_t alive, hipStream_t s) {
     const uint32_t per = std::min((uint32_t) ((p.n_waves + want - 1u) / want), kFinishMaxPer);
     const uint32_t blocks = (p.n_waves + per - 1u) / per;
     const size_t lds = p.sv.flat ? lds_bytes(p.sv, 64u) : sizeof(StackEntry) * (std::min(p.sv.stack_depth, kFinishLdsDepth) + 1u) * 64u;
-    if (p.sv.flat) {
-        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_finish<PathStateT, true, true>), dim3(blocks), dim3(64), lds, s, p, per);
-        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_finish<PathStateS, true, true>), dim3(blocks), dim3(64), lds, s, p, per);
-        else if (p.spectral) hipLaunchKernelGGL((k_finish<PathStateS, false, true>), dim3(blocks), dim3(64), lds, s, p, per);
-        else if (p.sv.general) hipLaunchKernelGGL((k_finish<PathState, true, true>), dim3(blocks), dim3(64), lds, s, p, per);
-        else hipLaunchKernelGGL((k_finish<PathState, false, true>), dim3(blocks), dim3(64), lds, s, p, per);
-    } else {
-        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_finish<PathStateT, true, false>), dim3(blocks), dim3(64), lds, s, p, per);
-        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_finish<PathStateS, true, false>), dim3(blocks), dim3(64), lds, s, p, per);
-        else if (p.spectral) hipLaunchKernelGGL((k_finish<PathStateS, false, false>), dim3(blocks), dim3(64), lds, s, p, per);
-        else if (p.sv.general) hipLaunchKernelGGL((k_finish<PathState, true, false>), dim3(blocks), dim3(64), lds, s, p, per);
-        else hipLaunchKernelGGL((k_finish<PathState, false, false>), dim3(blocks), dim3(64), lds, s, p, per);
-    }
+    with_flag(p.sv.flat != 0u, [&](auto flat) {
+        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_finish<MTS_VARIANT(st, general), decltype(flat)::value>), dim3(blocks), dim3(64), lds, s, p, per); });
+    });
     return hipGetLastError();
 }
 
@@ -1805,11 +1798,7 @@ hipError_t launch_split_stage(const RenderParams &p, int stage, hipStream_t s) {
         if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_trace<false, false>), trace_lds_bytes(p.sv))) return e;
         hipLaunchKernelGGL((k_trace<false, false>), dim3(trace_blocks), dim3(kTraceBlock), trace_lds_bytes(p.sv), s, p);
     } else if (stage == 1) {
-        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_shade<PathStateT, true, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
-        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
-        else if (p.spectral) hipLaunchKernelGGL((k_shade<PathStateS, false, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
-        else if (p.sv.general) hipLaunchKernelGGL((k_shade<PathState, true, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((k_shade<PathState, false, false>), dim3(shade_blocks), dim3(kBlock), 0, s, p);
+        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_shade<MTS_VARIANT(st, general), false>), dim3(shade_blocks), dim3(kBlock), 0, s, p); });
     } else {
         if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_trace<true, false>), trace_lds_bytes(p.sv))) return e;
         hipLaunchKernelGGL((k_trace<true, false>), dim3(trace_blocks), dim3(kTraceBlock), trace_lds_bytes(p.sv), s, p);
@@ -1824,21 +1813,13 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
         const uint32_t shade_blocks = p.gather_w > 4u ? (n_launch + p.gather_w - 1u) / p.gather_w : (n_launch * 64u + kBlock - 1) / kBlock;
         p.lds_queue_offset = (uint32_t) (shade_ring_offset(p.sv, kBlock) / 16u);
         const size_t lds = shade_ring_lds_bytes(p.sv, p.spectral != 0, p.gather_w);
-        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_shade<PathStateT, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else if (p.spectral) hipLaunchKernelGGL((k_shade<PathStateS, false, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else if (p.sv.general) hipLaunchKernelGGL((k_shade<PathState, true, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else hipLaunchKernelGGL((k_shade<PathState, false, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
+        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_shade<MTS_VARIANT(st, general), true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p); });
         return hipGetLastError();
     }
     if (p.split == 2) {       // LDS-resident scene: closest hit + shading fused, shadow rays queued and resolved in dense batches
         const uint32_t shade_blocks = (p.n_waves * 64u + kBlock - 1) / kBlock;
         const size_t lds = bounce_lds_bytes(p.sv);
-        if (p.spectral && p.sv.n_spectra) hipLaunchKernelGGL((k_shade<PathStateT, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else if (p.spectral && p.sv.general) hipLaunchKernelGGL((k_shade<PathStateS, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else if (p.spectral) hipLaunchKernelGGL((k_shade<PathStateS, false, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else if (p.sv.general) hipLaunchKernelGGL((k_shade<PathState, true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
-        else hipLaunchKernelGGL((k_shade<PathState, false, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p);
+        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_shade<MTS_VARIANT(st, general), true>), dim3(shade_blocks), dim3(kBlock), lds, s, p); });
         hipLaunchKernelGGL((k_trace<true, true>), dim3((p.n_waves + kFlatGroup - 1) / kFlatGroup), dim3(kBlock), lds, s, p);
         return hipGetLastError();
     }
@@ -1882,6 +1863,7 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
     }
     return hipGetLastError();
 }
+#undef MTS_VARIANT
 
 // reconstruction filter (rfilter.h:62-65, gaussian.cpp:45-47, box.cpp:34-36, tent.cpp:33-35, catmullrom.cpp:29-43,
 // mitchell.cpp:41-56, lanczos.cpp:38-48); FilterView::alpha / bias carry tent's 1 / radius and mitchell's B / C
