@@ -736,13 +736,13 @@ bool bsdf_param_fields(const DevBsdf &b, int32_t kind, int32_t comp, float DevBs
     }
 }
 
-// parameters_changed() of a (rough)plastic whose colours were set: the weight from the means the scene holds now.  The RGB variant reads
-// the colours of the record; the spectral one the means kept beside it.
+// parameters_changed() of a (rough)plastic whose colours were set: the weight from the means the scene holds now.  The specular mean is
+// spec_mean[] in both variants, the one textured_lobe_weight reads: every setter of specular_reflectance keeps it current.
 static void constant_lobe_weight(SceneState &st, uint32_t bsdf) {
     DevBsdf &d = st.bsdfs[bsdf];
     if (!is_plastic(d.type)) return;
     const float d_mean = d.texture >= 0 ? st.textures[d.texture].mean : (st.spectral ? st.diff_mean[bsdf] : rgb_mean(&d.r));
-    d.kr = plastic_lobe_weight(d_mean, st.spectral ? st.spec_mean[bsdf] : rgb_mean(&d.sr));
+    d.kr = plastic_lobe_weight(d_mean, st.spec_mean[bsdf]);
 }
 
 // Spectral variant: a colour-valued BSDF parameter (p = 0 reflectance, 1 specular_reflectance, 2 specular_transmittance) is an `srgb`
@@ -764,6 +764,7 @@ static int spectral_set_colour(SceneState &st, uint32_t bsdf, int p, const float
         st.jac_dirty = true;
     }
     if (p == 1) { d.sr = rgb[0]; d.sg = rgb[1]; d.sb = rgb[2]; st.spec_mean[bsdf] = mean; }
+    if (p == 2) { d.kr = rgb[0]; d.kg = rgb[1]; d.kb = rgb[2]; }       // dielectrics only (bsdf_param_fields): the RGB copy creation fills
     constant_lobe_weight(st, bsdf);
     return MTSAMD_OK;
 }
@@ -795,7 +796,9 @@ int set_bsdf_param(SceneState &st, uint32_t bsdf, int32_t kind, const float *val
         d.*f0 = value3[c];
         if (f1) d.*f1 = value3[c];
     }
-    if (!st.spectral) constant_lobe_weight(st, bsdf);       // spectral: only colours move the weight (spectral_set_colour)
+    if (st.spectral) return MTSAMD_OK;       // spectral: only colours move the weight (spectral_set_colour)
+    if (kind == MTSAMD_PARAM_SPECULAR_REFLECTANCE) st.spec_mean[bsdf] = rgb_mean(&d.sr);       // Texture::mean() follows the colour, as at creation
+    constant_lobe_weight(st, bsdf);
     return MTSAMD_OK;
 }
 

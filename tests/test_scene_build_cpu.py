@@ -169,7 +169,7 @@ def test_layout(driver):
 
 
 # ---- setter round trip -------------------------------------------------------------------------------------------------------------------
-U, V = [0.25, 0.5, 0.75], [0.625, 0.125, 0.375]
+U, V, W = [0.25, 0.5, 0.75], [0.625, 0.125, 0.375], [0.875, 0.75, 0.5]
 
 
 def _material(type, variant, texture=None, **kw):
@@ -204,6 +204,15 @@ def roundtrip_cases():
         add("radiance_area", lambda x: head + [mesh(1, 0, 0), bsdf(), emitter(AREA, radiance=[4 * c for c in x])], ("set_radiance", dict(emitter=0, value=[4 * c for c in V])))
         add("radiance_point", lambda x: head + [mesh(1, 0), bsdf(), emitter(POINT, radiance=[4 * c for c in x])], ("set_radiance", dict(emitter=0, value=[4 * c for c in V])))
         add("envmap", lambda x: head + [mesh(1, 0), bsdf(), envmap(2 * texels(int(x[0] * 8), 4, 8))], ("set_envmap", dict(value=2 * texels(int(V[0] * 8), 4, 8).ravel())))
+        # sequences on a textured (rough)plastic: the lobe weight reads the texture's mean and the specular mean, whichever was set last
+        ta, tb, tc = texels(2), texels(5), texels(7)
+        spec = lambda x: ("set_param", dict(bsdf=0, kind=P_SPECULAR, value=x))
+        tex = lambda t: ("set_texture", dict(texture=0, value=t.ravel()))
+        for type, tname in ((PLASTIC, "plastic"), (ROUGHPLASTIC, "roughplastic")):
+            for sname, start, ops in (("specular_texels", U, [spec(V), tex(tb)]), ("texels_specular", U, [tex(tb), spec(V)]),
+                                      ("specular_texels_specular", U, [spec(W), tex(tb), spec(V)]), ("texels_texels", V, [tex(tc), tex(tb)])):
+                cases["%s/sequence_%s_%s" % (variant, sname, tname)] = (_material(type, variant, texture=tb, specular_reflectance=V),
+                                                                         _material(type, variant, texture=ta, specular_reflectance=start) + ops)
     return cases
 
 
@@ -213,15 +222,6 @@ KNOWN_STALE = {
     # mtsamd_scene_update_texture recomputes Texture::mean() only for a bitmap that feeds a (rough)plastic lobe weight, its one reader; the
     # device copy of the record is never refreshed either
     "rgb/texture_diffuse": ("textures", [18], "mean of a bitmap no lobe weight reads"),
-    # RGB variant: mtsamd_scene_set_bsdf_param writes the record's colour and derives the lobe weight from it; spec_mean[] keeps the value of
-    # creation (a later texture update of a textured plastic reads that one)
-    # spectral variant: setting specular_transmittance converts the colour into the coefficients the kernels read (tc0..2); the RGB copy
-    # of the colour in the record (kr, kg, kb), which creation fills, keeps its old value
-    "spectral/specular_transmittance": ("bsdfs", [16, 17, 18], "RGB copy of specular_transmittance in a spectral record"),
-    "rgb/specular_reflectance_conductor": ("spec_mean", [0], "spec_mean is written at creation only in the RGB variant"),
-    "rgb/specular_reflectance_dielectric": ("spec_mean", [0], "spec_mean is written at creation only in the RGB variant"),
-    "rgb/specular_reflectance_plastic": ("spec_mean", [0], "spec_mean is written at creation only in the RGB variant"),
-    "rgb/specular_reflectance_roughplastic": ("spec_mean", [0], "spec_mean is written at creation only in the RGB variant"),
 }
 
 
@@ -231,7 +231,7 @@ def test_setter_round_trip(driver):
     for name, (a, b) in cases.items():
         scenes[name + "#created"], scenes[name + "#set"] = a, b
     out = driver(scenes)
-    assert len(cases) == 2 * 20
+    assert len(cases) == 2 * (20 + 2 * 4)          # + four sequences on each of the two textured plastics
     for name in cases:
         a, b = out[name + "#created"], out[name + "#set"]
         assert a["rc"] == 0 and b["rc"] == 0, (name, a["message"], b["message"])
