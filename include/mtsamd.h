@@ -239,6 +239,57 @@ MTSAMD_API int mtsamd_ray_intersect_si(const mtsamd_scene *scene, uint64_t n, co
                             float *t, uint32_t *prim, uint32_t *shape, float *si26,
                             void *stream);
 
+/* ---- operator API on device streams (RGB variant) ---------------------------
+ * The operators a Python integrator or a BSDF plot composes, one query per row.  Every array argument is a device
+ * pointer; inputs are one float array of n entries per component, `active` is an optional byte mask.  Outputs are
+ * planes of n floats behind one pointer (plane k starts at out + k * n).  Inactive rows write zeros (emitter index
+ * 0xffffffff); n = 0 is valid and launches nothing.  A scene of the spectral variant is refused
+ * (MTSAMD_ERR_UNSUPPORTED) before the device is touched; component selection (BSDFContext::type_mask / component)
+ * and TransportMode::Importance are not built. */
+typedef struct {
+    const uint32_t *shape;                 /* shape index of the interaction (SurfaceInteraction::shape): selects the BSDF;
+                                              a row whose index is out of range is treated as inactive */
+    const float *wi_x, *wi_y, *wi_z;       /* SurfaceInteraction::wi (local frame) */
+    const float *u, *v;                    /* SurfaceInteraction::uv for textured parameters; may be NULL (0, 0) */
+    const float *wo_x, *wo_y, *wo_z;       /* eval / pdf only */
+    const float *sample1;                  /* sample only */
+    const float *sample2_x, *sample2_y;    /* sample only */
+    const uint8_t *active;                 /* may be NULL */
+} mtsamd_bsdf_query;
+/* BSDF::eval and BSDF::pdf (include/mitsuba/render/bsdf.h, eval / pdf with the default BSDFContext).
+ * out4: value r, g, b (the cosine foreshortening factor included, as in the reference), pdf. */
+MTSAMD_API int mtsamd_bsdf_eval_pdf(const mtsamd_scene *scene, uint64_t n, const mtsamd_bsdf_query *query, float *out4, void *stream);
+/* BSDF::sample (bsdf.h).  out10: wo x, y, z, pdf, eta, delta flag (BSDFFlags::Delta of the sampled lobe, Null included),
+ * weight r, g, b (value / pdf), valid flag.  An invalid sample has weight 0 and valid 0. */
+MTSAMD_API int mtsamd_bsdf_sample(const mtsamd_scene *scene, uint64_t n, const mtsamd_bsdf_query *query, float *out10, void *stream);
+/* Scene::sample_emitter_direction without its visibility test (src/librender/scene.cpp:165-189; the caller traces the
+ * shadow rays with mtsamd_ray_test).  ref_p / sample2: 3 / 2 planes of n floats.  out15: DirectionSample p (3), n (3),
+ * d (3), dist, pdf, delta flag, then the emitted radiance / pdf (3).  emitter: index of the sampled emitter per row.
+ * A scene without emitters writes zeros. */
+MTSAMD_API int mtsamd_sample_emitter_direction(const mtsamd_scene *scene, uint64_t n, const float *ref_p3, const float *sample2,
+                                    const uint8_t *active, float *out15, uint32_t *emitter, void *stream);
+/* Scene::pdf_emitter_direction (scene.cpp:191-206) for the emitter `emitter[i]` seen from the reference point along
+ * d (3 planes) at distance dist, n (3 planes) = normal at the emitter.  Rows flagged delta (may be NULL), delta
+ * emitters and index 0xffffffff give 0. */
+MTSAMD_API int mtsamd_pdf_emitter_direction(const mtsamd_scene *scene, uint64_t n, const uint32_t *emitter, const float *d3, const float *n3,
+                                 const float *dist, const uint8_t *delta, const uint8_t *active, float *pdf, void *stream);
+/* Emitter::eval (include/mitsuba/render/emitter.h): an area emitter gives its radiance where wi.z > 0 (wi3: local wi of
+ * the interaction on the emitter), the environment emitter its radiance for a ray that escaped along the world
+ * direction d3; delta emitters and index 0xffffffff ("none") give 0.  out3: r, g, b. */
+MTSAMD_API int mtsamd_emitter_eval(const mtsamd_scene *scene, uint64_t n, const uint32_t *emitter, const float *wi3, const float *d3,
+                        const uint8_t *active, float *out3, void *stream);
+/* IndependentSampler::seed (src/samplers/independent.cpp:62-72): lane i becomes the PCG32 stream the render kernels
+ * give global sample index first + i under base_seed.  state / inc: n 64-bit words each, kept by the caller. */
+MTSAMD_API int mtsamd_sampler_seed(uint64_t n, uint64_t first, uint64_t base_seed, uint64_t *state, uint64_t *inc, void *stream);
+/* IndependentSampler::next_1d / next_2d (independent.cpp:76-94): dims = 1 or 2 planes of n floats; only active lanes
+ * draw and advance. */
+MTSAMD_API int mtsamd_sampler_next(uint64_t n, int32_t dims, uint64_t *state, const uint64_t *inc, const uint8_t *active, float *out,
+                        void *stream);
+/* Shape::bsdf / Shape::emitter (include/mitsuba/render/shape.h) for every shape: out3[3 i] = BSDF index, [3 i + 1] =
+ * MTSAMD_BSDF_* flag word of that BSDF, [3 i + 2] = emitter index or -1.  Host array of 3 * shape count entries. */
+enum { MTSAMD_BSDF_SMOOTH = 1, MTSAMD_BSDF_DELTA = 2, MTSAMD_BSDF_TWOSIDED = 4, MTSAMD_BSDF_NESTED = 8 };
+MTSAMD_API int mtsamd_scene_shape_tables(const mtsamd_scene *scene, int32_t *out3);
+
 /* ---- sensor / film / sampler / integrator ----------------------------------- */
 /* src/rfilters/{gaussian,box,tent,catmullrom,mitchell,lanczos}.cpp */
 typedef enum { MTSAMD_RFILTER_GAUSSIAN = 0, MTSAMD_RFILTER_BOX = 1, MTSAMD_RFILTER_TENT = 2, MTSAMD_RFILTER_CATMULLROM = 3,

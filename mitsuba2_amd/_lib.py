@@ -61,6 +61,10 @@ class Rays(C.Structure):
     _fields_ = [(n, vp) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "mint", "maxt", "active")]
 
 
+class BsdfQuery(C.Structure):
+    _fields_ = [(n, vp) for n in ("shape", "wi_x", "wi_y", "wi_z", "u", "v", "wo_x", "wo_y", "wo_z", "sample1", "sample2_x", "sample2_y", "active")]
+
+
 class RenderDesc(C.Structure):
     _fields_ = [("to_world", C.c_float * 16), ("fov_x_deg", C.c_float), ("near_clip", C.c_float), ("far_clip", C.c_float),
                 ("film_width", C.c_int32), ("film_height", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32),
@@ -97,6 +101,14 @@ SYMBOLS = {
     "mtsamd_ray_intersect_naive": (C.c_int, [vp, C.c_uint64, C.POINTER(Rays), vp, vp, vp, vp, vp, vp]),
     "mtsamd_ray_test": (C.c_int, [vp, C.c_uint64, C.POINTER(Rays), vp, vp]),
     "mtsamd_ray_intersect_si": (C.c_int, [vp, C.c_uint64, C.POINTER(Rays), vp, vp, vp, vp, vp]),
+    "mtsamd_bsdf_eval_pdf": (C.c_int, [vp, C.c_uint64, C.POINTER(BsdfQuery), vp, vp]),
+    "mtsamd_bsdf_sample": (C.c_int, [vp, C.c_uint64, C.POINTER(BsdfQuery), vp, vp]),
+    "mtsamd_sample_emitter_direction": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "mtsamd_pdf_emitter_direction": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mtsamd_emitter_eval": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "mtsamd_sampler_seed": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp]),
+    "mtsamd_sampler_next": (C.c_int, [C.c_uint64, C.c_int32, vp, vp, vp, vp, vp]),
+    "mtsamd_scene_shape_tables": (C.c_int, [vp, C.POINTER(C.c_int32)]),
     "mtsamd_render": (C.c_int, [vp, C.POINTER(RenderDesc), vp, u64p, vp]),
     "mtsamd_render_aov": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(C.c_int32), C.c_uint32, C.c_int32, vp, u64p, vp]),
     "mtsamd_sample_aovs": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(C.c_int32), C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp]),

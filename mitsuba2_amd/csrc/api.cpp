@@ -689,6 +689,108 @@ int mtsamd_ray_test(const mtsamd_scene *s, uint64_t n, const mtsamd_rays *rays, 
     return MTSAMD_OK;
 }
 
+// ---- operator API on device streams ------------------------------------------------------------
+// what the host can check: 1 = nothing to do (n == 0), 0 = go on, < 0 = refused
+static int check_operator(const mtsamd_scene *s, uint64_t n, const char *what) {
+    if (!s) return fail(MTSAMD_ERR_INVALID, "%s: null scene", what);
+    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "%s: the operator API is implemented for the RGB variant only", what);
+    return n == 0 ? 1 : 0;
+}
+
+static int bsdf_operator(const mtsamd_scene *s, uint64_t n, const mtsamd_bsdf_query *q, float *out, bool sample, void *stream) {
+    const char *what = sample ? "mtsamd_bsdf_sample" : "mtsamd_bsdf_eval_pdf";
+    if (int rc = check_operator(s, n, what)) return rc > 0 ? MTSAMD_OK : rc;
+    if (!q || !out || !q->shape || !q->wi_x || !q->wi_y || !q->wi_z || (q->u == nullptr) != (q->v == nullptr))
+        return fail(MTSAMD_ERR_INVALID, "%s: null argument", what);
+    if (sample ? (!q->sample1 || !q->sample2_x || !q->sample2_y) : (!q->wo_x || !q->wo_y || !q->wo_z))
+        return fail(MTSAMD_ERR_INVALID, "%s: the query lacks %s", what, sample ? "sample1 / sample2" : "wo");
+    const BsdfStreams b{ q->shape, q->wi_x, q->wi_y, q->wi_z, q->u, q->v, q->wo_x, q->wo_y, q->wo_z, q->sample1, q->sample2_x, q->sample2_y, q->active };
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(sample ? launch_bsdf_sample(s->view, n, b, out, (hipStream_t) stream) : launch_bsdf_eval_pdf(s->view, n, b, out, (hipStream_t) stream));
+    return MTSAMD_OK;
+}
+int mtsamd_bsdf_eval_pdf(const mtsamd_scene *s, uint64_t n, const mtsamd_bsdf_query *q, float *out4, void *stream) {
+    return bsdf_operator(s, n, q, out4, false, stream);
+}
+int mtsamd_bsdf_sample(const mtsamd_scene *s, uint64_t n, const mtsamd_bsdf_query *q, float *out10, void *stream) {
+    return bsdf_operator(s, n, q, out10, true, stream);
+}
+
+int mtsamd_sample_emitter_direction(const mtsamd_scene *s, uint64_t n, const float *ref_p3, const float *sample2, const uint8_t *active,
+                                    float *out15, uint32_t *emitter, void *stream) {
+    if (int rc = check_operator(s, n, "mtsamd_sample_emitter_direction")) return rc > 0 ? MTSAMD_OK : rc;
+    if (!ref_p3 || !sample2 || !out15 || !emitter) return fail(MTSAMD_ERR_INVALID, "mtsamd_sample_emitter_direction: null argument");
+    const EmitterSampleStreams q{ ref_p3, ref_p3 + n, ref_p3 + 2 * n, sample2, sample2 + n, active };
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_sample_emitter_direction(s->view, n, q, out15, emitter, (hipStream_t) stream));      // no emitters: zeros, as the device function
+    return MTSAMD_OK;
+}
+
+int mtsamd_pdf_emitter_direction(const mtsamd_scene *s, uint64_t n, const uint32_t *emitter, const float *d3, const float *n3, const float *dist,
+                                 const uint8_t *delta, const uint8_t *active, float *pdf, void *stream) {
+    if (int rc = check_operator(s, n, "mtsamd_pdf_emitter_direction")) return rc > 0 ? MTSAMD_OK : rc;
+    if (!emitter || !d3 || !n3 || !dist || !pdf) return fail(MTSAMD_ERR_INVALID, "mtsamd_pdf_emitter_direction: null argument");
+    const EmitterQueryStreams q{ emitter, d3, d3 + n, d3 + 2 * n, n3, n3 + n, n3 + 2 * n, dist, delta, active };
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_pdf_emitter_direction(s->view, n, q, pdf, (hipStream_t) stream));
+    return MTSAMD_OK;
+}
+
+int mtsamd_emitter_eval(const mtsamd_scene *s, uint64_t n, const uint32_t *emitter, const float *wi3, const float *d3, const uint8_t *active,
+                        float *out3, void *stream) {
+    if (int rc = check_operator(s, n, "mtsamd_emitter_eval")) return rc > 0 ? MTSAMD_OK : rc;
+    if (!emitter || !wi3 || !d3 || !out3) return fail(MTSAMD_ERR_INVALID, "mtsamd_emitter_eval: null argument");
+    const EmitterQueryStreams q{ emitter, d3, d3 + n, d3 + 2 * n, wi3, wi3 + n, wi3 + 2 * n, nullptr, nullptr, active };
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_emitter_eval(s->view, n, q, out3, (hipStream_t) stream));
+    return MTSAMD_OK;
+}
+
+int mtsamd_sampler_seed(uint64_t n, uint64_t first, uint64_t base_seed, uint64_t *state, uint64_t *inc, void *stream) {
+    if (n && (!state || !inc)) return fail(MTSAMD_ERR_INVALID, "mtsamd_sampler_seed: null argument");
+    HIP_TRY(launch_sampler_seed(n, first, base_seed, state, inc, (hipStream_t) stream));
+    return MTSAMD_OK;
+}
+
+int mtsamd_sampler_next(uint64_t n, int32_t dims, uint64_t *state, const uint64_t *inc, const uint8_t *active, float *out, void *stream) {
+    if (dims != 1 && dims != 2) return fail(MTSAMD_ERR_INVALID, "mtsamd_sampler_next: dims must be 1 or 2, not %d", dims);
+    if (n && (!state || !inc || !out)) return fail(MTSAMD_ERR_INVALID, "mtsamd_sampler_next: null argument");
+    HIP_TRY(launch_sampler_next(n, dims, state, inc, active, out, (hipStream_t) stream));
+    return MTSAMD_OK;
+}
+
+// BSDFFlags of a record as far as the kernels distinguish them: Smooth (bsdf_is_smooth), Delta (a discrete lobe; mask's null lobe is one)
+static int32_t bsdf_flag_word(const std::vector<DevBsdf> &table, const DevBsdf &b) {
+    const auto smooth = [](const DevBsdf &r) {
+        return r.type == kBsdfDiffuse || r.type == kBsdfRoughConductor || r.type == kBsdfPlastic || r.type == kBsdfRoughPlastic ||
+               r.type == kBsdfRoughDielectric || (r.flags & kBsdfNestSmooth) != 0u;
+    };
+    const auto delta = [](const DevBsdf &r) {
+        return r.type == kBsdfConductor || r.type == kBsdfDielectric || r.type == kBsdfThinDielectric || r.type == kBsdfPlastic || r.type == kBsdfMask;
+    };
+    int32_t w = (smooth(b) ? MTSAMD_BSDF_SMOOTH : 0) | (delta(b) ? MTSAMD_BSDF_DELTA : 0) | ((b.flags & kBsdfTwoSided) ? MTSAMD_BSDF_TWOSIDED : 0);
+    if (b.type >= kBsdfBlend) {
+        w |= MTSAMD_BSDF_NESTED;
+        for (uint32_t c : { b.nested0, b.nested1 })
+            if (c < table.size() && delta(table[c])) w |= MTSAMD_BSDF_DELTA;
+    }
+    return w;
+}
+
+int mtsamd_scene_shape_tables(const mtsamd_scene *s, int32_t *out3) {
+    if (!s || !out3) return fail(MTSAMD_ERR_INVALID, "null argument");
+    std::vector<DevShape> shapes(s->n_shapes);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(shapes.data(), s->d_shapes, shapes.size() * sizeof(DevShape), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < s->n_shapes; ++i) {
+        const int32_t b = shapes[i].bsdf;
+        out3[3 * i] = b;
+        out3[3 * i + 1] = b >= 0 && (size_t) b < s->bsdfs.size() ? bsdf_flag_word(s->bsdfs, s->bsdfs[b]) : 0;
+        out3[3 * i + 2] = shapes[i].emitter;
+    }
+    return MTSAMD_OK;
+}
+
 // ---- render ----------------------------------------------------------------------------------
 static int check_desc(const mtsamd_render_desc *d) {
     if (!d) return fail(MTSAMD_ERR_INVALID, "null render descriptor");

@@ -231,6 +231,22 @@ hipError_t launch_ray_intersect(const SceneView &sv, uint64_t n, const RayStream
                                 uint32_t *prim, uint32_t *shape, float *u, float *v, float *si26,
                                 hipStream_t s);
 hipError_t launch_ray_test(const SceneView &sv, uint64_t n, const RayStreams &r, uint8_t *hit, hipStream_t s);
+// Operator API on device streams (kernels.hip, "Operator API"): one query per row, SoA planes, optional byte mask
+struct BsdfStreams {
+    const uint32_t *shape;
+    const float *wix, *wiy, *wiz, *u, *v, *wox, *woy, *woz, *s1, *s2x, *s2y;      // u, v may be null (0); wo: eval / pdf, s1, s2: sample
+    const uint8_t *active;
+};
+struct EmitterSampleStreams { const float *px, *py, *pz, *sx, *sy; const uint8_t *active; };
+// pdf: n = normal at the emitter, dist, delta flags (may be null); eval: n = the local wi of the interaction, d = world direction of the ray
+struct EmitterQueryStreams { const uint32_t *emitter; const float *dx, *dy, *dz, *nx, *ny, *nz, *dist; const uint8_t *delta, *active; };
+hipError_t launch_bsdf_eval_pdf(const SceneView &sv, uint64_t n, const BsdfStreams &q, float *out4, hipStream_t s);
+hipError_t launch_bsdf_sample(const SceneView &sv, uint64_t n, const BsdfStreams &q, float *out10, hipStream_t s);
+hipError_t launch_sample_emitter_direction(const SceneView &sv, uint64_t n, const EmitterSampleStreams &q, float *out15, uint32_t *emitter, hipStream_t s);
+hipError_t launch_pdf_emitter_direction(const SceneView &sv, uint64_t n, const EmitterQueryStreams &q, float *pdf, hipStream_t s);
+hipError_t launch_emitter_eval(const SceneView &sv, uint64_t n, const EmitterQueryStreams &q, float *out3, hipStream_t s);
+hipError_t launch_sampler_seed(uint64_t n, uint64_t first, uint64_t base_seed, uint64_t *state, uint64_t *inc, hipStream_t s);
+hipError_t launch_sampler_next(uint64_t n, int dims, uint64_t *state, const uint64_t *inc, const uint8_t *active, float *out, hipStream_t s);
 hipError_t launch_camera_rays(const CameraView &cam, uint64_t n, const float *sx, const float *sy, const float *apx, const float *apy, float *ox,
                               float *oy, float *oz, float *dx, float *dy, float *dz, float *mint, float *maxt,
                               hipStream_t s);

@@ -3224,6 +3224,218 @@ hipError_t launch_ray_test(const SceneView &sv, uint64_t n, const RayStreams &r,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Operator API on device streams: BSDF::eval / pdf / sample (bsdf.h), Scene::sample_emitter_direction / pdf_emitter_direction
+// (scene.cpp:165-206), Emitter::eval (emitter.h) and the independent sampler (independent.cpp:62-72), one query per row.  The kernels
+// call the device functions of the render kernels and restate none of them; the order of operations around them is k_direct's.
+// Flat scenes stage their tables in LDS as every other kernel does; on hierarchy scenes Geo<false> reads global memory only and no
+// operator walks the tree, so nothing is staged and no traversal stack is reserved (as k_ray_walk).
+template <bool FLAT>
+MTS_DEV LdsView operator_lds(const SceneView &sv, float4 *smem) {
+    if (FLAT) return lds_stage<true>(sv, smem);
+    return LdsView{};
+}
+static size_t operator_lds_bytes(const SceneView &sv) { return sv.flat ? bounce_lds_bytes(sv) : 0u; }
+
+// the BSDF record of a row, or false: inactive row, shape index out of range (never dereferenced)
+template <bool FLAT>
+MTS_DEV bool operator_bsdf(const Geo<FLAT> &geo, const BsdfStreams &q, uint64_t i, DevBsdf &bsdf) {
+    if (q.active && q.active[i] == 0) return false;
+    const uint32_t shape = q.shape[i];
+    if (shape >= geo.sv.n_shapes) return false;
+    const int32_t index = geo.shape(shape).bsdf;
+    if (index < 0 || (uint32_t) index >= geo.sv.n_bsdfs) return false;
+    bsdf = geo.bsdf((uint32_t) index);      // blend / mask: overwritten with the child in use (surface_bsdf_*)
+    return true;
+}
+
+// out: 4 planes of n floats -- value (3), pdf
+template <bool FLAT, bool NEST>
+__global__ __launch_bounds__(kBlock) void k_bsdf_eval_pdf(const SceneView sv, uint64_t n, const BsdfStreams q, float *out) {
+    extern __shared__ float4 smem[];
+    const LdsView lds = operator_lds<FLAT>(sv, smem);
+    const Geo<FLAT> geo{ sv, lds };
+    for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t) gridDim.x * kBlock) {
+        f3 value = mk3(0.0f, 0.0f, 0.0f); float pdf = 0.0f;
+        DevBsdf bsdf;
+        if (operator_bsdf(geo, q, i, bsdf)) {
+            const f3 wi = mk3(q.wix[i], q.wiy[i], q.wiz[i]), wo = mk3(q.wox[i], q.woy[i], q.woz[i]);
+            f2 uv; uv.x = q.u ? q.u[i] : 0.0f; uv.y = q.v ? q.v[i] : 0.0f;
+            uint32_t texel; f2 tw1;
+            const f3 refl = eval_reflectance(sv, bsdf, uv, texel, tw1);
+            const NestInfo ni = nest_info<NEST>(bsdf, refl.x, refl.y, refl.z);
+            auto child_refl = [&](const DevBsdf &rec) { uint32_t t; f2 w; return eval_reflectance(sv, rec, uv, t, w); };
+            surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, [&](uint32_t k) { return geo.bsdf(k); }, child_refl, wi, wo, value, pdf);
+        }
+        out[i] = value.x; out[n + i] = value.y; out[2u * n + i] = value.z; out[3u * n + i] = pdf;
+    }
+}
+
+// out: 10 planes of n floats -- wo (3), pdf, eta, delta flag, weight (3), valid flag
+template <bool FLAT, bool NEST>
+__global__ __launch_bounds__(kBlock) void k_bsdf_sample(const SceneView sv, uint64_t n, const BsdfStreams q, float *out) {
+    extern __shared__ float4 smem[];
+    const LdsView lds = operator_lds<FLAT>(sv, smem);
+    const Geo<FLAT> geo{ sv, lds };
+    for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t) gridDim.x * kBlock) {
+        BsdfSample bs; bs.wo = mk3(0.0f, 0.0f, 0.0f); bs.pdf = 0.0f; bs.eta = 0.0f; bs.delta = false;
+        f3 weight = mk3(0.0f, 0.0f, 0.0f);
+        bool ok = false;
+        DevBsdf bsdf;
+        if (operator_bsdf(geo, q, i, bsdf)) {
+            const f3 wi = mk3(q.wix[i], q.wiy[i], q.wiz[i]);
+            f2 uv; uv.x = q.u ? q.u[i] : 0.0f; uv.y = q.v ? q.v[i] : 0.0f;
+            f2 s2; s2.x = q.s2x[i]; s2.y = q.s2y[i];
+            uint32_t texel; f2 tw1;
+            const f3 refl = eval_reflectance(sv, bsdf, uv, texel, tw1);
+            const NestInfo ni = nest_info<NEST>(bsdf, refl.x, refl.y, refl.z);
+            auto child_refl = [&](const DevBsdf &rec) { uint32_t t; f2 w; return eval_reflectance(sv, rec, uv, t, w); };
+            ok = surface_bsdf_sample<NEST>(bsdf, ni, refl, [&](uint32_t k) { return geo.bsdf(k); }, child_refl, wi, q.s1[i], s2, bs, weight);
+            if (!ok) weight = mk3(0.0f, 0.0f, 0.0f);
+        }
+        out[i] = bs.wo.x; out[n + i] = bs.wo.y; out[2u * n + i] = bs.wo.z; out[3u * n + i] = bs.pdf; out[4u * n + i] = bs.eta;
+        out[5u * n + i] = bs.delta ? 1.0f : 0.0f;
+        out[6u * n + i] = weight.x; out[7u * n + i] = weight.y; out[8u * n + i] = weight.z; out[9u * n + i] = ok ? 1.0f : 0.0f;
+    }
+}
+
+template <bool EVAL>
+static hipError_t launch_bsdf_operator(const SceneView &sv, uint64_t n, const BsdfStreams &q, float *out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid(stream_grid(n)), block(kBlock);
+    const size_t lds = operator_lds_bytes(sv);
+    // the nesting code is compiled into the instantiation that only scenes with a blendbsdf / mask launch (as k_direct)
+    with_flag(sv.flat != 0u, [&](auto flat) {
+        with_flag(sv.general == 2u, [&](auto nest) {
+            constexpr bool F = decltype(flat)::value, N = decltype(nest)::value;
+            if (EVAL) hipLaunchKernelGGL((k_bsdf_eval_pdf<F, N>), grid, block, lds, s, sv, n, q, out);
+            else hipLaunchKernelGGL((k_bsdf_sample<F, N>), grid, block, lds, s, sv, n, q, out);
+        });
+    });
+    return hipGetLastError();
+}
+hipError_t launch_bsdf_eval_pdf(const SceneView &sv, uint64_t n, const BsdfStreams &q, float *out4, hipStream_t s) {
+    return launch_bsdf_operator<true>(sv, n, q, out4, s);
+}
+hipError_t launch_bsdf_sample(const SceneView &sv, uint64_t n, const BsdfStreams &q, float *out10, hipStream_t s) {
+    return launch_bsdf_operator<false>(sv, n, q, out10, s);
+}
+
+// Scene::sample_emitter_direction without the visibility test (the caller traces the shadow rays with k_ray_test): the RGB form of
+// sample_emitter_direction<FLAT, true>.  out: 15 planes of n floats -- p (3), n (3), d (3), dist, pdf, delta flag, spec (3)
+template <bool FLAT>
+__global__ __launch_bounds__(kBlock) void k_sample_emitter_direction(const SceneView sv, uint64_t n, const EmitterSampleStreams q, float *out,
+                                                                     uint32_t *emitter) {
+    extern __shared__ float4 smem[];
+    const LdsView lds = operator_lds<FLAT>(sv, smem);
+    const Geo<FLAT> geo{ sv, lds };
+    for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t) gridDim.x * kBlock) {
+        float o[15];
+#pragma unroll
+        for (int k = 0; k < 15; ++k) o[k] = 0.0f;
+        uint32_t index = kNoPrim;
+        if ((q.active ? q.active[i] != 0 : true) && sv.n_emitters != 0u) {
+            f2 s2; s2.x = q.sx[i]; s2.y = q.sy[i];
+            DirectionSample ds; f3 spec;
+            sample_emitter_direction<FLAT, true>(geo, mk3(q.px[i], q.py[i], q.pz[i]), s2, ds, spec);
+            o[0] = ds.p.x; o[1] = ds.p.y; o[2] = ds.p.z; o[3] = ds.n.x; o[4] = ds.n.y; o[5] = ds.n.z;
+            o[6] = ds.d.x; o[7] = ds.d.y; o[8] = ds.d.z; o[9] = ds.dist; o[10] = ds.pdf; o[11] = ds.delta ? 1.0f : 0.0f;
+            o[12] = spec.x; o[13] = spec.y; o[14] = spec.z;
+            index = ds.emitter;
+        }
+#pragma unroll
+        for (int k = 0; k < 15; ++k) out[(size_t) k * n + i] = o[k];
+        emitter[i] = index;
+    }
+}
+hipError_t launch_sample_emitter_direction(const SceneView &sv, uint64_t n, const EmitterSampleStreams &q, float *out15, uint32_t *emitter, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const size_t lds = operator_lds_bytes(sv);
+    if (sv.flat) hipLaunchKernelGGL(k_sample_emitter_direction<true>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, q, out15, emitter);
+    else hipLaunchKernelGGL(k_sample_emitter_direction<false>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, q, out15, emitter);
+    return hipGetLastError();
+}
+
+// The two kernels below read one emitter record per row and nothing else of the scene, so they take it from global memory on flat
+// scenes too (staging a whole flat scene in LDS for it would cost more than it saves) and have no FLAT instantiation.
+// Scene::pdf_emitter_direction (scene.cpp:191-206) as k_direct evaluates it for a BSDF sample: area emitters pdf_emitter_direction,
+// the environment emitter pdf_environment, delta rows / delta emitters / no emitter 0
+__global__ __launch_bounds__(kBlock) void k_pdf_emitter_direction(const SceneView sv, uint64_t n, const EmitterQueryStreams q, float *pdf) {
+    for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t) gridDim.x * kBlock) {
+        float r = 0.0f;
+        const uint32_t index = q.emitter[i];
+        if ((q.active ? q.active[i] != 0 : true) && index < sv.n_emitters && !(q.delta && q.delta[i] != 0)) {
+            const DevEmitter e = sv.emitters[index];
+            const f3 d = mk3(q.dx[i], q.dy[i], q.dz[i]);
+            if (e.pad0 == kEmitterConstant || e.pad0 == kEmitterEnvmap) r = pdf_environment(sv, e, d);
+            else if (e.pad0 < kEmitterPoint) r = pdf_emitter_direction(sv.n_emitters, e.area_norm, d, mk3(q.nx[i], q.ny[i], q.nz[i]), q.dist[i]);
+        }
+        pdf[i] = r;
+    }
+}
+// Emitter::eval at a surface interaction (area.cpp:71-76: radiance where wi.z > 0) or for an escaped ray (environment_radiance along
+// the world direction d); delta emitters and "none" (0xffffffff) give 0.  out: 3 planes of n floats; q.nx/ny/nz carry the local wi
+__global__ __launch_bounds__(kBlock) void k_emitter_eval(const SceneView sv, uint64_t n, const EmitterQueryStreams q, float *out) {
+    for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t) gridDim.x * kBlock) {
+        f3 le = mk3(0.0f, 0.0f, 0.0f);
+        const uint32_t index = q.emitter[i];
+        if ((q.active ? q.active[i] != 0 : true) && index < sv.n_emitters) {
+            const DevEmitter e = sv.emitters[index];
+            if (e.pad0 == kEmitterConstant || e.pad0 == kEmitterEnvmap) le = environment_radiance(sv, e, mk3(q.dx[i], q.dy[i], q.dz[i]));
+            else if (e.pad0 < kEmitterPoint) le = q.nz[i] > 0.0f ? mk3(e.r, e.g, e.b) : mk3(0.0f, 0.0f, 0.0f);
+        }
+        out[i] = le.x; out[n + i] = le.y; out[2u * n + i] = le.z;
+    }
+}
+hipError_t launch_pdf_emitter_direction(const SceneView &sv, uint64_t n, const EmitterQueryStreams &q, float *pdf, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pdf_emitter_direction, dim3(stream_grid(n)), dim3(kBlock), 0, s, sv, n, q, pdf);
+    return hipGetLastError();
+}
+hipError_t launch_emitter_eval(const SceneView &sv, uint64_t n, const EmitterQueryStreams &q, float *out3, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_emitter_eval, dim3(stream_grid(n)), dim3(kBlock), 0, s, sv, n, q, out3);
+    return hipGetLastError();
+}
+
+// IndependentSampler (independent.cpp:62-72): one PCG32 stream per lane, held by the caller as (state, inc).  Lane i is the stream
+// generate_path gives global sample index first + i.
+__global__ __launch_bounds__(kBlock) void k_sampler_seed(uint64_t n, uint64_t first, uint64_t base_seed, uint64_t *state, uint64_t *inc) {
+    for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t) gridDim.x * kBlock) {
+        Pcg32 rng;
+        seed_sample(rng, first + i, base_seed);
+        state[i] = rng.state; inc[i] = rng.inc;
+    }
+}
+// next_1d / next_2d: DIMS floats per lane (planes of n); only active lanes advance (enoki's masked next_float32)
+template <int DIMS>
+__global__ __launch_bounds__(kBlock) void k_sampler_next(uint64_t n, uint64_t *state, const uint64_t *inc, const uint8_t *active, float *out) {
+    for (uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t) gridDim.x * kBlock) {
+        float v[DIMS];
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) v[k] = 0.0f;
+        if (active ? active[i] != 0 : true) {
+            Pcg32 rng = { state[i], inc[i] };
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) v[k] = pcg_next_f32(rng);
+            state[i] = rng.state;
+        }
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) out[(size_t) k * n + i] = v[k];
+    }
+}
+hipError_t launch_sampler_seed(uint64_t n, uint64_t first, uint64_t base_seed, uint64_t *state, uint64_t *inc, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sampler_seed, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, first, base_seed, state, inc);
+    return hipGetLastError();
+}
+hipError_t launch_sampler_next(uint64_t n, int dims, uint64_t *state, const uint64_t *inc, const uint8_t *active, float *out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (dims == 1) hipLaunchKernelGGL(k_sampler_next<1>, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, state, inc, active, out);
+    else hipLaunchKernelGGL(k_sampler_next<2>, dim3(stream_grid(n)), dim3(kBlock), 0, s, n, state, inc, active, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_camera_rays(const CameraView cam, uint64_t n, const float *sx, const float *sy,
                                                         const float *apx, const float *apy, float *ox, float *oy, float *oz, float *dx, float *dy, float *dz,
                                                         float *mint, float *maxt) {

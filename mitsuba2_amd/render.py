@@ -6,6 +6,7 @@ every compute call goes through the C ABI of ``libmtsamd.so`` (``include/mtsamd.
 to own device memory and streams.
 """
 import ctypes as C
+import enum
 import math
 from dataclasses import dataclass, field
 from typing import Optional
@@ -16,6 +17,7 @@ import torch
 from . import _lib as L
 
 RayEpsilon = float(np.float32(np.finfo(np.float32).eps / 2 * 1500))
+ShadowEpsilon = float(np.float32(RayEpsilon) * np.float32(10))      # math.h:38: ShadowEpsilon = RayEpsilon * 10
 
 
 def _stream():
@@ -28,6 +30,23 @@ def _ptr(t):
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _dot3(a, b):
+    """dot product of (N,3) tensors in the kernels' order of operations: fma(a.z, b.z, fma(a.y, b.y, a.x * b.x))"""
+    return torch.addcmul(torch.addcmul(a[:, 0] * b[:, 0], a[:, 1], b[:, 1]), a[:, 2], b[:, 2])
+
+
+def _planes(t, k, dev):
+    """(N, k) values -> contiguous (k, N) float32 planes on `dev`, the layout of the operator entry points"""
+    return torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1, k).t().contiguous()
+
+
+def _mask(active, dev):
+    """`active` argument of an operator -> byte mask tensor, or None for all lanes"""
+    if active is None or active is True:
+        return None
+    return torch.as_tensor(active, device=dev).reshape(-1).to(torch.uint8).contiguous()
 
 
 # --------------------------------------------------------------------------------------------
@@ -64,10 +83,54 @@ class SurfaceInteraction3f:
     dp_dv: Optional[torch.Tensor] = None
     wi: Optional[torch.Tensor] = None
     prim_uv: Optional[torch.Tensor] = None   # barycentric (u,v): the kd-tree "cache" (kdtree.h:2432-2452)
+    # what Scene.ray_intersect remembers for the operator API: the scene (si.bsdf(), si.emitter()) and the direction tensor of the rays
+    # (Emitter.eval on an escaped lane); the planes of a missed lane stay as they are
+    _scene: Optional[object] = field(default=None, repr=False, compare=False)
+    _ray_d: Optional[torch.Tensor] = field(default=None, repr=False, compare=False)
 
     def is_valid(self):
         """interaction.h:53-55"""
         return self.t != float("inf")
+
+    def bsdf(self, ray=None):
+        """SurfaceInteraction::bsdf (interaction.h:200-203): the BSDF of every lane's shape, as one per-lane handle.  `ray` is accepted
+        and unused (no BSDF of this backend needs ray differentials)."""
+        if self._scene is None:
+            raise RuntimeError("SurfaceInteraction3f.bsdf(): the interaction was not made by Scene.ray_intersect (no shapes to look up)")
+        return BSDF(scene=self._scene, lanes=self.shape_index)
+
+    def emitter(self, scene, active=True):
+        """SurfaceInteraction::emitter (interaction.h:161,225-231): the emitter of the shape on valid lanes, the scene's environment
+        emitter on the others (none: every query on that lane gives 0)."""
+        tables = scene._operator_tables()
+        dev = self.shape_index.device
+        shape = self.shape_index.to(torch.int64)
+        valid = (shape >= 0) & (shape < scene.shape_count())
+        per_shape = tables["emitter"].to(dev)[shape.clamp(0, max(scene.shape_count() - 1, 0))]
+        index = torch.where(valid, per_shape, torch.full_like(per_shape, scene._environment))
+        if active is not True and active is not None:
+            index = torch.where(torch.as_tensor(active, device=dev).bool().reshape(-1), index, torch.full_like(index, -1))
+        return Emitter(scene, lanes=index.to(torch.int32))
+
+    def to_local(self, v):
+        """Frame3f::to_local of the shading frame (frame.h:30-32)"""
+        return torch.stack([_dot3(v, self.sh_frame_s), _dot3(v, self.sh_frame_t), _dot3(v, self.sh_frame_n)], dim=1)
+
+    def to_world(self, v):
+        """Frame3f::to_world of the shading frame (frame.h:35-37)"""
+        return (self.sh_frame_s * v[:, 0:1] + self.sh_frame_t * v[:, 1:2]) + self.sh_frame_n * v[:, 2:3]
+
+    def spawn_ray(self, d):
+        """Interaction::spawn_ray (interaction.h:58-61): mint = RayEpsilon * (1 + max |p|), maxt = inf"""
+        mint = (1.0 + self.p.abs().amax(dim=1)) * RayEpsilon
+        return Ray3f(o=self.p, d=d, mint=mint, maxt=torch.full_like(mint, float("inf")))
+
+    def spawn_ray_to(self, t):
+        """Interaction::spawn_ray_to (interaction.h:64-69): the segment to point `t`, shortened by ShadowEpsilon at its far end"""
+        d = t - self.p
+        dist = _dot3(d, d).sqrt()
+        d = d * (1.0 / dist).unsqueeze(1)
+        return Ray3f(o=self.p, d=d, mint=(1.0 + self.p.abs().amax(dim=1)) * RayEpsilon, maxt=dist * (1.0 - ShadowEpsilon))
 
 
 # --------------------------------------------------------------------------------------------
@@ -207,6 +270,38 @@ class IndependentSampler:
 
     def sample_count(self): return self._sample_count
     def seed_value(self): return self._seed
+
+    # -- the wavefront sampler of a Python integrator (independent.cpp:61-94): one PCG32 stream per lane, on the device
+    def seed(self, seed_value, size, first=0, device="cuda"):
+        """Sampler::seed(seed_value, size): lane i becomes the stream the render kernels give global sample index first + i under
+        seed = seed_value, so an integrator composed from the operators draws the numbers the built-in ones draw."""
+        self._seed = int(seed_value)
+        dev = torch.device(device)
+        self._state = torch.empty((2, int(size)), dtype=torch.int64, device=dev)
+        L.check(L.lib().mtsamd_sampler_seed(int(size), int(first), int(seed_value) & 0xFFFFFFFFFFFFFFFF, _ptr(self._state[0]),
+                                            _ptr(self._state[1]), _stream()))
+
+    def wavefront_size(self):
+        return 0 if getattr(self, "_state", None) is None else self._state.shape[1]
+
+    def _next(self, dims, active):
+        if getattr(self, "_state", None) is None:
+            raise RuntimeError("IndependentSampler: seed(seed_value, size) must be called before samples are drawn")
+        n, dev = self._state.shape[1], self._state.device
+        act = _mask(active, dev)
+        if act is not None and act.shape[0] != n:
+            raise RuntimeError("IndependentSampler: the mask has %d lanes, the sampler %d" % (act.shape[0], n))
+        out = torch.empty((dims, n), dtype=torch.float32, device=dev)
+        L.check(L.lib().mtsamd_sampler_next(n, dims, _ptr(self._state[0]), _ptr(self._state[1]), _ptr(act), _ptr(out), _stream()))
+        return out
+
+    def next_1d(self, active=True):
+        """Sampler::next_1d (independent.cpp:76-88): (N,) floats; lanes masked out do not advance"""
+        return self._next(1, active)[0]
+
+    def next_2d(self, active=True):
+        """Sampler::next_2d (independent.cpp:90-94): (N,2)"""
+        return self._next(2, active).t().contiguous()
 
 
 class HDRFilm:
@@ -646,6 +741,8 @@ class Scene:
         self._handle = handle
         self._n_spectra = len(bindings)
         self._shape_count = len(meshes)
+        self._tables = None            # operator API: per-shape tables, read on first use
+        self._environment = next((i for i, e in enumerate(emitters) if e.get("type", "area") in ("constant", "envmap")), -1)      # scene.cpp:44-48
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -758,7 +855,8 @@ class Scene:
         L.check(L.lib().mtsamd_ray_intersect_si(self._handle, n, C.byref(r), _ptr(t), _ptr(prim), _ptr(shape), _ptr(si), _stream()))
         g = lambda a, b: si[a:b].t().contiguous()
         return SurfaceInteraction3f(t=t, prim_index=prim, shape_index=shape, p=g(0, 3), n=g(3, 6), uv=g(6, 8), sh_frame_s=g(8, 11),
-                                    sh_frame_t=g(11, 14), sh_frame_n=g(14, 17), dp_du=g(17, 20), dp_dv=g(20, 23), wi=g(23, 26))
+                                    sh_frame_t=g(11, 14), sh_frame_n=g(14, 17), dp_du=g(17, 20), dp_dv=g(20, 23), wi=g(23, 26),
+                                    _scene=self, _ray_d=ray.d)
 
     def ray_intersect_naive(self, ray, active=True):
         """Scene::ray_intersect_naive (scene.h:38-44): brute force, for tests."""
@@ -777,6 +875,368 @@ class Scene:
         hit = torch.empty(n, dtype=torch.uint8, device=dev)
         L.check(L.lib().mtsamd_ray_test(self._handle, n, C.byref(r), _ptr(hit), _stream()))
         return hit.bool()
+
+    # -- operator API (scene_v.cpp:37-86: shapes, sample_emitter_direction, pdf_emitter_direction)
+    def _require_rgb(self, what):
+        if self._variant != "rgb":
+            raise RuntimeError("%s: the operator API is implemented for the RGB variant only (this scene is %s)" % (what, self._variant))
+
+    def _operator_tables(self):
+        """per shape: BSDF index, MTSAMD_BSDF_* flag word, emitter index or -1 (mtsamd_scene_shape_tables, read once), and the
+        BSDFFlags of every top-level BSDF record"""
+        if self._tables is None:
+            n = self._shape_count
+            raw = (C.c_int32 * max(3 * n, 1))()
+            L.check(L.lib().mtsamd_scene_shape_tables(self._handle, raw))
+            a = np.array(raw[:3 * n], dtype=np.int32).reshape(n, 3)
+            dev = torch.device("cuda", self._device_index)
+            flags = np.array([bsdf_flags(self._bsdf_records[b]) for b in a[:, 0]], dtype=np.int32)
+            self._tables = dict(bsdf=a[:, 0].copy(), word=a[:, 1].copy(), emitter=torch.as_tensor(a[:, 2].copy(), device=dev),
+                                emitter_host=a[:, 2].copy(), flags=torch.as_tensor(flags, device=dev), flags_host=flags)
+        return self._tables
+
+    def shapes(self):
+        """Scene::shapes (scene.h:143-145)"""
+        return [Shape(self, i) for i in range(self._shape_count)]
+
+    def emitters(self):
+        """Scene::emitters (scene.h:135-137)"""
+        return [Emitter(self, index=i) for i in range(len(self._dict.get("emitters", [])))]
+
+    def environment(self):
+        """Scene::environment (scene.h:140): the `constant` / `envmap` emitter, or None"""
+        return Emitter(self, index=self._environment) if self._environment >= 0 else None
+
+    def sample_emitter_direction(self, ref, sample, test_visibility=True, active=True):
+        """Scene::sample_emitter_direction (scene.cpp:165-189) -> (DirectionSample3f, spec (N,3)).  `ref` needs only `p`.  With
+        test_visibility the shadow rays (ref.p, ds.d, RayEpsilon * (1 + max |p|), ds.dist * (1 - ShadowEpsilon)) go through ray_test and
+        `spec` is zeroed on occluded lanes."""
+        self._require_rgb("Scene.sample_emitter_direction")
+        dev = torch.device("cuda", self._device_index)
+        p, s2 = _planes(ref.p, 3, dev), _planes(sample, 2, dev)
+        n = p.shape[1]
+        if s2.shape[1] != n:
+            raise RuntimeError("sample_emitter_direction: one 2D sample per reference point is required")
+        act = _mask(active, dev)
+        out = torch.empty((15, n), dtype=torch.float32, device=dev)
+        index = torch.empty(n, dtype=torch.int32, device=dev)
+        L.check(L.lib().mtsamd_sample_emitter_direction(self._handle, n, _ptr(p), _ptr(s2), _ptr(act), _ptr(out), _ptr(index), _stream()))
+        g = lambda a, b: out[a:b].t().contiguous()
+        ds = DirectionSample3f(p=g(0, 3), n=g(3, 6), d=g(6, 9), dist=out[9].clone(), pdf=out[10].clone(), delta=out[11] > 0.5, object=index)
+        spec = g(12, 15)
+        if test_visibility:
+            ref_p = p.t().contiguous()
+            ray = Ray3f(o=ref_p, d=ds.d, mint=(1.0 + ref_p.abs().amax(dim=1)) * RayEpsilon, maxt=ds.dist * (1.0 - ShadowEpsilon))
+            # scene.cpp:179-186: only lanes with a non-zero pdf cast a shadow ray
+            lanes = ds.pdf != 0.0
+            if act is not None:
+                lanes = lanes & act.bool()
+            occluded = self.ray_test(ray, active=lanes)
+            spec = torch.where(occluded.unsqueeze(1), torch.zeros_like(spec), spec)
+        return ds, spec
+
+    def pdf_emitter_direction(self, ref, ds, active=True):
+        """Scene::pdf_emitter_direction (scene.cpp:191-206) of the emitters `ds.object` (per-lane indices, an Emitter handle or an
+        index) for the directions of `ds`.  `ref` is accepted for the reference's signature; the densities here depend on `ds` alone."""
+        self._require_rgb("Scene.pdf_emitter_direction")
+        dev = torch.device("cuda", self._device_index)
+        d, nrm = _planes(ds.d, 3, dev), _planes(ds.n, 3, dev)
+        n = d.shape[1]
+        index = _emitter_lanes(ds.object, n, dev)
+        dist = torch.as_tensor(ds.dist, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+        delta = _mask(ds.delta, dev) if ds.delta is not None else None
+        act = _mask(active, dev)
+        pdf = torch.empty(n, dtype=torch.float32, device=dev)
+        L.check(L.lib().mtsamd_pdf_emitter_direction(self._handle, n, _ptr(index), _ptr(d), _ptr(nrm), _ptr(dist), _ptr(delta), _ptr(act),
+                                                     _ptr(pdf), _stream()))
+        return pdf
+
+
+# --------------------------------------------------------------------------------------------
+# Operator API: BSDF / emitter / sampler queries on device streams (include/mitsuba/render/bsdf.h, records.h, emitter.h, shape.h;
+# bindings src/librender/python/bsdf_v.cpp, records_v.cpp, emitter_v.cpp, shape_v.cpp).  RGB variant.
+class TransportMode(enum.IntEnum):
+    """bsdf.h:20-29"""
+    Radiance = 0
+    Importance = 1
+
+
+class BSDFFlags(enum.IntFlag):
+    """bsdf.h:38-124"""
+    None_ = 0x00000
+    Null = 0x00001
+    DiffuseReflection = 0x00002
+    DiffuseTransmission = 0x00004
+    GlossyReflection = 0x00008
+    GlossyTransmission = 0x00010
+    DeltaReflection = 0x00020
+    DeltaTransmission = 0x00040
+    Delta1DReflection = 0x00080
+    Delta1DTransmission = 0x00100
+    Anisotropic = 0x01000
+    SpatiallyVarying = 0x02000
+    NonSymmetric = 0x04000
+    FrontSide = 0x08000
+    BackSide = 0x10000
+    NeedsDifferentials = 0x20000
+    Reflection = DiffuseReflection | DeltaReflection | Delta1DReflection | GlossyReflection
+    Transmission = DiffuseTransmission | DeltaTransmission | Delta1DTransmission | GlossyTransmission | Null
+    Diffuse = DiffuseReflection | DiffuseTransmission
+    Glossy = GlossyReflection | GlossyTransmission
+    Smooth = Diffuse | Glossy
+    Delta = Null | DeltaReflection | DeltaTransmission
+    Delta1D = Delta1DReflection | Delta1DTransmission
+    All = Diffuse | Glossy | Delta | Delta1D
+
+
+def has_flag(flags, f):
+    """has_flag (bsdf.h:133) for a flag word or a tensor of flag words"""
+    return (flags & int(f)) != 0
+
+
+def bsdf_flags(record):
+    """BSDF::flags() of a normalised record (mitsuba2_amd.bsdfs.normalize): the union of the component flags the plugin constructors
+    set (src/bsdfs/*.cpp); blendbsdf / mask: the union over the children (mask adds Null)"""
+    from . import bsdfs as B
+    F = BSDFFlags
+    t = record["type"]
+    if t in (B.BLEND, B.MASK):
+        flags = int(F.Null) if t == B.MASK else 0
+        for c in record["children"]:
+            flags |= bsdf_flags(c)
+    else:
+        aniso = int(F.Anisotropic) if record["alpha_u"] != record["alpha_v"] else 0
+        flags = {B.DIFFUSE: F.DiffuseReflection | F.FrontSide, B.CONDUCTOR: F.DeltaReflection | F.FrontSide,
+                 B.ROUGHCONDUCTOR: F.GlossyReflection | F.FrontSide | aniso,
+                 B.DIELECTRIC: F.DeltaReflection | F.DeltaTransmission | F.FrontSide | F.BackSide | F.NonSymmetric,
+                 B.THINDIELECTRIC: F.DeltaReflection | F.Null | F.FrontSide | F.BackSide,
+                 B.PLASTIC: F.DeltaReflection | F.DiffuseReflection | F.FrontSide,
+                 B.ROUGHPLASTIC: F.GlossyReflection | F.DiffuseReflection | F.FrontSide,
+                 B.ROUGHDIELECTRIC: F.GlossyReflection | F.GlossyTransmission | F.FrontSide | F.BackSide | F.NonSymmetric | aniso}[t]
+        flags = int(flags)
+    if record.get("twosided"):
+        flags |= int(F.FrontSide | F.BackSide)
+    return flags
+
+
+class BSDFContext:
+    """bsdf.h:146-190.  Only the defaults are built: mode = Radiance, type_mask = all components, component = -1 (all)."""
+
+    def __init__(self, mode=TransportMode.Radiance, type_mask=0x1FF, component=0xFFFFFFFF):
+        self.mode, self.type_mask, self.component = mode, type_mask, component
+        self._check()
+
+    def _check(self):
+        if int(self.mode) != int(TransportMode.Radiance):
+            raise RuntimeError("BSDFContext: TransportMode.Importance is not built in this backend (Radiance only)")
+        if int(self.type_mask) != 0x1FF or int(self.component) not in (0xFFFFFFFF, -1):
+            raise RuntimeError("BSDFContext: component selection is not built in this backend (type_mask and component must keep "
+                               "their defaults: all components)")
+
+
+@dataclass
+class BSDFSample3f:
+    """bsdf.h:193-252"""
+    wo: torch.Tensor            # (N,3) local frame
+    pdf: torch.Tensor
+    eta: torch.Tensor
+    sampled_type: torch.Tensor  # BSDFFlags per lane: a Delta lobe (Null included) or the Smooth lobes of the hemisphere of wo; 0 = invalid
+    sampled_component: Optional[torch.Tensor] = None
+    # the kernel's own flags, for callers that want them without decoding sampled_type: the sampled lobe is discrete; the sample is valid
+    delta: Optional[torch.Tensor] = None
+    valid: Optional[torch.Tensor] = None
+
+
+@dataclass
+class DirectionSample3f:
+    """records.h:20-209: PositionSample3f (p, n, pdf, delta, object) + d, dist.  `object` holds emitter indices (int32, -1 = none),
+    an Emitter handle or None."""
+    p: torch.Tensor
+    n: torch.Tensor
+    d: torch.Tensor = None
+    dist: torch.Tensor = None
+    pdf: torch.Tensor = None
+    delta: torch.Tensor = None
+    object: object = None
+
+    def __init__(self, p=None, n=None, d=None, dist=None, pdf=None, delta=None, object=None):
+        if isinstance(p, SurfaceInteraction3f):
+            # DirectionSample(it, ref) (records.h:168-174): n is the SHADING normal of `it` (PositionSample(si), records.h:92-99); d and
+            # dist come from it.p - ref.p, and lanes where `it` is not valid point along -it.wi (environment emitters)
+            it, ref = p, n
+            diff = it.p - ref.p
+            dist = _dot3(diff, diff).sqrt()
+            d = diff * (1.0 / dist).unsqueeze(1)
+            d = torch.where(it.is_valid().unsqueeze(1), d, -it.wi)
+            self.p, self.n, self.d, self.dist = it.p, it.sh_frame_n, d, dist
+            self.pdf, self.delta, self.object = torch.zeros_like(dist), torch.zeros_like(dist, dtype=torch.bool), object
+            return
+        self.p, self.n, self.d, self.dist, self.pdf, self.delta, self.object = p, n, d, dist, pdf, delta, object
+
+
+def _emitter_lanes(obj, n, dev):
+    """DirectionSample3f.object / an emitter argument -> (n,) int32 emitter indices on `dev`"""
+    if isinstance(obj, Emitter):
+        obj = obj._lanes if obj._lanes is not None else obj._index
+    if obj is None:
+        obj = -1
+    if isinstance(obj, (int, np.integer)):
+        return torch.full((n,), int(obj), dtype=torch.int32, device=dev)
+    t = torch.as_tensor(obj, device=dev).reshape(-1).to(torch.int32).contiguous()
+    if t.shape[0] != n:
+        raise RuntimeError("expected one emitter index per lane (%d), got %d" % (n, t.shape[0]))
+    return t
+
+
+class Shape:
+    """include/mitsuba/render/shape.h: the accessors an integrator uses"""
+
+    def __init__(self, scene, index):
+        self._scene, self._index = scene, int(index)
+
+    def bsdf(self):
+        return BSDF(scene=self._scene, shape=self._index)
+
+    def is_emitter(self):
+        return int(self._scene._operator_tables()["emitter_host"][self._index]) >= 0
+
+    def emitter(self):
+        e = int(self._scene._operator_tables()["emitter_host"][self._index])
+        return Emitter(self._scene, index=e) if e >= 0 else None
+
+
+class Emitter:
+    """include/mitsuba/render/emitter.h: one emitter of a scene (`index`), or a per-lane handle (`lanes`: int32 indices, -1 = none) as
+    SurfaceInteraction3f.emitter returns it."""
+
+    def __init__(self, scene, index=None, lanes=None):
+        self._scene, self._index, self._lanes = scene, (None if index is None else int(index)), lanes
+
+    def is_environment(self):
+        return self._index is not None and self._index == self._scene._environment
+
+    def eval(self, si, active=True):
+        """Emitter::eval(si) (area.cpp:71-76, constant.cpp:53-57, envmap.cpp:132-146): an area emitter gives its radiance where
+        si.wi.z > 0; the environment emitter is looked up along the direction of the ray that made `si` (a hand-made interaction:
+        -si.wi, as the reference); delta emitters and "none" give 0."""
+        scene = self._scene
+        scene._require_rgb("Emitter.eval")
+        dev = torch.device("cuda", scene._device_index)
+        wi = _planes(si.wi, 3, dev)
+        n = wi.shape[1]
+        d = _planes(si._ray_d if getattr(si, "_ray_d", None) is not None else -torch.as_tensor(si.wi, device=dev), 3, dev)
+        index = _emitter_lanes(self, n, dev)
+        act = _mask(active, dev)
+        out = torch.empty((3, n), dtype=torch.float32, device=dev)
+        L.check(L.lib().mtsamd_emitter_eval(scene._handle, n, _ptr(index), _ptr(wi), _ptr(d), _ptr(act), _ptr(out), _stream()))
+        return out.t().contiguous()
+
+
+class BSDF:
+    """include/mitsuba/render/bsdf.h: eval / pdf / sample / flags on device streams.  Three forms share the kernels: the BSDF of one
+    shape (``shape.bsdf()``), a per-lane handle over shape indices (``si.bsdf()``), and a BSDF loaded on its own
+    (``xml.load_string('<bsdf ...>')`` / ``xml.load_dict``), which is backed by a private one-triangle scene so that its record, textures
+    and roughplastic tables go through the one ingestion path."""
+
+    def __init__(self, scene=None, shape=None, lanes=None, plugin=None, device=0, variant="rgb"):
+        self._scene, self._shape, self._lanes = scene, shape, lanes
+        self._plugin, self._device, self._variant = plugin, int(device), variant
+        if plugin is not None:
+            from . import bsdfs as B
+            self._record = B.normalize(plugin)      # constructor-time validation, as the plugin constructors
+            self._shape = 0
+        elif scene is None:
+            raise RuntimeError("BSDF: a scene (with a shape index or per-lane shape indices) or a plugin dictionary is required")
+
+    def record(self):
+        """the normalised plugin parameters (mitsuba2_amd.bsdfs.normalize) of a single BSDF"""
+        if self._plugin is not None:
+            return self._record
+        if self._lanes is not None:
+            raise RuntimeError("BSDF.record(): a per-lane handle has no single record")
+        return self._scene._bsdf_records[int(self._scene._operator_tables()["bsdf"][self._shape])]
+
+    def _backing(self):
+        if self._scene is None:      # a BSDF on its own: one triangle carries it
+            tri = dict(positions=_f32([[0, 0, 0], [1, 0, 0], [0, 1, 0]]), faces=np.array([[0, 1, 2]], dtype=np.uint32), normals=None,
+                       texcoords=_f32([[0, 0], [1, 0], [0, 1]]), bsdf=0, emitter=-1)
+            self._scene = Scene(dict(meshes=[tri], bsdfs=[self._plugin], emitters=[]), device=self._device, variant=self._variant)
+        self._scene._require_rgb("BSDF")
+        return self._scene
+
+    def flags(self):
+        """BSDF::flags(): one flag word, or one per lane for a per-lane handle (0 on lanes without a shape)"""
+        if self._plugin is not None:
+            return bsdf_flags(self._record)
+        tables = self._scene._operator_tables()
+        if self._lanes is None:
+            return int(tables["flags_host"][self._shape])
+        shape = self._lanes.to(torch.int64)
+        valid = (shape >= 0) & (shape < self._scene.shape_count())
+        table = tables["flags"].to(shape.device)
+        return torch.where(valid, table[shape.clamp(0, max(self._scene.shape_count() - 1, 0))], torch.zeros_like(table[:1]))
+
+    def _query(self, ctx, si, active, extra):
+        """the query struct of n rows; returns (struct, tensors kept alive, n, device)"""
+        if not isinstance(ctx, BSDFContext):
+            raise RuntimeError("BSDF: the first argument is a BSDFContext")
+        ctx._check()
+        scene = self._backing()
+        dev = torch.device("cuda", scene._device_index)
+        wi = _planes(si.wi, 3, dev)
+        n = wi.shape[1]
+        uv = _planes(si.uv, 2, dev) if getattr(si, "uv", None) is not None else None      # no uv: zeros (a dummy interaction with just wi)
+        if self._lanes is not None:
+            shape = torch.as_tensor(self._lanes, device=dev).reshape(-1).to(torch.int32).contiguous()
+            if shape.shape[0] != n:
+                raise RuntimeError("BSDF: the per-lane handle has %d lanes, the interaction %d" % (shape.shape[0], n))
+        else:
+            shape = torch.full((n,), int(self._shape), dtype=torch.int32, device=dev)
+        act = _mask(active, dev)
+        planes = [_planes(e, k, dev) for e, k in extra]
+        for pl in planes + ([uv] if uv is not None else []):
+            if pl.shape[1] != n:
+                raise RuntimeError("BSDF: every argument needs one row per lane of the interaction (%d)" % n)
+        rows = [r for pl in planes for r in pl]
+        q = L.BsdfQuery()
+        q.shape, q.wi_x, q.wi_y, q.wi_z = _ptr(shape), _ptr(wi[0]), _ptr(wi[1]), _ptr(wi[2])
+        if uv is not None:
+            q.u, q.v = _ptr(uv[0]), _ptr(uv[1])
+        q.active = _ptr(act)
+        return q, rows, (shape, wi, uv, act, planes), n, dev, scene
+
+    def eval_pdf(self, ctx, si, wo, active=True):
+        """BSDF::eval and BSDF::pdf in one launch -> (value (N,3), pdf (N,))"""
+        q, rows, keep, n, dev, scene = self._query(ctx, si, active, [(wo, 3)])
+        q.wo_x, q.wo_y, q.wo_z = _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2])
+        out = torch.empty((4, n), dtype=torch.float32, device=dev)
+        L.check(L.lib().mtsamd_bsdf_eval_pdf(scene._handle, n, C.byref(q), _ptr(out), _stream()))
+        return out[0:3].t().contiguous(), out[3].clone()
+
+    def eval(self, ctx, si, wo, active=True):
+        """BSDF::eval (bsdf.h:360): the BSDF times the cosine foreshortening factor, (N,3)"""
+        return self.eval_pdf(ctx, si, wo, active)[0]
+
+    def pdf(self, ctx, si, wo, active=True):
+        """BSDF::pdf (bsdf.h:391)"""
+        return self.eval_pdf(ctx, si, wo, active)[1]
+
+    def sample(self, ctx, si, sample1, sample2, active=True):
+        """BSDF::sample (bsdf.h:329) -> (BSDFSample3f, weight (N,3)); an invalid sample has weight 0 and sampled_type 0"""
+        q, rows, keep, n, dev, scene = self._query(ctx, si, active, [(sample1, 1), (sample2, 2)])
+        q.sample1, q.sample2_x, q.sample2_y = _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2])
+        out = torch.empty((10, n), dtype=torch.float32, device=dev)
+        L.check(L.lib().mtsamd_bsdf_sample(scene._handle, n, C.byref(q), _ptr(out), _stream()))
+        wo = out[0:3].t().contiguous()
+        delta, valid = out[5] > 0.5, out[9] > 0.5
+        F = BSDFFlags
+        same = (wo[:, 2] * keep[1][2]) > 0
+        null = (wo == -keep[1].t()).all(dim=1)
+        kind = torch.where(delta, torch.where(same, int(F.DeltaReflection), torch.where(null, int(F.Null), int(F.DeltaTransmission))),
+                           torch.where(same, int(F.DiffuseReflection | F.GlossyReflection), int(F.DiffuseTransmission | F.GlossyTransmission)))
+        kind = torch.where(valid, kind, torch.zeros_like(kind)).to(torch.int32)
+        bs = BSDFSample3f(wo=wo, pdf=out[3].clone(), eta=out[4].clone(), sampled_type=kind, delta=delta, valid=valid)
+        return bs, out[6:9].t().contiguous()
 
 
 # --------------------------------------------------------------------------------------------

@@ -652,9 +652,24 @@ def _make_integrator(spec):
     return {"path": R.PathIntegrator, "direct": R.DirectIntegrator, "depth": R.DepthIntegrator}[spec.get("type", "path")](**args)
 
 
+class BSDFDescription:
+    """A root <bsdf> (or a BSDF plugin dictionary) up to the device upload: the plugin dictionary mitsuba2_amd.bsdfs.normalize takes"""
+
+    def __init__(self, plugin):
+        self.plugin = plugin
+
+
 def _instantiate(ctx, root, base_dir):
+    if root.tag == "bsdf":                           # a BSDF loaded on its own (the reference's load_string('<bsdf .../>'))
+        from . import bsdfs
+        entry = _bsdf_plugin_dict(ctx, root, base_dir)
+        try:
+            bsdfs.normalize(entry)                   # constructor-time validation (unknown plugin, bad parameters)
+        except RuntimeError as e:
+            raise XMLError(str(e))
+        return BSDFDescription(entry)
     if root.tag != "scene":
-        raise XMLError('root element "%s" must be a scene in this backend' % root.tag)
+        raise XMLError('root element "%s" must be a scene or a bsdf in this backend' % root.tag)
     desc = SceneDescription()
     desc.uses_tabulated_spectra = ctx.tabulated
     cache = {}
@@ -750,6 +765,8 @@ def parse_file(path, **params):
 def instantiate(desc, device=0, variant="rgb"):
     """SceneDescription -> render.Scene with its sensors and integrator (needs the HIP library and a GPU)."""
     from . import render as R
+    if isinstance(desc, BSDFDescription):           # no device work here: the BSDF uploads its one-triangle scene on first use
+        return R.BSDF(plugin=desc.plugin, device=device, variant=variant)
     sensors = []
     for s in desc.sensors:
         f = s["film"]
