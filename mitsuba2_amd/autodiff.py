@@ -12,6 +12,7 @@ sample is replayed with the same PCG32 stream and its vertices are swept backwar
 """
 import ctypes as C
 import math
+import weakref
 from contextlib import contextmanager
 
 import numpy as np
@@ -371,7 +372,13 @@ class _Render(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
-_render_counter = {}
+_render_counter = {}      # id(scene) -> number of render() calls so far
+_render_tracked = set()   # ids whose entry is dropped when their scene dies: id() values are reused, and a new scene must start at call 0
+
+
+def _forget_scene(key):
+    _render_counter.pop(key, None)
+    _render_tracked.discard(key)
 
 
 def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, params=None):
@@ -391,6 +398,9 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
             spp = (spp, spp)
     elif isinstance(spp, tuple):
         raise Exception("render(): unbiased=False requires that spp is either an integer or None!")
+    if id(scene) not in _render_tracked:
+        _render_tracked.add(id(scene))
+        weakref.finalize(scene, _forget_scene, id(scene))
     call = _render_counter.get(id(scene), 0)
     _render_counter[id(scene)] = call + 1
     base = sensor.sampler().seed_value() + call * 0xD1B54A32D192ED03

@@ -459,6 +459,16 @@ int upload_scene(mtsamd_scene *s, HostScene &hs) {
     return MTSAMD_OK;
 }
 
+// flat scenes: the frame words of the shading records, which build_flat_records leaves zero, are computed on the device by the
+// functions the path kernels would call per hit (k_flat_frames).  Every upload of flat_recs is followed by this step.
+int flat_frames(mtsamd_scene *s, const HostScene &hs) {
+    if (!MTS_FLAT_FRAMES || !hs.flat || s->n_prims == 0) return MTSAMD_OK;
+    hipError_t err = launch_flat_frames(s->d_flat, s->n_prims, s->d_shapes, hs.tri_uv.empty() ? nullptr : s->d_tri_uv, nullptr);
+    if (err == hipSuccess) err = hipDeviceSynchronize();
+    if (err != hipSuccess) return fail(MTSAMD_ERR_DEVICE, "flat frames: %s", hipGetErrorString(err));
+    return MTSAMD_OK;
+}
+
 // roughplastic: transmittance tables and internal reflectance are integrated on the device (roughplastic.cpp:380-399)
 int roughplastic_tables(mtsamd_scene *s) {
     std::vector<uint32_t> rough;
@@ -571,6 +581,7 @@ int mtsamd_scene_create_with_spectra(const mtsamd_scene_desc *desc, const mtsamd
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->cu_count = prop.multiProcessorCount;
     static_cast<SceneState &>(*s) = std::move(hs.state);
     if (int rc = upload_scene(s.get(), hs)) return rc;
+    if (int rc = flat_frames(s.get(), hs)) return rc;
     if (int rc = roughplastic_tables(s.get())) return rc;
     if (int rc = fill_scene_view(s.get(), hs)) return rc;
     *out = s.release();

@@ -96,7 +96,9 @@ struct SceneView {
     const float *area_pmf, *area_cdf;   // per prim (global index), valid inside emitter ranges
     // "flat" scenes (n_prims <= kFlatMaxPrims): no hierarchy pays off; the whole scene is kept in LDS
     // as 64-byte records in primitive order and every query is a wave-uniform loop over them.
-    //   r0 = (p0.xyz, e1.x) r1 = (e1.y, e1.z, e2.x, e2.y) r2 = (e2.z, p1.xyz) r3 = (p2.xyz, shape bits)
+    //   r0 = (p0.xyz, n.x) r1 = (n.y, n.z, s.x, s.y) r2 = (s.z, p1.xyz) r3 = (p2.xyz, shape bits)
+    // n: the geometric normal; s: the shading frame's s of a shape without vertex normals (zero otherwise).  The host writes zeros
+    // into the six words, k_flat_frames fills them once at scene creation with the device functions fill_si would call per hit;
     // plus 80-byte intersection records for primitive pairs (A = 2k, B = 2k+1), laid out for packed fp32 math:
     //   (p0x.ab, p0y.ab) (p0z.ab, e1x.ab) (e1y.ab, e1z.ab) (e2x.ab, e2y.ab) (e2z.ab, -, -)
     const float4 *flat_recs;
@@ -1025,6 +1027,11 @@ template <bool FLAT> struct Geo {
             p0 = mk3(tp[0], tp[1], tp[2]); p1 = mk3(tp[3], tp[4], tp[5]); p2 = mk3(tp[6], tp[7], tp[8]);
         }
     }
+    // flat scenes: the geometric normal and, for a shape without vertex normals, s of the shading frame (k_flat_frames)
+    MTS_DEV void tri_frame(uint32_t prim, f3 &n, f3 &s) const {
+        const float4 r0 = lds.flat[4u * prim], r1 = lds.flat[4u * prim + 1u], r2 = lds.flat[4u * prim + 2u];
+        n = mk3(r0.w, r1.x, r1.y); s = mk3(r1.z, r1.w, r2.x);
+    }
     MTS_DEV uint32_t prim_shape(uint32_t prim) const {
         return FLAT ? __float_as_uint(lds.flat[4u * prim + 3u].w) : sv.prim_shape[prim];
     }
@@ -1039,28 +1046,23 @@ struct SurfaceInteraction {
     f3 p, n; f2 uv; Frame sh; f3 dp_du, dp_dv, wi; uint32_t shape; DevShape shape_rec;
 };
 
-template <bool FLAT>
-MTS_DEV void fill_si(const Geo<FLAT> &g, f3 ray_d, uint32_t prim, float b1, float b2, SurfaceInteraction &si) {
-    const SceneView &sv = g.sv;
-    f3 p0, p1, p2;
-    g.tri_positions(prim, p0, p1, p2);
-    float b0 = 1.0f - b1 - b2;
-    f3 dp0 = p1 - p0, dp1 = p2 - p0;
-    si.p = (p0 * b0 + p1 * b1) + p2 * b2;
-    f3 n = normalize(cross(dp0, dp1));
-    si.n = n;
-    uint32_t shape = g.prim_shape(prim);
-    si.shape = shape;
-    si.shape_rec = g.shape(shape);
-    uint32_t flags = si.shape_rec.flags;
-    f3 dp_du, dp_dv;
+// What a hit's frame takes from the triangle alone.  fill_si evaluates these per hit; for flat scenes k_flat_frames (kernels.hip)
+// evaluates the very same functions once per primitive at scene creation and keeps n and s in the shading record (MTS_FLAT_FRAMES).
+#ifndef MTS_FLAT_FRAMES
+#define MTS_FLAT_FRAMES 1
+#endif
+MTS_DEV f3 tri_normal(f3 dp0, f3 dp1) { return normalize(cross(dp0, dp1)); }
+// The parameterisation of the triangle at the barycentrics (b0, b1, b2): uv, and dp_du, dp_dv -- an arbitrary basis of the plane, or the
+// texture coordinates' own (flags: the shape's, kShapeHasUV; tri_uv: 6 texture coordinates per primitive, not touched otherwise).  dp_du and dp_dv are constants
+// of the triangle; a caller that wants only them passes any barycentrics and drops uv.
+MTS_DEV void tri_parameterization(f3 n, f3 dp0, f3 dp1, uint32_t flags, const float *tri_uv, uint32_t prim, float b0, float b1, float b2, f2 &uv, f3 &dp_du, f3 &dp_dv) {
     coordinate_system(n, dp_du, dp_dv);
-    si.uv.x = b1; si.uv.y = b2;
+    uv.x = b1; uv.y = b2;
     if (flags & kShapeHasUV) {
-        const float *tu = sv.tri_uv + 6u * prim;
+        const float *tu = tri_uv + 6u * prim;
         f2 uv0 = { tu[0], tu[1] }, uv1 = { tu[2], tu[3] }, uv2 = { tu[4], tu[5] };
-        si.uv.x = (uv0.x * b0 + uv1.x * b1) + uv2.x * b2;
-        si.uv.y = (uv0.y * b0 + uv1.y * b1) + uv2.y * b2;
+        uv.x = (uv0.x * b0 + uv1.x * b1) + uv2.x * b2;
+        uv.y = (uv0.y * b0 + uv1.y * b1) + uv2.y * b2;
         f2 duv0 = { uv1.x - uv0.x, uv1.y - uv0.y }, duv1 = { uv2.x - uv0.x, uv2.y - uv0.y };
         float det = fmaf(duv0.x, duv1.y, -(duv0.y * duv1.x));
         float inv_det = rcp(det);
@@ -1073,15 +1075,47 @@ MTS_DEV void fill_si(const Geo<FLAT> &g, f3 ray_d, uint32_t prim, float b1, floa
                         fmaf(-duv1.x, dp0.z, duv0.x * dp1.z) * inv_det);
         }
     }
+}
+// s of the shading frame: dp_du made orthogonal to the shading normal (Gram-Schmidt)
+MTS_DEV f3 shading_tangent(f3 n, f3 dp_du) {
+    float dd = dot(n, dp_du);
+    return normalize(mk3(fmaf(-n.x, dd, dp_du.x), fmaf(-n.y, dd, dp_du.y), fmaf(-n.z, dd, dp_du.z)));
+}
+
+template <bool FLAT>
+MTS_DEV void fill_si(const Geo<FLAT> &g, f3 ray_d, uint32_t prim, float b1, float b2, SurfaceInteraction &si) {
+    const SceneView &sv = g.sv;
+    f3 p0, p1, p2;
+    g.tri_positions(prim, p0, p1, p2);
+    float b0 = 1.0f - b1 - b2;
+    f3 dp0 = p1 - p0, dp1 = p2 - p0;
+    si.p = (p0 * b0 + p1 * b1) + p2 * b2;
+    constexpr bool kStored = FLAT && MTS_FLAT_FRAMES;      // n and s of the record replace their arithmetic
+    f3 n, s_rec;
+    if constexpr (kStored) g.tri_frame(prim, n, s_rec);
+    else n = tri_normal(dp0, dp1);
+    si.n = n;
+    uint32_t shape = g.prim_shape(prim);
+    si.shape = shape;
+    si.shape_rec = g.shape(shape);
+    uint32_t flags = si.shape_rec.flags;
+    // only the ray queries, the AOVs and the adjoint recorders read dp_du / dp_dv; with stored frames a kernel that does not drops their arithmetic
+    f3 dp_du, dp_dv;
+    tri_parameterization(n, dp0, dp1, flags, sv.tri_uv, prim, b0, b1, b2, si.uv, dp_du, dp_dv);
     if (flags & kShapeHasNormals) {
         const float *tn = sv.tri_nrm + 9u * prim;
         f3 n0 = mk3(tn[0], tn[1], tn[2]), n1 = mk3(tn[3], tn[4], tn[5]), n2 = mk3(tn[6], tn[7], tn[8]);
         n = normalize((n0 * b0 + n1 * b1) + n2 * b2);
+        if constexpr (kStored) {       // all that is left of the per-hit frame arithmetic sits in this branch: a wave without such a lane skips it
+            f2 uv; f3 du, dv;
+            tri_parameterization(si.n, dp0, dp1, flags, sv.tri_uv, prim, b0, b1, b2, uv, du, dv);
+            s_rec = shading_tangent(n, du);
+        }
     }
     si.sh.n = n;
     si.dp_du = dp_du; si.dp_dv = dp_dv;
-    float dd = dot(n, dp_du);
-    si.sh.s = normalize(mk3(fmaf(-n.x, dd, dp_du.x), fmaf(-n.y, dd, dp_du.y), fmaf(-n.z, dd, dp_du.z)));
+    if constexpr (kStored) si.sh.s = s_rec;
+    else si.sh.s = shading_tangent(n, dp_du);
     si.sh.t = cross(n, si.sh.s);
     si.wi = to_local(si.sh, -ray_d);
 }
@@ -1187,8 +1221,11 @@ MTS_DEV void sample_emitter_direction(const Geo<FLAT> &g, f3 ref_p, f2 sample, D
         f3 n0 = mk3(tn[0], tn[1], tn[2]), n1 = mk3(tn[3], tn[4], tn[5]), n2 = mk3(tn[6], tn[7], tn[8]);
         float b0 = 1.0f - b.x - b.y;
         ds.n = normalize((n0 * b0 + n1 * b.x) + n2 * b.y);
+    } else if constexpr (FLAT && MTS_FLAT_FRAMES) {
+        f3 s;
+        g.tri_frame(prim, ds.n, s);
     } else {
-        ds.n = normalize(cross(e0, e1));
+        ds.n = tri_normal(e0, e1);
     }
     // Shape::sample_direction
     ds.d = ds.p - ref_p;

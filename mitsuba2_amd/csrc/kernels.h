@@ -263,6 +263,7 @@ hipError_t launch_moment_pack(const float *values5, const float *squares5, float
 // roughplastic: fills the 64-entry external transmittance table of bsdfs[index] and its internal diffuse reflectance
 // (DevBsdf::eb).  gl = Gauss-Legendre nodes / weights: [nodes_t(128) | weights_t(128) | nodes_r(128) | weights_r(128)]
 hipError_t launch_roughplastic_tables(DevBsdf *bsdfs, uint32_t index, float *table, const float *gl, int res_t, int res_r, hipStream_t s);
+hipError_t launch_flat_frames(float4 *flat, uint32_t n_prims, const DevShape *shapes, const float *tri_uv, hipStream_t s);
 hipError_t launch_film_develop(const float *xyzaw, uint64_t n, float *rgba, hipStream_t s);
 hipError_t launch_libm_eval(int fn, uint64_t n, const float *x, const float *y, float *out, hipStream_t s);
 hipError_t launch_spectrum_eval(const DevSpectrum *headers, const float *data, uint64_t n, const float *lambda, float *out, hipStream_t s);

@@ -3548,6 +3548,34 @@ hipError_t launch_roughplastic_tables(DevBsdf *bsdfs, uint32_t index, float *tab
     return hipGetLastError();
 }
 
+// Flat scenes: the frame words of the shading records (device_scene.h), one thread per primitive, by the functions fill_si calls per
+// hit on every other scene.  n for every primitive; s only where the shape has no vertex normals (the others interpolate per hit).
+__global__ __launch_bounds__(kBlock) void k_flat_frames(float4 *flat, uint32_t n_prims, const DevShape *shapes, const float *tri_uv) {
+    const uint32_t prim = blockIdx.x * (uint32_t) kBlock + threadIdx.x;
+    if (prim >= n_prims) return;
+    float4 r0 = flat[4u * prim], r2 = flat[4u * prim + 2u];
+    const float4 r3 = flat[4u * prim + 3u];
+    const f3 p0 = mk3(r0.x, r0.y, r0.z), p1 = mk3(r2.y, r2.z, r2.w), p2 = mk3(r3.x, r3.y, r3.z);
+    const uint32_t flags = shapes[__float_as_uint(r3.w)].flags;
+    const f3 dp0 = p1 - p0, dp1 = p2 - p0;
+    const f3 n = tri_normal(dp0, dp1);
+    f3 s = mk3(0.0f, 0.0f, 0.0f);
+    if (!(flags & kShapeHasNormals)) {
+        f2 uv; f3 dp_du, dp_dv;
+        tri_parameterization(n, dp0, dp1, flags, tri_uv, prim, 1.0f, 0.0f, 0.0f, uv, dp_du, dp_dv);
+        s = shading_tangent(n, dp_du);
+    }
+    r0.w = n.x; r2.x = s.z;
+    flat[4u * prim] = r0;
+    flat[4u * prim + 1u] = make_float4(n.y, n.z, s.x, s.y);
+    flat[4u * prim + 2u] = r2;
+}
+hipError_t launch_flat_frames(float4 *flat, uint32_t n_prims, const DevShape *shapes, const float *tri_uv, hipStream_t s) {
+    if (n_prims == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_flat_frames, dim3((n_prims + (uint32_t) kBlock - 1u) / (uint32_t) kBlock), dim3(kBlock), 0, s, flat, n_prims, shapes, tri_uv);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(kBlock) void k_square_stream(float4 *rgba, uint64_t n) {
     const uint64_t i = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;

@@ -606,9 +606,10 @@ void build_flat_records(const BuildOptions &opt, HostScene &hs) {
     for (uint32_t gp = 0; flat && gp < n_prims; ++gp) {
         const float *tp = &tri_pos[9 * (size_t) gp];
         uint32_t sh = hs.prim_shape[gp]; float shf; std::memcpy(&shf, &sh, 4);
-        hs.flat_recs[4 * gp + 0] = make_float4(tp[0], tp[1], tp[2], tp[3] - tp[0]);
-        hs.flat_recs[4 * gp + 1] = make_float4(tp[4] - tp[1], tp[5] - tp[2], tp[6] - tp[0], tp[7] - tp[1]);
-        hs.flat_recs[4 * gp + 2] = make_float4(tp[8] - tp[2], tp[3], tp[4], tp[5]);
+        // r0.w, r1 and r2.x: the per-triangle frame (n, s), computed on the device at scene creation; zero here
+        hs.flat_recs[4 * gp + 0] = make_float4(tp[0], tp[1], tp[2], 0.0f);
+        hs.flat_recs[4 * gp + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        hs.flat_recs[4 * gp + 2] = make_float4(0.0f, tp[3], tp[4], tp[5]);
         hs.flat_recs[4 * gp + 3] = make_float4(tp[6], tp[7], tp[8], shf);
     }
     const uint32_t n_pairs = hs.n_pairs = flat ? (n_prims + 1) / 2 : 0;
