@@ -1,7 +1,7 @@
 // api.cpp -- host side of libmtsamd: scene upload, BVH build, emitter tables, sensor/film setup,
 // the wavefront scheduler and the C ABI declared in include/mtsamd.h.  The two host-only halves live beside it: scene_build.{h,cpp}
-// computes what is uploaded, schedule.{h,cpp} plans jobs, passes, the pool drain and the film passes; this file carries them out on
-// the device (allocations, streams, events, copies, launches).
+// computes what is uploaded, schedule.{h,cpp} plans jobs, passes, the pool drain, the film passes and their splats; this file carries
+// them out on the device (allocations, streams, events, copies, launches).
 //
 // Reference call stack this replaces:
 //   Scene::Scene -> accel_init -> ShapeKDTree::build          src/librender/scene.cpp:22-98
@@ -866,6 +866,8 @@ static int ensure_workspace(mtsamd_scene *s, uint32_t n_waves, uint32_t seg_cap,
         if (!w.chain_any[k]) HIP_TRY(hipStreamCreateWithFlags(&w.chain_any[k], hipStreamNonBlocking));
     }
     for (auto &pe : w.chain_ev) if (!pe) HIP_TRY(hipEventCreateWithFlags(&pe, hipEventDisableTiming));
+    if (!w.film_stream) HIP_TRY(hipStreamCreateWithFlags(&w.film_stream, hipStreamNonBlocking));      // renders of several passes: the splat of a pass ...
+    for (auto &e : w.film_done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));      // ... beside the tracing of the next
     for (auto &e : w.tev) HIP_TRY(hipEventCreate(&e));
     w.have_events = true;
     w.n_waves = n_waves; w.seg_cap = seg_cap; w.pass_cap = pass_cap; w.spectral = s->spectral; w.split = split;
@@ -873,6 +875,9 @@ static int ensure_workspace(mtsamd_scene *s, uint32_t n_waves, uint32_t seg_cap,
     return 0;
 }
 
+} // extern "C"
+
+// ---- render jobs: C++ (templates, an anonymous namespace); the C ABI resumes at mtsamd_render ----
 namespace {
 struct Job {
     mtsamd_scene *s; const mtsamd_render_desc *d; hipStream_t stream;
@@ -883,6 +888,14 @@ struct Job {
     RowMap rows{};
     int store_xyz = 1;
     uint32_t plane_pix0 = 0, plane_pixels = 0;
+    // film renders (open_render): samples of one local row, the local sample ordinals [0, total) of the call, its passes of whole rows
+    uint64_t per_row = 0, total = 0; FilmPasses fp{};
+    struct Pass { uint64_t lr0, nrows, a, n; };      // the local rows [lr0, lr0 + nrows) hold the local sample ordinals [a, a + n)
+    Pass pass(uint64_t lr0) {          // the pass that starts at local row lr0; its sample stream is pixel-major from that row's first pixel on
+        const uint64_t nrows = std::min<uint64_t>(fp.rows_per_pass, (uint64_t) rows.local_rows - lr0);
+        plane_pix0 = (uint32_t) (lr0 * (uint64_t) d->crop_width); plane_pixels = 0u;
+        return Pass{ lr0, nrows, lr0 * per_row, nrows * per_row };
+    }
     double stage_ms[3] = { 0.0, 0.0, 0.0 }; uint64_t stage_launches[3] = { 0, 0, 0 };      // desc->profile: k_trace<closest>, k_shade, k_trace<any>
     uint64_t passes = 0;
     int buf = 0;                 // sample stream buffer this pass writes
@@ -895,7 +908,7 @@ struct Job {
 
 // The timed bracket of a pass: `body` issues the pass on j.stream between two events; once the second has completed, the time between
 // them is added to bounce_ms.  A body that fails or stops (rc != 0) leaves the bracket open.
-extern "C++" template <typename F> int timed(Job &j, F &&body) {       // (a template inside the file's extern "C" block)
+template <typename F> int timed(Job &j, F &&body) {
     Workspace &w = j.s->ws;
     HIP_TRY(hipEventRecord(w.tev[0], j.stream));
     if (int rc = body()) return rc;
@@ -1152,13 +1165,9 @@ int collect_stats(Job &j, uint64_t samples, uint64_t *stats_host) {
     stats_host[14] = j.passes; stats_host[15] = j.timed_out ? 1u : 0u;
     return 0;
 }
-} // namespace
-
-// tiled film splat: room for the scratch tiles of a pass (film_partial_floats)
-static int ensure_film_partials(Workspace &w, size_t need) { return grow(w.film_partials, w.film_partial_floats, need); }
 
 // Film rows owned by this call (include/mtsamd.h: row_begin/row_end window, or interleaved tiles).
-static int make_rows(const mtsamd_render_desc *d, RowMap &m) {
+int make_rows(const mtsamd_render_desc *d, RowMap &m) {
     if (d->part_count > 1) {
         if (d->part_index < 0 || d->part_index >= d->part_count || d->part_tile_rows <= 0)
             return fail(MTSAMD_ERR_INVALID, "invalid film partition (index %d of %d, %d rows per tile)", d->part_index, d->part_count, d->part_tile_rows);
@@ -1176,130 +1185,154 @@ static int make_rows(const mtsamd_render_desc *d, RowMap &m) {
     return 0;
 }
 
-int mtsamd_render(mtsamd_scene *s, const mtsamd_render_desc *d, float *film, uint64_t *stats_host, void *stream_) {
-    if (!s || !film) return fail(MTSAMD_ERR_INVALID, "null argument");
-    if (int rc = check_desc(d)) return rc;
+// setup_job for a pass that also holds n_streams float4 per sample in ws.aov_stream (0: a plain render): they count when the pass is
+// sized -- if the device cannot provide them the pass is halved, as setup_job halves it for the sample stream
+int setup_aov_job(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, hipStream_t stream, uint64_t max_pass, uint32_t n_streams) {
+    for (;;) {
+        if (int rc = setup_job(j, s, d, stream, max_pass)) return rc;
+        Workspace &w = s->ws;
+        const int rc = grow(w.aov_stream, w.aov_stream_slots, j.pass_cap * n_streams);
+        if (rc == MTSAMD_ERR_NOMEM && j.pass_cap > (1ull << 22)) { max_pass = j.pass_cap >> 1; continue; }
+        return rc;
+    }
+}
+
+// ---- film renders: what mtsamd_render and mtsamd_render_aov share around their pass loops ---------
+// trace_pass for a pass loop: false ends the loop -- a timeout inside the pass drops its samples, an error is left in rc_loop
+bool trace_rows(Job &j, const Job::Pass &p, int &rc_loop) { const int rc = trace_pass(j, p.a, p.n); if (rc < 0) rc_loop = rc; return rc == 0; }
+
+int check_call(const mtsamd_scene *s, const mtsamd_render_desc *d, const float *out) {          // of a call that renders `d` on `s` into `out`
+    if (!s || !out) return fail(MTSAMD_ERR_INVALID, "null argument");
+    return check_desc(d);
+}
+
+// The opening of a film render once its arguments are checked: the device, the rows the call owns, the job (with aov_streams float4 per
+// sample beside the sample stream) and its film passes.
+int open_render(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, hipStream_t stream, uint32_t aov_streams, int store_xyz) {
     HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = (hipStream_t) stream_;
     RowMap rows{};
     if (int rc = make_rows(d, rows)) return rc;
-    const uint64_t per_row = (uint64_t) d->crop_width * (uint64_t) d->sample_count;
-    const uint64_t total = per_row * (uint64_t) rows.local_rows;       // local sample ordinals [0, total)
-    Job j;
-    if (int rc = setup_job(j, s, d, stream, total)) return rc;
-    j.rows = rows; j.store_xyz = d->film_rgb ? 2 : 1;
-    const int R = (int) std::ceil(j.filter.radius);
+    j.per_row = (uint64_t) d->crop_width * (uint64_t) d->sample_count;
+    j.total = j.per_row * (uint64_t) rows.local_rows;
+    if (int rc = setup_aov_job(j, s, d, stream, j.total, aov_streams)) return rc;
+    j.rows = rows; j.store_xyz = store_xyz;
     // passes hold whole local rows so that the sample stream can be stored as one plane per sample number
-    FilmPasses fp;
-    if (int rc = plan_film_passes(rows, j.pass_cap, per_row, fp)) return rc;
-    const uint64_t rows_per_pass = fp.rows_per_pass;
-    const int32_t film_tile_h = fp.tile_h;
+    return plan_film_passes(rows, j.pass_cap, j.per_row, j.fp);
+}
+
+// The film stage of a render call (Film::put): the sample streams of whole local rows are splatted into 5-channel films, by the tiled
+// kernels where the filter allows it and by the gather kernel otherwise.  The stage owns that choice, the scratch tiles, the timing events
+// of Workspace::film_ev and the film time; the render calls say which rows, which streams into which films, and on which stream.
+struct FilmStage {
+    Job &j;
+    Workspace &w = j.s->ws;
     const bool tiled = film_tiles_supported(j.filter);
+    const int32_t R = (int32_t) std::ceil(j.filter.radius);
+    size_t brackets = 0;          // begin / end pairs of film_ev in use
+    FilmParams f{}; hipStream_t on = nullptr;      // the open bracket: its rows and its stream
+
+    // scratch tiles for every splat the call can issue (schedule.h, film_reserve_floats), before anything is queued
+    int reserve(bool per_pass) {
+        return tiled ? grow(w.film_partials, w.film_partial_floats, film_reserve_floats(j.fp, j.rows.local_rows, j.d->crop_width, j.d->sample_count, per_pass)) : 0;
+    }
+    // A bracket: begin event | puts of the local rows [lr0, lr0 + nrows), whatever else the caller queues on `st` between them | end event
+    int begin(hipStream_t st, uint64_t lr0, uint64_t nrows, int32_t tile_h) {
+        f = FilmParams{}; f.filter = j.filter; on = st;
+        film_splat_geometry(j.rows, *j.d, R, tiled, lr0, nrows, tile_h, f);
+        if (tiled) {
+            // the only regrow rule; after reserve() it never fires (tests/test_schedule_cpu.py).  An earlier splat may still read the tiles.
+            const size_t need = film_partial_floats(f);
+            if (need > w.film_partial_floats) HIP_TRY(hipStreamSynchronize(st));
+            if (int rc = grow(w.film_partials, w.film_partial_floats, need)) return rc;
+            f.partials = w.film_partials;
+        }
+        for (hipEvent_t e = nullptr; w.film_ev.size() < 2 * (brackets + 1); w.film_ev.push_back(e)) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(w.film_ev[2 * brackets], st));
+        return 0;
+    }
+    int put(const float4 *rgba, const float2 *pos, float *film) {
+        f.out_rgba = rgba; f.out_pos = pos; f.film = film;
+        HIP_TRY(tiled ? launch_film_tiles(f, on) : launch_film_gather(f, on));
+        return 0;
+    }
+    int end() { HIP_TRY(hipEventRecord(w.film_ev[2 * brackets++ + 1], on)); return 0; }
+    // The close of a film render, once every stream it used has been synchronised: stage time, statistics, final sync
+    int close(uint64_t *stats_host) {
+        for (size_t k = 0; k < brackets; ++k) {
+            float fms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&fms, w.film_ev[2 * k], w.film_ev[2 * k + 1]));
+            j.film_ms += fms;
+        }
+        if (int rc = collect_stats(j, j.total, stats_host)) return rc;
+        HIP_TRY(hipStreamSynchronize(j.stream));
+        return MTSAMD_OK;
+    }
+};
+} // namespace
+
+extern "C" {
+int mtsamd_render(mtsamd_scene *s, const mtsamd_render_desc *d, float *film, uint64_t *stats_host, void *stream_) {
+    if (int rc = check_call(s, d, film)) return rc;
+    hipStream_t stream = (hipStream_t) stream_;
+    Job j;
+    if (int rc = open_render(j, s, d, stream, 0, d->film_rgb ? 2 : 1)) return rc;
+    FilmStage fs{ j };
+    Workspace &ws = s->ws;
     // moment integrator: the sample stream is splatted twice (values, then squared values) into two scratch films
     float *film_target = film, *film_sq = nullptr;
     const uint64_t n_pixels = (uint64_t) d->crop_width * (uint64_t) d->crop_height;
     if (d->moment) {
         if (d->film_rgb) return fail(MTSAMD_ERR_UNSUPPORTED, "the moment integrator writes XYZ channels (film_rgb must be 0)");
-        Workspace &w = s->ws;
-        if (int rc = grow(w.moment_film, w.moment_floats, 2 * 5 * n_pixels)) return rc;
-        HIP_TRY(hipMemsetAsync(w.moment_film, 0, 2 * 5 * n_pixels * sizeof(float), stream));
-        film_target = w.moment_film; film_sq = w.moment_film + 5 * n_pixels;
+        if (int rc = grow(ws.moment_film, ws.moment_floats, 2 * 5 * n_pixels)) return rc;
+        HIP_TRY(hipMemsetAsync(ws.moment_film, 0, 2 * 5 * n_pixels * sizeof(float), stream));
+        film_target = ws.moment_film; film_sq = ws.moment_film + 5 * n_pixels;
     }
     // Several passes: the film splat of pass k runs on its own stream while pass k + 1 is traced into the other sample stream buffer.
-    Workspace &ws = s->ws;
-    bool overlap = fp.n_passes > 1;
+    bool overlap = j.fp.n_passes > 1;
     hipStream_t fstream = stream;
     if (overlap) {
-        const uint64_t cap2 = std::min<uint64_t>(rows_per_pass * per_row, j.pass_cap);
-        const int rc = grow(ws.out_rgba2, ws.out_pos2, ws.pass_cap2, cap2);
+        const int rc = grow(ws.out_rgba2, ws.out_pos2, ws.pass_cap2, std::min<uint64_t>(j.fp.rows_per_pass * j.per_row, j.pass_cap));
         if (rc == MTSAMD_ERR_NOMEM) {          // no room for the second sample stream: the splat of a pass runs before the next pass
             (void) hipFree(ws.out_rgba2); (void) hipFree(ws.out_pos2); ws.out_rgba2 = nullptr; ws.out_pos2 = nullptr;
             overlap = false;
         } else if (rc) return rc;
     }
     if (overlap) {
-        if (!ws.film_stream) HIP_TRY(hipStreamCreateWithFlags(&ws.film_stream, hipStreamNonBlocking));
-        for (auto &e : ws.film_done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         fstream = ws.film_stream;
         // the film (and the moment scratch films) may still be written by work queued on `stream` before this call
         HIP_TRY(hipEventRecord(ws.film_done[0], stream));
         HIP_TRY(hipStreamWaitEvent(fstream, ws.film_done[0], 0));
     }
-    if (tiled) {          // scratch tiles of the largest pass
-        FilmParams f{};
-        f.crop_w = d->crop_width; f.pass_rows = (int32_t) std::min<uint64_t>(rows_per_pass, (uint64_t) rows.local_rows); f.tile_h = film_tile_h;
-        f.spp = d->sample_count;
-        film_tile_grid(f);
-        size_t need = film_partial_floats(f);
-        const uint64_t last_rows = (uint64_t) rows.local_rows % rows_per_pass;      // a shorter last pass has fewer tiles but more sample runs
-        if (last_rows) { f.pass_rows = (int32_t) last_rows; film_tile_grid(f); need = std::max(need, film_partial_floats(f)); }
-        if (int rc = ensure_film_partials(ws, need)) return rc;
-    }
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> film_ev;      // timing of the splats on their stream
+    if (int rc = fs.reserve(true)) return rc;
     int rc_loop = 0;
-    uint64_t pass_index = 0;
-    for (uint64_t lr0 = 0; lr0 < (uint64_t) rows.local_rows; lr0 += rows_per_pass, ++pass_index) {
-        const uint64_t nrows = std::min<uint64_t>(rows_per_pass, (uint64_t) rows.local_rows - lr0);
-        const uint64_t a = lr0 * per_row, n = nrows * per_row;
-        j.plane_pix0 = (uint32_t) (lr0 * (uint64_t) d->crop_width);
-        j.plane_pixels = 0u;          // sample stream: pixel-major
-        j.buf = overlap ? (int) (pass_index & 1u) : 0;
+    for (uint64_t lr0 = 0; lr0 < (uint64_t) j.rows.local_rows; lr0 += j.fp.rows_per_pass) {          // pass k = j.passes: the loop ends with the first pass that is dropped
+        const Job::Pass p = j.pass(lr0);
+        j.buf = overlap ? (int) (j.passes & 1u) : 0;
         if (j.expired()) { j.timed_out = true; break; }
         // the buffer this pass writes was read by the splat of pass k - 2
-        if (overlap && pass_index >= 2) HIP_TRY(hipStreamWaitEvent(stream, ws.film_done[j.buf], 0));
-        if (int rc = trace_pass(j, a, n)) {
-            if (rc > 0) break;               // timeout inside the pass: its samples are dropped
-            rc_loop = rc;
-            break;
-        }
+        if (overlap && j.passes >= 2) HIP_TRY(hipStreamWaitEvent(stream, ws.film_done[j.buf], 0));
+        if (!trace_rows(j, p, rc_loop)) break;
         j.passes += 1;
         // Film::put: splat this pass into the film rows its samples can reach (trace_pass returns when its samples are complete)
-        FilmParams f{};
-        f.out_rgba = j.buf ? ws.out_rgba2 : ws.out_rgba; f.out_pos = j.buf ? ws.out_pos2 : ws.out_pos; f.film = film_target; f.filter = j.filter;
-        f.first_ordinal = a; f.n_samples = n; f.spp = d->sample_count; f.rows = rows;
-        f.plane_pix0 = j.plane_pix0; f.plane_pixels = j.plane_pixels;
-        f.crop_x = d->crop_x; f.crop_y = d->crop_y; f.crop_w = d->crop_width; f.crop_h = d->crop_height;
-        film_row_window(rows, lr0, nrows, R, d->crop_height, f.row0, f.row1);
-        if (tiled) {
-            f.pass_lr0 = (int32_t) lr0; f.pass_rows = (int32_t) nrows; f.tile_h = film_tile_h;
-            film_tile_grid(f);
-            f.partials = ws.film_partials;
-        }
-        if (ws.film_ev.size() < 2 * (film_ev.size() + 1)) {
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            HIP_TRY(hipEventCreate(&e0)); ws.film_ev.push_back(e0);
-            HIP_TRY(hipEventCreate(&e1)); ws.film_ev.push_back(e1);
-        }
-        film_ev.push_back({ ws.film_ev[2 * film_ev.size()], ws.film_ev[2 * film_ev.size() + 1] });
-        HIP_TRY(hipEventRecord(film_ev.back().first, fstream));
-        if (tiled) HIP_TRY(launch_film_tiles(f, fstream));
-        else HIP_TRY(launch_film_gather(f, fstream));
+        float4 *rgba = j.buf ? ws.out_rgba2 : ws.out_rgba;
+        const float2 *pos = j.buf ? ws.out_pos2 : ws.out_pos;
+        if (int rc = fs.begin(fstream, p.lr0, p.nrows, j.fp.tile_h)) return rc;
+        if (int rc = fs.put(rgba, pos, film_target)) return rc;
         if (film_sq) {
-            HIP_TRY(launch_square_stream(const_cast<float4 *>(f.out_rgba), n, fstream));
-            f.film = film_sq;
-            if (tiled) HIP_TRY(launch_film_tiles(f, fstream));
-            else HIP_TRY(launch_film_gather(f, fstream));
+            HIP_TRY(launch_square_stream(rgba, p.n, fstream));
+            if (int rc = fs.put(rgba, pos, film_sq)) return rc;
         }
-        HIP_TRY(hipEventRecord(film_ev.back().second, fstream));
+        if (int rc = fs.end()) return rc;
         if (overlap) HIP_TRY(hipEventRecord(ws.film_done[j.buf], fstream));
     }
     if (overlap) {          // `stream` continues after the last splat
         HIP_TRY(hipEventRecord(ws.film_done[0], fstream));
         HIP_TRY(hipStreamWaitEvent(stream, ws.film_done[0], 0));
         HIP_TRY(hipStreamSynchronize(fstream));
-    } else {
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
+    } else HIP_TRY(hipStreamSynchronize(stream));
     if (rc_loop) return rc_loop;
-    for (auto &e : film_ev) {
-        float fms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&fms, e.first, e.second));
-        j.film_ms += fms;
-    }
     if (film_sq) HIP_TRY(launch_moment_pack(film_target, film_sq, film, n_pixels, stream));
-    if (int rc = collect_stats(j, total, stats_host)) return rc;
-    HIP_TRY(hipStreamSynchronize(stream));
-    return MTSAMD_OK;
+    return fs.close(stats_host);
 }
 
 // ---- aov integrator (src/integrators/aov.cpp) -------------------------------------------------
@@ -1326,18 +1359,6 @@ static int aov_channels(const int32_t *types, uint32_t n_aovs, AovParams &a) {
     return 0;
 }
 
-// setup_job for a pass that also holds n_streams float4 per sample in ws.aov_stream: they count when the pass is sized -- if the device
-// cannot provide them the pass is halved, as setup_job halves it for the sample stream
-static int setup_aov_job(Job &j, mtsamd_scene *s, const mtsamd_render_desc *d, hipStream_t stream, uint64_t max_pass, uint32_t n_streams) {
-    for (;;) {
-        if (int rc = setup_job(j, s, d, stream, max_pass)) return rc;
-        Workspace &w = s->ws;
-        const int rc = grow(w.aov_stream, w.aov_stream_slots, j.pass_cap * n_streams);
-        if (rc == MTSAMD_ERR_NOMEM && j.pass_cap > (1ull << 22)) { max_pass = j.pass_cap >> 1; continue; }
-        return rc;
-    }
-}
-
 // the part of RenderParams k_aov reads (generate_path, the scene, the statistics); first_ordinal / plane_pix0 are set per pass
 static void aov_render_params(const Job &j, RenderParams &p) {
     p = RenderParams{};
@@ -1351,8 +1372,7 @@ static void aov_render_params(const Job &j, RenderParams &p) {
 
 int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32_t *aov_types, uint32_t n_aovs, int32_t nested, float *film,
                       uint64_t *stats_host, void *stream_) {
-    if (!s || !film) return fail(MTSAMD_ERR_INVALID, "null argument");
-    if (int rc = check_desc(d_)) return rc;
+    if (int rc = check_call(s, d_, film)) return rc;
     if (d_->moment) return fail(MTSAMD_ERR_UNSUPPORTED, "the aov integrator nests path, direct or depth, not moment (desc->moment must be 0)");
     if (d_->film_rgb) return fail(MTSAMD_ERR_UNSUPPORTED, "the aov integrator writes X,Y,Z,A,W and its own R,G,B,A channels (film_rgb must be 0)");
     AovParams ap{};
@@ -1361,25 +1381,13 @@ int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32
     mtsamd_render_desc dd = *d_;
     if (!nested) dd.integrator = 0;       // nothing is traced: the scheduler only sizes the pass
     const mtsamd_render_desc *d = &dd;
-    HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t) stream_;
-    RowMap rows{};
-    if (int rc = make_rows(d, rows)) return rc;
-    const uint64_t per_row = (uint64_t) d->crop_width * (uint64_t) d->sample_count;
-    const uint64_t total = per_row * (uint64_t) rows.local_rows;
     const uint32_t C = ap.n_channels, n_groups = (C + 2u) / 3u, n_films = 1u + n_groups + (nested ? 1u : 0u);
     Job j;
-    if (int rc = setup_aov_job(j, s, d, stream, total, n_groups + (nested ? 1u : 0u))) return rc;
     // the linear-RGB stream drops non-finite samples only, the rule of a film with AOVs (integrator.cpp:249-251); spectral variant: XYZ
-    j.rows = rows; j.store_xyz = s->spectral ? 1 : 2;
+    if (int rc = open_render(j, s, d, stream, n_groups + (nested ? 1u : 0u), s->spectral ? 1 : 2)) return rc;
+    FilmStage fs{ j };
     const int mode = !nested ? 0 : (s->spectral ? 2 : 1);
-    const int R = (int) std::ceil(j.filter.radius);
-    // passes hold whole local rows, cut into source tiles for the film kernel as in mtsamd_render
-    FilmPasses fp;
-    if (int rc = plan_film_passes(rows, j.pass_cap, per_row, fp)) return rc;
-    const uint64_t rows_per_pass = fp.rows_per_pass, n_passes = fp.n_passes;
-    const int32_t film_tile_h = fp.tile_h, tile_h_one = fp.tile_h_one;
-    const bool tiled = film_tiles_supported(j.filter);
     Workspace &ws = s->ws;
     const uint64_t n_pixels = (uint64_t) d->crop_width * (uint64_t) d->crop_height;
     // one scratch 5-channel film per stream: X,Y,Z,A,W | the channel groups | R,G,B,A (k_aov_pack interleaves them)
@@ -1394,104 +1402,61 @@ int mtsamd_render_aov(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32
     // to be free: if the device cannot provide it the call fails.  Above the limit each pass is splatted before the next is traced, as
     // mtsamd_render does.
     const uint32_t n_kept = n_groups + (nested ? 2u : 1u);          // groups, second colour space, the nested stream
-    const uint64_t keep_slots = total * n_kept + total / 2 + 1;
-    const bool retain = n_passes > 1 && total <= (1ull << 30) && keep_slots * sizeof(float4) <= s->aov_keep_limit;
+    const uint64_t keep_slots = j.total * n_kept + j.total / 2 + 1;
+    const bool retain = j.fp.n_passes > 1 && j.total <= (1ull << 30) && keep_slots * sizeof(float4) <= s->aov_keep_limit;
     struct Keep { Workspace &w; ~Keep() { (void) hipFree(w.aov_keep); w.aov_keep = nullptr; } } keep{ ws };
+    // the scratch tiles first: they must not fail after the kept streams took the memory
+    if (int rc = fs.reserve(!retain)) return rc;
     if (retain) {
-        if (tiled) {          // the scratch tiles of the one splat first: they must not fail after the streams took the memory
-            FilmParams f{};
-            f.crop_w = d->crop_width; f.pass_rows = rows.local_rows; f.tile_h = tile_h_one; f.spp = d->sample_count;
-            film_tile_grid(f);
-            if (int rc = ensure_film_partials(ws, film_partial_floats(f))) return rc;
-        }
         (void) hipFree(ws.aov_keep); ws.aov_keep = nullptr;
         if (int rc = ws_alloc((void **) &ws.aov_keep, keep_slots * sizeof(float4))) return rc;
     }
     float4 *groups = retain ? ws.aov_keep : ws.aov_stream;
-    const uint64_t stride = retain ? total : j.pass_cap;            // slots per stream
+    const uint64_t stride = retain ? j.total : j.pass_cap;            // slots per stream
     float4 *conv = nested ? groups + (size_t) n_groups * stride : nullptr;
     float4 *strm = retain ? groups + (size_t) (n_kept - 1u) * stride : ws.out_rgba;
     float2 *spos = retain ? reinterpret_cast<float2 *>(groups + (size_t) n_kept * stride) : ws.out_pos;
     aov_render_params(j, ap.rp);
     ap.group_stride = stride;
-    size_t film_events = 0;
-    // Film::put of the streams of the local rows [lr0, lr0 + nrows), held from slot `off` on, into their scratch films
-    auto splat = [&](uint64_t lr0, uint64_t nrows, uint64_t off, int32_t tile_h) -> int {
-        FilmParams f{};
-        f.out_pos = spos + off; f.filter = j.filter;
-        f.first_ordinal = lr0 * per_row; f.n_samples = nrows * per_row; f.spp = d->sample_count; f.rows = rows;
-        f.plane_pix0 = (uint32_t) (lr0 * (uint64_t) d->crop_width); f.plane_pixels = 0u;
-        f.crop_x = d->crop_x; f.crop_y = d->crop_y; f.crop_w = d->crop_width; f.crop_h = d->crop_height;
-        film_row_window(rows, lr0, nrows, R, d->crop_height, f.row0, f.row1);
-        if (tiled) {
-            f.pass_lr0 = (int32_t) lr0; f.pass_rows = (int32_t) nrows; f.tile_h = tile_h;
-            film_tile_grid(f);
-            const size_t need = film_partial_floats(f);
-            if (need > ws.film_partial_floats) HIP_TRY(hipStreamSynchronize(stream));               // an earlier splat may still read the scratch tiles
-            if (int rc = ensure_film_partials(ws, need)) return rc;
-            f.partials = ws.film_partials;
-        }
-        while (ws.film_ev.size() < 2 * (film_events + 1)) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e)); ws.film_ev.push_back(e);
-        }
-        HIP_TRY(hipEventRecord(ws.film_ev[2 * film_events], stream));
-        for (uint32_t k = 0; k < n_films; ++k) {
-            if (k == 0) f.out_rgba = (mode == 1 ? conv : strm) + off;                // X, Y, Z, A
-            else if (k <= n_groups) f.out_rgba = groups + (size_t) (k - 1u) * stride + off;
-            else f.out_rgba = (mode == 1 ? strm : conv) + off;                       // R, G, B, A
-            f.film = ws.aov_film + (size_t) k * 5 * n_pixels;
-            if (tiled) HIP_TRY(launch_film_tiles(f, stream));
-            else HIP_TRY(launch_film_gather(f, stream));
-        }
-        HIP_TRY(hipEventRecord(ws.film_ev[2 * film_events + 1], stream));
-        ++film_events;
-        return 0;
+    // Film::put of the streams of the local rows [lr0, lr0 + nrows), held from slot 0 on, into their scratch films
+    auto splat = [&](uint64_t lr0, uint64_t nrows, int32_t tile_h) -> int {
+        if (int rc = fs.begin(stream, lr0, nrows, tile_h)) return rc;
+        if (int rc = fs.put(mode == 1 ? conv : strm, spos, ws.aov_film)) return rc;                       // X, Y, Z, A
+        for (uint32_t k = 0; k < n_groups; ++k) { if (int rc = fs.put(groups + (size_t) k * stride, spos, ws.aov_film + (size_t) (1u + k) * 5 * n_pixels)) return rc; }
+        if (nested) { if (int rc = fs.put(mode == 1 ? strm : conv, spos, ws.aov_film + (size_t) (1u + n_groups) * 5 * n_pixels)) return rc; }      // R, G, B, A
+        return fs.end();
     };
     int rc_loop = 0;
     uint64_t rows_done = 0;
-    for (uint64_t lr0 = 0; lr0 < (uint64_t) rows.local_rows; lr0 += rows_per_pass) {
-        const uint64_t nrows = std::min<uint64_t>(rows_per_pass, (uint64_t) rows.local_rows - lr0);
-        const uint64_t a = lr0 * per_row, n = nrows * per_row, off = retain ? a : 0;
-        j.plane_pix0 = (uint32_t) (lr0 * (uint64_t) d->crop_width);
-        j.plane_pixels = 0u;          // sample stream: pixel-major
+    for (uint64_t lr0 = 0; lr0 < (uint64_t) j.rows.local_rows; lr0 += j.fp.rows_per_pass) {
+        const Job::Pass p = j.pass(lr0);
+        const uint64_t off = retain ? p.a : 0;
         j.buf = 0;
         if (s->cancel.load(std::memory_order_relaxed)) { rc_loop = fail(MTSAMD_ERR_CANCELLED, "render cancelled"); break; }
         if (j.expired()) { j.timed_out = true; break; }
         if (nested) {
-            if (int rc = trace_pass(j, a, n)) {
-                if (rc > 0) break;               // timeout inside the pass: its samples are dropped
-                rc_loop = rc;
-                break;
-            }
-            if (retain) HIP_TRY(hipMemcpyAsync(strm + off, ws.out_rgba, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            if (!trace_rows(j, p, rc_loop)) break;
+            if (retain) HIP_TRY(hipMemcpyAsync(strm + off, ws.out_rgba, p.n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
         }
         j.passes += 1;
-        ap.rp.first_ordinal = a; ap.rp.plane_pix0 = j.plane_pix0; ap.rp.plane_pixels = 0u;
+        ap.rp.first_ordinal = p.a; ap.rp.plane_pix0 = j.plane_pix0; ap.rp.plane_pixels = 0u;
         ap.rp.out_pos = spos + off; ap.groups = groups + off;
         HIP_TRY(hipEventRecord(ws.tev[0], stream));
-        HIP_TRY(launch_aov(ap, n, stream));
+        HIP_TRY(launch_aov(ap, p.n, stream));
         HIP_TRY(hipEventRecord(ws.tev[1], stream));
-        HIP_TRY(launch_aov_finish(strm + off, conv ? conv + off : nullptr, groups + off, stride, n_groups, mode, n, stream));
-        if (!retain) { if (int rc = splat(lr0, nrows, 0, film_tile_h)) return rc; }
+        HIP_TRY(launch_aov_finish(strm + off, conv ? conv + off : nullptr, groups + off, stride, n_groups, mode, p.n, stream));
+        if (!retain) { if (int rc = splat(p.lr0, p.nrows, j.fp.tile_h)) return rc; }
         HIP_TRY(hipEventSynchronize(ws.tev[1]));
         float ms = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms, ws.tev[0], ws.tev[1]));
         j.bounce_ms += ms; j.iterations += 1;
-        rows_done = lr0 + nrows;
+        rows_done = p.lr0 + p.nrows;
     }
-    if (retain && rows_done > 0 && !rc_loop) { if (int rc = splat(0, rows_done, 0, tile_h_one)) return rc; }
+    if (retain && rows_done > 0 && !rc_loop) { if (int rc = splat(0, rows_done, j.fp.tile_h_one)) return rc; }
     HIP_TRY(hipStreamSynchronize(stream));
     if (rc_loop) return rc_loop;
-    for (size_t k = 0; k < film_events; ++k) {
-        float fms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&fms, ws.film_ev[2 * k], ws.film_ev[2 * k + 1]));
-        j.film_ms += fms;
-    }
     HIP_TRY(launch_aov_pack(ws.aov_film, n_pixels, C, nested ? 1 : 0, film, stream));
-    if (int rc = collect_stats(j, total, stats_host)) return rc;
-    HIP_TRY(hipStreamSynchronize(stream));
-    return MTSAMD_OK;
+    return fs.close(stats_host);
 }
 
 int mtsamd_scene_set_aov_keep_limit(mtsamd_scene *s, uint64_t bytes) {
@@ -1502,8 +1467,7 @@ int mtsamd_scene_set_aov_keep_limit(mtsamd_scene *s, uint64_t bytes) {
 
 int mtsamd_sample_aovs(mtsamd_scene *s, const mtsamd_render_desc *d_, const int32_t *aov_types, uint32_t n_aovs, uint64_t first, uint64_t count,
                        float *aovs, float *pos, void *stream_) {
-    if (!s || !aovs) return fail(MTSAMD_ERR_INVALID, "null argument");
-    if (int rc = check_desc(d_)) return rc;
+    if (int rc = check_call(s, d_, aovs)) return rc;
     AovParams ap{};
     if (int rc = aov_channels(aov_types, n_aovs, ap)) return rc;
     if (ap.n_channels == 0) return fail(MTSAMD_ERR_INVALID, "no AOV requested");
@@ -1784,8 +1748,7 @@ int mtsamd_cancel(mtsamd_scene *s) {
 
 int mtsamd_sample_radiance(mtsamd_scene *s, const mtsamd_render_desc *d, uint64_t first, uint64_t count, float *rgba,
                            float *pos, void *stream_) {
-    if (!s || !rgba) return fail(MTSAMD_ERR_INVALID, "null argument");
-    if (int rc = check_desc(d)) return rc;
+    if (int rc = check_call(s, d, rgba)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t) stream_;
     const uint64_t total = (uint64_t) d->crop_width * d->crop_height * (uint64_t) d->sample_count;

@@ -110,6 +110,9 @@ __host__ __device__ inline uint32_t chunk_owner(uint32_t wave, uint32_t n, uint3
     return s_min * chains + extra_before + (i - s_min);
 }
 
+// tiled film splat: source tiles of kFilmTile^2 pixels; scratch tiles of kFilmPartial floats, laid out for the widest supported apron (R = 2)
+constexpr int kFilmTile = 16, kFilmDest = kFilmTile + 4, kFilmPartial = kFilmDest * kFilmDest * 5;
+
 struct FilmParams {
     const float4 *out_rgba;
     const float2 *out_pos;
@@ -221,11 +224,9 @@ hipError_t launch_mega(const RenderParams &p, hipStream_t s);      // small pass
 // CIE x, y, z and D65 tables (95 floats each) -> device; call once before the first spectral launch
 hipError_t upload_spectral_tables(const float *x, const float *y, const float *z, const float *d65);
 hipError_t launch_film_gather(const FilmParams &p, hipStream_t s);
-// tiled variant for filters with <= 4 taps (gaussian stddev 0.5, box, tent): k_film_accum + k_film_merge
+// tiled variant for filters with <= 4 taps (gaussian stddev 0.5, box, tent): k_film_accum + k_film_merge; which filters it takes, its
+// tile grid and the size of `partials` are host arithmetic (schedule.h, film splat)
 hipError_t launch_film_tiles(const FilmParams &p, hipStream_t s);
-bool film_tiles_supported(const FilterView &f);
-void film_tile_grid(FilmParams &p);                 // tiles_x / tiles_y from crop_w / pass_rows
-size_t film_partial_floats(const FilmParams &p);    // size of `partials`
 // mode 0: closest (BVH), 1: closest (brute force)
 hipError_t launch_ray_intersect(const SceneView &sv, uint64_t n, const RayStreams &r, int mode, float *t,
                                 uint32_t *prim, uint32_t *shape, float *u, float *v, float *si26,

@@ -2743,9 +2743,7 @@ __global__ __launch_bounds__(kBlock) void k_film_gather(const FilmParams F) {
 // q - R + k) -- and the threads gather, branch-free and in a fixed order, the (16 + 2R)^2 film pixels the block's samples reach
 // (imageblock.cpp:148-161 as a gather).  The (16 + 2R)^2 x 5 sums go to a scratch tile; k_film_merge adds the <= 4 overlapping
 // tiles of every film pixel in a fixed order.  No atomics: the film is bitwise reproducible.  HBM traffic: 24 B per sample, once.
-constexpr int kFilmTile = 16, kFilmTaps = 5;      // taps per axis seen from the source pixel: 2R+1 <= 5
-constexpr int kFilmDest = kFilmTile + 4;          // scratch tiles are laid out for the widest supported apron (R = 2)
-constexpr int kFilmPartial = kFilmDest * kFilmDest * 5;      // floats per scratch tile
+constexpr int kFilmTaps = 5;      // taps per axis seen from the source pixel: 2R+1 <= 5 (kFilmTile, kFilmDest, kFilmPartial: kernels.h)
 
 // Filter weights of one sample along one axis for the 2R+1 film pixels q-R .. q+R around its source pixel q
 // (block coordinates t = q + border + k - R), exactly as imageblock.cpp:117-147 evaluates them: 0 outside [lo, hi]
@@ -3017,17 +3015,6 @@ __global__ __launch_bounds__(kBlock) void k_film_merge(const FilmParams F) {
     float *dst = F.film + 5u * ((size_t) y * (size_t) F.crop_w + (size_t) x);
 #pragma unroll
     for (int k = 0; k < 5; ++k) dst[k] += acc[k];
-}
-
-bool film_tiles_supported(const FilterView &f) { return f.taps <= 4 && (int) ceilf(f.radius) <= 2; }
-size_t film_partial_floats(const FilmParams &p) { return (size_t) p.slices * (size_t) p.tiles_x * (size_t) p.tiles_y * kFilmPartial; }
-void film_tile_grid(FilmParams &p) {
-    p.tiles_x = (p.crop_w + kFilmTile - 1) / kFilmTile;
-    p.tiles_y = (p.pass_rows + p.tile_h - 1) / p.tile_h;
-    // few tiles with many samples each (a rank's share of a partitioned film, a pass of a large film): cut the samples of a pixel
-    // into runs of >= 64 so that about 2048 workgroups share the stream
-    const int tiles = std::max(p.tiles_x * p.tiles_y, 1);
-    p.slices = std::max(1, std::min({ 2048 / tiles, p.spp / 64, 64 }));
 }
 
 hipError_t launch_film_tiles(const FilmParams &p, hipStream_t s) {

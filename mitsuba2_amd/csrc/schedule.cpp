@@ -2,6 +2,7 @@
 #include "schedule.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace mtsamd {
 
@@ -155,6 +156,41 @@ void film_row_window(const RowMap &rows, uint64_t lr0, uint64_t nrows, int32_t R
     // global rows are monotone in the local row index
     const int32_t g0 = row_to_global(rows, (int32_t) lr0), g1 = row_to_global(rows, (int32_t) (lr0 + nrows - 1));
     row0 = std::max<int32_t>(0, g0 - R); row1 = std::min<int32_t>(crop_h, g1 + R + 1);
+}
+
+bool film_tiles_supported(const FilterView &f) { return f.taps <= 4 && (int) ceilf(f.radius) <= 2; }
+size_t film_partial_floats(const FilmParams &p) { return (size_t) p.slices * (size_t) p.tiles_x * (size_t) p.tiles_y * kFilmPartial; }
+void film_tile_grid(FilmParams &p) {
+    p.tiles_x = (p.crop_w + kFilmTile - 1) / kFilmTile;
+    p.tiles_y = (p.pass_rows + p.tile_h - 1) / p.tile_h;
+    // few tiles with many samples each (a rank's share of a partitioned film, a pass of a large film): cut the samples of a pixel
+    // into runs of >= 64 so that about 2048 workgroups share the stream
+    const int tiles = std::max(p.tiles_x * p.tiles_y, 1);
+    p.slices = std::max(1, std::min({ 2048 / tiles, p.spp / 64, 64 }));
+}
+
+void film_splat_geometry(const RowMap &rows, const mtsamd_render_desc &d, int32_t R, bool tiled, uint64_t lr0, uint64_t nrows, int32_t tile_h, FilmParams &f) {
+    const uint64_t per_row = (uint64_t) d.crop_width * (uint64_t) d.sample_count;
+    f.first_ordinal = lr0 * per_row; f.n_samples = nrows * per_row; f.spp = d.sample_count; f.rows = rows;
+    f.plane_pix0 = (uint32_t) (lr0 * (uint64_t) d.crop_width); f.plane_pixels = 0u;          // sample stream: pixel-major
+    f.crop_x = d.crop_x; f.crop_y = d.crop_y; f.crop_w = d.crop_width; f.crop_h = d.crop_height;
+    film_row_window(rows, lr0, nrows, R, d.crop_height, f.row0, f.row1);
+    if (!tiled) return;
+    f.pass_lr0 = (int32_t) lr0; f.pass_rows = (int32_t) nrows; f.tile_h = tile_h;
+    film_tile_grid(f);
+}
+
+size_t film_reserve_floats(const FilmPasses &fp, int32_t local_rows, int32_t crop_w, int32_t spp, bool per_pass) {
+    const uint64_t all = (uint64_t) local_rows, step = fp.rows_per_pass;
+    FilmParams f{};
+    f.crop_w = crop_w; f.spp = spp; f.tile_h = per_pass ? fp.tile_h : fp.tile_h_one;
+    size_t need = 0;
+    // fewer rows have fewer tiles but may have more sample runs: the largest need is found by evaluation, not at the largest row count
+    auto take = [&](uint64_t nrows) { f.pass_rows = (int32_t) nrows; film_tile_grid(f); need = std::max(need, film_partial_floats(f)); };
+    take(per_pass ? std::min(step, all) : all);
+    if (per_pass) take(all % step);          // the short last pass (no rows: no tiles)
+    else for (uint64_t done = step; done < all; done += step) take(done);
+    return need;
 }
 
 } // namespace mtsamd

@@ -1,5 +1,5 @@
-// schedule.h -- the host-only plan of the wavefront scheduler: everything that decides what a render job, a pass, the drain of a pass and
-// the film passes look like, as plain arithmetic.  Nothing declared here calls the HIP runtime or reads the environment (kernels.h is
+// schedule.h -- the host-only plan of the wavefront scheduler: everything that decides what a render job, a pass, the drain of a pass,
+// the film passes and the splat of their rows (window, tile grid, scratch tiles) look like, as plain arithmetic.  Nothing declared here calls the HIP runtime or reads the environment (kernels.h is
 // included for RowMap, chain_first and chunk_owner, which the kernels share), so every constant of the scheduler is tested on a machine
 // without a GPU (tests/test_schedule_cpu.py); api.cpp carries the plan out: events, stream waits, copies, launches.
 #pragma once
@@ -94,5 +94,17 @@ struct FilmPasses {
 int plan_film_passes(const RowMap &rows, uint64_t pass_cap, uint64_t per_row, FilmPasses &fp);
 // target (global) film rows [row0, row1) that the samples of the local rows [lr0, lr0 + nrows) reach through a filter of radius R
 void film_row_window(const RowMap &rows, uint64_t lr0, uint64_t nrows, int32_t R, int32_t crop_h, int32_t &row0, int32_t &row1);
+
+// ---- film splat ---------------------------------------------------------------------------------------------------------------
+// Film::put of the local rows [lr0, lr0 + nrows) (api.cpp, FilmStage): launch_film_tiles for the filters it takes, else launch_film_gather.
+bool film_tiles_supported(const FilterView &f);
+void film_tile_grid(FilmParams &p);                 // tiles_x / tiles_y / slices from crop_w / pass_rows / tile_h / spp
+size_t film_partial_floats(const FilmParams &p);    // size of `partials`
+// Every geometry field of `f` for those rows of a render of `d` through a filter of radius R: ordinals, plane layout, crop, target row window
+// and -- tiled, source tiles of tile_h rows -- the tile grid.  Left to the caller: the streams, the film, the filter and `partials`.
+void film_splat_geometry(const RowMap &rows, const mtsamd_render_desc &d, int32_t R, bool tiled, uint64_t lr0, uint64_t nrows, int32_t tile_h, FilmParams &f);
+// Scratch-tile floats a render reserves: the most any of its splats needs.  per_pass: every pass on its own (tile_h); otherwise one
+// splat of the rows [0, rows_done) with tile_h_one, rows_done being any multiple of rows_per_pass a timeout can leave, or local_rows.
+size_t film_reserve_floats(const FilmPasses &fp, int32_t local_rows, int32_t crop_w, int32_t spp, bool per_pass);
 
 } // namespace mtsamd

@@ -1,6 +1,7 @@
 // schedule_driver.cpp -- stand-alone host program around mitsuba2_amd/csrc/schedule.{h,cpp} for tests/test_schedule_cpu.py: reads cases
 // (one per line: a kind, a name, key=value fields), prints what the plan gives as `name key=value ...` lines.  It holds no expectation
-// of its own except the two brute-force walks the Python file cannot afford: every sample of a pass exactly once, and the row window.
+// of its own except the brute-force walks the Python file cannot afford: every sample of a pass exactly once, the row window, and the
+// tile grid of a splat over the source pixels of its rows.
 #include "schedule.h"
 
 #include <algorithm>
@@ -76,6 +77,25 @@ static std::string walk(const PassPlan &p, uint32_t nw, const std::vector<uint64
     return "";
 }
 
+// k_film_accum's thread-to-pixel map (kernels.hip): "" if the kFilmTile x kFilmTile threads of the tiles_x * tiles_y workgroups take every
+// source pixel of the splat's rows exactly once and the rows of every tile are contiguous on the film
+static std::string tile_walk(const FilmParams &f) {
+    std::vector<uint8_t> seen((size_t) f.pass_rows * f.crop_w, 0);
+    char msg[128];
+    for (int tcy = 0; tcy < f.tiles_y; ++tcy)
+        for (int tcx = 0; tcx < f.tiles_x; ++tcx)
+            for (int ly = 0; ly < kFilmTile; ++ly)
+                for (int lx = 0; lx < kFilmTile; ++lx) {
+                    const int qx = tcx * kFilmTile + lx, lr = f.pass_lr0 + tcy * f.tile_h + ly;
+                    if (!(qx < f.crop_w && ly < f.tile_h && lr < f.pass_lr0 + f.pass_rows)) continue;
+                    if (seen[(size_t) (lr - f.pass_lr0) * f.crop_w + qx]++) { std::snprintf(msg, sizeof(msg), "row_%d_column_%d_twice", lr, qx); return msg; }
+                    if (ly > 0 && row_to_global(f.rows, lr) != row_to_global(f.rows, lr - 1) + 1) { std::snprintf(msg, sizeof(msg), "tile_row_%d_splits_at_row_%d", tcy, lr); return msg; }
+                }
+    for (size_t i = 0; i < seen.size(); ++i)
+        if (!seen[i]) { std::snprintf(msg, sizeof(msg), "row_%d_column_%d_missed", f.pass_lr0 + (int) (i / f.crop_w), (int) (i % f.crop_w)); return msg; }
+    return "";
+}
+
 static void print_error(int rc) { std::printf(" rc=%d\nmessage %s\n", rc, last_error()); }
 
 int main(int argc, char **argv) {
@@ -114,6 +134,38 @@ int main(int argc, char **argv) {
             }
             print_list("passes", lr.data(), lr.size()); print_list("window", window.data(), window.size()); print_list("brute", brute.data(), brute.size());
             std::printf("\n");
+            continue;
+        }
+        if (kind == "splat") {
+            // the splats of a film render (api.cpp, FilmStage): one `pass` line per pass splatted on its own, one `once` line per row count
+            // [0, rows_done) the kept-stream aov path can splat, and the scratch tiles reserved for either
+            const RowMap rows{ (int32_t) get(a, "row0"), (int32_t) get(a, "local_rows"), (int32_t) get(a, "tile_rows"), (int32_t) get(a, "part"), (int32_t) get(a, "count", 1) };
+            mtsamd_render_desc d{};
+            d.crop_x = (int32_t) get(a, "crop_x"); d.crop_y = (int32_t) get(a, "crop_y"); d.crop_width = (int32_t) get(a, "crop_w"); d.crop_height = (int32_t) get(a, "crop_h");
+            d.sample_count = (int32_t) get(a, "spp");
+            const int32_t R = (int32_t) get(a, "R");
+            const uint64_t per_row = (uint64_t) d.crop_width * (uint64_t) d.sample_count, all = (uint64_t) rows.local_rows;
+            FilmPasses fp;
+            if (int rc = plan_film_passes(rows, (uint64_t) get(a, "pass_cap"), per_row, fp)) { print_error(rc); continue; }
+            std::printf(" rc=0 rows_per_pass=%llu n_passes=%llu tile_h=%d tile_h_one=%d reserve_pass=%zu reserve_once=%zu floats_per_tile=%d\n", (unsigned long long) fp.rows_per_pass,
+                        (unsigned long long) fp.n_passes, fp.tile_h, fp.tile_h_one, film_reserve_floats(fp, rows.local_rows, d.crop_width, d.sample_count, true),
+                        film_reserve_floats(fp, rows.local_rows, d.crop_width, d.sample_count, false), kFilmPartial);
+            auto splat = [&](const char *what, uint64_t lr0, uint64_t nrows, int32_t tile_h) {
+                FilmParams f{};
+                film_splat_geometry(rows, d, R, true, lr0, nrows, tile_h, f);
+                int32_t r0, r1;
+                film_row_window(rows, lr0, nrows, R, d.crop_height, r0, r1);
+                const bool same_rows = f.rows.row0 == rows.row0 && f.rows.local_rows == rows.local_rows && f.rows.tile_rows == rows.tile_rows && f.rows.part == rows.part && f.rows.count == rows.count;
+                const std::string w = tile_walk(f);
+                std::printf("%s %s lr0=%llu nrows=%llu first_ordinal=%llu n_samples=%llu spp=%d same_rows=%d plane_pix0=%u plane_pixels=%u crop_x=%d crop_y=%d crop_w=%d crop_h=%d"
+                            " row0=%d row1=%d window0=%d window1=%d pass_lr0=%d pass_rows=%d tile_h=%d tiles_x=%d tiles_y=%d slices=%d need=%zu walk=%s\n", name.c_str(), what,
+                            (unsigned long long) lr0, (unsigned long long) nrows, (unsigned long long) f.first_ordinal, (unsigned long long) f.n_samples, f.spp, same_rows, f.plane_pix0,
+                            f.plane_pixels, f.crop_x, f.crop_y, f.crop_w, f.crop_h, f.row0, f.row1, r0, r1, f.pass_lr0, f.pass_rows, f.tile_h, f.tiles_x, f.tiles_y, f.slices,
+                            film_partial_floats(f), w.empty() ? "ok" : w.c_str());
+            };
+            for (uint64_t lr0 = 0; lr0 < all; lr0 += fp.rows_per_pass) splat("pass", lr0, std::min<uint64_t>(fp.rows_per_pass, all - lr0), fp.tile_h);
+            for (uint64_t done = fp.rows_per_pass; done < all; done += fp.rows_per_pass) splat("once", 0, done, fp.tile_h_one);
+            splat("once", 0, all, fp.tile_h_one);
             continue;
         }
         JobShape js;

@@ -81,9 +81,9 @@ def _oracle_film(sp, pos, vals):
 WORST = [0.0]
 
 
-def _check_film(got, want, S, spp, what):
-    """|got - want| <= K * 2^-23 * S with K = 25 * spp terms (radius-2 filter): the reordering bound of fp32 sums"""
-    bound = 25 * spp * 2.0 ** -23 * S
+def _check_film(got, want, S, spp, what, taps=25):
+    """|got - want| <= K * 2^-23 * S with K = taps * spp terms (25: radius-2 filter, 81: radius 4): the reordering bound of fp32 sums"""
+    bound = taps * spp * 2.0 ** -23 * S
     err = np.abs(got.astype(np.float64) - want)
     ratio = float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.where(err > 0, np.inf, 0))))
     WORST[0] = max(WORST[0], ratio)
@@ -279,6 +279,22 @@ def test_pass_by_pass_splat_above_the_keep_limit():
         pw, _ = _render_raw(plain, scene, sensor)
         assert passes == 3 and torch.equal(film[..., :5], pw) and float(pw[..., :3].max()) > 0
     assert torch.equal(_render_raw(alone, scene, sensor)[0], one)           # back under the default limit
+
+
+def test_pass_by_pass_splat_through_the_gather_kernel():
+    """A gaussian of stddev 1.0 has radius 4: too wide for the tiled film kernels, every splat goes through k_film_gather.  Keep limit 0:
+    three passes of eight rows, each splatted on its own; a film pixel sums up to 81 * spp terms."""
+    from mitsuba2_amd import render as R
+    sp = _sensor_params("sphere_n", 32, 24, 4, rfilter_param=1.0)
+    scene, sensor = _gpu_scene("sphere_n"), R.make_sensor(sp)
+    pos, vals, _ = _expected("sphere_n", sp)
+    want, S = _oracle_film(sp, pos, vals)
+    alone = R.AOVIntegrator(ALL)
+    alone.max_pass_log2 = 10
+    with _keep_limit(scene, 0):
+        film, passes = _render_raw(alone, scene, sensor)
+    assert passes == 3
+    _check_film(film.cpu().numpy(), want, S, 4, "pass by pass, gather kernel", taps=81)
 
 
 def test_rows_add_up_and_renders_are_deterministic():

@@ -7,7 +7,8 @@ program is built a second time with -fsanitize=address,undefined and has to prin
 * the schedule table of mtsamd_render_desc::pipeline / integrator, the clamps of the wave count, the target and the pass limit;
 * direct / mega / launch rounds and their thresholds;
 * the drain state machine on scripted read-backs;
-* film passes and their target row windows."""
+* film passes and their target row windows;
+* the splat of a pass: every geometry field of its FilmParams, the tile grid over its source pixels, the scratch tiles a render reserves."""
 import os
 import shutil
 import subprocess
@@ -53,7 +54,8 @@ def driver(tmp_path_factory):
         assert b.returncode == 0, err
 
     def run(lines):
-        """case lines -> {name: {key: value}}; a drain case also has "cp": the list of its checkpoints"""
+        """case lines -> {name: {key: value}}; a drain case also has "cp": the list of its checkpoints, a splat case "pass" and "once": the
+        lists of its splats"""
         path = str(tmp / "cases.txt")
         with open(path, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -67,10 +69,11 @@ def driver(tmp_path_factory):
                 continue
             words = rest.split()
             rec = {k: _value(v) for k, v in (w.split("=", 1) for w in words if "=" in w)}
-            if words and words[0] == "cp":
-                out[name]["cp"].append(rec)
+            if words and words[0] in ("cp", "pass", "once"):
+                out[name][words[0]].append(rec)
             else:
-                rec["cp"] = []
+                rec.update(cp=[], once=[])
+                rec["pass"] = []
                 out[name] = last = rec
         assert len(out) == len(lines)
         return out
@@ -360,3 +363,87 @@ def test_film_passes(driver):
                 assert th == th1 and rpp == rows_fit - rows_fit % th1, name
         assert rec["window"] == rec["brute"], name          # min / max of row_to_global over the pass, widened by R, clamped to the crop
         assert all(0 <= a < b <= crop_h for a, b in zip(rec["window"][0::2], rec["window"][1::2])), name
+
+
+# ---- film splat ------------------------------------------------------------------------------------------------------------------------------
+FILM_TILE, FLOATS_PER_TILE = 16, 20 * 20 * 5          # source tile width; scratch tile: (16 + 2 * 2)^2 film pixels of 5 channels
+
+
+def splat_case(name, crop_w, local, spp, rows_fit, R=2, partition=None, extra=0):
+    """a render whose passes hold rows_fit local rows (+ `extra` samples); partition = (part, count, tile_rows) or None: rows [3, 3 + local)"""
+    crop_h = local + 5 if partition is None else None
+    if partition is None:
+        rows = dict(row0=3, local_rows=local, tile_rows=crop_h, part=0, count=1)
+    else:
+        part, count, tile_rows = partition
+        crop_h = local           # here `local` is the film height; the call owns its share of it
+        rows = dict(row0=0, local_rows=local_rows(crop_h, tile_rows, part, count), tile_rows=tile_rows, part=part, count=count)
+    fields = dict(crop_x=7, crop_y=2, crop_w=crop_w, crop_h=crop_h, spp=spp, R=R, pass_cap=rows_fit * crop_w * spp + extra, **rows)
+    return case("splat", name, **fields), fields
+
+
+def slices_rule(tiles, spp):
+    """runs of >= 64 samples per pixel so that about 2048 workgroups share the stream, at most 64 of them"""
+    return max(1, min(2048 // max(tiles, 1), spp // 64, 64))
+
+
+SPLATS = [
+    ("short_last_pass", dict(crop_w=96, local=64, spp=16, rows_fit=5, extra=11)),          # 12 passes of 5 rows and one of 4
+    ("one_pass", dict(crop_w=33, local=40, spp=64, rows_fit=1000)),
+    ("one_row_film", dict(crop_w=50, local=1, spp=64, rows_fit=1)),
+    ("one_row_passes", dict(crop_w=17, local=9, spp=1, rows_fit=1, R=4)),
+    ("spp1", dict(crop_w=100, local=70, spp=1, rows_fit=17, R=0)),
+    ("spp64", dict(crop_w=100, local=70, spp=64, rows_fit=32, R=1)),
+    ("spp4096", dict(crop_w=100, local=200, spp=4096, rows_fit=96)),                       # 6 x 7 tiles: 2048 // 42 = 48 slices; last pass 7 tiles: 64
+    ("spp4096_few_tiles", dict(crop_w=16, local=20, spp=4096, rows_fit=7)),                # 1 - 2 tiles: 64 slices
+    # 10 tile rows x 4 tiles take 51 slices (2040 scratch tiles), 8 x 4 take 64 (2048): fewer rows, more scratch
+    ("short_needs_more", dict(crop_w=64, local=288, spp=4096, rows_fit=160)),              # per pass: 160 rows, then 128
+    ("fewer_done_needs_more", dict(crop_w=64, local=160, spp=4096, rows_fit=128)),         # kept streams: [0, 128) against [0, 160)
+] + [("tiles4_%d_%d" % (part, fit), dict(crop_w=40, local=50, spp=spp, rows_fit=fit, partition=(part, 2, 4)))
+     for part, fit, spp in ((0, 3, 1), (1, 8, 64), (0, 9, 4096), (1, 1000, 64))] + \
+    [("tiles32_%d_%d" % (part, fit), dict(crop_w=70, local=200, spp=spp, rows_fit=fit, partition=(part, 3, 32)))
+     for part, fit, spp in ((0, 5, 64), (1, 16, 1), (2, 40, 4096), (0, 1000, 64), (2, 100, 64))]
+
+
+def test_film_splats(driver):
+    lines, meta = zip(*(splat_case(name, **kw) for name, kw in SPLATS))
+    out = driver(list(lines))
+    more = set()
+    for (name, _), f in zip(SPLATS, meta):
+        rec = out[name]
+        per_row, lr_all, rpp = f["crop_w"] * f["spp"], f["local_rows"], rec["rows_per_pass"]
+        assert rec["rc"] == 0 and rec["floats_per_tile"] == FLOATS_PER_TILE, name
+        assert [(s["lr0"], s["nrows"]) for s in rec["pass"]] == [(a, min(rpp, lr_all - a)) for a in range(0, lr_all, rpp)] and len(rec["pass"]) == rec["n_passes"], name
+        assert [(s["lr0"], s["nrows"]) for s in rec["once"]] == [(0, k) for k in range(rpp, lr_all, rpp)] + [(0, lr_all)], name
+        for what, tile_h in (("pass", rec["tile_h"]), ("once", rec["tile_h_one"])):
+            for s in rec[what]:
+                key = (name, what, s["lr0"], s["nrows"])
+                # ordinals and plane layout: the pass holds whole local rows, pixel-major
+                assert (s["first_ordinal"], s["n_samples"], s["spp"]) == (s["lr0"] * per_row, s["nrows"] * per_row, f["spp"]), key
+                assert (s["plane_pix0"], s["plane_pixels"], s["same_rows"]) == (s["lr0"] * f["crop_w"], 0, 1), key
+                assert [s[k] for k in ("crop_x", "crop_y", "crop_w", "crop_h")] == [f[k] for k in ("crop_x", "crop_y", "crop_w", "crop_h")], key
+                assert (s["row0"], s["row1"]) == (s["window0"], s["window1"]) and 0 <= s["row0"] < s["row1"] <= f["crop_h"], key          # film_row_window
+                # the tile grid covers every source pixel of these rows exactly once, with tiles whose rows are contiguous on the film
+                assert (s["pass_lr0"], s["pass_rows"], s["tile_h"]) == (s["lr0"], s["nrows"], tile_h), key
+                assert s["tiles_x"] == -(-f["crop_w"] // FILM_TILE) and s["tiles_y"] == -(-s["nrows"] // tile_h), key
+                assert s["walk"] == "ok", (key, s["walk"])
+                assert s["slices"] == slices_rule(s["tiles_x"] * s["tiles_y"], f["spp"]), key
+                assert s["need"] == s["slices"] * s["tiles_x"] * s["tiles_y"] * FLOATS_PER_TILE, key
+            # the reservation covers every splat and is the largest need: nothing is reserved that no splat can use
+            assert rec["reserve_" + what] == max(s["need"] for s in rec[what]), (name, what)
+            assert all(rec["reserve_" + what] >= s["need"] for s in rec[what]), (name, what)
+            if max(rec[what], key=lambda s: s["nrows"])["need"] < rec["reserve_" + what]:          # the splat of the most rows is not the largest
+                more.add((name, what))
+    # `slices` moves between 1 and 64 with the sample count
+    assert {s["slices"] for s in out["spp1"]["pass"]} == {1} == {s["slices"] for s in out["spp64"]["pass"]}
+    assert {s["slices"] for s in out["spp4096_few_tiles"]["pass"]} == {64} and [s["slices"] for s in out["spp4096"]["pass"]] == [48, 48, 64]
+    assert out["one_row_film"]["pass"][0]["tiles_y"] == 1 and out["one_row_film"]["n_passes"] == 1 and out["one_row_passes"]["n_passes"] == 9
+    assert out["short_last_pass"]["pass"][-1]["nrows"] == 4 and out["short_last_pass"]["n_passes"] == 13
+    assert [out["tiles4_%d_%d" % k]["tile_h"] for k in ((0, 3), (1, 8), (0, 9), (1, 1000))] == [2, 4, 4, 4]
+    assert [out["tiles32_%d_%d" % k]["tile_h"] for k in ((0, 5), (1, 16), (2, 40), (0, 1000), (2, 100))] == [4, 16, 16, 16, 16]
+    # fewer rows can need more scratch than all of them: the full pass against the short last one, [0, 160) against [0, 128)
+    short = out["short_needs_more"]["pass"]
+    assert [(s["nrows"], s["slices"], s["need"] // FLOATS_PER_TILE) for s in short] == [(160, 51, 2040), (128, 64, 2048)]
+    done = out["fewer_done_needs_more"]["once"]
+    assert [(s["nrows"], s["need"] // FLOATS_PER_TILE) for s in done] == [(128, 2048), (160, 2040)]
+    assert {("short_needs_more", "pass"), ("fewer_done_needs_more", "once")} <= more
