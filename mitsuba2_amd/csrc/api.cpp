@@ -526,7 +526,8 @@ int fill_scene_view(mtsamd_scene *s, const HostScene &hs) {
     v.general = s->nested_bsdfs ? 2u : (s->general_bsdfs || s->delta_emitters || s->environment >= 0) ? 1u : 0u;       // the diffuse / area-light fast path (kernels.hip) handles none of these
     v.flat_pairs = s->d_pairs; v.n_pairs = hs.n_pairs; v.n_clusters = hs.n_clusters;
     v.n_spectra = hs.n_spectra;
-    if (bounce_lds_bytes(v) > 150 * 1024) return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", v.stack_depth);
+    // hierarchy scenes only: a flat scene is within kFlatLdsCap in every launch, or build_host_scene would not have kept it flat
+    if (bounce_lds_bytes(v) > kFlatLdsCap) return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", v.stack_depth);
     return MTSAMD_OK;
 }
 

@@ -162,6 +162,17 @@ inline size_t shade_ring_offset(const SceneView &sv, uint32_t block) { return (l
 inline size_t shade_ring_lds_bytes(const SceneView &sv, bool spectral, uint32_t gather_w) {
     return shade_ring_offset(sv, 64u * kShadeWaves) + kShadeWaves * shadow_ring_bytes(spectral) + (gather_w > 4u ? 4u * ((size_t) gather_w + 1u) : 0u);
 }
+// The largest dynamic LDS any launch asks for on a flat scene (sv.flat set; the counts n_prims, n_pairs, n_clusters, n_shapes, n_bsdfs and
+// n_emitters are all it reads).  Every launch that stages a flat scene sizes its LDS by one of three formulas: lds_bytes(sv, 64)
+// (k_mega, k_finish), lds_bytes(sv, 256) (every other kernel) or shade_ring_lds_bytes (k_shade with the ring; gathering launches use
+// gather_w <= 1024).  The tables grow with the BSDF, emitter and shape counts, which the triangle count does not bound, so the builder
+// keeps a scene flat only while this fits kFlatLdsCap (scene_build.cpp); kernels.hip opts every flat launch into its byte count.
+constexpr uint32_t kGatherMax = 1024u;
+constexpr size_t kFlatLdsCap = 150u * 1024u;                 // of the 160 KiB of a CU: room for static LDS
+inline size_t flat_launch_lds_max(const SceneView &sv, bool spectral) {
+    const size_t a = lds_bytes(sv, 64u), b = lds_bytes(sv, 64u * kShadeWaves), c = shade_ring_lds_bytes(sv, spectral, kGatherMax);
+    return a > b ? (a > c ? a : c) : (b > c ? b : c);
+}
 // The headline's k_shade runs 4 workgroups per CU (160 KiB of LDS): the fixed part -- rings, work lists, static LDS (<= 512 B) -- has
 // to leave room for a Cornell-box-sized scene (5.2 KB; 6 KiB here).  A larger MTS_FLAT_WL_ROUNDS fails here instead of silently
 // costing a workgroup per CU (tests/test_shade_lds_cpu.py checks the real Cornell box against the compiler's figures).

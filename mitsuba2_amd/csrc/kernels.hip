@@ -381,6 +381,18 @@ void k_bounce(const RenderParams P) {
 }
 
 size_t bounce_lds_bytes(const SceneView &sv) { return lds_bytes(sv, kBlock); }
+// Dynamic LDS above 48 KiB is something a kernel opts into.  Deep hierarchies ask for that much, and so do flat scenes with large shape,
+// BSDF or emitter tables (kernels.h, flat_launch_lds_max): every launch whose LDS grows with the scene goes through launch_lds, which
+// opts the instantiation it launches into the byte count it passes.
+static hipError_t allow_lds(const void *fn, size_t bytes) {
+    return bytes > 48u * 1024u ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes) : hipSuccess;
+}
+template <typename... P, typename... A>
+static hipError_t launch_lds(void (*fn)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A &&...args) {
+    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(fn), lds)) return e;
+    hipLaunchKernelGGL(fn, grid, block, lds, s, static_cast<P>(args)...);
+    return hipGetLastError();
+}
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1008,14 +1020,14 @@ hipError_t launch_direct(const RenderParams &p, uint64_t n, hipStream_t s) {
     const uint32_t blocks = (uint32_t) ((n + kBlock - 1) / kBlock);
     const size_t lds = bounce_lds_bytes(p.sv);
     if (p.sv.general == 2u) {      // scenes with blendbsdf / mask
-        if (p.sv.flat) hipLaunchKernelGGL((k_direct<true, true, true>), dim3(blocks), dim3(kBlock), lds, s, p, n);
-        else hipLaunchKernelGGL((k_direct<false, true, true>), dim3(blocks), dim3(kBlock), lds, s, p, n);
+        if (p.sv.flat) return launch_lds(k_direct<true, true, true>, dim3(blocks), dim3(kBlock), lds, s, p, n);
+        else return launch_lds(k_direct<false, true, true>, dim3(blocks), dim3(kBlock), lds, s, p, n);
     } else if (p.sv.general) {
-        if (p.sv.flat) hipLaunchKernelGGL((k_direct<true, true>), dim3(blocks), dim3(kBlock), lds, s, p, n);
-        else hipLaunchKernelGGL((k_direct<false, true>), dim3(blocks), dim3(kBlock), lds, s, p, n);
+        if (p.sv.flat) return launch_lds(k_direct<true, true>, dim3(blocks), dim3(kBlock), lds, s, p, n);
+        else return launch_lds(k_direct<false, true>, dim3(blocks), dim3(kBlock), lds, s, p, n);
     } else {
-        if (p.sv.flat) hipLaunchKernelGGL((k_direct<true, false>), dim3(blocks), dim3(kBlock), lds, s, p, n);
-        else hipLaunchKernelGGL((k_direct<false, false>), dim3(blocks), dim3(kBlock), lds, s, p, n);
+        if (p.sv.flat) return launch_lds(k_direct<true, false>, dim3(blocks), dim3(kBlock), lds, s, p, n);
+        else return launch_lds(k_direct<false, false>, dim3(blocks), dim3(kBlock), lds, s, p, n);
     }
     return hipGetLastError();
 }
@@ -1079,7 +1091,6 @@ __global__ __launch_bounds__(kBlock) void k_aov(const AovParams A, uint64_t n) {
     }
 }
 
-static hipError_t allow_lds(const void *fn, size_t bytes);
 hipError_t launch_aov(const AovParams &a, uint64_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t) ((n + kBlock - 1) / kBlock);
@@ -1559,10 +1570,11 @@ template <typename F> static void with_flag(bool v, F &&f) { if (v) f(std::true_
 hipError_t launch_mega(const RenderParams &p, hipStream_t s) {
     const size_t lds = p.sv.flat ? lds_bytes(p.sv, 64u) : sizeof(StackEntry) * (std::min(p.sv.stack_depth, kFinishLdsDepth) + 1u) * 64u;
     const uint32_t blocks = p.n_waves;
+    hipError_t err = hipSuccess;
     with_flag(p.sv.flat != 0u, [&](auto flat) {
-        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_mega<MTS_VARIANT(st, general), decltype(flat)::value>), dim3(blocks), dim3(64), lds, s, p); });
+        with_variant(p, [&](auto st, auto general) { err = launch_lds(k_mega<MTS_VARIANT(st, general), decltype(flat)::value>, dim3(blocks), dim3(64), lds, s, p); });
     });
-    return hipGetLastError();
+    return err;
 }
 
 hipError_t launch_finish(const RenderParams &p, uint64_t alive, hipStream_t s) {
@@ -1571,10 +1583,11 @@ hipError_t launch_finish(const RenderParams &p, uint64_t alive, hipStream_t s) {
     const uint32_t per = std::min((uint32_t) ((p.n_waves + want - 1u) / want), kFinishMaxPer);
     const uint32_t blocks = (p.n_waves + per - 1u) / per;
     const size_t lds = p.sv.flat ? lds_bytes(p.sv, 64u) : sizeof(StackEntry) * (std::min(p.sv.stack_depth, kFinishLdsDepth) + 1u) * 64u;
+    hipError_t err = hipSuccess;
     with_flag(p.sv.flat != 0u, [&](auto flat) {
-        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_finish<MTS_VARIANT(st, general), decltype(flat)::value>), dim3(blocks), dim3(64), lds, s, p, per); });
+        with_variant(p, [&](auto st, auto general) { err = launch_lds(k_finish<MTS_VARIANT(st, general), decltype(flat)::value>, dim3(blocks), dim3(64), lds, s, p, per); });
     });
-    return hipGetLastError();
+    return err;
 }
 
 // k_trace<false>: closest hit of every path's ray (input pool).
@@ -1785,9 +1798,6 @@ size_t trace_spill_words(const SceneView &sv, uint32_t n_waves) {
     const size_t finish = (size_t) n_waves * spill_f * 64u;      // at most one k_finish workgroup per scheduling wave
     return (sizeof(StackEntry) / 4) * std::max(trace, finish);
 }
-static hipError_t allow_lds(const void *fn, size_t bytes) {
-    return bytes > 48u * 1024u ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes) : hipSuccess;
-}
 
 // split pipeline of hierarchy scenes, one stage at a time: 0 = k_trace<closest>, 1 = k_shade, 2 = k_trace<any>.  Stage 2 of one
 // iteration and stage 0 of the next touch disjoint arrays, so the host runs them on two streams (api.cpp).
@@ -1813,15 +1823,17 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
         const uint32_t shade_blocks = p.gather_w > 4u ? (n_launch + p.gather_w - 1u) / p.gather_w : (n_launch * 64u + kBlock - 1) / kBlock;
         p.lds_queue_offset = (uint32_t) (shade_ring_offset(p.sv, kBlock) / 16u);
         const size_t lds = shade_ring_lds_bytes(p.sv, p.spectral != 0, p.gather_w);
-        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_shade<MTS_VARIANT(st, general), true, true>), dim3(shade_blocks), dim3(kBlock), lds, s, p); });
-        return hipGetLastError();
+        hipError_t err = hipSuccess;
+        with_variant(p, [&](auto st, auto general) { err = launch_lds(k_shade<MTS_VARIANT(st, general), true, true>, dim3(shade_blocks), dim3(kBlock), lds, s, p); });
+        return err;
     }
     if (p.split == 2) {       // LDS-resident scene: closest hit + shading fused, shadow rays queued and resolved in dense batches
         const uint32_t shade_blocks = (p.n_waves * 64u + kBlock - 1) / kBlock;
         const size_t lds = bounce_lds_bytes(p.sv);
-        with_variant(p, [&](auto st, auto general) { hipLaunchKernelGGL((k_shade<MTS_VARIANT(st, general), true>), dim3(shade_blocks), dim3(kBlock), lds, s, p); });
-        hipLaunchKernelGGL((k_trace<true, true>), dim3((p.n_waves + kFlatGroup - 1) / kFlatGroup), dim3(kBlock), lds, s, p);
-        return hipGetLastError();
+        hipError_t err = hipSuccess;
+        with_variant(p, [&](auto st, auto general) { err = launch_lds(k_shade<MTS_VARIANT(st, general), true>, dim3(shade_blocks), dim3(kBlock), lds, s, p); });
+        if (err != hipSuccess) return err;
+        return launch_lds(k_trace<true, true>, dim3((p.n_waves + kFlatGroup - 1) / kFlatGroup), dim3(kBlock), lds, s, p);
     }
     if (p.split) {
         hipError_t e = launch_split_stage(p, 0, s);
@@ -1833,33 +1845,33 @@ hipError_t launch_bounce(const RenderParams &p_, hipStream_t s) {
     if (p.spectral) {
         if (p.sv.n_spectra) {
             if (p.sv.general == 2u) {
-                if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectra<true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-                else hipLaunchKernelGGL((k_bounce_spectra<false, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+                if (p.sv.flat) return launch_lds(k_bounce_spectra<true, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+                else return launch_lds(k_bounce_spectra<false, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
             } else {
-                if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectra<true, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-                else hipLaunchKernelGGL((k_bounce_spectra<false, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+                if (p.sv.flat) return launch_lds(k_bounce_spectra<true, false>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+                else return launch_lds(k_bounce_spectra<false, false>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
             }
         } else if (p.sv.general == 2u) {
-            if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectral<true, true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-            else hipLaunchKernelGGL((k_bounce_spectral<false, true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            if (p.sv.flat) return launch_lds(k_bounce_spectral<true, true, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            else return launch_lds(k_bounce_spectral<false, true, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
         } else if (p.sv.general) {
-            if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectral<true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-            else hipLaunchKernelGGL((k_bounce_spectral<false, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            if (p.sv.flat) return launch_lds(k_bounce_spectral<true, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            else return launch_lds(k_bounce_spectral<false, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
         } else {
-            if (p.sv.flat) hipLaunchKernelGGL((k_bounce_spectral<true, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-            else hipLaunchKernelGGL((k_bounce_spectral<false, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            if (p.sv.flat) return launch_lds(k_bounce_spectral<true, false>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+            else return launch_lds(k_bounce_spectral<false, false>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
         }
         return hipGetLastError();
     }
     if (p.sv.general == 2u) {
-        if (p.sv.flat) hipLaunchKernelGGL((k_bounce<true, true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-        else hipLaunchKernelGGL((k_bounce<false, true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+        if (p.sv.flat) return launch_lds(k_bounce<true, true, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+        else return launch_lds(k_bounce<false, true, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
     } else if (p.sv.general) {
-        if (p.sv.flat) hipLaunchKernelGGL((k_bounce<true, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-        else hipLaunchKernelGGL((k_bounce<false, true>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+        if (p.sv.flat) return launch_lds(k_bounce<true, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+        else return launch_lds(k_bounce<false, true>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
     } else {
-        if (p.sv.flat) hipLaunchKernelGGL((k_bounce<true, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
-        else hipLaunchKernelGGL((k_bounce<false, false>), dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+        if (p.sv.flat) return launch_lds(k_bounce<true, false>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
+        else return launch_lds(k_bounce<false, false>, dim3(blocks), dim3(kBlock), bounce_lds_bytes(p.sv), s, p);
     }
     return hipGetLastError();
 }
@@ -1959,8 +1971,7 @@ static hipError_t launch_adjoint_kernel(const AdjointParams &a, hipStream_t s) {
     if (a.n_samples == 0) return hipSuccess;
     uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(a.rp.sv.flat ? K_FLAT : K_TREE, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
-    return hipGetLastError();
+    return launch_lds(a.rp.sv.flat ? K_FLAT : K_TREE, dim3((uint32_t) blocks), dim3(kBlock), bounce_lds_bytes(a.rp.sv), s, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2461,9 +2472,6 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_spectral(const AdjointParams
 }
 
 hipError_t launch_adjoint_spectral(const AdjointParams &a, hipStream_t s) {
-    const size_t lds = bounce_lds_bytes(a.rp.sv);
-    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral<true>), lds)) return e;
-    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral<false>), lds)) return e;
     return launch_adjoint_kernel<k_adjoint_spectral<true>, k_adjoint_spectral<false>>(a, s);
 }
 
@@ -2646,9 +2654,6 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_spectral_emitters(const Adjo
 }
 
 hipError_t launch_adjoint_spectral_emitters(const AdjointParams &a, hipStream_t s) {
-    const size_t lds = bounce_lds_bytes(a.rp.sv);
-    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral_emitters<true>), lds)) return e;
-    if (hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_adjoint_spectral_emitters<false>), lds)) return e;
     return launch_adjoint_kernel<k_adjoint_spectral_emitters<true>, k_adjoint_spectral_emitters<false>>(a, s);
 }
 
@@ -3192,19 +3197,19 @@ hipError_t launch_ray_intersect(const SceneView &sv, uint64_t n, const RayStream
         return hipGetLastError();
     }
     if (mode == 0 && sv.flat)
-        hipLaunchKernelGGL((k_ray_intersect<0, true>), dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
+        return launch_lds(k_ray_intersect<0, true>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
     else if (mode == 0)
-        hipLaunchKernelGGL((k_ray_intersect<0, false>), dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
+        return launch_lds(k_ray_intersect<0, false>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
     else if (sv.flat)
-        hipLaunchKernelGGL((k_ray_intersect<1, true>), dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
+        return launch_lds(k_ray_intersect<1, true>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
     else
-        hipLaunchKernelGGL((k_ray_intersect<1, false>), dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
+        return launch_lds(k_ray_intersect<1, false>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, r, t, prim, shape, u, v, si26);
     return hipGetLastError();
 }
 
 hipError_t launch_ray_test(const SceneView &sv, uint64_t n, const RayStreams &r, uint8_t *hit, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (sv.flat) hipLaunchKernelGGL(k_ray_test<true>, dim3(stream_grid(n)), dim3(kBlock), bounce_lds_bytes(sv), s, sv, n, r, hit);
+    if (sv.flat) return launch_lds(k_ray_test<true>, dim3(stream_grid(n)), dim3(kBlock), bounce_lds_bytes(sv), s, sv, n, r, hit);
     else hipLaunchKernelGGL((k_ray_walk<true>), dim3(walk_grid(sv, n)), dim3(kBlock), walk_lds(sv), s,
                             sv, n, r, (float *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (float *) nullptr, (float *) nullptr, hit);
     return hipGetLastError();
@@ -3290,15 +3295,16 @@ static hipError_t launch_bsdf_operator(const SceneView &sv, uint64_t n, const Bs
     if (n == 0) return hipSuccess;
     const dim3 grid(stream_grid(n)), block(kBlock);
     const size_t lds = operator_lds_bytes(sv);
+    hipError_t err = hipSuccess;
     // the nesting code is compiled into the instantiation that only scenes with a blendbsdf / mask launch (as k_direct)
     with_flag(sv.flat != 0u, [&](auto flat) {
         with_flag(sv.general == 2u, [&](auto nest) {
             constexpr bool F = decltype(flat)::value, N = decltype(nest)::value;
-            if (EVAL) hipLaunchKernelGGL((k_bsdf_eval_pdf<F, N>), grid, block, lds, s, sv, n, q, out);
-            else hipLaunchKernelGGL((k_bsdf_sample<F, N>), grid, block, lds, s, sv, n, q, out);
+            if (EVAL) err = launch_lds(k_bsdf_eval_pdf<F, N>, grid, block, lds, s, sv, n, q, out);
+            else err = launch_lds(k_bsdf_sample<F, N>, grid, block, lds, s, sv, n, q, out);
         });
     });
-    return hipGetLastError();
+    return err;
 }
 hipError_t launch_bsdf_eval_pdf(const SceneView &sv, uint64_t n, const BsdfStreams &q, float *out4, hipStream_t s) {
     return launch_bsdf_operator<true>(sv, n, q, out4, s);
@@ -3337,8 +3343,8 @@ __global__ __launch_bounds__(kBlock) void k_sample_emitter_direction(const Scene
 hipError_t launch_sample_emitter_direction(const SceneView &sv, uint64_t n, const EmitterSampleStreams &q, float *out15, uint32_t *emitter, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const size_t lds = operator_lds_bytes(sv);
-    if (sv.flat) hipLaunchKernelGGL(k_sample_emitter_direction<true>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, q, out15, emitter);
-    else hipLaunchKernelGGL(k_sample_emitter_direction<false>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, q, out15, emitter);
+    if (sv.flat) return launch_lds(k_sample_emitter_direction<true>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, q, out15, emitter);
+    else return launch_lds(k_sample_emitter_direction<false>, dim3(stream_grid(n)), dim3(kBlock), lds, s, sv, n, q, out15, emitter);
     return hipGetLastError();
 }
 

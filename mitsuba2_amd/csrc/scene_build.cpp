@@ -601,7 +601,18 @@ void build_accelerator(const Input &in, const BuildOptions &opt, HostScene &hs) 
 void build_flat_records(const BuildOptions &opt, HostScene &hs) {
     const uint32_t n_prims = hs.state.n_prims;
     const std::vector<float> &tri_pos = hs.tri_pos;
-    const bool flat = hs.flat = n_prims <= opt.flat_max;
+    // Flat: few enough triangles, and tables small enough that the largest launch fits the LDS cap.  The shape, BSDF and emitter counts
+    // are not bounded by the triangle count (delta emitters own no triangle, nested materials add records); a scene over the cap is
+    // traversed through its hierarchy like any larger one.  The scene's variant decides the figure (spectral ring entries are larger).
+    bool flat = n_prims <= opt.flat_max;
+    if (flat) {
+        SceneView sv = {};
+        sv.flat = 1u; sv.n_prims = n_prims; sv.n_pairs = (n_prims + 1) / 2;
+        for (uint32_t k = 0; k < sv.n_pairs; ++k) sv.n_clusters += k == 0 || hs.prim_shape[2 * k] != hs.prim_shape[2 * (k - 1)];
+        sv.n_shapes = hs.state.n_shapes; sv.n_bsdfs = (uint32_t) hs.state.bsdfs.size(); sv.n_emitters = (uint32_t) hs.state.emitters.size();
+        flat = flat_launch_lds_max(sv, hs.state.spectral) <= kFlatLdsCap;
+    }
+    hs.flat = flat;
     hs.flat_recs.assign(flat ? 4 * (size_t) n_prims : 0, float4{});
     for (uint32_t gp = 0; flat && gp < n_prims; ++gp) {
         const float *tp = &tri_pos[9 * (size_t) gp];

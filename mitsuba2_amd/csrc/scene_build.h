@@ -84,7 +84,7 @@ struct HostScene {
     // variant: model coefficients); null for a checkerboard
     std::vector<const float *> tex_src;
     std::vector<std::vector<float>> tex_coeffs;
-    bool flat = false;                                  // n_prims <= flat_max: the scene lives in LDS
+    bool flat = false;                                  // n_prims <= flat_max and flat_launch_lds_max() <= kFlatLdsCap: the scene lives in LDS
     std::vector<float4> flat_recs, pair_recs;           // pair_recs: 5 per pair, then 2 per cluster
     uint32_t n_pairs = 0, n_clusters = 0;
     bool has_envmap = false;

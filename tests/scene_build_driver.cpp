@@ -145,6 +145,15 @@ static void run(Scene &sc, const std::vector<std::pair<std::string, Args>> &ops,
     dump("flags", flags, 13);
     const uint32_t bvh[] = { st.bvh.root, st.bvh.wroot, st.bvh.wdepth, st.bvh.n_nodes, st.bvh.n_slots };
     dump("bvh", bvh, 5);
+    // LDS demand of the scene as a flat one (kernels.h; whatever hs.flat says, so that the test sees both sides of the cap), and the BVH4 a demoted scene walks
+    SceneView sv = {};
+    sv.flat = 1u; sv.n_prims = st.n_prims; sv.n_pairs = (st.n_prims + 1) / 2;
+    for (uint32_t k = 0; k < sv.n_pairs; ++k) sv.n_clusters += k == 0 || hs.prim_shape[2 * k] != hs.prim_shape[2 * (k - 1)];
+    sv.n_shapes = st.n_shapes; sv.n_bsdfs = (uint32_t) st.bsdfs.size(); sv.n_emitters = (uint32_t) st.emitters.size();
+    const uint32_t limits[] = { (uint32_t) lds_bytes(sv, 64u), (uint32_t) lds_bytes(sv, 256u), (uint32_t) shade_ring_lds_bytes(sv, false, 4u),
+                                (uint32_t) shade_ring_lds_bytes(sv, true, 1024u), (uint32_t) flat_launch_lds_max(sv, false),
+                                (uint32_t) flat_launch_lds_max(sv, true), (uint32_t) kFlatLdsCap, st.bvh.n_wnodes, st.bvh.wdepth };
+    dump("limits", limits, 9);
     dump("tri_pos", hs.tri_pos); dump("tri_nrm", hs.tri_nrm); dump("tri_uv", hs.tri_uv); dump("prim_shape", hs.prim_shape); dump("shapes", hs.shapes);
     dump("area_pmf", hs.area_pmf); dump("area_cdf", hs.area_cdf);
     dump("bsdfs", st.bsdfs); dump("emitters", st.emitters); dump("textures", st.textures);
