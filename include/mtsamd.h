@@ -182,6 +182,26 @@ typedef struct {
  * The setters below refuse a parameter that holds a spectrum, and the spectral adjoint entry points refuse such a scene. */
 MTSAMD_API int mtsamd_scene_create_with_spectra(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
                                      const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, int device, mtsamd_scene **out);
+/* ---- textured BSDF parameters (RGB variant) -------------------------------------
+ * Binds texture `texture` of the description's texture table to one parameter of plain BSDF record `bsdf`, as the reference's
+ * props.texture<Texture>(...) parameters allow: param = MTSAMD_PARAM_ALPHA (alpha_u and alpha_v share the texture), MTSAMD_PARAM_ALPHA_U,
+ * MTSAMD_PARAM_ALPHA_V (roughconductor.cpp:173-182, roughdielectric.cpp:177-186; read per hit with Texture::eval_1: the luminance of a
+ * bitmap texel, the first colour channel of a checkerboard cell; not clamped), MTSAMD_PARAM_SPECULAR_REFLECTANCE (conductor,
+ * roughconductor, dielectric, roughdielectric, thindielectric) or MTSAMD_PARAM_SPECULAR_TRANSMITTANCE (the three dielectrics), read with
+ * Texture::eval.  The value the description holds for a bound parameter is ignored by the kernels.  Children of blendbsdf / mask are
+ * records of their own and bindable; blend / mask records themselves are not (their weight is mtsamd_bsdf_desc::texture), nor are
+ * (rough)plastic parameters, eta / k, or anything in a spectral scene.  A texture may serve several bindings;
+ * mtsamd_scene_update_texture updates it for all of them. */
+typedef struct {
+    uint32_t bsdf;             /* bsdf record */
+    int32_t param;             /* mtsamd_bsdf_param */
+    int32_t texture;           /* index into mtsamd_scene_desc::textures */
+} mtsamd_texture_binding;
+/* mtsamd_scene_create for a scene with such bindings; mtsamd_scene_create is its case of no bindings.  Such a scene renders with the
+ * fused kernels that blendbsdf / mask scenes run (every `pipeline` value gives the same samples).  mtsamd_scene_set_bsdf_param refuses a
+ * parameter that holds a texture, and the adjoint entry points refuse such a scene. */
+MTSAMD_API int mtsamd_scene_create_with_textures(const mtsamd_scene_desc *desc, const mtsamd_texture_binding *bindings, uint32_t n_bindings,
+                                      int device, mtsamd_scene **out);
 /* Texture::eval of one spectrum (regular.cpp:68-75, irregular.cpp:76-83, blackbody.cpp:64-83) at n wavelengths: runs the device function
  * the render kernels call.  lambda_dev / out_dev: n floats on the device.  Returns when out_dev is complete. */
 MTSAMD_API int mtsamd_spectrum_eval(const mtsamd_spectrum_desc *desc, uint64_t n, const float *lambda_dev, float *out_dev, void *stream);
@@ -441,9 +461,10 @@ MTSAMD_API int mtsamd_render_adjoint_envmap(mtsamd_scene *scene, const mtsamd_re
  * to (model coefficients, scale) on the host as scene creation converts them; the hierarchy is built from the RGB luminances either way. */
 /* Parameters of the BSDF models beyond `diffuse` (what traverse() exposes of e.g. roughconductor.cpp:393-404, plastic.cpp:299-307):
  * REFLECTANCE = diffuse.reflectance / (rough)plastic.diffuse_reflectance, SPECULAR_REFLECTANCE, SPECULAR_TRANSMITTANCE (dielectrics),
- * ETA / K (conductors), ALPHA (isotropic roughness of roughconductor / roughdielectric; one component). */
+ * ETA / K (conductors), ALPHA (isotropic roughness of roughconductor / roughdielectric; one component).  ALPHA_U / ALPHA_V name one
+ * roughness alone and exist for mtsamd_texture_binding only: the setters and the parameter adjoint do not take them. */
 typedef enum { MTSAMD_PARAM_REFLECTANCE = 0, MTSAMD_PARAM_SPECULAR_REFLECTANCE = 1, MTSAMD_PARAM_ETA = 2, MTSAMD_PARAM_K = 3, MTSAMD_PARAM_ALPHA = 4,
-               MTSAMD_PARAM_SPECULAR_TRANSMITTANCE = 5 } mtsamd_bsdf_param;
+               MTSAMD_PARAM_SPECULAR_TRANSMITTANCE = 5, MTSAMD_PARAM_ALPHA_U = 6, MTSAMD_PARAM_ALPHA_V = 7 } mtsamd_bsdf_param;
 /* parameters_changed() of a BSDF after one of these parameters was edited (constants): value3 = 3 floats (ALPHA: 1).  Spectral
  * variant: the three colour kinds become srgb spectra (as above), ETA / K must keep three equal components (uniform spectra). */
 MTSAMD_API int mtsamd_scene_set_bsdf_param(mtsamd_scene *scene, uint32_t bsdf, int32_t param, const float *value3);

@@ -57,6 +57,10 @@ class SpectrumBinding(C.Structure):
     _fields_ = [("target", C.c_int32), ("index", C.c_uint32), ("param", C.c_int32), ("spectrum", C.c_uint32)]
 
 
+class TextureBinding(C.Structure):
+    _fields_ = [("bsdf", C.c_uint32), ("param", C.c_int32), ("texture", C.c_int32)]
+
+
 class Rays(C.Structure):
     _fields_ = [(n, vp) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "mint", "maxt", "active")]
 
@@ -89,6 +93,7 @@ SYMBOLS = {
     "mtsamd_scene_create": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.POINTER(vp)]),
     "mtsamd_scene_create_with_spectra": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(SpectrumDesc), C.c_uint32, C.POINTER(SpectrumBinding), C.c_uint32,
                                                    C.c_int, C.POINTER(vp)]),
+    "mtsamd_scene_create_with_textures": (C.c_int, [C.POINTER(SceneDesc), C.POINTER(TextureBinding), C.c_uint32, C.c_int, C.POINTER(vp)]),
     "mtsamd_spectrum_eval": (C.c_int, [C.POINTER(SpectrumDesc), C.c_uint64, vp, vp, vp]),
     "mtsamd_spectrum_mean": (C.c_int, [C.POINTER(SpectrumDesc), f32p]),
     "mtsamd_scene_destroy": (None, [vp]),

@@ -78,6 +78,27 @@ def _rgb(v, default):
     return [float(x) for x in a]
 
 
+# parameters the reference declares as textures (props.texture<Texture>) beyond the (diffuse) reflectance, and the models that read them
+# per hit: `alpha` / `alpha_u` / `alpha_v` (Texture::eval_1; roughconductor.cpp:173-182, roughdielectric.cpp:177-186), specular_reflectance
+# and specular_transmittance (Texture::eval).  parameter -> mtsamd_bsdf_param of the texture binding (include/mtsamd.h)
+TEXTURE_PARAMS = {"alpha": 4, "alpha_u": 6, "alpha_v": 7, "specular_reflectance": 1, "specular_transmittance": 5}
+
+
+def _texture(v, t, key, allowed=True, why=None):
+    """`v` if parameter `key` of plugin `t` holds a texture dictionary (`bitmap` / `checkerboard`) this backend reads there, else None
+    (a constant).  allowed = False: the parameter takes no texture here; the error names it."""
+    if not isinstance(v, dict):
+        return None
+    from . import spectrum as S
+    if S.is_spectrum(v):
+        return None
+    if not allowed:
+        raise RuntimeError("%s: '%s' takes no texture in this backend: %s" % (t, key, why))
+    if v.get("type") not in ("bitmap", "checkerboard"):
+        raise RuntimeError("Texture plugin '%s' is not supported by this backend (bitmap, checkerboard)" % v.get("type"))
+    return v
+
+
 def is_transmissive(n):
     """a normalised record has a transmission component (what TwoSidedBRDF refuses, twosided.cpp:78-80)"""
     if n["type"] == MASK:
@@ -152,9 +173,21 @@ def flatten(records):
     return flat
 
 
+def _specular_colour(out, b, t, key, uniform_bit, allowed=True, why=None):
+    """specular_reflectance / specular_transmittance of plugin `t`: a colour or a constant into out[key], or a texture into
+    out["textures"][key] (the colour of the record, 1, is then not used)"""
+    tex = _texture(b.get(key), t, key, allowed, why)
+    if tex is not None:
+        out.setdefault("textures", {})[key] = tex
+        return
+    out[key] = _rgb(b.get(key), 1.0)
+    out["uniform_mask"] |= uniform_bit if _is_uniform(b.get(key), 1.0) else 0
+
+
 def normalize(b):
     """Plugin dictionary -> flat record: dict(type, twosided, reflectance (rgb list or bitmap dict), specular_reflectance,
-    specular_transmittance, eta, k, int_ior, ext_ior, alpha_u, alpha_v, distribution, sample_visible, nonlinear)."""
+    specular_transmittance, eta, k, int_ior, ext_ior, alpha_u, alpha_v, distribution, sample_visible, nonlinear) and, if some other
+    parameter holds a texture, textures = {alpha_u | alpha_v | specular_reflectance | specular_transmittance: texture dictionary}."""
     t = b.get("type", "diffuse")
     twosided = False
     if t == "twosided":                                      # twosided.cpp:63-92
@@ -203,11 +236,12 @@ def normalize(b):
         if "eta" in b or material == "none":
             if "material" in b and b["material"] != "none" and "eta" in b:
                 raise RuntimeError("Should specify either (eta, k) or material, not both.")
+            for key in ("eta", "k"):
+                _texture(b.get(key), t, key, False, "indices of refraction are constants (or spectra in the spectral variant)")
             out["eta"], out["k"] = _rgb(b.get("eta"), 0.0), _rgb(b.get("k"), 1.0)
         else:
             raise RuntimeError('conductor material "%s": the measured IOR tables (data/ior/*.spd) are not shipped; specify eta and k (constants, or spectra in the spectral variant, e.g. {"type": "spectrum", "filename": "<material>.eta.spd"})' % material)
-        out["specular_reflectance"] = _rgb(b.get("specular_reflectance"), 1.0)
-        out["uniform_mask"] |= 2 if _is_uniform(b.get("specular_reflectance"), 1.0) else 0
+        _specular_colour(out, b, t, "specular_reflectance", 2)
         known |= {"material", "eta", "k", "specular_reflectance"}
     if tid in (ROUGHCONDUCTOR, ROUGHPLASTIC, ROUGHDIELECTRIC):
         distr = str(b.get("distribution", "beckmann")).lower()
@@ -220,9 +254,16 @@ def normalize(b):
                 raise RuntimeError("Microfacet model: both 'alpha_u' and 'alpha_v' must be specified.")
             if "alpha" in b:
                 raise RuntimeError("Microfacet model: please specify either 'alpha' or 'alpha_u'/'alpha_v'.")
-            out["alpha_u"], out["alpha_v"] = float(b["alpha_u"]), float(b["alpha_v"])
+            given = {"alpha_u": b["alpha_u"], "alpha_v": b["alpha_v"]}
         else:
-            out["alpha_u"] = out["alpha_v"] = float(b.get("alpha", 0.1))
+            given = {"alpha_u": b.get("alpha", 0.1), "alpha_v": b.get("alpha", 0.1)}      # a textured `alpha`: both share the one texture
+        for key, v in given.items():
+            name = key if "alpha_u" in b or "alpha_v" in b else "alpha"
+            tex = _texture(v, t, name, tid != ROUGHPLASTIC, "the roughness of roughplastic is a float (roughplastic.cpp:222)")
+            if tex is not None:       # read per hit; the constant of the record is not used
+                out.setdefault("textures", {})[key] = tex
+            else:
+                out[key] = float(v)
         known |= {"distribution", "sample_visible", "alpha", "alpha_u", "alpha_v"}
         if tid == ROUGHPLASTIC and out["alpha_u"] != out["alpha_v"]:
             raise RuntimeError("The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!")
@@ -233,12 +274,11 @@ def normalize(b):
             raise RuntimeError("The interior and exterior indices of refraction must be positive!")
         if tid in (ROUGHPLASTIC, ROUGHDIELECTRIC) and out["int_ior"] == out["ext_ior"]:
             raise RuntimeError("The interior and exterior indices of refraction must be positive and differ!")
-        out["specular_reflectance"] = _rgb(b.get("specular_reflectance"), 1.0)
-        out["uniform_mask"] |= 2 if _is_uniform(b.get("specular_reflectance"), 1.0) else 0
+        _specular_colour(out, b, t, "specular_reflectance", 2, tid not in (PLASTIC, ROUGHPLASTIC),
+                         "its mean feeds the lobe weight of a (rough)plastic (plastic.cpp:170-175): not implemented for a texture")
         known |= {"int_ior", "ext_ior", "specular_reflectance"}
     if tid in (DIELECTRIC, ROUGHDIELECTRIC, THINDIELECTRIC):
-        out["specular_transmittance"] = _rgb(b.get("specular_transmittance"), 1.0)
-        out["uniform_mask"] |= 4 if _is_uniform(b.get("specular_transmittance"), 1.0) else 0
+        _specular_colour(out, b, t, "specular_transmittance", 4)
         known |= {"specular_transmittance"}
     if tid in (PLASTIC, ROUGHPLASTIC):
         dr = b.get("diffuse_reflectance")                  # a colour, a constant or a texture (bitmap / checkerboard)

@@ -561,16 +561,29 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
     delete s;
 }
 
+// the three creation entry points: a scene holds tabulated spectra (spectral variant) or textured parameters (RGB variant), or neither
+static int create_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra, const mtsamd_spectrum_binding *bindings,
+                        uint32_t n_bindings, const mtsamd_texture_binding *tex_bindings, uint32_t n_tex_bindings, int device, mtsamd_scene **out);
+
 int mtsamd_scene_create(const mtsamd_scene_desc *desc, int device, mtsamd_scene **out) {
-    return mtsamd_scene_create_with_spectra(desc, nullptr, 0, nullptr, 0, device, out);
+    return create_scene(desc, nullptr, 0, nullptr, 0, nullptr, 0, device, out);
 }
 
 int mtsamd_scene_create_with_spectra(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
                                      const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, int device, mtsamd_scene **out) {
+    return create_scene(desc, spectra, n_spectra, bindings, n_bindings, nullptr, 0, device, out);
+}
+
+int mtsamd_scene_create_with_textures(const mtsamd_scene_desc *desc, const mtsamd_texture_binding *bindings, uint32_t n_bindings, int device, mtsamd_scene **out) {
+    return create_scene(desc, nullptr, 0, nullptr, 0, bindings, n_bindings, device, out);
+}
+
+static int create_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra, const mtsamd_spectrum_binding *bindings,
+                        uint32_t n_bindings, const mtsamd_texture_binding *tex_bindings, uint32_t n_tex_bindings, int device, mtsamd_scene **out) {
     if (!desc || !out) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_create: null argument");
     *out = nullptr;
     HostScene hs;       // everything the host can check and compute comes first: it needs no device
-    if (int rc = build_host_scene(desc, spectra, n_spectra, bindings, n_bindings, build_options(), hs)) return rc;
+    if (int rc = build_host_scene(desc, spectra, n_spectra, bindings, n_bindings, build_options(), hs, tex_bindings, n_tex_bindings)) return rc;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(MTSAMD_ERR_INVALID, "invalid device index %d (have %d)", device, ndev);
@@ -1546,6 +1559,7 @@ int mtsamd_render_adjoint_param(mtsamd_scene *s, const mtsamd_render_desc *d, co
     AdjointParams a{};
     if (int rc = fill_adjoint(s, d, dimage, film, a)) return rc;
     if (!grad1 || bsdf >= s->bsdfs.size()) return fail(MTSAMD_ERR_INVALID, "invalid argument");
+    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the parameter adjoint does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
     if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the parameter adjoint does not handle blendbsdf / mask materials");
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
     const DevBsdf &b = s->bsdfs[bsdf];
@@ -1571,6 +1585,7 @@ int mtsamd_render_adjoint_envmap(mtsamd_scene *s, const mtsamd_render_desc *d, c
     if (int rc = fill_adjoint(s, d, dimage, film, a)) return rc;
     if (!grad_envmap) return fail(MTSAMD_ERR_INVALID, "null argument");
     if (s->environment < 0 || !s->d_envmap) return fail(MTSAMD_ERR_UNSUPPORTED, "the scene has no envmap emitter");
+    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the envmap adjoint does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
     if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the envmap adjoint does not handle blendbsdf / mask materials");
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
     a.grad_env = grad_envmap;
@@ -1585,6 +1600,7 @@ int mtsamd_render_adjoint_textures(mtsamd_scene *s, const mtsamd_render_desc *d,
     if (!grad_tex) return fail(MTSAMD_ERR_INVALID, "null argument");
     if (d->max_depth < 0 || d->max_depth > 16)
         return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the texture adjoint does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
     if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the texture adjoint does not handle blendbsdf / mask materials");
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
     a.grad_tex = grad_tex;
@@ -1599,6 +1615,7 @@ int mtsamd_render_adjoint_spectral(mtsamd_scene *s, const mtsamd_render_desc *d,
     if (s->view.n_spectra) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not replay scenes with tabulated spectra (%u bound here): node values are not differentiated", s->view.n_spectra);
     if (d->max_depth < 1 || d->max_depth > 16)
         return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
     if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle blendbsdf / mask materials");
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
     if (s->bsdfs.size() > 32 && grad_bsdf) return fail(MTSAMD_ERR_UNSUPPORTED, "at most 32 BSDFs with constant-reflectance gradients");
@@ -1643,6 +1660,7 @@ int mtsamd_render_adjoint_spectral_emitters(mtsamd_scene *s, const mtsamd_render
     if (s->view.n_spectra) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not replay scenes with tabulated spectra (%u bound here): node values are not differentiated", s->view.n_spectra);
     if (d->max_depth < 1 || d->max_depth > 16)
         return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
     if (s->nested_bsdfs) return fail(MTSAMD_ERR_UNSUPPORTED, "the spectral adjoint does not handle blendbsdf / mask materials");
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
     if (s->emitters.size() > 32 && grad_emitters) return fail(MTSAMD_ERR_UNSUPPORTED, "at most 32 emitters with radiance gradients");

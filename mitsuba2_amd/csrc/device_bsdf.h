@@ -21,6 +21,9 @@ constexpr uint32_t kBsdfTwoSided = 1u, kBsdfGGX = 2u, kBsdfSampleVisible = 4u, k
 // blend / mask: some child has a smooth component (BSDFFlags::Smooth of the union of the nested flags); the weight / opacity texture
 // is a bitmap, whose eval_1 is the luminance of the texel (bitmap.cpp:215-231)
 constexpr uint32_t kBsdfNestSmooth = 128u, kBsdfWeightLum = 256u;
+// plain records: some parameter is read from a texture at the hit (DevBsdf::nested0/1, bsdf_param_texture(); resolve_textured() in
+// device_scene.h); Texture::eval_1 of alpha_u / alpha_v is the luminance of the texel (a bitmap) instead of its first channel
+constexpr uint32_t kBsdfTexParams = 512u, kBsdfAlphaULum = 1024u, kBsdfAlphaVLum = 2048u;
 // spectral variant: the parameter is a `uniform` spectrum (its constant sits in the first colour channel) instead of `srgb`
 constexpr uint32_t kBsdfUniformRefl = 16u, kBsdfUniformSpec = 32u, kBsdfUniformTrans = 64u;
 constexpr float kInvSqrtPi = 0.56418958354775628695f, kEps = kEpsilon;
@@ -208,7 +211,14 @@ struct DevBsdf {
     // spectra0 / spectra1: 1 + pool index of the spectrum bound to a parameter, 10 bits each, 0 = none (bsdf_spectrum());
     // spectra0 = reflectance | specular_reflectance << 10 | specular_transmittance << 20, spectra1 = eta | k << 10
     const float *table; uint32_t nested0, nested1;      // roughplastic: external transmittance table (device memory); blend / mask: child records
+    // plain records with kBsdfTexParams: nested0 / nested1 hold four 16-bit fields "1 + texture index" (0 = the constant of the record),
+    // nested0 = alpha_u | alpha_v << 16, nested1 = specular_reflectance | specular_transmittance << 16 (bsdf_param_texture())
 };
+enum { kTexAlphaU = 0, kTexAlphaV = 1, kTexSpec = 2, kTexTrans = 3 };
+constexpr uint32_t kMaxParamTextures = 65535u;
+__host__ __device__ inline uint32_t bsdf_param_texture(const DevBsdf &b, int slot) {       // 1 + texture index, or 0
+    return ((slot < 2 ? b.nested0 : b.nested1) >> (16 * (slot & 1))) & 65535u;
+}
 constexpr uint32_t kMaxSpectra = 1023u;
 enum { kSpecRefl = 0, kSpecSpec = 1, kSpecTrans = 2, kSpecEta = 3, kSpecK = 4 };
 __host__ __device__ inline uint32_t bsdf_spectrum(const DevBsdf &b, int param) {       // 1 + pool index, or 0

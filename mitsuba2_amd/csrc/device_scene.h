@@ -1282,10 +1282,14 @@ MTS_DEV float pdf_emitter_direction(uint32_t n_emitters, float area_norm, f3 d, 
 // Diffuse reflectance at a surface interaction: the constant `srgb` colour (src/spectra/srgb.cpp:27-52) or
 // BitmapTextureImpl::interpolate (src/textures/bitmap.cpp:250-293, identity to_uv).  `texel` / `w1` return the bilinear
 // footprint (index of v00, weights towards +x / +y) for the adjoint; texel = kNoPrim for constant reflectance.
-MTS_DEV f3 eval_reflectance(const SceneView &sv, const DevBsdf &b, f2 uv, uint32_t &texel, f2 &w1) {
+// This is the one texture lookup: OWN = false reads texture `index` of the scene's table instead of the record's own (a textured
+// parameter, resolve_textured below).  The selection is a template argument so that the default instantiation stays, instruction for
+// instruction, the function every kernel compiled before there were textured parameters.
+template <bool OWN = true>
+MTS_DEV f3 eval_reflectance(const SceneView &sv, const DevBsdf &b, f2 uv, uint32_t &texel, f2 &w1, int32_t index = -1) {
     texel = kNoPrim; w1.x = w1.y = 0.0f;
-    if (b.texture < 0) return mk3(b.r, b.g, b.b);
-    const DevTexture t = sv.textures[b.texture];
+    if (OWN && b.texture < 0) return mk3(b.r, b.g, b.b);
+    const DevTexture t = sv.textures[OWN ? b.texture : index];
     {   // m_transform.transform_affine(si.uv) (bitmap.cpp:254, checkerboard.cpp:49)
         const float u2 = fmaf(t.uvm[0], uv.x, fmaf(t.uvm[1], uv.y, t.uvm[2])), v2 = fmaf(t.uvm[3], uv.x, fmaf(t.uvm[4], uv.y, t.uvm[5]));
         uv.x = u2; uv.y = v2;
@@ -1306,6 +1310,30 @@ MTS_DEV f3 eval_reflectance(const SceneView &sv, const DevBsdf &b, f2 uv, uint32
     { float v0 = fmaf(w0x, v00[1], w1.x * v00[4]), v1 = fmaf(w0x, v01[1], w1.x * v01[4]); r.y = fmaf(w0y, v0, w1.y * v1); }
     { float v0 = fmaf(w0x, v00[2], w1.x * v00[5]), v1 = fmaf(w0x, v01[2], w1.x * v01[5]); r.z = fmaf(w0y, v0, w1.y * v1); }
     return r;
+}
+
+// Textured parameters of a plain record (kBsdfTexParams): alpha_u / alpha_v of the rough models (Texture::eval_1, roughconductor.cpp:212-214,
+// roughdielectric.cpp:222-224), specular_reflectance and specular_transmittance (Texture::eval, conductor.cpp:240, dielectric.cpp:245, ...)
+// are looked up at the hit and written over the constants of `cur`, the caller's working copy of the record, so the model code reads
+// them where it reads constants.  Nothing clamps the roughness here, as nothing does in the reference: mdf_make sees what the texture
+// returns.  The four lookups are written out one after the other on purpose: as one loop over the slots (one lookup site) the step
+// cost bounce_step<.., NEST = true> 4 to 20 bytes of new scratch per lane at its 128-VGPR cap; in this form VGPRs and scratch of the
+// render kernels are what they were ("Textured parameters").
+MTS_DEV void resolve_textured(const SceneView &sv, DevBsdf &cur, f2 uv) {
+    if (!(cur.flags & kBsdfTexParams)) return;
+    uint32_t texel; f2 w1;
+    const uint32_t tu = bsdf_param_texture(cur, kTexAlphaU), tv = bsdf_param_texture(cur, kTexAlphaV);
+    if (tu) {       // luminance: spectrum.h:239-241, as nest_info
+        const f3 v = eval_reflectance<false>(sv, cur, uv, texel, w1, (int32_t) (tu - 1u));
+        cur.alpha_u = (cur.flags & kBsdfAlphaULum) ? fmaf(0.072169f, v.z, fmaf(0.715160f, v.y, 0.212671f * v.x)) : v.x;
+    }
+    if (tv) {
+        const f3 v = eval_reflectance<false>(sv, cur, uv, texel, w1, (int32_t) (tv - 1u));
+        cur.alpha_v = (cur.flags & kBsdfAlphaVLum) ? fmaf(0.072169f, v.z, fmaf(0.715160f, v.y, 0.212671f * v.x)) : v.x;
+    }
+    const uint32_t ts = bsdf_param_texture(cur, kTexSpec), tt = bsdf_param_texture(cur, kTexTrans);
+    if (ts) { const f3 v = eval_reflectance<false>(sv, cur, uv, texel, w1, (int32_t) (ts - 1u)); cur.sr = v.x; cur.sg = v.y; cur.sb = v.z; }
+    if (tt) { const f3 v = eval_reflectance<false>(sv, cur, uv, texel, w1, (int32_t) (tt - 1u)); cur.kr = v.x; cur.kg = v.y; cur.kb = v.z; }      // dielectrics: k.* holds the transmittance
 }
 
 // SmoothDiffuse

@@ -102,6 +102,21 @@ struct NoProbe {
     MTS_DEV void bsdf_sampled(const SceneView &sv, const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, f3 thr, const BsdfSample &bs, f3 weight, float s1, f2 s2) { }
 };
 
+// `table(i)` of surface_bsdf_sample / surface_bsdf_eval_pdf: record i of the scene's BSDF table as the model code reads it at `uv`.  The
+// NEST instantiation resolves the textured parameters of the record -- a blend / mask child, right where it replaces the working record
+// (cur = table(child)); NEST = false is the plain load (and is never called: only nests have children).
+template <bool NEST, bool FLAT> struct BsdfTable;
+template <bool FLAT> struct BsdfTable<false, FLAT> {
+    const Geo<FLAT> &geo;
+    MTS_DEV BsdfTable(const Geo<FLAT> &g, const f2 &) : geo(g) { }
+    MTS_DEV DevBsdf operator()(uint32_t i) const { return geo.bsdf(i); }
+};
+template <bool FLAT> struct BsdfTable<true, FLAT> {
+    const Geo<FLAT> &geo; const f2 &uv;
+    MTS_DEV BsdfTable(const Geo<FLAT> &g, const f2 &t) : geo(g), uv(t) { }
+    MTS_DEV DevBsdf operator()(uint32_t i) const { DevBsdf rec = geo.bsdf(i); resolve_textured(geo.sv, rec, uv); return rec; }
+};
+
 // DEFER: 0 = both ray queries inline (fused kernel); 1 = closest hit precomputed + shadow ray queued (split pipeline of
 // hierarchy scenes); 2 = closest hit inline, shadow ray queued (flat scenes: the any-hit loop then runs on dense batches)
 template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false, class Probe = NoProbe>
@@ -163,6 +178,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
     if (s.depth >= (uint32_t) P.max_depth || !active) return false;
 
     DevBsdf bsdf = geo.bsdf((uint32_t) si.shape_rec.bsdf);      // blend / mask: overwritten with the child in use (surface_bsdf_*)
+    if (NEST) resolve_textured(sv, bsdf, si.uv);             // textured alpha / specular colours of the record of the hit
     uint32_t texel; f2 tw1;
     const f3 refl = eval_reflectance(sv, bsdf, si.uv, texel, tw1);
     const NestInfo ni = nest_info<NEST>(bsdf, refl.x, refl.y, refl.z);
@@ -197,7 +213,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
             f3 wo = to_local(si.sh, ds.d);
             const f3 wo_b = flip ? mk3(wo.x, wo.y, -wo.z) : wo;
             f3 bv; float bp;
-            if (GENERAL) surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, [&](uint32_t i) { return geo.bsdf(i); }, child_refl, si.wi, wo, bv, bp);
+            if (GENERAL) surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, BsdfTable<NEST, FLAT>(geo, si.uv), child_refl, si.wi, wo, bv, bp);
             else diffuse_eval_pdf(refl, wi_b, wo_b, bv, bp);
             float mis = (GENERAL && ds.delta) ? 1.0f : mis_weight(ds.pdf, bp);      // path.cpp:170
             f3 contrib = mk3(((mis * s.thr.x) * bv.x) * spec.x, ((mis * s.thr.y) * bv.y) * spec.y,
@@ -237,7 +253,7 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
     f3 wo, weight; float pdf;
     if (GENERAL) {
         BsdfSample bs;
-        surface_bsdf_sample<NEST>(bsdf, ni, refl, [&](uint32_t i) { return geo.bsdf(i); }, child_refl, si.wi, s1, s2, bs, weight);
+        surface_bsdf_sample<NEST>(bsdf, ni, refl, BsdfTable<NEST, FLAT>(geo, si.uv), child_refl, si.wi, s1, s2, bs, weight);
         wo = bs.wo; pdf = bs.pdf;
         s.eta *= bs.eta;                                     // harmless for a failed sample: the path ends below
         s.flags = bs.delta ? (s.flags | kFlagDelta) : (s.flags & ~kFlagDelta);
@@ -943,6 +959,7 @@ __global__ __launch_bounds__(kBlock) void k_direct(const RenderParams P, uint64_
                 s.res = mk3(s.res.x + e.r, s.res.y + e.g, s.res.z + e.b);
             }
             DevBsdf bsdf = geo.bsdf((uint32_t) si.shape_rec.bsdf);      // blend / mask: overwritten with the child in use (surface_bsdf_*)
+            if (NEST) resolve_textured(sv, bsdf, si.uv);
             uint32_t texel; f2 tw1;
             const f3 refl = eval_reflectance(sv, bsdf, si.uv, texel, tw1);
             const NestInfo ni = nest_info<NEST>(bsdf, refl.x, refl.y, refl.z);
@@ -955,7 +972,7 @@ __global__ __launch_bounds__(kBlock) void k_direct(const RenderParams P, uint64_
                     if (ds.pdf == 0.0f) continue;
                     const f3 wo = to_local(si.sh, ds.d);
                     f3 bv; float bp;
-                    if (GENERAL) surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, [&](uint32_t i) { return geo.bsdf(i); }, child_refl, si.wi, wo, bv, bp);
+                    if (GENERAL) surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, BsdfTable<NEST, FLAT>(geo, si.uv), child_refl, si.wi, wo, bv, bp);
                     else diffuse_eval_pdf(refl, si.wi, wo, bv, bp);
                     const float mis = (GENERAL && ds.delta) ? 1.0f : mis_weight(ds.pdf * frac_lum, bp * frac_bsdf) * weight_lum;      // direct.cpp:155-156
                     const f3 contrib = mk3((mis * bv.x) * spec.x, (mis * bv.y) * spec.y, (mis * bv.z) * spec.z);
@@ -974,7 +991,7 @@ __global__ __launch_bounds__(kBlock) void k_direct(const RenderParams P, uint64_
                 f3 wo, weight; float pdf; bool delta = false;
                 if (GENERAL) {
                     BsdfSample bs;
-                    surface_bsdf_sample<NEST>(bsdf, ni, refl, [&](uint32_t i) { return geo.bsdf(i); }, child_refl, si.wi, s1, s2, bs, weight);
+                    surface_bsdf_sample<NEST>(bsdf, ni, refl, BsdfTable<NEST, FLAT>(geo, si.uv), child_refl, si.wi, s1, s2, bs, weight);
                     wo = bs.wo; pdf = bs.pdf; delta = bs.delta;
                 } else {
                     diffuse_sample(refl, si.wi, s2, wo, pdf, weight);
@@ -3252,11 +3269,12 @@ __global__ __launch_bounds__(kBlock) void k_bsdf_eval_pdf(const SceneView sv, ui
         if (operator_bsdf(geo, q, i, bsdf)) {
             const f3 wi = mk3(q.wix[i], q.wiy[i], q.wiz[i]), wo = mk3(q.wox[i], q.woy[i], q.woz[i]);
             f2 uv; uv.x = q.u ? q.u[i] : 0.0f; uv.y = q.v ? q.v[i] : 0.0f;
+            if (NEST) resolve_textured(sv, bsdf, uv);      // textured parameters of the row's record
             uint32_t texel; f2 tw1;
             const f3 refl = eval_reflectance(sv, bsdf, uv, texel, tw1);
             const NestInfo ni = nest_info<NEST>(bsdf, refl.x, refl.y, refl.z);
             auto child_refl = [&](const DevBsdf &rec) { uint32_t t; f2 w; return eval_reflectance(sv, rec, uv, t, w); };
-            surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, [&](uint32_t k) { return geo.bsdf(k); }, child_refl, wi, wo, value, pdf);
+            surface_bsdf_eval_pdf<NEST>(bsdf, ni, refl, BsdfTable<NEST, FLAT>(geo, uv), child_refl, wi, wo, value, pdf);
         }
         out[i] = value.x; out[n + i] = value.y; out[2u * n + i] = value.z; out[3u * n + i] = pdf;
     }
@@ -3277,11 +3295,12 @@ __global__ __launch_bounds__(kBlock) void k_bsdf_sample(const SceneView sv, uint
             const f3 wi = mk3(q.wix[i], q.wiy[i], q.wiz[i]);
             f2 uv; uv.x = q.u ? q.u[i] : 0.0f; uv.y = q.v ? q.v[i] : 0.0f;
             f2 s2; s2.x = q.s2x[i]; s2.y = q.s2y[i];
+            if (NEST) resolve_textured(sv, bsdf, uv);      // textured parameters of the row's record
             uint32_t texel; f2 tw1;
             const f3 refl = eval_reflectance(sv, bsdf, uv, texel, tw1);
             const NestInfo ni = nest_info<NEST>(bsdf, refl.x, refl.y, refl.z);
             auto child_refl = [&](const DevBsdf &rec) { uint32_t t; f2 w; return eval_reflectance(sv, rec, uv, t, w); };
-            ok = surface_bsdf_sample<NEST>(bsdf, ni, refl, [&](uint32_t k) { return geo.bsdf(k); }, child_refl, wi, q.s1[i], s2, bs, weight);
+            ok = surface_bsdf_sample<NEST>(bsdf, ni, refl, BsdfTable<NEST, FLAT>(geo, uv), child_refl, wi, q.s1[i], s2, bs, weight);
             if (!ok) weight = mk3(0.0f, 0.0f, 0.0f);
         }
         out[i] = bs.wo.x; out[n + i] = bs.wo.y; out[2u * n + i] = bs.wo.z; out[3u * n + i] = bs.pdf; out[4u * n + i] = bs.eta;

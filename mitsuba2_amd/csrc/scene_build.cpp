@@ -176,6 +176,44 @@ int bsdf_spectrum_slot(int32_t type, int32_t param) {
     }
 }
 
+// Textured parameters (mtsamd_texture_binding): the slots of DevBsdf::nested0/1 a binding fills (bit k = slot k: kTexAlphaU, kTexAlphaV,
+// kTexSpec, kTexTrans), or 0 with *why set: a record of this type has no such texture parameter in the reference, or none built here
+const char *texture_param_name(int32_t param) {
+    switch (param) {
+    case MTSAMD_PARAM_REFLECTANCE: return "reflectance";
+    case MTSAMD_PARAM_SPECULAR_REFLECTANCE: return "specular_reflectance";
+    case MTSAMD_PARAM_SPECULAR_TRANSMITTANCE: return "specular_transmittance";
+    case MTSAMD_PARAM_ETA: return "eta";
+    case MTSAMD_PARAM_K: return "k";
+    case MTSAMD_PARAM_ALPHA: return "alpha";
+    case MTSAMD_PARAM_ALPHA_U: return "alpha_u";
+    case MTSAMD_PARAM_ALPHA_V: return "alpha_v";
+    default: return "(unknown)";
+    }
+}
+uint32_t texture_param_slots(int32_t type, int32_t param, const char **why) {
+    const bool conductor = type == MTSAMD_BSDF_CONDUCTOR || type == MTSAMD_BSDF_ROUGHCONDUCTOR;
+    const bool dielectric = type == MTSAMD_BSDF_DIELECTRIC || type == MTSAMD_BSDF_ROUGHDIELECTRIC || type == MTSAMD_BSDF_THINDIELECTRIC;
+    const bool plastic = type == MTSAMD_BSDF_PLASTIC || type == MTSAMD_BSDF_ROUGHPLASTIC;
+    const bool rough = type == MTSAMD_BSDF_ROUGHCONDUCTOR || type == MTSAMD_BSDF_ROUGHDIELECTRIC;
+    *why = "this model has no such parameter";
+    switch (param) {
+    case MTSAMD_PARAM_ALPHA: case MTSAMD_PARAM_ALPHA_U: case MTSAMD_PARAM_ALPHA_V:
+        if (type == MTSAMD_BSDF_ROUGHPLASTIC) { *why = "the roughness of roughplastic is a float (roughplastic.cpp:222), not a texture"; return 0u; }
+        if (!rough) return 0u;
+        return param == MTSAMD_PARAM_ALPHA ? 3u : (param == MTSAMD_PARAM_ALPHA_U ? 1u : 2u);
+    case MTSAMD_PARAM_SPECULAR_REFLECTANCE:
+        if (plastic) { *why = "the mean of a (rough)plastic's specular_reflectance feeds its lobe weight: a texture there is not implemented"; return 0u; }
+        return (conductor || dielectric) ? 4u : 0u;
+    case MTSAMD_PARAM_SPECULAR_TRANSMITTANCE: return dielectric ? 8u : 0u;
+    case MTSAMD_PARAM_ETA: case MTSAMD_PARAM_K:
+        *why = "indices of refraction take no texture here (constants, or spectra in the spectral variant)"; return 0u;
+    case MTSAMD_PARAM_REFLECTANCE:
+        *why = "a textured reflectance is mtsamd_bsdf_desc::texture"; return 0u;
+    default: return 0u;
+    }
+}
+
 // the description with its spectra, as every stage sees it
 struct Input {
     const mtsamd_scene_desc &desc;
@@ -184,6 +222,7 @@ struct Input {
     std::vector<double> integrals;       // per spectrum (check_spectrum)
     uint64_t total = 0;                  // primitives
     bool any_nrm = false, any_uv = false;
+    const mtsamd_texture_binding *tex_bindings = nullptr; uint32_t n_tex_bindings = 0;       // textured parameters
     // BSDF `b` has a spectrum bound to the slot of `param` (slot >= 0: to that slot): the value in the description is ignored
     bool bound(uint32_t b, int32_t param, int slot = -1) const {
         for (uint32_t i = 0; i < n_bindings; ++i)
@@ -264,6 +303,36 @@ int validate_emitters(const mtsamd_scene_desc *desc, const std::vector<int32_t> 
     return MTSAMD_OK;
 }
 
+// textured parameters: every binding names a texture of the table and a parameter that the reference reads through a texture on a
+// plain record of that model; the types of the records and the texture table have been checked
+int check_texture_bindings(const Input &in) {
+    const mtsamd_scene_desc *desc = &in.desc;
+    if (in.n_tex_bindings && !in.tex_bindings) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_create_with_textures: null argument");
+    std::vector<uint32_t> taken(desc->bsdf_count, 0u);       // slots bound so far, per record
+    for (uint32_t i = 0; i < in.n_tex_bindings; ++i) {
+        const mtsamd_texture_binding &b = in.tex_bindings[i];
+        const char *name = texture_param_name(b.param);
+        if (desc->spectral) {
+            if (b.param == MTSAMD_PARAM_ALPHA || b.param == MTSAMD_PARAM_ALPHA_U || b.param == MTSAMD_PARAM_ALPHA_V)
+                return fail(MTSAMD_ERR_UNSUPPORTED, "eval_1(): a bitmap / checkerboard %s is converted into spectra in the spectral variant (bitmap.cpp:218-222); use a constant", name);
+            return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: a textured %s is implemented for the RGB variant only", i, name);
+        }
+        if (b.bsdf >= desc->bsdf_count) return fail(MTSAMD_ERR_INVALID, "binding %u: bsdf index %u out of range", i, b.bsdf);
+        const int32_t type = desc->bsdfs[b.bsdf].type;
+        if (type == MTSAMD_BSDF_BLEND || type == MTSAMD_BSDF_MASK)
+            return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: bsdf %u is a blendbsdf / mask: bind %s on its children, which are records of their own", i, b.bsdf, name);
+        const char *why;
+        const uint32_t slots = texture_param_slots(type, b.param, &why);
+        if (!slots) return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: bsdf %u (type %d) takes no texture for %s: %s", i, b.bsdf, type, name, why);
+        if (b.texture < 0 || (uint32_t) b.texture >= desc->texture_count) return fail(MTSAMD_ERR_INVALID, "binding %u: invalid texture index %d for %s", i, b.texture, name);
+        if ((uint32_t) b.texture >= kMaxParamTextures) return fail(MTSAMD_ERR_UNSUPPORTED, "binding %u: texture index %d for %s: a parameter can name the first %u textures only", i, b.texture, name, kMaxParamTextures);
+        if (taken[b.bsdf] & slots)       // roughconductor.cpp:173-177: 'alpha' together with 'alpha_u' / 'alpha_v', or a parameter given twice
+            return fail(MTSAMD_ERR_INVALID, "binding %u: %s of bsdf %u is bound already (Microfacet model: please specify either 'alpha' or 'alpha_u'/'alpha_v'.)", i, name, b.bsdf);
+        taken[b.bsdf] |= slots;
+    }
+    return MTSAMD_OK;
+}
+
 int validate_bsdfs(const Input &in) {
     const mtsamd_scene_desc *desc = &in.desc;
     for (uint32_t b = 0; b < desc->bsdf_count; ++b) {
@@ -295,7 +364,7 @@ int validate_bsdfs(const Input &in) {
         if (td.kind == 0 && (!td.data || td.width < 2 || td.height < 2))
             return fail(MTSAMD_ERR_INVALID, "texture %u: image must be at least 2x2 pixels in size", t);      // bitmap.cpp:101-107
     }
-    return MTSAMD_OK;
+    return check_texture_bindings(in);
 }
 
 int validate(Input &in, int32_t &environment) {
@@ -495,6 +564,29 @@ void bind_bsdf_spectra(const Input &in, SceneState &st) {
     if (in.n_spectra) st.general_bsdfs = true;       // the spectrum pool is read by the general step
 }
 
+// textured parameters (checked by check_texture_bindings): "1 + texture index" into the 16-bit fields of nested0 / nested1, which a plain
+// record does not use otherwise (DevBsdf), and the flags resolve_textured reads.  Such a scene runs the kernels of nested scenes: they
+// are the ones that treat the record of a hit as working storage.
+void bind_bsdf_textures(const Input &in, SceneState &st) {
+    for (uint32_t i = 0; i < in.n_tex_bindings; ++i) {
+        const mtsamd_texture_binding &bn = in.tex_bindings[i];
+        DevBsdf &d = st.bsdfs[bn.bsdf];
+        const char *why;
+        const uint32_t slots = texture_param_slots(in.desc.bsdfs[bn.bsdf].type, bn.param, &why);
+        const bool lum = in.desc.textures[bn.texture].kind == 0;       // Texture::eval_1 of a bitmap: luminance (bitmap.cpp:215-231)
+        for (int slot = 0; slot < 4; ++slot) {
+            if (!(slots & (1u << slot))) continue;
+            uint32_t &word = slot < 2 ? d.nested0 : d.nested1;
+            const int shift = 16 * (slot & 1);
+            word = (word & ~(65535u << shift)) | (((uint32_t) bn.texture + 1u) << shift);
+            if (lum && slot == kTexAlphaU) d.flags |= kBsdfAlphaULum;
+            if (lum && slot == kTexAlphaV) d.flags |= kBsdfAlphaVLum;
+        }
+        d.flags |= kBsdfTexParams;
+        st.textured_params = st.nested_bsdfs = true;
+    }
+}
+
 int build_bsdfs(const Input &in, SceneState &st) {
     const mtsamd_scene_desc *desc = &in.desc;
     st.bsdfs.resize(desc->bsdf_count);
@@ -517,6 +609,7 @@ int build_bsdfs(const Input &in, SceneState &st) {
             if (int rc = spectral_bsdf_colours(in, b, st)) return rc;
     }
     bind_bsdf_spectra(in, st);
+    bind_bsdf_textures(in, st);
     return MTSAMD_OK;
 }
 
@@ -704,8 +797,10 @@ int build_envmap_emitter(const mtsamd_scene_desc *desc, HostScene &hs) {
 } // namespace
 
 int build_host_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
-                     const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, const BuildOptions &options, HostScene &hs) {
+                     const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, const BuildOptions &options, HostScene &hs,
+                     const mtsamd_texture_binding *tex_bindings, uint32_t n_tex_bindings) {
     Input in{ *desc, spectra, n_spectra, bindings, n_bindings };
+    in.tex_bindings = tex_bindings; in.n_tex_bindings = n_tex_bindings;
     hs = HostScene{};
     SceneState &st = hs.state;
     if (int rc = validate(in, st.environment)) return rc;
@@ -791,6 +886,12 @@ int set_bsdf_reflectance(SceneState &st, uint32_t bsdf, const float *rgb) {
 
 int set_bsdf_param(SceneState &st, uint32_t bsdf, int32_t kind, const float *value3) {
     DevBsdf &d = st.bsdfs[bsdf];
+    if (d.flags & kBsdfTexParams) {       // a textured parameter is edited through its texture (mtsamd_scene_update_texture), not set to a constant
+        const bool textured = kind == MTSAMD_PARAM_ALPHA ? (bsdf_param_texture(d, kTexAlphaU) || bsdf_param_texture(d, kTexAlphaV))
+                            : kind == MTSAMD_PARAM_SPECULAR_REFLECTANCE ? bsdf_param_texture(d, kTexSpec) != 0u
+                            : kind == MTSAMD_PARAM_SPECULAR_TRANSMITTANCE ? bsdf_param_texture(d, kTexTrans) != 0u : false;
+        if (textured) return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: %s holds a texture; update the texture instead of setting a constant", bsdf, texture_param_name(kind));
+    }
     if (st.spectral) {       // colours become srgb spectra; eta / k must stay uniform spectra (one value); alpha is a plain number
         if (kind == MTSAMD_PARAM_REFLECTANCE || kind == MTSAMD_PARAM_SPECULAR_REFLECTANCE || kind == MTSAMD_PARAM_SPECULAR_TRANSMITTANCE) {
             float DevBsdf::*f0, DevBsdf::*f1;

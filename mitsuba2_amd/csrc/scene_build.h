@@ -41,6 +41,8 @@ struct SceneState {
     int32_t environment = -1;        // index of the `constant` / `envmap` emitter
     bool general_bsdfs = false;      // any BSDF other than one-sided `diffuse`: the kernels with the BSDF switch are used
     bool nested_bsdfs = false;       // blendbsdf / mask: the fused schedule (k_bounce*, k_direct) is the one that carries the nesting code
+    bool textured_params = false;    // some record reads alpha / specular colours from a texture (kBsdfTexParams): implies nested_bsdfs, whose
+                                     // kernels resolve them; the setters refuse such a parameter and the adjoints such a scene
     bool non_diffuse_bsdfs = false;  // any BSDF other than `diffuse` (one- or two-sided): what the adjoint path replay cannot differentiate
     bool delta_emitters = false;     // point / spot / directional emitters: handled by the same general kernels
     bool spectral = false;
@@ -92,9 +94,11 @@ struct HostScene {
     DevEnvmap dev_env{};                                // all fields but the two device pointers
 };
 
-// Returns the ABI error code; the error text is set exactly as mtsamd_scene_create sets it.
+// Returns the ABI error code; the error text is set exactly as mtsamd_scene_create sets it.  tex_bindings: the textured parameters of
+// mtsamd_scene_create_with_textures; they end up in the records (DevBsdf::nested0/1 and flags), so state.bsdfs shows them.
 int build_host_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
-                     const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, const BuildOptions &options, HostScene &hs);
+                     const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, const BuildOptions &options, HostScene &hs,
+                     const mtsamd_texture_binding *tex_bindings = nullptr, uint32_t n_tex_bindings = 0);
 
 // ---- host half of the setters: they edit `st` and name what the device copy now lacks ------------------------------------------
 // One scalar parameter of a BSDF record: which float(s) of DevBsdf it is.  false: the model has no such (differentiable) parameter.

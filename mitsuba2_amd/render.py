@@ -656,6 +656,20 @@ class Scene:
             md[i].bsdf, md[i].emitter = int(m["bsdf"]), int(m.get("emitter", -1))
         tex = []                       # bitmap textures (src/textures/bitmap.cpp): reflectance = dict(type="bitmap", data=(H,W,3))
         self._bsdf_texture = {}
+        self._param_texture = {}       # (bsdf record, parameter name) -> texture index: the textured parameters beside the reflectance
+        tex_bindings = []              # (bsdf record, mtsamd_bsdf_param, texture index): mtsamd_texture_binding
+
+        def add_texture(spec):
+            kind = spec.get("type")
+            if kind not in ("bitmap", "checkerboard"):
+                raise RuntimeError("Texture plugin '%s' is not supported by this backend (bitmap, checkerboard)" % kind)
+            data = None
+            if kind == "bitmap":
+                data = _f32(spec["data"])
+                if data.ndim != 3 or data.shape[2] != 3:
+                    raise RuntimeError("bitmap texture: expected (H, W, 3) linear RGB data")
+            tex.append((kind, data, spec))
+            return len(tex) - 1
         from . import bsdfs as B
         from . import spectrum as S
         self._bsdf_records = [B.normalize(b) for b in bsdfs]      # plugin defaults / validation (src/bsdfs/*.cpp constructors)
@@ -667,19 +681,8 @@ class Scene:
             bd[i].nested = (C.c_int32 * 2)(*n.get("nested", [-1, -1]))
             refl = n["reflectance"]
             if isinstance(refl, dict):
-                kind = refl.get("type")
-                if kind not in ("bitmap", "checkerboard"):
-                    raise RuntimeError("Texture plugin '%s' is not supported by this backend (bitmap, checkerboard)" % kind)
-                if kind == "bitmap":
-                    data = _f32(refl["data"])
-                    if data.ndim != 3 or data.shape[2] != 3:
-                        raise RuntimeError("bitmap texture: expected (H, W, 3) linear RGB data")
-                else:
-                    data = None
                 bd[i].reflectance = (C.c_float * 3)(0.5, 0.5, 0.5)
-                bd[i].texture = len(tex)
-                self._bsdf_texture[i] = len(tex)
-                tex.append((kind, data, refl))
+                bd[i].texture = self._bsdf_texture[i] = add_texture(refl)
             else:
                 bd[i].reflectance = (C.c_float * 3)(*[float(x) for x in refl])
                 bd[i].texture = -1
@@ -688,6 +691,16 @@ class Scene:
             bd[i].int_ior, bd[i].ext_ior, bd[i].alpha_u, bd[i].alpha_v = n["int_ior"], n["ext_ior"], n["alpha_u"], n["alpha_v"]
             bd[i].distribution, bd[i].sample_visible, bd[i].nonlinear = n["distribution"], int(n["sample_visible"]), int(n["nonlinear"])
             bd[i].uniform_mask = n["uniform_mask"]
+            shared = {}                # a textured `alpha` is one texture behind alpha_u and alpha_v
+            for pname, spec in n.get("textures", {}).items():
+                if id(spec) not in shared:
+                    shared[id(spec)] = add_texture(spec)
+                self._param_texture[(i, pname)] = shared[id(spec)]
+            pt = {k: self._param_texture[(i, k)] for k in n.get("textures", {})}
+            if "alpha_u" in pt and pt.get("alpha_v") == pt["alpha_u"]:
+                tex_bindings.append((i, B.TEXTURE_PARAMS["alpha"], pt.pop("alpha_u")))
+                del pt["alpha_v"]
+            tex_bindings += [(i, B.TEXTURE_PARAMS[k], t) for k, t in pt.items()]
             for param, spec in (n.get("spectra", {}) if variant == "spectral" else {}).items():
                 # tabulated spectra replace the colour (RGB variant: the pre-integrated colour stays)
                 bindings.append((0, i, param, spec if "kind" in spec else S.parse(spec)))
@@ -731,7 +744,12 @@ class Scene:
             sd.spectral = 1
             sd.rgb2spec_path = srgb_coeff_path().encode()
         handle = C.c_void_p()
-        if bindings:
+        if tex_bindings:               # RGB variant only: the library refuses them in a spectral scene, with or without spectra
+            tb = (L.TextureBinding * len(tex_bindings))()
+            for i, (index, param, texture) in enumerate(tex_bindings):
+                tb[i].bsdf, tb[i].param, tb[i].texture = index, param, texture
+            L.check(lib.mtsamd_scene_create_with_textures(C.byref(sd), tb, len(tex_bindings), self._device_index, C.byref(handle)))
+        elif bindings:
             sp, bn = spectrum_descs([b[3] for b in bindings], keep), (L.SpectrumBinding * len(bindings))()
             for i, (target, index, param, _) in enumerate(bindings):
                 bn[i].target, bn[i].index, bn[i].param, bn[i].spectrum = target, index, param, i
@@ -771,9 +789,16 @@ class Scene:
     def set_bsdf_reflectance(self, index, rgb):
         L.check(L.lib().mtsamd_scene_set_bsdf_reflectance(self._handle, int(index), (C.c_float * 3)(*[float(x) for x in rgb])))
 
-    def texture_index(self, bsdf):
-        """Index of the bitmap texture attached to BSDF `bsdf` (None if its reflectance is constant)."""
-        return self._bsdf_texture.get(int(bsdf))
+    def texture_index(self, bsdf, param="reflectance"):
+        """Index of the texture behind a parameter of BSDF record `bsdf` (None if that parameter is constant): its (diffuse) reflectance
+        or blend weight by default, or "alpha_u", "alpha_v" ("alpha": the texture both share), "specular_reflectance",
+        "specular_transmittance"."""
+        if param in ("reflectance", "diffuse_reflectance", "weight", "opacity"):
+            return self._bsdf_texture.get(int(bsdf))
+        if param == "alpha":
+            u, v = self._param_texture.get((int(bsdf), "alpha_u")), self._param_texture.get((int(bsdf), "alpha_v"))
+            return u if u == v else None
+        return self._param_texture.get((int(bsdf), param))
 
     def update_texture(self, texture, data):
         """parameters_changed() for a BitmapTexture's `data` (bitmap.cpp:295-299); data: (H,W,3) tensor or array."""
