@@ -199,7 +199,8 @@ typedef struct {
 } mtsamd_texture_binding;
 /* mtsamd_scene_create for a scene with such bindings; mtsamd_scene_create is its case of no bindings.  Such a scene renders with the
  * fused kernels that blendbsdf / mask scenes run (every `pipeline` value gives the same samples).  mtsamd_scene_set_bsdf_param refuses a
- * parameter that holds a texture, and the adjoint entry points refuse such a scene. */
+ * parameter that holds a texture.  The texels of such bitmaps are differentiated by mtsamd_render_adjoint_param_textures; the other adjoint
+ * entry points refuse such a scene. */
 MTSAMD_API int mtsamd_scene_create_with_textures(const mtsamd_scene_desc *desc, const mtsamd_texture_binding *bindings, uint32_t n_bindings,
                                       int device, mtsamd_scene **out);
 /* Texture::eval of one spectrum (regular.cpp:68-75, irregular.cpp:76-83, blackbody.cpp:64-83) at n wavelengths: runs the device function
@@ -462,7 +463,8 @@ MTSAMD_API int mtsamd_render_adjoint_envmap(mtsamd_scene *scene, const mtsamd_re
 /* Parameters of the BSDF models beyond `diffuse` (what traverse() exposes of e.g. roughconductor.cpp:393-404, plastic.cpp:299-307):
  * REFLECTANCE = diffuse.reflectance / (rough)plastic.diffuse_reflectance, SPECULAR_REFLECTANCE, SPECULAR_TRANSMITTANCE (dielectrics),
  * ETA / K (conductors), ALPHA (isotropic roughness of roughconductor / roughdielectric; one component).  ALPHA_U / ALPHA_V name one
- * roughness alone and exist for mtsamd_texture_binding only: the setters and the parameter adjoint do not take them. */
+ * roughness alone and exist for mtsamd_texture_binding and mtsamd_render_adjoint_param_textures only: the setters and the parameter
+ * adjoint do not take them. */
 typedef enum { MTSAMD_PARAM_REFLECTANCE = 0, MTSAMD_PARAM_SPECULAR_REFLECTANCE = 1, MTSAMD_PARAM_ETA = 2, MTSAMD_PARAM_K = 3, MTSAMD_PARAM_ALPHA = 4,
                MTSAMD_PARAM_SPECULAR_TRANSMITTANCE = 5, MTSAMD_PARAM_ALPHA_U = 6, MTSAMD_PARAM_ALPHA_V = 7 } mtsamd_bsdf_param;
 /* parameters_changed() of a BSDF after one of these parameters was edited (constants): value3 = 3 floats (ALPHA: 1).  Spectral
@@ -486,6 +488,26 @@ MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_ren
  * concatenated, offsets from mtsamd_scene_texture_info), ACCUMULATED into.  Needs 0 <= max_depth <= 16; no blendbsdf / mask. */
 MTSAMD_API int mtsamd_render_adjoint_textures(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
                                    const float *film_dev, float *grad_textures_dev, void *stream);
+/* The derivative with respect to the texels of bitmaps bound to BSDF PARAMETERS (mtsamd_texture_binding; 'bsdf.alpha.data',
+ * 'bsdf.specular_reflectance.data', ...: src/textures/bitmap.cpp:295-299 behind roughconductor.cpp:393-404) in any RGB scene of plain BSDF
+ * records the path integrator renders.  param = MTSAMD_PARAM_ALPHA_U, _ALPHA_V, _ALPHA (alpha_u then alpha_v), _SPECULAR_REFLECTANCE,
+ * _SPECULAR_TRANSMITTANCE, or -1 for all four slots in turn; every slot is one replay of every camera sample with its PCG32 stream, whose
+ * vertices are swept backwards as mtsamd_render_adjoint_textures sweeps them.  Sampling is detached as in mtsamd_render_adjoint_param:
+ * directions, pdfs, lobe choices, MIS weights AND the Russian-roulette probability are those of the primal path, so the texel gradients of
+ * a uniform map sum to what mtsamd_render_adjoint_param gives for the constant.  The model code is differentiated by a central difference
+ * at the fixed directions, between two copies of the record perturbed in the slot after the lookup: step h, absolute and the same at
+ * every hit (<= 0: 1 % of the value looked up at the hit, of at least 0.05).  h MUST STAY BELOW THE SMALLEST ROUGHNESS OF THE MAP: nothing
+ * clamps alpha - h.  A colour slot moves its three channels together (the models are diagonal in their specular colours); a roughness
+ * reaches the RGB texel through what Texture::eval_1 applied, the luminance weights of a bitmap.  A texture bound to alpha_u and one
+ * bound to alpha_v each receive their own replay.  A texture bound to ALPHA (one lookup behind both roughnesses) is one parameter: the
+ * alpha_u replay moves alpha_u and alpha_v of such a record together -- the central difference mtsamd_render_adjoint_param(ALPHA) takes --
+ * and the alpha_v replay leaves the record alone, so the two replays of ALPHA still add up to its total derivative (adding the two
+ * partial differences instead would miss the mixed third derivatives, 0.8 % at alpha = 0.1, h = 0.01).  A discrete lobe (conductor, dielectric,
+ * thindielectric) counts where both perturbed records re-sample the very direction of the primal path.  Checkerboards have no texels.
+ * grad_textures_dev: the layout of mtsamd_render_adjoint, ACCUMULATED into; a slot that no record binds leaves it untouched.  Needs
+ * 0 <= max_depth <= 16; refuses spectral scenes, blendbsdf / mask records and any other param. */
+MTSAMD_API int mtsamd_render_adjoint_param_textures(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
+                                         const float *film_dev, int32_t param, float h, float *grad_textures_dev, void *stream);
 /* Spectral variant: the derivative with respect to the reflectance family -- diffuse.reflectance and (rough)plastic.diffuse_reflectance
  * (plain or inside `twosided`), given as a constant `srgb` colour or as a bitmap -- in ANY spectral scene the path integrator renders.
  * The film channels differentiated are the X, Y, Z the spectral variant writes (with or without film_rgb).  Every camera sample is

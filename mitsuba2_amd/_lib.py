@@ -126,6 +126,7 @@ SYMBOLS = {
     "mtsamd_render_adjoint": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp]),
     "mtsamd_render_adjoint_envmap": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, vp, vp]),
     "mtsamd_render_adjoint_textures": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, vp, vp]),
+    "mtsamd_render_adjoint_param_textures": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, C.c_int32, C.c_float, vp, vp]),
     "mtsamd_render_adjoint_spectral": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, vp, vp, vp]),
     "mtsamd_render_adjoint_spectral_emitters": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, vp, vp, vp]),
     "mtsamd_scene_update_envmap": (C.c_int, [vp, f32p, C.c_int32]),

@@ -7,7 +7,10 @@ The reference records the whole render in Enoki's autodiff graph and calls ``ek.
 the ordinary wavefront render into an R,G,B,A,W film, and the backward pass is ``mtsamd_render_adjoint``: every camera
 sample is replayed with the same PCG32 stream and its vertices are swept backwards (``k_adjoint`` in
 ``csrc/kernels.hip``); outside diffuse scenes bitmap texels of diffuse / (rough)plastic reflectances go through
-``mtsamd_render_adjoint_textures`` (``k_adjoint_tex``, the same sweep over the general path step).  PyTorch only provides the autograd plumbing (as ``render_torch`` does in the reference,
+``mtsamd_render_adjoint_textures`` (``k_adjoint_tex``, the same sweep over the general path step), and the texels of bitmaps bound to
+``alpha`` / ``alpha_u`` / ``alpha_v`` / ``specular_reflectance`` / ``specular_transmittance`` (``'<bsdf>.alpha.data'``, ...) through
+``mtsamd_render_adjoint_param_textures`` (``k_adjoint_param_tex``: that sweep with a central difference of the model code, one replay per
+parameter slot).  PyTorch only provides the autograd plumbing (as ``render_torch`` does in the reference,
 ``autodiff.py:380-482``).
 """
 import ctypes as C
@@ -42,6 +45,40 @@ def _texture_parameters(records):
             continue
         name = b.get("id", "bsdf_%d" % i) + (".brdf_0" if b.get("twosided") else "")
         out.append(("%s.%s.data" % (name, names[b["type"]]), i, refl["data"]))
+    return out
+
+
+def _parameter_texture_parameters(scene):
+    """The bitmap texels mtsamd_render_adjoint_param_textures differentiates: bitmaps bound to alpha / alpha_u / alpha_v of the rough
+    models and to specular_reflectance / specular_transmittance of the conductors and dielectrics, on top-level plain records (inside
+    `twosided`: "brdf_0").  Returns (key, texture index, slots, texels): slots are the mtsamd_bsdf_param values whose replays add up to the
+    gradient of the texture.  A texture that serves more than one binding gets no key -- its texels would have to collect the replays of
+    every slot that reads it; the `alpha` pair is the exception ('<id>.alpha.data': alpha_u and alpha_v of ONE record sharing a texture,
+    the sum of the two replays).  Checkerboards have no texels; a scene with a blendbsdf / mask record has no such keys (the entry
+    point refuses it)."""
+    records = scene._bsdf_records
+    if any(b["type"] in (B.BLEND, B.MASK) for b in records):
+        return []
+    users = {}
+    for (i, pname), t in getattr(scene, "_param_texture", {}).items():
+        users.setdefault(t, []).append((i, pname))
+    out = []
+    for t, used in sorted(users.items()):
+        i = used[0][0]
+        names = sorted(p for _, p in used)
+        if i >= len(records) or any(j != i for j, _ in used):
+            continue
+        spec = records[i]["textures"][names[0]]
+        if spec.get("type") != "bitmap":
+            continue
+        if names == ["alpha_u", "alpha_v"]:
+            pname, slots = "alpha", (B.TEXTURE_PARAMS["alpha_u"], B.TEXTURE_PARAMS["alpha_v"])
+        elif len(names) == 1:
+            pname, slots = names[0], (B.TEXTURE_PARAMS[names[0]],)
+        else:
+            continue
+        name = records[i].get("id", "bsdf_%d" % i) + (".brdf_0" if records[i].get("twosided") else "")
+        out.append(("%s.%s.data" % (name, pname), t, slots, spec["data"]))
     return out
 
 
@@ -112,14 +149,15 @@ class ParameterMap:
                 if b["type"] not in types:
                     continue
                 src = b["reflectance"] if kind == 0 else b[pname]
-                if isinstance(src, dict):
-                    continue              # textured: no constant parameter
+                if isinstance(src, dict) or pname in b.get("textures", {}):
+                    continue              # textured: no constant parameter (the setter refuses it; its texels have a '.data' key)
                 if _is_spectral(scene) and (kind in (2, 3) or (b.get("uniform_mask", 0) >> {0: 0, 1: 1, 5: 2}[kind]) & 1 or kind in b.get("spectra", {})):
                     continue              # spectral variant: eta / k, `uniform` and tabulated spectra are not srgb colours
                 key = "%s.%s.value" % (name, pname)
                 self.properties[key] = torch.as_tensor([float(x) for x in src], dtype=torch.float32, device=dev)
                 self._kind[key] = ("bsdf_param", flat_index, kind)
-            if b["type"] in (B.ROUGHCONDUCTOR, B.ROUGHDIELECTRIC) and b["alpha_u"] == b["alpha_v"]:
+            if b["type"] in (B.ROUGHCONDUCTOR, B.ROUGHDIELECTRIC) and b["alpha_u"] == b["alpha_v"] and \
+                    not {"alpha_u", "alpha_v"} & set(b.get("textures", {})):
                 key = name + ".alpha.value"
                 self.properties[key] = torch.as_tensor([float(b["alpha_u"])], dtype=torch.float32, device=dev)
                 self._kind[key] = ("bsdf_param", flat_index, 4)
@@ -127,6 +165,10 @@ class ParameterMap:
         for key, i, data in (_texture_parameters(scene._bsdf_records) if not diffuse_scene and not _is_spectral(scene) else []):
             self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
             self._kind[key] = ("texture", scene.texture_index(i), i)
+        # bitmaps bound to alpha / specular colours (RGB scenes): one replay per slot, mtsamd_render_adjoint_param_textures
+        for key, t, slots, data in (_parameter_texture_parameters(scene) if not _is_spectral(scene) else []):
+            self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
+            self._kind[key] = ("param_texture", t, slots)
         # spectral variant with `replay`: the same texel keys, in diffuse and general scenes alike (mtsamd_render_adjoint_spectral)
         for key, i, data in (_texture_parameters(scene._bsdf_records) if self._replay else []):
             self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
@@ -197,7 +239,7 @@ class ParameterMap:
                 with torch.no_grad():
                     v.clamp_(min=0.0)
             seen[k] = (v, v._version)
-            if kind == "texture":
+            if kind in ("texture", "param_texture"):
                 self._scene.update_texture(idx, v)
             elif kind == "emitter":
                 self._scene.set_emitter_radiance(idx, v.detach().cpu().tolist())
@@ -350,9 +392,18 @@ class _Render(torch.autograd.Function):
         if "envmap" in kinds:
             g_env = torch.zeros_like(next(pmap[k] for k in keys if pmap._kind[k][0] == "envmap"))
             L.check(L.lib().mtsamd_render_adjoint_envmap(scene._handle, C.byref(d), _ptr(gi), _ptr(film), _ptr(g_env), _stream()))
+        # texels behind alpha / specular colours: one replay per slot the kept keys need, each into a zeroed buffer of its own
+        g_slot = {}
+        for slot in sorted({s for k in keys if pmap._kind[k][0] == "param_texture" for s in pmap._kind[k][2]}):
+            g_slot[slot] = torch.zeros_like(g_tex)
+            L.check(L.lib().mtsamd_render_adjoint_param_textures(scene._handle, C.byref(d), _ptr(gi), _ptr(film), int(slot), float(pmap.fd_step),
+                                                                 _ptr(g_slot[slot]), _stream()))
         grads = []
         for k in keys:
             kind, idx, _ = pmap._kind[k]
+            if kind == "param_texture":
+                grads.append(sum(_texture_slice(scene, g_slot[s], idx) for s in pmap._kind[k][2]))
+                continue
             if kind == "bsdf_param":          # one replay per scalar component (forward-mode derivative carried beside the path)
                 n = pmap[k].numel()
                 g = torch.zeros(n, dtype=torch.float32, device=dev)

@@ -1608,6 +1608,44 @@ int mtsamd_render_adjoint_textures(mtsamd_scene *s, const mtsamd_render_desc *d,
     return MTSAMD_OK;
 }
 
+int mtsamd_render_adjoint_param_textures(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, int32_t param,
+                                         float h, float *grad_tex, void *stream_) {
+    AdjointParams a{};
+    if (int rc = fill_adjoint(s, d, dimage, film, a)) return rc;
+    if (!grad_tex) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (d->max_depth < 0 || d->max_depth > 16)
+        return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    for (const DevBsdf &b : s->bsdfs)
+        if (b.type >= kBsdfBlend) return fail(MTSAMD_ERR_UNSUPPORTED, "the textured-parameter adjoint does not handle blendbsdf / mask materials");
+    if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the adjoint pass differentiates the path integrator");
+    int slots[4], n_slots = 0;
+    switch (param) {
+    case MTSAMD_PARAM_ALPHA_U: slots[n_slots++] = kTexAlphaU; break;
+    case MTSAMD_PARAM_ALPHA_V: slots[n_slots++] = kTexAlphaV; break;
+    case MTSAMD_PARAM_ALPHA: slots[n_slots++] = kTexAlphaU; slots[n_slots++] = kTexAlphaV; break;
+    case MTSAMD_PARAM_SPECULAR_REFLECTANCE: slots[n_slots++] = kTexSpec; break;
+    case MTSAMD_PARAM_SPECULAR_TRANSMITTANCE: slots[n_slots++] = kTexTrans; break;
+    case -1: for (int k = 0; k < 4; ++k) slots[n_slots++] = k; break;
+    default:
+        return fail(MTSAMD_ERR_INVALID, "parameter %d cannot hold a differentiable texture (alpha, alpha_u, alpha_v, specular_reflectance, specular_transmittance, or -1 for all)", param);
+    }
+    a.grad_tex = grad_tex;
+    a.pg_inv_2h = h;                  // k_adjoint_param_tex: the step itself
+    a.rp.sv.general = std::max(a.rp.sv.general, 1u);
+    for (int k = 0; k < n_slots; ++k) {
+        bool bound = false;               // a slot no record binds launches nothing; a textured `alpha` (one texture behind both) is alpha_u's
+        for (const DevBsdf &b : s->bsdfs) {
+            if (!(b.flags & kBsdfTexParams) || bsdf_param_texture(b, slots[k]) == 0u) continue;
+            if (slots[k] == kTexAlphaV && bsdf_param_texture(b, kTexAlphaU) == bsdf_param_texture(b, kTexAlphaV)) continue;
+            bound = true;
+        }
+        if (!bound) continue;
+        a.pg_bsdf = slots[k];
+        HIP_TRY(launch_adjoint_param_tex(a, (hipStream_t) stream_));
+    }
+    return MTSAMD_OK;
+}
+
 int mtsamd_render_adjoint_spectral(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, float *grad_bsdf,
                                    float *grad_tex, void *stream_) {
     AdjointParams a{};

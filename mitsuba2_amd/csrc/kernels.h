@@ -143,6 +143,9 @@ struct AdjointParams {
     float *grad_env;            // k_adjoint_env: envmap height * width * 3, accumulated
     // k_adjoint_param: record `pg_bsdf` of the BSDF table with ONE scalar parameter at +h / -h, 1 / (2 h), and the float the derivative is added to
     int32_t pg_bsdf; DevBsdf pg_plus, pg_minus; float pg_inv_2h; float *grad_param;
+    // k_adjoint_param_tex reads two of these fields in its own way (no field of its own: the argument block of the kernels above stays
+    // what it was): pg_bsdf = the slot of the launch (kTexAlphaU .. kTexTrans), pg_inv_2h = the step h itself (<= 0: 1 % of the value at
+    // the hit); it adds into grad_tex
 };
 
 struct RayStreams {
@@ -217,6 +220,7 @@ hipError_t launch_adjoint(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_env(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_param(const AdjointParams &a, hipStream_t s);
 hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s);      // k_adjoint_tex: into grad_tex (not null)
+hipError_t launch_adjoint_param_tex(const AdjointParams &a, hipStream_t s);      // k_adjoint_param_tex: one slot of the textured parameters, into grad_tex (not null)
 // k_adjoint_spectral accumulates in the coefficients (a, b, c) of x = a u^2 + b u + c over the centred wavelength u = (l - kCoeffMid) / kCoeffHalf
 constexpr float kCoeffMid = 595.0f, kCoeffHalf = 235.0f;
 // k_adjoint_spectral: gradients w.r.t. the srgb MODEL COEFFICIENTS (centred basis) of the reflectance family, into grad_bsdf / grad_tex (either may be null)

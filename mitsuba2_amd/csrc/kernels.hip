@@ -3730,4 +3730,174 @@ hipError_t launch_spectrum_eval(const DevSpectrum *headers, const float *data, u
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// (Last in the file on purpose: the assembler numbers functions and long-branch labels in the order the kernels are emitted, and
+// scripts/isa_compare.py compares every kernel above with its text before this one existed.)
+// Derivative w.r.t. the texels of bitmaps bound to a BSDF PARAMETER (resolve_textured: alpha_u / alpha_v of the rough models, the specular
+// colours of the conductors and dielectrics) in any RGB scene of plain records: the backward sweep of k_adjoint_tex joined with the central
+// difference of ParamGradProbe.  One launch differentiates ONE slot (A.pg_bsdf: kTexAlphaU .. kTexTrans, uniform over the launch) for every
+// record that binds it (a textured `alpha` -- one bitmap behind alpha_u and alpha_v -- is differentiated as the one parameter it is, in
+// the alpha_u launch: ParamTexRecorder::surface).  Sampling is detached as in k_adjoint_param: directions, pdfs, lobe choices, MIS
+// weights AND the Russian-roulette probability are those of the primal path (only invq is recorded, there is no rr_channel term), so
+// the texel gradients of a uniform map sum to what k_adjoint_param gives for the constant, at any depth.
+//
+// What the replay keeps of one vertex: T, invq, E, Nc, W as VertexRecG, and dNc / dW = (f(rec + h) - f(rec - h)) / 2h with respect to the
+// slot's parameter at the vertex, per colour channel.  The two working records are perturbed AFTER resolve_textured, as
+// ParamGradProbe::dvalue perturbs bp / bm.  A colour slot moves its three channels with one +- pair (the models are diagonal in their
+// specular colours); a roughness slot differentiates every channel with respect to the scalar, `lum` says how resolve_textured made it
+// from the RGB texel.  texel / w1: the bilinear footprint of the SLOT's lookup (kNoPrim: constant or checkerboard -- no gradient).
+struct VertexRecP {
+    f3 T; float invq;
+    f3 E; uint32_t texel;
+    f3 Nc; int32_t texture;
+    f3 W; uint32_t lum;
+    f3 dNc; f3 dW; f2 w1;
+};
+static_assert(sizeof(VertexRecP) <= sizeof(VertexRecG), "the per-lane record array of k_adjoint_param_tex stays within that of k_adjoint_tex");
+
+// Fills the VertexRecP of one step.  The step is absolute (`h`, the same at every vertex; <= 0: 1 % of the value looked up at the hit,
+// of at least 0.05 as mtsamd_render_adjoint_param takes it); it must stay below the smallest roughness of the map.
+struct ParamTexRecorder {
+    static constexpr bool kFactoredEmitter = false, kMirrorTwoSided = false, kSamples = true;
+    VertexRecP &r;
+    const SceneView &sv; int slot; float h;
+    bool here;                  // does the record of the hit read the slot from a bitmap?
+    bool pair;                  // ... alpha_u AND alpha_v from that one bitmap (a textured `alpha`): the lookup moves both
+    f3 hs, i2h;                 // the step per channel at this vertex and 1 / ((v + h) - (v - h))
+    f3 nc, dnc;                 // Nc and dNc of the emitter sample, recorded once it is known to be unoccluded
+    MTS_DEV void perturbed(const DevBsdf &b, DevBsdf &bp, DevBsdf &bm) const {
+        bp = b; bm = b;
+        if (slot == kTexAlphaU) {
+            bp.alpha_u = b.alpha_u + hs.x; bm.alpha_u = b.alpha_u - hs.x;
+            if (pair) { bp.alpha_v = b.alpha_v + hs.x; bm.alpha_v = b.alpha_v - hs.x; }
+        } else if (slot == kTexAlphaV) { bp.alpha_v = b.alpha_v + hs.x; bm.alpha_v = b.alpha_v - hs.x; }
+        else if (slot == kTexSpec) {
+            bp.sr = b.sr + hs.x; bp.sg = b.sg + hs.y; bp.sb = b.sb + hs.z;
+            bm.sr = b.sr - hs.x; bm.sg = b.sg - hs.y; bm.sb = b.sb - hs.z;
+        } else {                // dielectrics: k.* holds the transmittance
+            bp.kr = b.kr + hs.x; bp.kg = b.kg + hs.y; bp.kb = b.kb + hs.z;
+            bm.kr = b.kr - hs.x; bm.kg = b.kg - hs.y; bm.kb = b.kb - hs.z;
+        }
+    }
+    // d(value)/d(parameter) of the model at fixed directions, per channel
+    MTS_DEV f3 dvalue(const DevBsdf &b, f3 refl, f3 wi, f3 wo) const {
+        DevBsdf bp, bm; f3 vp, vm; float pp, pm;
+        perturbed(b, bp, bm);
+        bsdf_eval_pdf(bp, refl, wi, wo, vp, pp);
+        bsdf_eval_pdf(bm, refl, wi, wo, vm, pm);
+        return mk3((vp.x - vm.x) * i2h.x, (vp.y - vm.y) * i2h.y, (vp.z - vm.z) * i2h.z);
+    }
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) {
+        static_assert(GENERAL && DEFER == 0, "the textured-parameter gradient rides on the general fused step");
+        r.T = s.thr; r.invq = 1.0f;
+        r.E = r.Nc = r.W = r.dNc = r.dW = mk3(0.0f, 0.0f, 0.0f);
+        r.texel = kNoPrim; r.texture = -1; r.lum = 0u; r.w1.x = r.w1.y = 0.0f;
+        here = pair = false;
+    }
+    MTS_DEV void emitted(float ew, int32_t, f3 le) { r.E = mk3(ew * le.x, ew * le.y, ew * le.z); }
+    MTS_DEV void escaped(const SceneView &, const PathState &, const DevEmitter &, float ew, f3 le) { emitted(ew, -1, le); }
+    MTS_DEV void roulette(f3, float, float rq, bool) { r.invq = rq; }
+    // `bsdf` is the working record after resolve_textured; the footprint of the slot's lookup is taken here, by one more lookup
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, f3, uint32_t, f2, f3) {
+        here = pair = false;
+        const uint32_t ti = (bsdf.flags & kBsdfTexParams) ? bsdf_param_texture(bsdf, slot) : 0u;
+        if (!ti) return;
+        // one texture behind alpha_u and alpha_v is ONE parameter, alpha(texel) -> f(alpha, alpha): its central difference moves both
+        // roughnesses together, in the alpha_u launch, and the alpha_v launch leaves the record alone.  (The sum of the two partial
+        // differences misses the mixed third derivatives: 0.8 % of the derivative of a GGX lobe at alpha = 0.1, h = 0.01.)
+        if (slot <= kTexAlphaV && bsdf_param_texture(bsdf, kTexAlphaU) == bsdf_param_texture(bsdf, kTexAlphaV)) {
+            if (slot == kTexAlphaV) return;
+            pair = true;
+        }
+        uint32_t texel; f2 w1;
+        f3 v = eval_reflectance<false>(sv, bsdf, si.uv, texel, w1, (int32_t) (ti - 1u));
+        if (texel == kNoPrim) return;                        // a checkerboard has no texels
+        here = true;
+        r.texel = texel; r.w1 = w1; r.texture = (int32_t) (ti - 1u);
+        if (slot == kTexAlphaU) { r.lum = (bsdf.flags & kBsdfAlphaULum) ? 1u : 0u; v = mk3(bsdf.alpha_u, bsdf.alpha_u, bsdf.alpha_u); }
+        if (slot == kTexAlphaV) { r.lum = (bsdf.flags & kBsdfAlphaVLum) ? 1u : 0u; v = mk3(bsdf.alpha_v, bsdf.alpha_v, bsdf.alpha_v); }
+        hs = mk3(h, h, h);
+        if (!(h > 0.0f)) hs = mk3(0.01f * fmaxf(fabsf(v.x), 0.05f), 0.01f * fmaxf(fabsf(v.y), 0.05f), 0.01f * fmaxf(fabsf(v.z), 0.05f));
+        i2h = mk3(1.0f / ((v.x + hs.x) - (v.x - hs.x)), 1.0f / ((v.y + hs.y) - (v.y - hs.y)), 1.0f / ((v.z + hs.z) - (v.z - hs.z)));
+    }
+    MTS_DEV bool emitter_sample(const SceneView &, const DevBsdf &bsdf, f3 refl, const NeeTerms &t) {
+        nc = mk3((t.mis * t.bv.x) * t.spec.x, (t.mis * t.bv.y) * t.spec.y, (t.mis * t.bv.z) * t.spec.z);
+        dnc = mk3(0.0f, 0.0f, 0.0f);
+        if (here) {
+            const f3 dbv = dvalue(bsdf, refl, t.wi, t.wo);
+            dnc = mk3((t.mis * dbv.x) * t.spec.x, (t.mis * dbv.y) * t.spec.y, (t.mis * dbv.z) * t.spec.z);
+        }
+        return nc.x != 0.0f || nc.y != 0.0f || nc.z != 0.0f || dnc.x != 0.0f || dnc.y != 0.0f || dnc.z != 0.0f;
+    }
+    MTS_DEV void unoccluded(const SceneView &, const SurfaceInteraction &, f3, const NeeTerms &) { r.Nc = nc; r.dNc = dnc; }
+    // T_next = T' * W; dW at the sampled direction: d(value) / pdf for a smooth lobe, the re-sampled weight for a discrete one
+    MTS_DEV void bsdf_sampled(const SceneView &, const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, f3, const BsdfSample &bs, f3 weight, float s1, f2 s2) {
+        r.W = weight;
+        if (here && !bs.delta && bs.pdf > 0.0f) {
+            const f3 dv = dvalue(bsdf, refl, si.wi, bs.wo);
+            const float ip = rcp(bs.pdf);
+            r.dW = mk3(dv.x * ip, dv.y * ip, dv.z * ip);
+        } else if (here && bs.delta) {
+            // a discrete lobe (ParamGradProbe::bsdf_sampled): both perturbed records are re-sampled with the same numbers and count only
+            // if they land on the very direction of the primal sample
+            DevBsdf bp, bm; f3 wp, wm; BsdfSample bp_, bm_;
+            perturbed(bsdf, bp, bm);
+            const bool okp = bsdf_sample(bp, refl, si.wi, s1, s2, bp_, wp);
+            const bool okm = bsdf_sample(bm, refl, si.wi, s1, s2, bm_, wm);
+            if (okp && okm && bp_.delta && bm_.delta && bp_.wo.x == bs.wo.x && bp_.wo.y == bs.wo.y && bp_.wo.z == bs.wo.z &&
+                bm_.wo.x == bs.wo.x && bm_.wo.y == bs.wo.y && bm_.wo.z == bs.wo.z)
+                r.dW = mk3((wp.x - wm.x) * i2h.x, (wp.y - wm.y) * i2h.y, (wp.z - wm.z) * i2h.z);
+        }
+    }
+};
+
+// Every camera sample is replayed through the fused step of nested scenes (the one that resolves textured parameters) and swept
+// backwards:  b = delta Nc + W a,  a = delta E + invq b;  at a vertex whose record reads the slot from a bitmap
+//   colours:    gg[c] = T'_c (delta_c dNc_c + a_c dW_c)
+//   roughness:  g = sum_c T'_c (delta_c dNc_c + a_c dW_c), chained to the RGB texel by what resolve_textured applied: the luminance
+//               weights where the kBsdfAlpha?Lum flag is set, else (1, 0, 0)
+// is scattered over the footprint of the slot's lookup at the texture's grad_offset.
+template <bool FLAT>
+__global__ __launch_bounds__(kBlock) void k_adjoint_param_tex(const AdjointParams A) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = A.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    const int slot = A.pg_bsdf;
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < A.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        PathState s; const f3 delta = adjoint_sample(A, k, s);
+        if (delta.x == 0.0f && delta.y == 0.0f && delta.z == 0.0f) continue;       // every term below is proportional to delta
+        VertexRecP rec[kAdjointMaxDepth];
+        int n = 0;
+        Counters c = { 0u, 0u, 0u, 0u };
+        bool alive = true;
+        while (alive && n < kAdjointMaxDepth) {
+            ParamTexRecorder pr = { rec[n], P.sv, slot, A.pg_inv_2h };
+            alive = bounce_step<FLAT, 0, true, true>(P, lds, s, c, pr);
+            ++n;
+        }
+        f3 a = mk3(0.0f, 0.0f, 0.0f);
+        for (int v = n - 1; v >= 0; --v) {
+            const VertexRecP &r = rec[v];
+            if (r.texel != kNoPrim) {
+                const f3 Tp = r.T * r.invq;
+                float gg[3] = { Tp.x * fmaf(delta.x, r.dNc.x, a.x * r.dW.x), Tp.y * fmaf(delta.y, r.dNc.y, a.y * r.dW.y),
+                                Tp.z * fmaf(delta.z, r.dNc.z, a.z * r.dW.z) };
+                if (slot == kTexAlphaU || slot == kTexAlphaV) {
+                    const float g = (gg[0] + gg[1]) + gg[2];
+                    gg[0] = r.lum ? 0.212671f * g : g; gg[1] = r.lum ? 0.715160f * g : 0.0f; gg[2] = r.lum ? 0.072169f * g : 0.0f;
+                }
+                // a sample whose derivative is not finite is dropped, as k_adjoint_param drops it
+                if (isfinite(gg[0]) && isfinite(gg[1]) && isfinite(gg[2])) {
+                    const DevTexture t = P.sv.textures[r.texture];
+                    scatter_texel_grad(A.grad_tex, t, r.texel, r.w1, gg);
+                }
+            }
+            const f3 b = mk3(fmaf(delta.x, r.Nc.x, r.W.x * a.x), fmaf(delta.y, r.Nc.y, r.W.y * a.y), fmaf(delta.z, r.Nc.z, r.W.z * a.z));
+            a = mk3(delta.x * r.E.x + r.invq * b.x, delta.y * r.E.y + r.invq * b.y, delta.z * r.E.z + r.invq * b.z);
+        }
+    }
+}
+
+hipError_t launch_adjoint_param_tex(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_param_tex<true>, k_adjoint_param_tex<false>>(a, s); }
+
 } // namespace mtsamd

@@ -42,7 +42,8 @@ struct SceneState {
     bool general_bsdfs = false;      // any BSDF other than one-sided `diffuse`: the kernels with the BSDF switch are used
     bool nested_bsdfs = false;       // blendbsdf / mask: the fused schedule (k_bounce*, k_direct) is the one that carries the nesting code
     bool textured_params = false;    // some record reads alpha / specular colours from a texture (kBsdfTexParams): implies nested_bsdfs, whose
-                                     // kernels resolve them; the setters refuse such a parameter and the adjoints such a scene
+                                     // kernels resolve them; the setters refuse such a parameter and the adjoints such a scene (all but
+                                     // mtsamd_render_adjoint_param_textures, which differentiates the texels of these maps)
     bool non_diffuse_bsdfs = false;  // any BSDF other than `diffuse` (one- or two-sided): what the adjoint path replay cannot differentiate
     bool delta_emitters = false;     // point / spot / directional emitters: handled by the same general kernels
     bool spectral = false;
