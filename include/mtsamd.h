@@ -225,6 +225,30 @@ MTSAMD_API int mtsamd_scene_set_emitter_radiance(mtsamd_scene *scene, uint32_t e
  * asynchronous on `stream`.  Spectral variant: the texels are clamped to [0, 1] and converted to model coefficients on the host, as
  * scene creation converts them (the call waits for `stream` first and returns when the scene holds the new texels). */
 MTSAMD_API int mtsamd_scene_update_texture(mtsamd_scene *scene, uint32_t texture, const float *rgb, void *stream);
+/* Mesh `vertex_positions_buf` (mesh.cpp:781-804) of shape `shape`, i.e. parameters_changed({"vertex_positions_buf"}) of that mesh: its
+ * vertex and face counts and its face indices stay those of creation.  positions / normals: host OR device pointers (told apart as
+ * mtsamd_scene_update_texture tells them apart) to 3 * vertex_count floats of that mesh; `normals` is required exactly when the mesh was
+ * created with normals and an error otherwise (recompute_vertex_normals is left to the caller).  The accelerator keeps its topology and
+ * gets new boxes (a refit: on the device for hierarchy scenes); the area distribution of an emitter shape, the scene's bounding box,
+ * the bounding sphere in the constant / envmap / directional emitter records and the records of a flat scene follow.  Samples and
+ * queries afterwards equal, bit for bit, those of a scene created from the moved vertices.  Refused with MTSAMD_ERR_INVALID before
+ * anything is written: a shape index out of range, missing or surplus normals, a non-finite coordinate, an area emitter left without
+ * area ("DiscreteDistribution: no probability mass found!").  Every other setter's state is kept.  Waits for `stream` and returns when
+ * the scene is consistent. */
+MTSAMD_API int mtsamd_scene_set_vertex_positions(mtsamd_scene *scene, uint32_t shape, const float *positions, const float *normals, void *stream);
+/* Test aid: copies one device array of the accelerator to the host.  MTSAMD_ERR_INVALID unless `bytes` is that array's size. */
+enum {
+    MTSAMD_ACCEL_NODES = 0,      /* BVH2 nodes, 64 bytes each */
+    MTSAMD_ACCEL_QNODES = 1,     /* BVH2 nodes on the 16-bit grid, 32 bytes each */
+    MTSAMD_ACCEL_WNODES = 2,     /* BVH4 nodes in the encoding the build uses, 64 bytes each */
+    MTSAMD_ACCEL_TRIS = 3,       /* triangle slots, 48 bytes each */
+    MTSAMD_ACCEL_TRI_POS = 4,    /* 36 bytes per primitive */
+    MTSAMD_ACCEL_TRI_NRM = 5,    /* 36 bytes per primitive; empty if no mesh has normals */
+    MTSAMD_ACCEL_AREA_PMF = 6,   /* 4 bytes per primitive */
+    MTSAMD_ACCEL_AREA_CDF = 7,
+    MTSAMD_ACCEL_GRID = 8        /* q_lo[3], q_step[3] as the kernels receive them: 24 bytes */
+};
+MTSAMD_API int mtsamd_scene_read_accel(const mtsamd_scene *scene, int32_t which, void *host_dst, uint64_t bytes);
 
 /* ---- scene queries on SoA ray streams --------------------------------------
  * The stream layout follows the reference's device-stream precedent OptixParams

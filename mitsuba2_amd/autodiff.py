@@ -86,7 +86,7 @@ class ParameterMap:
     """Dictionary-like view of the differentiable scene parameters (util.py:16-130): torch tensors on the scene's GPU.
     Writes take effect in the scene after :meth:`update` (``parameters_changed``)."""
 
-    def __init__(self, scene, replay=False):
+    def __init__(self, scene, replay=False, geometry=False):
         self._scene = scene
         # spectral variant only: differentiate the reflectance family (constant srgb colours and bitmap texels of diffuse.reflectance /
         # (rough)plastic.diffuse_reflectance) by the spectral path replay, mtsamd_render_adjoint_spectral, instead of central differences,
@@ -196,6 +196,15 @@ class ParameterMap:
             self.properties[key] = torch.as_tensor(E.normalize(em)["radiance"], dtype=torch.float32, device=dev)
             self._kind[key] = ("emitter", e, e)
 
+        # '<shape id>.vertex_positions_buf' of every mesh (mesh.cpp:781-804): the flat 3N buffer.  Settable, not differentiable: there is
+        # no reparameterised integrator behind it (render() refuses a tensor that requires a gradient)
+        for i, m in enumerate(scene._dict["meshes"] if geometry else []):
+            key = m.get("id", "shape_%d" % i) + ".vertex_positions_buf"
+            self.properties[key] = torch.as_tensor(np.ascontiguousarray(m["positions"], np.float32).reshape(-1), dtype=torch.float32, device=dev).clone()
+            self._kind[key] = ("vertices", i, i)
+            # the scene was created from these positions: update() pushes the buffer only once it holds something else
+            self.__dict__.setdefault("_pushed", {})[key] = (self.properties[key], self.properties[key]._version)
+
     def __getitem__(self, k): return self.properties[k]
     def __contains__(self, k): return k in self.properties
     def __len__(self): return len(self.properties)
@@ -239,7 +248,9 @@ class ParameterMap:
                 with torch.no_grad():
                     v.clamp_(min=0.0)
             seen[k] = (v, v._version)
-            if kind in ("texture", "param_texture"):
+            if kind == "vertices":
+                self._scene.update_vertices(idx, v)
+            elif kind in ("texture", "param_texture"):
                 self._scene.update_texture(idx, v)
             elif kind == "emitter":
                 self._scene.set_emitter_radiance(idx, v.detach().cpu().tolist())
@@ -252,11 +263,14 @@ class ParameterMap:
                 self._scene.set_bsdf_reflectance(idx, v.detach().cpu().tolist())
 
 
-def traverse(scene, replay=False):
+def traverse(scene, replay=False, geometry=False):
     """mitsuba.python.util.traverse (util.py:132-179) for the supported parameters.  ``replay=True`` (spectral scenes; ignored for RGB
     ones) adds the bitmap texels of the reflectance family and the emitted colour of shapeless emitters, and differentiates the reflectance
-    family and the emitter family (envmap texels included) with one spectral path replay each per backward pass."""
-    return ParameterMap(scene, replay=replay)
+    family and the emitter family (envmap texels included) with one spectral path replay each per backward pass.  ``geometry=True`` adds
+    '<shape id>.vertex_positions_buf' of every mesh (the flat 3N buffer of mesh.cpp:781-804); update() pushes it through
+    Scene.update_vertices.  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
+    which is why they have to be asked for: render() raises on one that requires a gradient."""
+    return ParameterMap(scene, replay=replay, geometry=geometry)
 
 
 def _replayed(pmap, key):
@@ -459,6 +473,10 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
     def differentiable(spp_, seed):
         d = _desc(scene, sensor, integrator, spp_, seed)
         keys = [k for k, v in params.items() if v.requires_grad] if params is not None else []
+        for k in keys:
+            if params._kind[k][0] == "vertices":
+                raise RuntimeError("%s is settable, not differentiable: there is no reparameterised integrator for vertex positions; "
+                                   "clear requires_grad on it" % k)
         if not keys:
             if params is not None:
                 params.update()

@@ -14,6 +14,7 @@
 #include "envmap.h"
 #include "kernels.h"
 #include "scene_build.h"
+#include "refit.h"
 #include "schedule.h"
 #include "spectral_upsampling.h"
 #include "cie_data.h"
@@ -388,6 +389,17 @@ struct mtsamd_scene : SceneState {
     float *d_jac = nullptr, *d_cgrad = nullptr;
     float *d_ejac = nullptr, *d_egrad = nullptr;
     DevTexture *d_textures = nullptr;       // the table `textures`, whose `data` are device pointers owned by the scene
+    // vertex updates (mtsamd_scene_set_vertex_positions), hierarchy scenes: the refit table (bvh.h) as refit.hip reads it, and scratch for
+    // one shape: staged vertex arrays, triangle areas, the flag of the finite check
+    uint32_t *d_faces = nullptr, *d_prim_slot = nullptr, *d_slot_prim = nullptr, *d_order = nullptr, *d_refit_flag = nullptr;
+    int2 *d_kids = nullptr;
+    int32_t *d_node_child = nullptr, *d_wide_child = nullptr;
+    float *d_boxes = nullptr, *d_stage_pos = nullptr, *d_stage_nrm = nullptr, *d_stage_area = nullptr;
+    std::vector<uint32_t> class_start;      // height classes of d_order
+    int32_t refit_root = 0;
+    size_t n_tri_nrm = 0;                   // floats in d_tri_nrm
+    uint32_t n_pairs = 0, n_clusters = 0;
+    BuildOptions options;
     SceneView view{};
     Workspace ws;
     std::atomic<int> cancel{ 0 };
@@ -456,6 +468,37 @@ int upload_scene(mtsamd_scene *s, HostScene &hs) {
         one[0].data = reinterpret_cast<const float4 *>(s->d_env_texels); one[0].warp = s->d_env_warp;
         if ((rc = upload(&s->d_envmap, one))) return rc;
     }
+    return MTSAMD_OK;
+}
+
+// What a vertex update of a hierarchy scene needs on the device.  A flat scene is updated on the host (at most kFlatMaxPrims
+// primitives) and keeps the host arrays instead; a hierarchy scene drops the host copies of what the device now owns.
+int upload_refit_table(mtsamd_scene *s, HostScene &hs) {
+    s->n_tri_nrm = hs.tri_nrm.size(); s->n_pairs = hs.n_pairs; s->n_clusters = hs.n_clusters;
+    if (hs.flat || s->n_prims == 0) return MTSAMD_OK;
+    BvhOutput &bvh = s->bvh;
+    RefitTable &rt = bvh.refit;
+    SceneGeometry &g = s->geometry;
+    std::vector<uint32_t> prim_slot(s->n_prims, 0u);
+    for (size_t i = 0; i < rt.slot_prim.size(); ++i) prim_slot[rt.slot_prim[i]] = (uint32_t) i;
+    std::vector<int2> kids(rt.left.size());
+    for (size_t t = 0; t < kids.size(); ++t) kids[t] = rt.left[t] >= 0 ? make_int2(rt.left[t], rt.right[t]) : make_int2(-1, (int32_t) rt.ref2[t]);
+    uint32_t max_vertices = 0, max_faces = 0;
+    for (size_t i = 0; i < g.shapes.size(); ++i) { max_vertices = std::max(max_vertices, g.shape_vertices[i]); max_faces = std::max(max_faces, g.shape_faces[i]); }
+    int rc = 0;
+    if ((rc = upload(&s->d_faces, g.faces)) || (rc = upload(&s->d_prim_slot, prim_slot)) || (rc = upload(&s->d_slot_prim, rt.slot_prim)) ||
+        (rc = upload(&s->d_kids, kids)) || (rc = upload(&s->d_order, rt.order)) || (rc = upload(&s->d_node_child, rt.node_child)) ||
+        (rc = upload(&s->d_wide_child, rt.wide_child)) || (rc = upload(&s->d_boxes, rt.boxes)))
+        return rc;
+    HIP_TRY(hipMalloc((void **) &s->d_stage_pos, sizeof(float) * 3 * (size_t) std::max(max_vertices, 1u)));
+    HIP_TRY(hipMalloc((void **) &s->d_stage_nrm, sizeof(float) * 3 * (size_t) std::max(max_vertices, 1u)));
+    HIP_TRY(hipMalloc((void **) &s->d_stage_area, sizeof(float) * (size_t) std::max(max_faces, 1u)));
+    HIP_TRY(hipMalloc((void **) &s->d_refit_flag, sizeof(uint32_t)));
+    s->class_start = rt.class_start; s->refit_root = rt.root;
+    // the device owns these now; the counts (n_nodes, n_wnodes, n_slots), roots, bbox and grid stay
+    bvh.nodes = {}; bvh.qnodes = {}; bvh.wnodes = {}; bvh.wnodes_h = {}; bvh.wnodes_p = {}; bvh.tris = {};
+    rt = RefitTable{};
+    g.faces = {}; g.prim_shape = {};
     return MTSAMD_OK;
 }
 
@@ -557,6 +600,8 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
     (void) hipFree(s->d_area_pmf); (void) hipFree(s->d_area_cdf); (void) hipFree(s->d_rough_tables);
     (void) hipFree(s->d_env_texels); (void) hipFree(s->d_env_warp); (void) hipFree(s->d_envmap); (void) hipFree(s->d_flat); (void) hipFree(s->d_pairs);
     for (auto &t : s->textures) (void) hipFree((void *) t.data);
+    (void) hipFree(s->d_faces); (void) hipFree(s->d_prim_slot); (void) hipFree(s->d_slot_prim); (void) hipFree(s->d_order); (void) hipFree(s->d_refit_flag); (void) hipFree(s->d_kids);
+    (void) hipFree(s->d_node_child); (void) hipFree(s->d_wide_child); (void) hipFree(s->d_boxes); (void) hipFree(s->d_stage_pos); (void) hipFree(s->d_stage_nrm); (void) hipFree(s->d_stage_area);
     (void) hipFree(s->d_textures); (void) hipFree(s->d_jac); (void) hipFree(s->d_cgrad); (void) hipFree(s->d_ejac); (void) hipFree(s->d_egrad);
     delete s;
 }
@@ -594,7 +639,9 @@ static int create_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_des
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->cu_count = prop.multiProcessorCount;
     static_cast<SceneState &>(*s) = std::move(hs.state);
+    s->options = build_options();
     if (int rc = upload_scene(s.get(), hs)) return rc;
+    if (int rc = upload_refit_table(s.get(), hs)) return rc;
     if (int rc = flat_frames(s.get(), hs)) return rc;
     if (int rc = roughplastic_tables(s.get())) return rc;
     if (int rc = fill_scene_view(s.get(), hs)) return rc;
@@ -664,6 +711,130 @@ int mtsamd_scene_set_emitter_radiance(mtsamd_scene *s, uint32_t emitter, const f
     if (int rc = set_emitter_radiance(*s, emitter, rgb)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipMemcpy(s->d_emitters + emitter, &s->emitters[emitter], sizeof(DevEmitter), hipMemcpyHostToDevice));
+    return MTSAMD_OK;
+}
+
+// ---- vertex updates ------------------------------------------------------------------------------------------------------------------
+// A flat scene: everything is rebuilt on the host by the code creation runs (set_vertex_positions) and uploaded again; then the frames.
+static int flat_vertex_update(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, hipStream_t stream) {
+    SceneGeometry &g = s->geometry;
+    const size_t nv = 3 * (size_t) g.shape_vertices[shape];
+    std::vector<float> pos(nv), nrm(normals ? nv : 0);
+    HIP_TRY(hipStreamSynchronize(stream));          // whatever writes the arrays, and the renders that read the old scene
+    HIP_TRY(hipMemcpy(pos.data(), positions, nv * sizeof(float), hipMemcpyDefault));
+    if (normals) HIP_TRY(hipMemcpy(nrm.data(), normals, nv * sizeof(float), hipMemcpyDefault));
+    FlatRecords fr; fr.flat = true;
+    if (int rc = set_vertex_positions(*s, s->options, shape, pos.data(), normals ? nrm.data() : nullptr, g.tri_pos, g.tri_nrm, g.area_pmf, g.area_cdf, fr)) return rc;
+    if (fr.n_pairs != s->n_pairs || fr.n_clusters != s->n_clusters) return fail(MTSAMD_ERR_DEVICE, "vertex update: the flat records changed their size");
+    const BvhOutput &bvh = s->bvh;
+    auto put = [](void *dst, const void *src, size_t bytes) { return bytes == 0 ? hipSuccess : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); };
+    HIP_TRY(put(s->d_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float)));
+    HIP_TRY(put(s->d_qnodes, bvh.qnodes.data(), bvh.qnodes.size() * sizeof(uint32_t)));
+    const std::vector<uint32_t> &wn = MTS_NODE_P15 ? bvh.wnodes_p : (MTS_NODE_F16 ? bvh.wnodes_h : bvh.wnodes);
+    HIP_TRY(put(s->d_wnodes, wn.data(), wn.size() * sizeof(uint32_t)));
+    HIP_TRY(put(s->d_tris, bvh.tris.data(), bvh.tris.size() * sizeof(float)));
+    HIP_TRY(put(s->d_tri_pos, g.tri_pos.data(), g.tri_pos.size() * sizeof(float)));
+    HIP_TRY(put(s->d_tri_nrm, g.tri_nrm.data(), g.tri_nrm.size() * sizeof(float)));
+    HIP_TRY(put(s->d_area_pmf, g.area_pmf.data(), g.area_pmf.size() * sizeof(float)));
+    HIP_TRY(put(s->d_area_cdf, g.area_cdf.data(), g.area_cdf.size() * sizeof(float)));
+    HIP_TRY(put(s->d_emitters, s->emitters.data(), s->emitters.size() * sizeof(DevEmitter)));
+    HIP_TRY(put(s->d_flat, fr.flat_recs.data(), fr.flat_recs.size() * sizeof(float4)));
+    HIP_TRY(put(s->d_pairs, fr.pair_recs.data(), fr.pair_recs.size() * sizeof(float4)));
+    for (int k = 0; k < 3; ++k) { s->view.q_lo[k] = bvh.q_lo[k]; s->view.q_step[k] = bvh.q_step[k]; s->view.q_inv_step[k] = 1.0f / bvh.q_step[k]; }
+    if (MTS_FLAT_FRAMES) {
+        HIP_TRY(launch_flat_frames(s->d_flat, s->n_prims, s->d_shapes, s->view.tri_uv, nullptr));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    return MTSAMD_OK;
+}
+
+static RefitView refit_view(const mtsamd_scene *s) {
+    RefitView rv{};
+    rv.faces = s->d_faces; rv.prim_slot = s->d_prim_slot; rv.slot_prim = s->d_slot_prim; rv.kids = s->d_kids; rv.order = s->d_order;
+    rv.node_child = s->d_node_child; rv.wide_child = s->d_wide_child; rv.boxes = s->d_boxes;
+    rv.n_nodes = s->bvh.n_nodes; rv.n_wide = s->bvh.n_wnodes;
+    rv.tri_pos = s->d_tri_pos; rv.tri_nrm = s->n_tri_nrm ? s->d_tri_nrm : nullptr;
+    rv.tris = s->d_tris; rv.nodes = s->d_nodes; rv.qnodes = s->d_qnodes; rv.wnodes = s->d_wnodes;
+    return rv;
+}
+
+int mtsamd_scene_set_vertex_positions(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, void *stream_) {
+    if (!s) return fail(MTSAMD_ERR_INVALID, "null scene");
+    if (int rc = check_vertex_update(*s, shape, positions, normals)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t) stream_;
+    SceneGeometry &g = s->geometry;
+    if (g.flat) return flat_vertex_update(s, shape, positions, normals, stream);
+    const uint32_t nv = 3u * g.shape_vertices[shape], off = g.shapes[shape].first_prim, n_faces = g.shape_faces[shape];
+    const int32_t em = g.shapes[shape].emitter;
+    const RefitView rv = refit_view(s);
+    // 1. stage the arrays (host or device pointers alike) and look before writing: finite coordinates, and the areas of an emitter shape
+    HIP_TRY(hipMemcpyAsync(s->d_stage_pos, positions, nv * sizeof(float), hipMemcpyDefault, stream));
+    if (normals) HIP_TRY(hipMemcpyAsync(s->d_stage_nrm, normals, nv * sizeof(float), hipMemcpyDefault, stream));
+    HIP_TRY(hipMemsetAsync(s->d_refit_flag, 0, sizeof(uint32_t), stream));
+    HIP_TRY(launch_refit_check(rv, s->d_stage_pos, nv, off, n_faces, em >= 0 ? s->d_stage_area : nullptr, s->d_refit_flag, stream));
+    uint32_t flag = 0;
+    std::vector<float> pmf(em >= 0 ? n_faces : 0), cdf(pmf.size());
+    HIP_TRY(hipMemcpyAsync(&flag, s->d_refit_flag, sizeof(flag), hipMemcpyDeviceToHost, stream));
+    if (em >= 0 && n_faces) HIP_TRY(hipMemcpyAsync(pmf.data(), s->d_stage_area, n_faces * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (flag) return fail(MTSAMD_ERR_INVALID, "shape %u: a vertex has a non-finite coordinate", shape);
+    DevEmitter e{};
+    if (em >= 0) {       // the cdf is a sequential double sum: the host's, not a scan that rounds differently
+        e = s->emitters[em];
+        if (int rc = area_distribution(pmf.data(), n_faces, cdf.data(), e)) return rc;
+    }
+    // 2. commit: primitives and slots of the shape, then every box from the leaves up, one launch per height class
+    HIP_TRY(launch_refit_gather(rv, s->d_stage_pos, normals ? s->d_stage_nrm : nullptr, off, n_faces, stream));
+    for (size_t h = 0; h + 1 < s->class_start.size(); ++h)
+        HIP_TRY(launch_refit_boxes(rv, s->class_start[h], s->class_start[h + 1] - s->class_start[h], h == 0, stream));
+    // 3. the scene box: the root's.  Extent, grid, bounding sphere and the records that hold it are the host's arithmetic.
+    HIP_TRY(hipMemcpyAsync(s->bvh.bbox, s->d_boxes + 6 * (size_t) s->refit_root, 6 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    RefitGrid grid{};
+    scene_grid(s->bvh.bbox, &grid.extent, s->bvh.q_lo, s->bvh.q_step);
+    for (int k = 0; k < 3; ++k) {
+        grid.glo[k] = (double) s->bvh.q_lo[k]; grid.gstep[k] = (double) s->bvh.q_step[k];
+        s->view.q_lo[k] = s->bvh.q_lo[k]; s->view.q_step[k] = s->bvh.q_step[k]; s->view.q_inv_step[k] = 1.0f / s->bvh.q_step[k];
+    }
+    if (em >= 0) s->emitters[em] = e;
+    set_scene_bounds(*s);
+    // 4. emit the node arrays, push the emitter tables
+    HIP_TRY(launch_refit_emit(rv, grid, stream));
+    if (em >= 0 && n_faces) {
+        HIP_TRY(hipMemcpyAsync(s->d_area_pmf + off, pmf.data(), n_faces * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(s->d_area_cdf + off, cdf.data(), n_faces * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
+    if (!s->emitters.empty()) HIP_TRY(hipMemcpyAsync(s->d_emitters, s->emitters.data(), s->emitters.size() * sizeof(DevEmitter), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return MTSAMD_OK;
+}
+
+int mtsamd_scene_read_accel(const mtsamd_scene *s, int32_t which, void *host_dst, uint64_t bytes) {
+    if (!s || !host_dst) return fail(MTSAMD_ERR_INVALID, "null argument");
+    const void *src = nullptr; uint64_t size = 0;
+    float grid[6];
+    switch (which) {
+    case MTSAMD_ACCEL_NODES: src = s->d_nodes; size = 64ull * s->bvh.n_nodes; break;
+    case MTSAMD_ACCEL_QNODES: src = s->d_qnodes; size = 32ull * s->bvh.n_nodes; break;
+    case MTSAMD_ACCEL_WNODES: src = s->d_wnodes; size = 64ull * s->bvh.n_wnodes; break;
+    case MTSAMD_ACCEL_TRIS: src = s->d_tris; size = 48ull * s->bvh.n_slots; break;
+    case MTSAMD_ACCEL_TRI_POS: src = s->d_tri_pos; size = 36ull * s->n_prims; break;
+    case MTSAMD_ACCEL_TRI_NRM: src = s->d_tri_nrm; size = 4ull * s->n_tri_nrm; break;
+    case MTSAMD_ACCEL_AREA_PMF: src = s->d_area_pmf; size = 4ull * s->n_prims; break;
+    case MTSAMD_ACCEL_AREA_CDF: src = s->d_area_cdf; size = 4ull * s->n_prims; break;
+    case MTSAMD_ACCEL_GRID: size = 24; break;
+    default: return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_read_accel: unknown array %d", which);
+    }
+    if (bytes != size) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_read_accel: array %d holds %llu bytes, not %llu", which, (unsigned long long) size, (unsigned long long) bytes);
+    if (which == MTSAMD_ACCEL_GRID) {
+        for (int k = 0; k < 3; ++k) { grid[k] = s->view.q_lo[k]; grid[3 + k] = s->view.q_step[k]; }
+        std::memcpy(host_dst, grid, sizeof(grid));
+        return MTSAMD_OK;
+    }
+    if (size == 0) return MTSAMD_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(host_dst, src, size, hipMemcpyDeviceToHost));
     return MTSAMD_OK;
 }
 

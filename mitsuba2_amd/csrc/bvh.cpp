@@ -1,5 +1,6 @@
 // bvh.cpp -- binned-SAH BVH2 builder (host).  See bvh.h.
 #include "bvh.h"
+#include "refit_encode.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -177,6 +178,146 @@ inline float bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
 } // namespace
 
+void scene_grid(const float bbox[6], double *extent_out, float q_lo[3], float q_step[3]) {
+    double extent = 0.0;
+    for (int k = 0; k < 3; ++k) extent = std::max({ extent, std::fabs((double) bbox[k]), std::fabs((double) bbox[3 + k]), (double) bbox[3 + k] - (double) bbox[k] });
+    for (int k = 0; k < 3; ++k) {
+        const double lo = bbox[k], hi = bbox[3 + k];
+        const double pad = (hi - lo + extent + 1.0) * 1e-5;
+        const double glo = lo - pad;
+        // the padded scene box ends at cell 65532: every snapped plane stays below 65534, so that the 15-bit variant of the BVH4
+        // nodes (even cells only) can round a far plane up without leaving the grid
+        const double gstep = std::max((hi + pad - glo) / 65532.0, 1e-30);
+        q_lo[k] = (float) glo; q_step[k] = (float) gstep;
+    }
+    *extent_out = extent;
+}
+
+// ---- emission: from the exact box of every builder node (RefitTable::boxes) to everything the device reads.  build_bvh and refit_bvh
+// both end here; csrc/refit.hip restates it per node, operation by operation, and is held to the same bytes.
+static void emit_bvh(const float *tri_pos, BvhOutput &out) {
+    const RefitTable &rt = out.refit;
+    auto box_of = [&](int32_t t) { Box bx; for (int k = 0; k < 3; ++k) { bx.lo[k] = rt.boxes[6 * (size_t) t + k]; bx.hi[k] = rt.boxes[6 * (size_t) t + 3 + k]; } return bx; };
+    for (int k = 0; k < 6; ++k) out.bbox[k] = rt.boxes[6 * (size_t) rt.root + k];
+    double extent;
+    scene_grid(out.bbox, &extent, out.q_lo, out.q_step);
+    const size_t n_nodes = rt.node_child.size() / 2, n_wide = rt.wide_child.size() / 4, n_slots = rt.slot_prim.size();
+    out.tris.resize(12 * n_slots);
+    for (size_t s = 0; s < n_slots; ++s) {
+        const uint32_t p = rt.slot_prim[s];
+        const float *tp = tri_pos + 9 * (size_t) p;
+        float p0[3] = { tp[0], tp[1], tp[2] };
+        float e1[3] = { tp[3] - tp[0], tp[4] - tp[1], tp[5] - tp[2] };
+        float e2[3] = { tp[6] - tp[0], tp[7] - tp[1], tp[8] - tp[2] };
+        float rec[12] = { p0[0], p0[1], p0[2], e1[0], e1[1], e1[2], e2[0], e2[1], e2[2], bits(p), 0.0f, 0.0f };
+        std::memcpy(out.tris.data() + 12 * s, rec, sizeof(rec));
+    }
+    out.nodes.assign(16 * n_nodes, 0.0f);
+    for (size_t i = 0; i < n_nodes; ++i) {
+        const int32_t l = rt.node_child[2 * i], r = rt.node_child[2 * i + 1];
+        float llo[3], lhi[3], rlo[3], rhi[3];
+        padded(box_of(l), extent, llo, lhi);
+        padded(box_of(r), extent, rlo, rhi);
+        float *q = out.nodes.data() + 16 * i;
+        q[0] = llo[0]; q[1] = llo[1]; q[2] = llo[2]; q[3] = lhi[0];
+        q[4] = lhi[1]; q[5] = lhi[2]; q[6] = rlo[0]; q[7] = rlo[1];
+        q[8] = rlo[2]; q[9] = rhi[0]; q[10] = rhi[1]; q[11] = rhi[2];
+        q[12] = bits(rt.ref2[l]); q[13] = bits(rt.ref2[r]); q[14] = 0.0f; q[15] = 0.0f;
+    }
+    // 32-byte nodes: child boxes snapped outward (by at least 1/8 cell: the device decodes them with an error below 0.07 cells)
+    // to a 65536^3 grid over the (padded) scene box.  One traversal step then costs two
+    // 16-byte loads per lane instead of four; the walk only culls with the boxes, so hits are unchanged.
+    // the device decodes with the float values: they are the reference for the snapping below
+    double glo[3], gstep[3];
+    for (int k = 0; k < 3; ++k) { glo[k] = (double) out.q_lo[k]; gstep[k] = (double) out.q_step[k]; }
+    auto qlo = [&](float v, int k) -> uint32_t {
+        double q = std::floor(((double) v - glo[k]) / gstep[k] - 0.125);
+        return (uint32_t) std::min(65535.0, std::max(0.0, q));
+    };
+    auto qhi = [&](float v, int k) -> uint32_t {
+        double q = std::ceil(((double) v - glo[k]) / gstep[k] + 0.125);
+        return (uint32_t) std::min(65535.0, std::max(0.0, q));
+    };
+    out.qnodes.assign(8 * n_nodes, 0u);
+    for (size_t i = 0; i < n_nodes; ++i) {
+        const float *q = out.nodes.data() + 16 * i;
+        const float llo[3] = { q[0], q[1], q[2] }, lhi[3] = { q[3], q[4], q[5] }, rlo[3] = { q[6], q[7], q[8] }, rhi[3] = { q[9], q[10], q[11] };
+        uint32_t *w = out.qnodes.data() + 8 * i;
+        // one word per child and axis: lo | hi << 16 (the walk swaps the halves with one v_perm_b32 according to the sign
+        // of the ray direction and so gets (near plane, far plane) without min / max)
+        for (int k = 0; k < 3; ++k) {
+            w[k] = qlo(llo[k], k) | (qhi(lhi[k], k) << 16);
+            w[3 + k] = qlo(rlo[k], k) | (qhi(rhi[k], k) << 16);
+        }
+        std::memcpy(&w[6], &q[12], 4); std::memcpy(&w[7], &q[13], 4);
+    }
+    // ---- BVH4, same grid
+    out.wnodes.clear(); out.wnodes_h.clear(); out.wnodes_p.clear();
+    if (n_wide == 0) return;
+    // fp16 with directed rounding: the largest half <= v / the smallest half >= v (v an integer in [-32768, 32768])
+    auto half_of = [](float v, bool up) -> uint32_t {
+        uint32_t sign = v < 0.0f ? 0x8000u : 0u;
+        float a = std::fabs(v);
+        if (a == 0.0f) return sign;
+        int e; float m = std::frexp(a, &e);                       // a = m 2^e, m in [0.5, 1)
+        // 11 significant bits: a = k 2^(e - 11), k in [1024, 2048)
+        const float scaled = std::ldexp(m, 11);
+        const bool away = (v >= 0.0f) == up;                       // towards +inf of a positive / -inf of a negative value: magnitude up
+        float k = away ? std::ceil(scaled) : std::floor(scaled);
+        if (k >= 2048.0f) { k = 1024.0f; ++e; }
+        const int be = e - 1 + 15;                                // biased exponent of k 2^(e - 11) = (k / 1024) 2^(e - 1)
+        return sign | ((uint32_t) be << 10) | ((uint32_t) k - 1024u);
+    };
+    // wnodes_p: 15-bit planes on the even cells of the same grid, stored as 0x8000 | q15: the two bytes are the upper mantissa (and the
+    // lowest exponent bit) of the float 65536 + 2 q15, which the walk assembles with one v_perm_b32 per plane -- no integer-to-float convert
+    out.wnodes_h.assign(16 * n_wide, 0u); out.wnodes_p.assign(16 * n_wide, 0u); out.wnodes.assign(16 * n_wide, 0u);
+    for (size_t i = 0; i < n_wide; ++i) {
+        uint32_t *wh = out.wnodes_h.data() + 16 * i, *wp = out.wnodes_p.data() + 16 * i, *w = out.wnodes.data() + 16 * i;
+        for (int c = 0; c < 4; ++c) {
+            const int32_t t = rt.wide_child[4 * i + c];
+            if (t < 0) {
+                wh[4 * c] = wh[4 * c + 1] = wh[4 * c + 2] = 0x7800u | (0xf800u << 16);      // lo = +32768, hi = -32768
+                wp[4 * c] = wp[4 * c + 1] = wp[4 * c + 2] = 0xffffu | (0x8000u << 16);      // lo = 65534, hi = 0
+                w[4 * c] = w[4 * c + 1] = w[4 * c + 2] = 65535u;                            // lo = 65535, hi = 0
+                wh[4 * c + 3] = wp[4 * c + 3] = w[4 * c + 3] = 0x7fffffffu;
+                continue;
+            }
+            float lo[3], hi[3];
+            padded(box_of(t), extent, lo, hi);
+            for (int k = 0; k < 3; ++k) {
+                const uint32_t ql = qlo(lo[k], k), qh = qhi(hi[k], k);
+                const float vlo = (float) ql - 32768.0f, vhi = (float) qh - 32768.0f;
+                wh[4 * c + k] = half_of(vlo, false) | (half_of(vhi, true) << 16);
+                const uint32_t l15 = ql >> 1, h15 = std::min(32767u, (qh + 1u) >> 1);      // qhi <= 65534 (grid above)
+                wp[4 * c + k] = (0x8000u | l15) | ((0x8000u | h15) << 16);
+                w[4 * c + k] = ql | (qh << 16);
+            }
+            wh[4 * c + 3] = wp[4 * c + 3] = w[4 * c + 3] = rt.ref4[t];
+        }
+    }
+}
+
+void refit_bvh(const float *tri_pos, BvhOutput &out) {
+    RefitTable &rt = out.refit;
+    if (rt.order.empty()) return;
+    for (uint32_t i = rt.class_start[0]; i < rt.class_start[1]; ++i) {       // leaves: the exact box of their triangles
+        const uint32_t t = rt.order[i], ref = rt.ref2[t], first = ref & ((1u << kLeafCountShift) - 1u), count = (ref >> kLeafCountShift) & 15u;
+        float *bx = &rt.boxes[6 * (size_t) t];
+        for (int k = 0; k < 3; ++k) { bx[k] = INFINITY; bx[3 + k] = -INFINITY; }
+        for (uint32_t s = first; s < first + count; ++s) {
+            const float *tp = tri_pos + 9 * (size_t) rt.slot_prim[s];
+            for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) { bx[k] = enc_min(bx[k], tp[3 * j + k]); bx[3 + k] = enc_max(bx[3 + k], tp[3 * j + k]); }
+        }
+    }
+    for (size_t i = rt.class_start[1]; i < rt.order.size(); ++i) {            // then every height class from its children
+        const uint32_t t = rt.order[i];
+        const float *l = &rt.boxes[6 * (size_t) rt.left[t]], *r = &rt.boxes[6 * (size_t) rt.right[t]];
+        float *bx = &rt.boxes[6 * (size_t) t];
+        for (int k = 0; k < 3; ++k) { bx[k] = enc_min(l[k], r[k]); bx[3 + k] = enc_max(l[3 + k], r[3 + k]); }
+    }
+    emit_bvh(tri_pos, out);
+}
+
 void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out, const BvhOptions *opt) {
     Builder b;
     b.tri_pos = tri_pos; b.n_prims = n_prims; b.max_leaf = std::min<uint32_t>(std::max<uint32_t>(max_leaf, 1), 15);
@@ -184,7 +325,6 @@ void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOut
     if (!opt) opt = &defaults;
     b.kBins = std::min(std::max(opt->bins, 2), kMaxBins); b.kIntersectCost = opt->intersect_cost; b.sweep_below = opt->sweep_below;
     b.prim_box.resize(n_prims); b.centroid.resize(3 * (size_t) n_prims); b.perm.resize(n_prims);
-    Box scene; scene.reset();
     for (uint32_t p = 0; p < n_prims; ++p) {
         Box bx; bx.reset();
         for (int j = 0; j < 3; ++j) {
@@ -194,19 +334,16 @@ void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOut
         b.prim_box[p] = bx;
         for (int k = 0; k < 3; ++k) b.centroid[3 * (size_t) p + k] = 0.5 * (bx.lo[k] + bx.hi[k]);
         b.perm[p] = p;
-        scene.grow(bx);
-    }
-    double extent = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        extent = std::max({ extent, std::fabs(scene.lo[k]), std::fabs(scene.hi[k]), scene.hi[k] - scene.lo[k] });
-        out.bbox[k] = (float) scene.lo[k]; out.bbox[3 + k] = (float) scene.hi[k];
     }
     b.nodes.reserve(2 * (size_t) n_prims);
     int32_t root = b.build(0, n_prims, 0);
 
-    // emit: inner nodes in BFS order (the top of the tree comes first, so a prefix of the node
-    // array is what gets staged in LDS), triangle slots in the order their leaves are reached.
-    std::vector<int32_t> inner_index(b.nodes.size(), -1);
+    // ---- topology: what stays when the vertices move (refit_bvh).  Inner nodes in BFS order (the top of the tree comes first, so a
+    // prefix of the node array is what gets staged in LDS), triangle slots in the order their leaves are reached.
+    RefitTable &rt = out.refit;
+    rt = RefitTable{};
+    const size_t n_tmp = b.nodes.size();
+    std::vector<int32_t> inner_index(n_tmp, -1);
     std::vector<int32_t> bfs;
     if (opt->dfs_order) {                                          // experiment: pre-order layout
         std::vector<int32_t> st;
@@ -229,90 +366,38 @@ void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOut
             if (b.nodes[n.right].left >= 0) q.push(n.right);
         }
     }
-    out.nodes.assign(16 * bfs.size(), 0.0f);
-    out.tris.clear(); out.tris.reserve(12 * (size_t) n_prims);
+    rt.root = root;
+    rt.left.resize(n_tmp); rt.right.resize(n_tmp); rt.ref2.assign(n_tmp, 0u); rt.ref4.assign(n_tmp, 0u);
+    rt.boxes.resize(6 * n_tmp);
+    for (size_t t = 0; t < n_tmp; ++t) {
+        rt.left[t] = b.nodes[t].left; rt.right[t] = b.nodes[t].right;
+        for (int k = 0; k < 3; ++k) { rt.boxes[6 * t + k] = (float) b.nodes[t].box.lo[k]; rt.boxes[6 * t + 3 + k] = (float) b.nodes[t].box.hi[k]; }
+    }
     uint32_t slot = 0;
-    auto emit_leaf = [&](const TmpNode &n) -> uint32_t {
+    auto leaf_slots = [&](int32_t t) -> uint32_t {
+        const TmpNode &n = b.nodes[t];
         uint32_t start = slot;
-        for (uint32_t i = 0; i < n.count; ++i) {
-            uint32_t p = b.perm[n.first + i];
-            const float *tp = tri_pos + 9 * (size_t) p;
-            float p0[3] = { tp[0], tp[1], tp[2] };
-            float e1[3] = { tp[3] - tp[0], tp[4] - tp[1], tp[5] - tp[2] };
-            float e2[3] = { tp[6] - tp[0], tp[7] - tp[1], tp[8] - tp[2] };
-            float rec[12] = { p0[0], p0[1], p0[2], e1[0], e1[1], e1[2], e2[0], e2[1], e2[2], bits(p), 0.0f, 0.0f };
-            out.tris.insert(out.tris.end(), rec, rec + 12);
-            ++slot;
-        }
+        for (uint32_t i = 0; i < n.count; ++i) { rt.slot_prim.push_back(b.perm[n.first + i]); ++slot; }
         return kLeafFlag | (n.count << kLeafCountShift) | start;
     };
-    std::vector<uint32_t> leaf_ref(b.nodes.size(), 0u);
     auto child_ref = [&](int32_t t) -> uint32_t {
-        const TmpNode &n = b.nodes[t];
-        if (n.left >= 0) return (uint32_t) inner_index[t];
-        return leaf_ref[t] = emit_leaf(n);
+        if (b.nodes[t].left >= 0) return rt.ref2[t] = (uint32_t) inner_index[t];
+        return rt.ref2[t] = rt.ref4[t] = leaf_slots(t);
     };
+    rt.node_child.resize(2 * bfs.size());
     for (size_t i = 0; i < bfs.size(); ++i) {
         const TmpNode &n = b.nodes[bfs[i]];
-        float llo[3], lhi[3], rlo[3], rhi[3];
-        padded(b.nodes[n.left].box, extent, llo, lhi);
-        padded(b.nodes[n.right].box, extent, rlo, rhi);
-        uint32_t cl = child_ref(n.left), cr = child_ref(n.right);
-        float *q = out.nodes.data() + 16 * i;
-        q[0] = llo[0]; q[1] = llo[1]; q[2] = llo[2]; q[3] = lhi[0];
-        q[4] = lhi[1]; q[5] = lhi[2]; q[6] = rlo[0]; q[7] = rlo[1];
-        q[8] = rlo[2]; q[9] = rhi[0]; q[10] = rhi[1]; q[11] = rhi[2];
-        q[12] = bits(cl); q[13] = bits(cr); q[14] = 0.0f; q[15] = 0.0f;
+        rt.node_child[2 * i] = n.left; rt.node_child[2 * i + 1] = n.right;
+        child_ref(n.left); child_ref(n.right);
     }
-    // 32-byte nodes: child boxes snapped outward (by at least 1/8 cell: the device decodes them with an error below 0.07 cells)
-    // to a 65536^3 grid over the (padded) scene box.  One traversal step then costs two
-    // 16-byte loads per lane instead of four; the walk only culls with the boxes, so hits are unchanged.
-    {
-        double glo[3], gstep[3];
-        for (int k = 0; k < 3; ++k) {
-            const double pad = (scene.hi[k] - scene.lo[k] + extent + 1.0) * 1e-5;
-            glo[k] = scene.lo[k] - pad;
-            // the padded scene box ends at cell 65532: every snapped plane stays below 65534, so that the 15-bit variant of the BVH4
-            // nodes (even cells only) can round a far plane up without leaving the grid
-            gstep[k] = std::max((scene.hi[k] + pad - glo[k]) / 65532.0, 1e-30);
-            out.q_lo[k] = (float) glo[k]; out.q_step[k] = (float) gstep[k];
-            // the device decodes with the float values: make them the reference for the snapping below
-            glo[k] = (double) out.q_lo[k]; gstep[k] = (double) out.q_step[k];
-        }
-        auto qlo = [&](float v, int k) -> uint32_t {
-            double q = std::floor(((double) v - glo[k]) / gstep[k] - 0.125);
-            return (uint32_t) std::min(65535.0, std::max(0.0, q));
-        };
-        auto qhi = [&](float v, int k) -> uint32_t {
-            double q = std::ceil(((double) v - glo[k]) / gstep[k] + 0.125);
-            return (uint32_t) std::min(65535.0, std::max(0.0, q));
-        };
-        out.qnodes.assign(8 * bfs.size(), 0u);
-        for (size_t i = 0; i < bfs.size(); ++i) {
-            const float *q = out.nodes.data() + 16 * i;
-            const float llo[3] = { q[0], q[1], q[2] }, lhi[3] = { q[3], q[4], q[5] }, rlo[3] = { q[6], q[7], q[8] }, rhi[3] = { q[9], q[10], q[11] };
-            uint32_t *w = out.qnodes.data() + 8 * i;
-            // one word per child and axis: lo | hi << 16 (the walk swaps the halves with one v_perm_b32 according to the sign
-            // of the ray direction and so gets (near plane, far plane) without min / max)
-            for (int k = 0; k < 3; ++k) {
-                w[k] = qlo(llo[k], k) | (qhi(lhi[k], k) << 16);
-                w[3 + k] = qlo(rlo[k], k) | (qhi(rhi[k], k) << 16);
-            }
-            std::memcpy(&w[6], &q[12], 4); std::memcpy(&w[7], &q[13], 4);
-        }
-    }
-    if (bfs.empty()) out.root = emit_leaf(b.nodes[root]);   // whole scene is one leaf
+    if (bfs.empty()) out.root = child_ref(root);   // whole scene is one leaf
     else out.root = 0;
-    // ---- BVH4: collapse (open the child of largest surface area until four children), BFS order, same grid
-    out.wnodes.clear(); out.wnodes_h.clear(); out.wnodes_p.clear(); out.wroot = out.root; out.n_wnodes = 0; out.wdepth = 1;
+    // BVH4: collapse (open the child of largest surface area until four children), BFS order
+    out.wroot = out.root; out.n_wnodes = 0; out.wdepth = 1;
     if (!bfs.empty()) {
-        double glo[3], gstep[3];
-        for (int k = 0; k < 3; ++k) { glo[k] = (double) out.q_lo[k]; gstep[k] = (double) out.q_step[k]; }
-        auto qlo = [&](float v, int k) -> uint32_t { return (uint32_t) std::min(65535.0, std::max(0.0, std::floor(((double) v - glo[k]) / gstep[k] - 0.125))); };
-        auto qhi = [&](float v, int k) -> uint32_t { return (uint32_t) std::min(65535.0, std::max(0.0, std::ceil(((double) v - glo[k]) / gstep[k] + 0.125))); };
         struct Wide { int32_t child[4]; int n; uint32_t depth; };
         std::vector<Wide> wide;
-        std::vector<int32_t> wide_of(b.nodes.size(), -1);      // BVH2 inner node -> wide node that replaces it
+        std::vector<int32_t> wide_of(n_tmp, -1);      // BVH2 inner node -> wide node that replaces it
         std::queue<std::pair<int32_t, uint32_t>> q;
         q.push({ root, 1u });
         wide_of[root] = 0; wide.push_back(Wide{});
@@ -333,67 +418,25 @@ void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOut
             wide[wide_of[t]] = wn;
             out.wdepth = std::max(out.wdepth, depth);
         }
-        // fp16 with directed rounding: the largest half <= v / the smallest half >= v (v an integer in [-32768, 32768])
-        auto half_of = [](float v, bool up) -> uint32_t {
-            uint32_t sign = v < 0.0f ? 0x8000u : 0u;
-            float a = std::fabs(v);
-            if (a == 0.0f) return sign;
-            int e; float m = std::frexp(a, &e);                       // a = m 2^e, m in [0.5, 1)
-            // 11 significant bits: a = k 2^(e - 11), k in [1024, 2048)
-            const float scaled = std::ldexp(m, 11);
-            const bool away = (v >= 0.0f) == up;                       // towards +inf of a positive / -inf of a negative value: magnitude up
-            float k = away ? std::ceil(scaled) : std::floor(scaled);
-            if (k >= 2048.0f) { k = 1024.0f; ++e; }
-            const int be = e - 1 + 15;                                // biased exponent of k 2^(e - 11) = (k / 1024) 2^(e - 1)
-            return sign | ((uint32_t) be << 10) | ((uint32_t) k - 1024u);
-        };
         out.n_wnodes = (uint32_t) wide.size();
-        out.wnodes_h.assign(16 * wide.size(), 0u);
-        for (size_t i = 0; i < wide.size(); ++i) {
-            uint32_t *w = out.wnodes_h.data() + 16 * i;
-            for (int c = 0; c < 4; ++c) {
-                if (c >= wide[i].n) { w[4 * c] = w[4 * c + 1] = w[4 * c + 2] = 0x7800u | (0xf800u << 16); w[4 * c + 3] = 0x7fffffffu; continue; }      // lo = +32768, hi = -32768
-                const int32_t t = wide[i].child[c];
-                float lo[3], hi[3];
-                padded(b.nodes[t].box, extent, lo, hi);
-                for (int k = 0; k < 3; ++k) {
-                    const float vlo = (float) qlo(lo[k], k) - 32768.0f, vhi = (float) qhi(hi[k], k) - 32768.0f;
-                    w[4 * c + k] = half_of(vlo, false) | (half_of(vhi, true) << 16);
-                }
-                w[4 * c + 3] = b.nodes[t].left >= 0 ? (uint32_t) wide_of[t] : leaf_ref[t];
-            }
-        }
-        // 15-bit planes on the even cells of the same grid, stored as 0x8000 | q15: the two bytes are the upper mantissa (and the lowest
-        // exponent bit) of the float 65536 + 2 q15, which the walk assembles with one v_perm_b32 per plane -- no integer-to-float convert
-        out.wnodes_p.assign(16 * wide.size(), 0u);
-        for (size_t i = 0; i < wide.size(); ++i) {
-            uint32_t *w = out.wnodes_p.data() + 16 * i;
-            for (int c = 0; c < 4; ++c) {
-                if (c >= wide[i].n) { w[4 * c] = w[4 * c + 1] = w[4 * c + 2] = 0xffffu | (0x8000u << 16); w[4 * c + 3] = 0x7fffffffu; continue; }      // lo = 65534, hi = 0
-                const int32_t t = wide[i].child[c];
-                float lo[3], hi[3];
-                padded(b.nodes[t].box, extent, lo, hi);
-                for (int k = 0; k < 3; ++k) {
-                    const uint32_t l15 = qlo(lo[k], k) >> 1, h15 = std::min(32767u, (qhi(hi[k], k) + 1u) >> 1);      // qhi <= 65534 (grid above)
-                    w[4 * c + k] = (0x8000u | l15) | ((0x8000u | h15) << 16);
-                }
-                w[4 * c + 3] = b.nodes[t].left >= 0 ? (uint32_t) wide_of[t] : leaf_ref[t];
-            }
-        }
-        out.wnodes.assign(16 * wide.size(), 0u);
-        for (size_t i = 0; i < wide.size(); ++i) {
-            uint32_t *w = out.wnodes.data() + 16 * i;
-            for (int c = 0; c < 4; ++c) {
-                if (c >= wide[i].n) { w[4 * c] = w[4 * c + 1] = w[4 * c + 2] = 65535u; w[4 * c + 3] = 0x7fffffffu; continue; }      // lo = 65535, hi = 0
-                const int32_t t = wide[i].child[c];
-                float lo[3], hi[3];
-                padded(b.nodes[t].box, extent, lo, hi);
-                for (int k = 0; k < 3; ++k) w[4 * c + k] = qlo(lo[k], k) | (qhi(hi[k], k) << 16);
-                w[4 * c + 3] = b.nodes[t].left >= 0 ? (uint32_t) wide_of[t] : leaf_ref[t];
-            }
-        }
+        rt.wide_child.assign(4 * wide.size(), -1);
+        for (size_t i = 0; i < wide.size(); ++i)
+            for (int c = 0; c < wide[i].n; ++c) rt.wide_child[4 * i + c] = wide[i].child[c];
+        for (size_t t = 0; t < n_tmp; ++t) if (b.nodes[t].left >= 0) rt.ref4[t] = (uint32_t) wide_of[t];
         out.wroot = 0;
     }
+    // height above the leaves; children follow their parent in the builder's array, so one backward pass sees them first
+    rt.height.assign(n_tmp, 0u);
+    uint32_t top = 0;
+    for (size_t t = n_tmp; t-- > 0;)
+        if (rt.left[t] >= 0) { rt.height[t] = 1u + std::max(rt.height[rt.left[t]], rt.height[rt.right[t]]); top = std::max(top, rt.height[t]); }
+    rt.class_start.assign(top + 2, 0u);
+    for (size_t t = 0; t < n_tmp; ++t) rt.class_start[rt.height[t] + 1]++;
+    for (uint32_t h = 0; h <= top; ++h) rt.class_start[h + 1] += rt.class_start[h];
+    rt.order.resize(n_tmp);
+    { std::vector<uint32_t> at(rt.class_start.begin(), rt.class_start.end() - 1);
+      for (size_t t = 0; t < n_tmp; ++t) rt.order[at[rt.height[t]]++] = (uint32_t) t; }
+    emit_bvh(tri_pos, out);
     out.n_nodes = (uint32_t) bfs.size();
     out.n_slots = slot;
     out.depth = b.max_depth + 1;

@@ -11,6 +11,21 @@
 
 namespace mtsamd {
 
+// What a refit needs of the topology (build_bvh fills it, refit_bvh and the device refit read it).  Builder nodes are the nodes of the
+// binary tree the SAH build made, leaves included; `boxes` holds the exact (unpadded) box of each, from which every output is emitted.
+struct RefitTable {
+    std::vector<int32_t> left, right;       // per builder node: children, -1 for a leaf
+    std::vector<uint32_t> ref2, ref4;       // per builder node: its child reference in the BVH2 / the BVH4 (a leaf: flag | count << 27 | first slot)
+    std::vector<uint32_t> height;           // per builder node: height above its leaves (a leaf: 0)
+    std::vector<uint32_t> order, class_start;      // builder nodes sorted by height; class h is order[class_start[h] .. class_start[h + 1])
+    // where the boxes are written, read from the side of the output: the builder node whose box is the left / right half of BVH2
+    // node i (2 per node) and child c of wide node w (4 per node, -1: absent)
+    std::vector<int32_t> node_child, wide_child;
+    std::vector<uint32_t> slot_prim;        // per triangle slot: its primitive
+    std::vector<float> boxes;               // per builder node: lo[3], hi[3]
+    int32_t root = 0;
+};
+
 struct BvhOutput {
     std::vector<float> nodes;      // 16 floats per node (see device_scene.h for the layout)
     std::vector<uint32_t> qnodes;  // 8 words per node: the same child boxes on a 16-bit grid over the scene box, rounded outward
@@ -27,6 +42,7 @@ struct BvhOutput {
     uint32_t root = 0;             // child reference of the root
     uint32_t n_nodes = 0, n_slots = 0, depth = 0;
     float bbox[6] = { 0, 0, 0, 0, 0, 0 };
+    RefitTable refit;
 };
 
 // builder knobs (defaults = the shipped configuration; experiment builds read others from the environment, api.cpp)
@@ -40,4 +56,13 @@ struct BvhOptions {
 // positions: 9 floats per primitive (p0, p1, p2), n_prims >= 1
 void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out, const BvhOptions *opt = nullptr);
 
+} // namespace mtsamd
+
+namespace mtsamd {
+// Same topology, new positions (9 floats per primitive, as for build_bvh): leaf boxes, their propagation upwards, and the emission of
+// build_bvh with the new scene box -- extent, padding and quantisation grid are recomputed, nothing is clamped into the old grid.
+// With the positions of creation every array comes out byte for byte as build_bvh left it.
+void refit_bvh(const float *tri_pos, BvhOutput &out);
+// What the emission derives from the scene box (6 floats: lo, hi): `extent` of the box padding and the quantisation grid
+void scene_grid(const float bbox[6], double *extent, float q_lo[3], float q_step[3]);
 } // namespace mtsamd

@@ -384,25 +384,11 @@ int validate(Input &in, int32_t &environment) {
 // ---- stage 2: meshes -> one global primitive list, area distributions and the records of the area emitters --------------------
 // Mesh::area_distr_build (mesh.cpp:284-307) + DiscreteDistribution::update (distr_1d.h:49-88) over the faces [off, off + face_count)
 int area_emitter(const mtsamd_emitter_desc &ed, uint32_t shape, uint32_t off, uint32_t face_count, HostScene &hs, DevEmitter &e) {
-    double sum = 0.0; uint32_t lo = 0xffffffffu, hi = 0xffffffffu;
-    for (uint32_t f = 0; f < face_count; ++f) {
-        const float *tp = &hs.tri_pos[9 * (size_t) (off + f)];
-        float e1[3] = { tp[3] - tp[0], tp[4] - tp[1], tp[5] - tp[2] }, e2[3] = { tp[6] - tp[0], tp[7] - tp[1], tp[8] - tp[2] };
-        float cx = std::fma(e1[1], e2[2], -(e1[2] * e2[1])), cy = std::fma(e1[2], e2[0], -(e1[0] * e2[2])),
-              cz = std::fma(e1[0], e2[1], -(e1[1] * e2[0]));
-        float area = 0.5f * std::sqrt(std::fma(cz, cz, std::fma(cy, cy, cx * cx)));
-        hs.area_pmf[off + f] = area;
-        sum += (double) area;
-        hs.area_cdf[off + f] = (float) sum;
-        if (area > 0.0f) { if (lo == 0xffffffffu) lo = f; hi = f; }
-    }
-    if (lo == 0xffffffffu) return fail(MTSAMD_ERR_INVALID, "DiscreteDistribution: no probability mass found!");
+    for (uint32_t f = 0; f < face_count; ++f) hs.area_pmf[off + f] = triangle_area(&hs.tri_pos[9 * (size_t) (off + f)]);
     std::memset(&e, 0, sizeof(e));
     e.r = ed.radiance[0]; e.g = ed.radiance[1]; e.b = ed.radiance[2];
     e.shape = shape; e.first_prim = off; e.n_prims = face_count;
-    e.area_sum = (float) sum; e.area_norm = (float) (1.0 / sum);
-    e.valid_lo = lo; e.valid_hi = hi;
-    return MTSAMD_OK;
+    return area_distribution(&hs.area_pmf[off], face_count, &hs.area_cdf[off], e);
 }
 
 int flatten_meshes(const Input &in, HostScene &hs) {
@@ -412,17 +398,21 @@ int flatten_meshes(const Input &in, HostScene &hs) {
     hs.prim_shape.assign(total, 0u);
     hs.shapes.assign(desc->mesh_count, DevShape{});
     hs.area_pmf.assign(total, 0.0f); hs.area_cdf.assign(total, 0.0f);
+    SceneGeometry &g = hs.state.geometry;       // what a vertex update needs later
+    g.faces.assign(3 * total, 0u); g.shape_vertices.assign(desc->mesh_count, 0u); g.shape_faces.assign(desc->mesh_count, 0u);
     uint32_t off = 0;
     for (uint32_t i = 0; i < desc->mesh_count; ++i) {
         const mtsamd_mesh_desc &m = desc->meshes[i];
         DevShape &sh = hs.shapes[i];
         sh.bsdf = m.bsdf; sh.emitter = m.emitter; sh.first_prim = off;
         sh.flags = (m.normals ? kShapeHasNormals : 0u) | (m.texcoords ? kShapeHasUV : 0u);
+        g.shape_vertices[i] = m.vertex_count; g.shape_faces[i] = m.face_count;
         for (uint32_t f = 0; f < m.face_count; ++f) {
             uint32_t gp = off + f;
             hs.prim_shape[gp] = i;
             for (int j = 0; j < 3; ++j) {
                 uint32_t vi = m.faces[3 * f + j];
+                g.faces[3 * (size_t) gp + j] = vi;
                 for (int k = 0; k < 3; ++k) hs.tri_pos[9 * (size_t) gp + 3 * j + k] = m.positions[3 * (size_t) vi + k];
                 if (m.normals) for (int k = 0; k < 3; ++k) hs.tri_nrm[9 * (size_t) gp + 3 * j + k] = m.normals[3 * (size_t) vi + k];
                 if (m.texcoords) for (int k = 0; k < 2; ++k) hs.tri_uv[6 * (size_t) gp + 2 * j + k] = m.texcoords[2 * (size_t) vi + k];
@@ -432,6 +422,7 @@ int flatten_meshes(const Input &in, HostScene &hs) {
             if (int rc = area_emitter(desc->emitters[m.emitter], i, off, m.face_count, hs, hs.state.emitters[m.emitter])) return rc;
         off += m.face_count;
     }
+    g.shapes = hs.shapes; g.prim_shape = hs.prim_shape;
     return MTSAMD_OK;
 }
 
@@ -672,8 +663,6 @@ void build_accelerator(const Input &in, const BuildOptions &opt, HostScene &hs) 
     SceneState &st = hs.state;
     if (st.n_prims > 0) build_bvh(hs.tri_pos.data(), st.n_prims, opt.max_leaf, st.bvh, &opt.bvh);
     else { st.bvh = BvhOutput{}; st.bvh.root = st.bvh.wroot = 0x80000000u; st.bvh.wdepth = 1; }       // a leaf with no triangles (BVH2 and BVH4 root: without wroot the walks of the split pipeline started at node 0 of an empty node array)
-    float centre[3], radius;
-    bounding_sphere(st.bvh.bbox, centre, &radius);
     if (st.environment >= 0) {       // ConstantBackgroundEmitter::set_scene (constant.cpp:47-51): bounding sphere of Scene::bbox()
         DevEmitter &e = st.emitters[st.environment];
         const float sc[4] = { e.c0, e.c1, e.c2, e.d65_scale };            // spectral variant: filled by build_emitters
@@ -682,18 +671,24 @@ void build_accelerator(const Input &in, const BuildOptions &opt, HostScene &hs) 
         const mtsamd_emitter_desc &ed = in.desc.emitters[st.environment];
         e.r = ed.radiance[0]; e.g = ed.radiance[1]; e.b = ed.radiance[2];
         e.shape = 0xffffffffu; e.pad0 = ed.type == MTSAMD_EMITTER_ENVMAP ? kEmitterEnvmap : kEmitterConstant;
-        e.cx = centre[0]; e.cy = centre[1]; e.cz = centre[2]; e.radius = radius;
     }
-    for (DevEmitter &e : st.emitters)           // DirectionalEmitter::set_scene (directional.cpp:65-70)
-        if (e.pad0 == kEmitterDirectional) e.radius = radius;
+    set_scene_bounds(st);
     for (uint32_t i = 0; i < in.n_bindings; ++i)       // a tabulated radiance is the radiance itself (no D65 factor)
         if (in.bindings[i].target == MTSAMD_SPECTRUM_TARGET_EMITTER) st.emitters[in.bindings[i].index].spectrum = in.bindings[i].spectrum + 1u;
 }
 
 // ---- stage 7: flat scenes: 64-byte records in primitive order, pair records and cluster boxes (device_scene.h) -----------------
-void build_flat_records(const BuildOptions &opt, HostScene &hs) {
-    const uint32_t n_prims = hs.state.n_prims;
-    const std::vector<float> &tri_pos = hs.tri_pos;
+void build_flat_scene(const BuildOptions &opt, HostScene &hs) {
+    build_flat_records(opt, hs.state, hs.tri_pos, hs);
+    hs.state.geometry.flat = hs.flat;
+    if (hs.flat) { hs.state.geometry.tri_pos = hs.tri_pos; hs.state.geometry.tri_nrm = hs.tri_nrm; hs.state.geometry.area_pmf = hs.area_pmf; hs.state.geometry.area_cdf = hs.area_cdf; }
+}
+
+} // namespace
+
+void build_flat_records(const BuildOptions &opt, const SceneState &state, const std::vector<float> &tri_pos, FlatRecords &out) {
+    const uint32_t n_prims = state.n_prims;
+    const std::vector<uint32_t> &prim_shape = state.geometry.prim_shape;
     // Flat: few enough triangles, and tables small enough that the largest launch fits the LDS cap.  The shape, BSDF and emitter counts
     // are not bounded by the triangle count (delta emitters own no triangle, nested materials add records); a scene over the cap is
     // traversed through its hierarchy like any larger one.  The scene's variant decides the figure (spectral ring entries are larger).
@@ -701,23 +696,23 @@ void build_flat_records(const BuildOptions &opt, HostScene &hs) {
     if (flat) {
         SceneView sv = {};
         sv.flat = 1u; sv.n_prims = n_prims; sv.n_pairs = (n_prims + 1) / 2;
-        for (uint32_t k = 0; k < sv.n_pairs; ++k) sv.n_clusters += k == 0 || hs.prim_shape[2 * k] != hs.prim_shape[2 * (k - 1)];
-        sv.n_shapes = hs.state.n_shapes; sv.n_bsdfs = (uint32_t) hs.state.bsdfs.size(); sv.n_emitters = (uint32_t) hs.state.emitters.size();
-        flat = flat_launch_lds_max(sv, hs.state.spectral) <= kFlatLdsCap;
+        for (uint32_t k = 0; k < sv.n_pairs; ++k) sv.n_clusters += k == 0 || prim_shape[2 * k] != prim_shape[2 * (k - 1)];
+        sv.n_shapes = state.n_shapes; sv.n_bsdfs = (uint32_t) state.bsdfs.size(); sv.n_emitters = (uint32_t) state.emitters.size();
+        flat = flat_launch_lds_max(sv, state.spectral) <= kFlatLdsCap;
     }
-    hs.flat = flat;
-    hs.flat_recs.assign(flat ? 4 * (size_t) n_prims : 0, float4{});
+    out.flat = flat;
+    out.flat_recs.assign(flat ? 4 * (size_t) n_prims : 0, float4{});
     for (uint32_t gp = 0; flat && gp < n_prims; ++gp) {
         const float *tp = &tri_pos[9 * (size_t) gp];
-        uint32_t sh = hs.prim_shape[gp]; float shf; std::memcpy(&shf, &sh, 4);
+        uint32_t sh = prim_shape[gp]; float shf; std::memcpy(&shf, &sh, 4);
         // r0.w, r1 and r2.x: the per-triangle frame (n, s), computed on the device at scene creation; zero here
-        hs.flat_recs[4 * gp + 0] = make_float4(tp[0], tp[1], tp[2], 0.0f);
-        hs.flat_recs[4 * gp + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        hs.flat_recs[4 * gp + 2] = make_float4(0.0f, tp[3], tp[4], tp[5]);
-        hs.flat_recs[4 * gp + 3] = make_float4(tp[6], tp[7], tp[8], shf);
+        out.flat_recs[4 * gp + 0] = make_float4(tp[0], tp[1], tp[2], 0.0f);
+        out.flat_recs[4 * gp + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        out.flat_recs[4 * gp + 2] = make_float4(0.0f, tp[3], tp[4], tp[5]);
+        out.flat_recs[4 * gp + 3] = make_float4(tp[6], tp[7], tp[8], shf);
     }
-    const uint32_t n_pairs = hs.n_pairs = flat ? (n_prims + 1) / 2 : 0;
-    hs.pair_recs.assign(5 * (size_t) n_pairs, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    const uint32_t n_pairs = out.n_pairs = flat ? (n_prims + 1) / 2 : 0;
+    out.pair_recs.assign(5 * (size_t) n_pairs, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     for (uint32_t k = 0; k < n_pairs; ++k) {
         float a[9] = { 0 }, b[9] = { 0 };       // p0, e1, e2 of primitives 2k and 2k+1 (zero = never hit)
         for (int which = 0; which < 2; ++which) {
@@ -729,33 +724,35 @@ void build_flat_records(const BuildOptions &opt, HostScene &hs) {
             r[3] = tp[3] - tp[0]; r[4] = tp[4] - tp[1]; r[5] = tp[5] - tp[2];
             r[6] = tp[6] - tp[0]; r[7] = tp[7] - tp[1]; r[8] = tp[8] - tp[2];
         }
-        hs.pair_recs[5 * k + 0] = make_float4(a[0], b[0], a[1], b[1]);
-        hs.pair_recs[5 * k + 1] = make_float4(a[2], b[2], a[3], b[3]);
-        hs.pair_recs[5 * k + 2] = make_float4(a[4], b[4], a[5], b[5]);
-        hs.pair_recs[5 * k + 3] = make_float4(a[6], b[6], a[7], b[7]);
-        hs.pair_recs[5 * k + 4] = make_float4(a[8], b[8], 0.0f, 0.0f);
+        out.pair_recs[5 * k + 0] = make_float4(a[0], b[0], a[1], b[1]);
+        out.pair_recs[5 * k + 1] = make_float4(a[2], b[2], a[3], b[3]);
+        out.pair_recs[5 * k + 2] = make_float4(a[4], b[4], a[5], b[5]);
+        out.pair_recs[5 * k + 3] = make_float4(a[6], b[6], a[7], b[7]);
+        out.pair_recs[5 * k + 4] = make_float4(a[8], b[8], 0.0f, 0.0f);
     }
     // clusters of consecutive pairs that belong to one shape, with their bounding box padded by 1e-4 of the scene's extent (the box
     // test of coherent waves only culls; device_scene.h, traverse_flat_clustered).  Appended to the pair records.
-    hs.n_clusters = 0;
+    out.n_clusters = 0;
     if (!flat || n_pairs == 0) return;
     float ext = 0.0f;
     for (uint32_t gp = 0; gp < n_prims; ++gp) for (int q = 0; q < 9; ++q) ext = std::max(ext, std::fabs(tri_pos[9 * (size_t) gp + q]));
     const float pad = 1e-4f * std::max(ext, 1e-3f);
     for (uint32_t k0 = 0, k1; k0 < n_pairs; k0 = k1) {
         k1 = k0 + 1;
-        while (k1 < n_pairs && hs.prim_shape[2 * k1] == hs.prim_shape[2 * k0]) ++k1;
+        while (k1 < n_pairs && prim_shape[2 * k1] == prim_shape[2 * k0]) ++k1;
         float lo[3] = { 3e38f, 3e38f, 3e38f }, hi[3] = { -3e38f, -3e38f, -3e38f };
         for (uint32_t gp = 2 * k0; gp < std::min(2 * k1, n_prims); ++gp)
             for (int vtx = 0; vtx < 3; ++vtx) for (int a = 0; a < 3; ++a) {
                 lo[a] = std::min(lo[a], tri_pos[9 * (size_t) gp + 3 * vtx + a]); hi[a] = std::max(hi[a], tri_pos[9 * (size_t) gp + 3 * vtx + a]);
             }
         const uint32_t cnt = k1 - k0; float cntf; std::memcpy(&cntf, &cnt, 4);
-        hs.pair_recs.push_back(make_float4(lo[0] - pad, lo[1] - pad, lo[2] - pad, cntf));
-        hs.pair_recs.push_back(make_float4(hi[0] + pad, hi[1] + pad, hi[2] + pad, 0.0f));
-        ++hs.n_clusters;
+        out.pair_recs.push_back(make_float4(lo[0] - pad, lo[1] - pad, lo[2] - pad, cntf));
+        out.pair_recs.push_back(make_float4(hi[0] + pad, hi[1] + pad, hi[2] + pad, 0.0f));
+        ++out.n_clusters;
     }
 }
+
+namespace {
 
 // ---- stage 8: the BSDF records, and behind them the spectrum pool: headers, then node / value arrays ---------------------------
 void build_bsdf_block(const Input &in, HostScene &hs) {
@@ -811,7 +808,7 @@ int build_host_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *
     if (int rc = build_bsdfs(in, st)) return rc;
     if (int rc = build_textures(desc, hs)) return rc;
     build_accelerator(in, options, hs);
-    build_flat_records(options, hs);
+    build_flat_scene(options, hs);
     build_bsdf_block(in, hs);
     return build_envmap_emitter(desc, hs);
 }
@@ -950,6 +947,96 @@ int set_envmap_texels(SceneState &st, const float *rgb, EnvmapHost &eh) {
         spectral_envmap_texels(st.rgb2spec, eh.texels.data(), eh.texels.size() / 4);
         st.ejac_dirty = true;
     }
+    return MTSAMD_OK;
+}
+
+// ---- geometry: the pieces of creation that depend on vertex positions, and the vertex update made of them -------------------------
+float triangle_area(const float *tp) {       // Mesh::face_area in fp32, the cross product with explicit fma (mesh.cpp:284-307)
+    float e1[3] = { tp[3] - tp[0], tp[4] - tp[1], tp[5] - tp[2] }, e2[3] = { tp[6] - tp[0], tp[7] - tp[1], tp[8] - tp[2] };
+    float cx = std::fma(e1[1], e2[2], -(e1[2] * e2[1])), cy = std::fma(e1[2], e2[0], -(e1[0] * e2[2])),
+          cz = std::fma(e1[0], e2[1], -(e1[1] * e2[0]));
+    return 0.5f * std::sqrt(std::fma(cz, cz, std::fma(cy, cy, cx * cx)));
+}
+
+// DiscreteDistribution::update (distr_1d.h:49-88): sequential double sum
+int area_distribution(const float *areas, uint32_t face_count, float *cdf, DevEmitter &e) {
+    double sum = 0.0; uint32_t lo = 0xffffffffu, hi = 0xffffffffu;
+    for (uint32_t f = 0; f < face_count; ++f) {
+        sum += (double) areas[f];
+        cdf[f] = (float) sum;
+        if (areas[f] > 0.0f) { if (lo == 0xffffffffu) lo = f; hi = f; }
+    }
+    if (lo == 0xffffffffu) return fail(MTSAMD_ERR_INVALID, "DiscreteDistribution: no probability mass found!");
+    e.area_sum = (float) sum; e.area_norm = (float) (1.0 / sum);
+    e.valid_lo = lo; e.valid_hi = hi;
+    return MTSAMD_OK;
+}
+
+void set_scene_bounds(SceneState &st) {
+    float centre[3], radius;
+    bounding_sphere(st.bvh.bbox, centre, &radius);
+    if (st.environment >= 0) {       // ConstantBackgroundEmitter::set_scene (constant.cpp:47-51): bounding sphere of Scene::bbox()
+        DevEmitter &e = st.emitters[st.environment];
+        e.cx = centre[0]; e.cy = centre[1]; e.cz = centre[2]; e.radius = radius;
+    }
+    for (DevEmitter &e : st.emitters)           // DirectionalEmitter::set_scene (directional.cpp:65-70)
+        if (e.pad0 == kEmitterDirectional) e.radius = radius;
+}
+
+int check_vertex_update(const SceneState &st, uint32_t shape, const float *positions, const float *normals) {
+    const SceneGeometry &g = st.geometry;
+    if (shape >= g.shapes.size()) return fail(MTSAMD_ERR_INVALID, "invalid shape index %u (the scene has %u shapes)", shape, (uint32_t) g.shapes.size());
+    if (!positions) return fail(MTSAMD_ERR_INVALID, "shape %u: null vertex positions", shape);
+    const bool has = (g.shapes[shape].flags & kShapeHasNormals) != 0u;
+    if (has && !normals) return fail(MTSAMD_ERR_INVALID, "shape %u was created with vertex normals: new normals are required with new positions", shape);
+    if (!has && normals) return fail(MTSAMD_ERR_INVALID, "shape %u was created without vertex normals: none can be set", shape);
+    return MTSAMD_OK;
+}
+
+int check_finite(uint32_t shape, const float *positions, size_t n_floats) {
+    for (size_t i = 0; i < n_floats; ++i)
+        if (!std::isfinite(positions[i])) return fail(MTSAMD_ERR_INVALID, "shape %u: vertex %u has a non-finite coordinate", shape, (uint32_t) (i / 3));
+    return MTSAMD_OK;
+}
+
+void gather_shape(const SceneGeometry &g, uint32_t shape, const float *positions, const float *normals, float *tri_pos, float *tri_nrm) {
+    const uint32_t off = g.shapes[shape].first_prim;
+    for (uint32_t f = 0; f < g.shape_faces[shape]; ++f)
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t vi = g.faces[3 * (size_t) (off + f) + j];
+            for (int k = 0; k < 3; ++k) {
+                tri_pos[9 * (size_t) f + 3 * j + k] = positions[3 * (size_t) vi + k];
+                if (normals) tri_nrm[9 * (size_t) f + 3 * j + k] = normals[3 * (size_t) vi + k];
+            }
+        }
+}
+
+int set_vertex_positions(SceneState &st, const BuildOptions &opt, uint32_t shape, const float *positions, const float *normals,
+                         std::vector<float> &tri_pos, std::vector<float> &tri_nrm, std::vector<float> &area_pmf, std::vector<float> &area_cdf, FlatRecords &flat) {
+    if (int rc = check_vertex_update(st, shape, positions, normals)) return rc;
+    const SceneGeometry &g = st.geometry;
+    if (int rc = check_finite(shape, positions, 3 * (size_t) g.shape_vertices[shape])) return rc;
+    const uint32_t off = g.shapes[shape].first_prim, n = g.shape_faces[shape];
+    std::vector<float> pos(9 * (size_t) n), nrm(normals ? 9 * (size_t) n : 0), pmf(n), cdf(n);
+    gather_shape(g, shape, positions, normals, pos.data(), nrm.data());
+    const int32_t em = g.shapes[shape].emitter;
+    DevEmitter e{};
+    if (em >= 0) {       // refused before anything is written
+        e = st.emitters[em];
+        for (uint32_t f = 0; f < n; ++f) pmf[f] = triangle_area(&pos[9 * (size_t) f]);
+        if (int rc = area_distribution(pmf.data(), n, cdf.data(), e)) return rc;
+    }
+    std::copy(pos.begin(), pos.end(), tri_pos.begin() + 9 * (size_t) off);
+    if (normals) std::copy(nrm.begin(), nrm.end(), tri_nrm.begin() + 9 * (size_t) off);
+    if (em >= 0) {
+        st.emitters[em] = e;
+        std::copy(pmf.begin(), pmf.end(), area_pmf.begin() + off); std::copy(cdf.begin(), cdf.end(), area_cdf.begin() + off);
+    }
+    refit_bvh(tri_pos.data(), st.bvh);
+    set_scene_bounds(st);
+    const bool was_flat = flat.flat;
+    build_flat_records(opt, st, tri_pos, flat);
+    if (flat.flat != was_flat) return fail(MTSAMD_ERR_DEVICE, "vertex update: the scene changed its kind");       // flatness depends on counts only
     return MTSAMD_OK;
 }
 

@@ -36,6 +36,16 @@ int check_spectrum(const mtsamd_spectrum_desc &sp, uint32_t index, double *integ
 float spectrum_table_mean(double integral);
 void build_spectrum_pool(const mtsamd_spectrum_desc *spectra, uint32_t n, std::vector<DevSpectrum> &headers, std::vector<float> &data);
 
+// The geometry a scene keeps for mtsamd_scene_set_vertex_positions: counts and face indices are those of creation
+struct SceneGeometry {
+    std::vector<DevShape> shapes;                       // host copy of the shape records (first_prim, emitter, flags)
+    std::vector<uint32_t> shape_vertices, shape_faces;  // per shape
+    std::vector<uint32_t> faces;                        // 3 per primitive: vertex indices within the primitive's mesh
+    std::vector<uint32_t> prim_shape;
+    bool flat = false;
+    std::vector<float> tri_pos, tri_nrm, area_pmf, area_cdf;      // flat scenes only (at most kFlatMaxPrims primitives): their records are rebuilt on the host
+};
+
 // What stays on the host for the life of a scene (mtsamd_scene embeds it): the records the setters edit and the queries read.
 struct SceneState {
     int32_t environment = -1;        // index of the `constant` / `envmap` emitter
@@ -65,6 +75,7 @@ struct SceneState {
     std::vector<float> env_rgb;
     bool ejac_dirty = true;
     int32_t env_w = 0, env_h = 0;           // envmap emitter: its size (0: none)
+    SceneGeometry geometry;
 };
 
 // builder knobs: the shipped values; experiment builds (-DMTSAMD_EXPERIMENTS) fill them from the environment in api.cpp
@@ -74,8 +85,15 @@ struct BuildOptions {
     uint32_t flat_max = kFlatMaxPrims;
 };
 
+// flat scenes: the LDS-resident records (build_flat_records)
+struct FlatRecords {
+    bool flat = false;                                  // n_prims <= flat_max and flat_launch_lds_max() <= kFlatLdsCap: the scene lives in LDS
+    std::vector<float4> flat_recs, pair_recs;           // pair_recs: 5 per pair, then 2 per cluster
+    uint32_t n_pairs = 0, n_clusters = 0;
+};
+
 // Everything creation computes on the host.  `state` outlives creation; the rest is uploaded and dropped.
-struct HostScene {
+struct HostScene : FlatRecords {
     SceneState state;
     std::vector<float> tri_pos, tri_nrm, tri_uv;       // 9 / 9 / 6 floats per primitive (normals, uvs: empty if no mesh has them)
     std::vector<uint32_t> prim_shape;
@@ -87,9 +105,6 @@ struct HostScene {
     // variant: model coefficients); null for a checkerboard
     std::vector<const float *> tex_src;
     std::vector<std::vector<float>> tex_coeffs;
-    bool flat = false;                                  // n_prims <= flat_max and flat_launch_lds_max() <= kFlatLdsCap: the scene lives in LDS
-    std::vector<float4> flat_recs, pair_recs;           // pair_recs: 5 per pair, then 2 per cluster
-    uint32_t n_pairs = 0, n_clusters = 0;
     bool has_envmap = false;
     EnvmapHost env;                                     // texels (spectral variant: coefficients + scale) and sampling hierarchy
     DevEnvmap dev_env{};                                // all fields but the two device pointers
@@ -100,6 +115,22 @@ struct HostScene {
 int build_host_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *spectra, uint32_t n_spectra,
                      const mtsamd_spectrum_binding *bindings, uint32_t n_bindings, const BuildOptions &options, HostScene &hs,
                      const mtsamd_texture_binding *tex_bindings = nullptr, uint32_t n_tex_bindings = 0);
+
+// ---- the parts of creation that depend on vertex positions, callable on their own: creation and the vertex update share them ----------
+float triangle_area(const float *tri_pos9);
+// cdf and emitter fields (area_sum, area_norm, valid_lo / hi) of `face_count` areas; an emitter without area is refused with the reference's text
+int area_distribution(const float *areas, uint32_t face_count, float *cdf, DevEmitter &e);
+void set_scene_bounds(SceneState &st);       // bounding sphere of st.bvh.bbox into the records of the constant, envmap and directional emitters
+void build_flat_records(const BuildOptions &opt, const SceneState &st, const std::vector<float> &tri_pos, FlatRecords &out);
+// refusals of a vertex update that need no look at the data, and the one that needs the (host) data
+int check_vertex_update(const SceneState &st, uint32_t shape, const float *positions, const float *normals);
+int check_finite(uint32_t shape, const float *positions, size_t n_floats);
+// per primitive of `shape`: 9 floats of positions (and normals) from its vertex arrays, in primitive order from 0
+void gather_shape(const SceneGeometry &g, uint32_t shape, const float *positions, const float *normals, float *tri_pos, float *tri_nrm);
+// The whole update on the host: parameters_changed({"vertex_positions_buf"}) of one mesh over whole-scene arrays.  Flat scenes are
+// updated this way; for hierarchy scenes it is the specification the device refit (refit.hip) is held to.  Nothing is written on a refusal.
+int set_vertex_positions(SceneState &st, const BuildOptions &opt, uint32_t shape, const float *positions, const float *normals,
+                         std::vector<float> &tri_pos, std::vector<float> &tri_nrm, std::vector<float> &area_pmf, std::vector<float> &area_cdf, FlatRecords &flat);
 
 // ---- host half of the setters: they edit `st` and name what the device copy now lacks ------------------------------------------
 // One scalar parameter of a BSDF record: which float(s) of DevBsdf it is.  false: the model has no such (differentiable) parameter.

@@ -826,6 +826,71 @@ class Scene:
                 if t == int(texture) and i < len(self._bsdf_records):
                     self._bsdf_records[i]["reflectance"]["data"] = np.clip(np.array(new, np.float32).reshape(shape), 0.0, 1.0)
 
+    def update_vertices(self, shape, positions, normals=None):
+        """parameters_changed({"vertex_positions_buf"}) of mesh `shape` (mesh.cpp:781-804): new vertex positions, same vertex count and
+        faces.  positions: (N, 3) or flat 3N, a numpy array or a torch tensor on the host or the device (a device tensor is read where it
+        is).  A mesh with vertex normals gets `normals`, or -- None -- normals recomputed from the new positions with
+        loaders.compute_vertex_normals (recompute_vertex_normals), which runs on the host: a device tensor makes one round trip for it.
+        The accelerator is refitted, not rebuilt; bbox(), the emitter tables and the scene description follow."""
+        shape = int(shape)
+        if not 0 <= shape < self._shape_count:
+            raise RuntimeError("invalid shape index %d (the scene has %d shapes)" % (shape, self._shape_count))
+        mesh = self._dict["meshes"][shape]
+        n_vertices = _f32(mesh["positions"]).reshape(-1, 3).shape[0]
+        dev = torch.device("cuda", self._device_index)
+
+        def as_arg(x, what):
+            """-> (pointer argument, object to keep alive, host copy)"""
+            if isinstance(x, torch.Tensor):
+                t = x.detach().to(torch.float32).contiguous()
+                if t.numel() != 3 * n_vertices:
+                    raise RuntimeError("%s has %d values, expected 3 * %d" % (what, t.numel(), n_vertices))
+                host = None if t.is_cuda else t.numpy()
+                if t.is_cuda:
+                    t = t.to(dev)
+                    return _ptr(t), t, host
+                return host.ctypes.data_as(C.c_void_p), host, host
+            a = _f32(x)
+            if a.size != 3 * n_vertices:
+                raise RuntimeError("%s has %d values, expected 3 * %d" % (what, a.size, n_vertices))
+            return a.ctypes.data_as(C.c_void_p), a, a
+        p_arg, p_keep, p_host = as_arg(positions, "positions")
+        n_arg, n_keep, n_host = None, None, None
+        if mesh.get("normals") is not None:
+            if normals is None:
+                from . import loaders
+                if p_host is None:
+                    p_host = p_keep.cpu().numpy()
+                normals = loaders.compute_vertex_normals(p_host.reshape(-1, 3), mesh["faces"])
+            n_arg, n_keep, n_host = as_arg(normals, "normals")
+        elif normals is not None:
+            raise RuntimeError("shape %d was created without vertex normals: none can be set" % shape)
+        L.check(L.lib().mtsamd_scene_set_vertex_positions(self._handle, shape, p_arg, n_arg, _stream()))
+        # the scene description follows the device, as for the other setters
+        if p_host is None:
+            p_host = p_keep.cpu().numpy()
+        mesh["positions"] = np.array(p_host, np.float32).reshape(-1, 3)
+        if n_keep is not None:
+            if n_host is None:
+                n_host = n_keep.cpu().numpy()
+            mesh["normals"] = np.array(n_host, np.float32).reshape(-1, 3)
+
+    def read_accel(self, which, words=None):
+        """Test aid (mtsamd_scene_read_accel): one device array of the accelerator as a flat numpy array of 32-bit words.  which:
+        "nodes", "qnodes", "wnodes", "tris", "tri_pos", "tri_nrm", "area_pmf", "area_cdf" or "grid".  `words`: the array's length where
+        info() does not give it (the wide nodes); a wrong length is an error."""
+        names = ("nodes", "qnodes", "wnodes", "tris", "tri_pos", "tri_nrm", "area_pmf", "area_cdf", "grid")
+        info = self.info()
+        n_prims, n_nodes = info["primitives"], info["bvh_nodes"]
+        has_normals = any(m.get("normals") is not None for m in self._dict["meshes"])
+        sizes = dict(nodes=16 * n_nodes, qnodes=8 * n_nodes, tris=12 * n_prims, tri_pos=9 * n_prims, tri_nrm=9 * n_prims if has_normals else 0,
+                     area_pmf=n_prims, area_cdf=n_prims, grid=6)
+        if words is None:
+            words = sizes[which]
+        out = np.zeros(max(int(words), 1), np.uint32)
+        L.check(L.lib().mtsamd_scene_read_accel(self._handle, names.index(which), out.ctypes.data_as(C.c_void_p), 4 * int(words)))
+        return out[:int(words)]
+
     def update_envmap(self, data, rebuild_distribution=True):
         """parameters_changed() for the envmap emitter's `data` (envmap.cpp:220-253); data: (H, W, 3) linear RGB tensor or array.
         ``rebuild_distribution=False`` keeps the importance-sampling hierarchy of the previous texels."""
