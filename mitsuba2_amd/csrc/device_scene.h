@@ -18,6 +18,7 @@
 #include "device_bsdf.h"
 #include "device_envmap.h"
 #include "flat_worklist.h"
+#include "flat_cull.h"
 
 namespace mtsamd {
 
@@ -102,7 +103,7 @@ struct SceneView {
     // plus 80-byte intersection records for primitive pairs (A = 2k, B = 2k+1), laid out for packed fp32 math:
     //   (p0x.ab, p0y.ab) (p0z.ab, e1x.ab) (e1y.ab, e1z.ab) (e2x.ab, e2y.ab) (e2z.ab, -, -)
     const float4 *flat_recs;
-    const float4 *flat_pairs;  // 5 float4 per primitive pair, followed by 2 float4 per pair cluster (padded box; .w of the first = pair count)
+    const float4 *flat_pairs;  // 5 float4 per primitive pair, followed by 2 float4 per pair cluster (padded box; .w of the first = pair count; flat_cull.h)
     uint32_t flat, n_pairs, n_clusters;
     int32_t env_emitter;       // index of the environment emitter or -1 (scene.cpp:44-48)
     const DevEnvmap *envmap;   // its image + sampling hierarchy if it is an `envmap`
@@ -124,7 +125,7 @@ struct LdsView {
     uint32_t spill_stride, stack_lds_depth;      // ... that takes the entries beyond the first stack_lds_depth
     const float4 *flat;        // 4 per prim (shading records)
     const float4 *pairs;       // 5 per primitive pair (intersection records), + 1 all-zero pair
-    const float4 *clusters;    // 2 per cluster of consecutive pairs (one shape): (lo.xyz, pair count), (hi.xyz, -)
+    const float4 *clusters;    // 2 per cluster of consecutive pairs (one shape): (centre.xyz, pair count), (half-extent.xyz, pair mask) (flat_cull.h)
     const DevShape *shapes;
     const DevBsdf *bsdfs;
     const DevEmitter *emitters;
@@ -810,10 +811,12 @@ MTS_DEV bool traverse_flat(const SceneView &sv, const LdsView &lds, f3 o, f3 d, 
 // ray reaches before its closest hit so far is skipped by the whole wave (a wave-uniform branch: no divergence, nothing to compact).
 // The boxes only cull: primitive order, arithmetic and tie rule of the triangle tests are those of traverse_flat, so the hit is
 // bit-identical.  A wall pixel of the Cornell box tests 1 pair instead of 18.  Incoherent waves (any lane at depth > 1) keep the plain
-// loop: there some lane reaches nearly every box and the 8 box tests (~20 VALU each) would only be added work.
+// loop: there some lane reaches nearly every box and the 8 box tests would only be added work.
 #ifndef MTS_FLAT_CULL
 #define MTS_FLAT_CULL 1
 #endif
+// The cull itself is flat_cull.h (MTS_FLAT_CULL_FORM; 0 keeps the lo / hi form of the slab test below, for A/B builds: with it the
+// library assembles to what it was).  The clustered loops hold the lean form of the query, the work lists the folded one (flat_cull.h).
 MTS_DEV bool traverse_flat_clustered(const SceneView &sv, const LdsView &lds, f3 o, f3 d, float mint, float maxt, Hit &hit, uint32_t &tri_tests) {
     float best = maxt, bu = 0.0f, bv = 0.0f;
     uint32_t best_prim = kNoPrim;
@@ -822,6 +825,16 @@ MTS_DEV bool traverse_flat_clustered(const SceneView &sv, const LdsView &lds, f3
 #endif                         // 4 / 8: work-list fallbacks / queries (traverse_flat_worklist)
     if (!(MTS_CULL_STATS & 1)) tri_tests += sv.n_prims;            // nominal count, as the plain loop (the statistics do not depend on the schedule)
     const v2f ox = splat(o.x), oy = splat(o.y), oz = splat(o.z), dx = splat(d.x), dy = splat(d.y), dz = splat(d.z);
+#if MTS_FLAT_CULL_FORM
+    const CullLean q = cull_ray<CullLean>(o.x, o.y, o.z, d.x, d.y, d.z);
+    const float4 *rec = lds.pairs;
+    uint32_t k = 0u;
+    for (uint32_t c = 0; c < sv.n_clusters; ++c) {
+        const float4 r0 = lds.clusters[2u * c], r1 = lds.clusters[2u * c + 1u];
+        const uint32_t n = cull_count(r0);
+        // reach test against the padded box; the interval is [mint, best]
+        if (__ballot(cull_reach(q, r0, r1, mint, best)) == 0ull) { rec += 5u * n; k += n; continue; }
+#else
     const f3 inv = mk3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
     const float4 *rec = lds.pairs;
     uint32_t k = 0u;
@@ -835,6 +848,7 @@ MTS_DEV bool traverse_flat_clustered(const SceneView &sv, const LdsView &lds, f3
         const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), mint));
         const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), best));
         if (__ballot(tn <= tf) == 0ull) { rec += 5u * n; k += n; continue; }
+#endif
         if (MTS_CULL_STATS & 1) tri_tests += 2u * n;
         for (uint32_t i = 0; i < n; ++i, ++k) {
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
@@ -859,6 +873,14 @@ MTS_DEV bool traverse_flat_clustered_any(const SceneView &sv, const LdsView &lds
     bool any = false;
     if (!(MTS_CULL_STATS & 2)) tri_tests += sv.n_prims;     // nominal count, as the plain loop
     const v2f ox = splat(o.x), oy = splat(o.y), oz = splat(o.z), dx = splat(d.x), dy = splat(d.y), dz = splat(d.z);
+#if MTS_FLAT_CULL_FORM
+    const CullLean q = cull_ray<CullLean>(o.x, o.y, o.z, d.x, d.y, d.z);
+    const float4 *rec = lds.pairs;
+    for (uint32_t c = 0; c < sv.n_clusters; ++c) {
+        const float4 r0 = lds.clusters[2u * c], r1 = lds.clusters[2u * c + 1u];
+        const uint32_t n = cull_count(r0);
+        if (__ballot(!any && cull_reach(q, r0, r1, mint, maxt)) == 0ull) { rec += 5u * n; continue; }
+#else
     const f3 inv = mk3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
     const float4 *rec = lds.pairs;
     for (uint32_t c = 0; c < sv.n_clusters; ++c) {
@@ -870,6 +892,7 @@ MTS_DEV bool traverse_flat_clustered_any(const SceneView &sv, const LdsView &lds
         const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), mint));
         const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), maxt));
         if (__ballot(!any && tn <= tf) == 0ull) { rec += 5u * n; continue; }
+#endif
         if (MTS_CULL_STATS & 2) tri_tests += 2u * n;
         for (uint32_t i = 0; i < n; ++i) {
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
@@ -900,6 +923,14 @@ MTS_DEV bool traverse_flat_worklist(const SceneView &sv, const LdsView &lds, f3 
     const uint64_t active = __ballot(1);
     const uint32_t n_act = (uint32_t) __popcll(active), lane = lane_id(), rank = mask_rank(active);
     // pairs whose cluster box the segment reaches
+#if MTS_FLAT_CULL_FORM
+    const CullFolded q = cull_ray<CullFolded>(o.x, o.y, o.z, d.x, d.y, d.z);
+    uint32_t pairs = 0u;
+    for (uint32_t c = 0; c < sv.n_clusters; ++c) {
+        const float4 r0 = lds.clusters[2u * c], r1 = lds.clusters[2u * c + 1u];
+        pairs |= cull_reach(q, r0, r1, mint, maxt) ? cull_mask(r1) : 0u;       // the cluster's pair mask, shifted together by the host
+    }
+#else
     const f3 inv = mk3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
     uint32_t pairs = 0u, first = 0u;
     for (uint32_t c = 0; c < sv.n_clusters; ++c) {
@@ -914,6 +945,7 @@ MTS_DEV bool traverse_flat_worklist(const SceneView &sv, const LdsView &lds, f3 
         pairs |= tn <= tf ? bits : 0u;
         first += n;
     }
+#endif
     // exclusive prefix of the item counts over the active lanes and their total, one ballot per bit of the count (<= 32)
     const uint32_t cnt = (uint32_t) __popc(pairs);
     uint32_t pos = 0u, total = 0u;

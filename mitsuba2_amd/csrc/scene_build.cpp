@@ -745,9 +745,11 @@ void build_flat_records(const BuildOptions &opt, const SceneState &state, const 
             for (int vtx = 0; vtx < 3; ++vtx) for (int a = 0; a < 3; ++a) {
                 lo[a] = std::min(lo[a], tri_pos[9 * (size_t) gp + 3 * vtx + a]); hi[a] = std::max(hi[a], tri_pos[9 * (size_t) gp + 3 * vtx + a]);
             }
-        const uint32_t cnt = k1 - k0; float cntf; std::memcpy(&cntf, &cnt, 4);
-        out.pair_recs.push_back(make_float4(lo[0] - pad, lo[1] - pad, lo[2] - pad, cntf));
-        out.pair_recs.push_back(make_float4(hi[0] + pad, hi[1] + pad, hi[2] + pad, 0.0f));
+        for (int a = 0; a < 3; ++a) { lo[a] -= pad; hi[a] += pad; }
+        float4 r0, r1;
+        cull_encode<MTS_FLAT_CULL_FORM>(lo, hi, k0, k1 - k0, r0, r1);      // flat_cull.h: the record the device's reach predicate reads
+        out.pair_recs.push_back(r0);
+        out.pair_recs.push_back(r1);
         ++out.n_clusters;
     }
 }
