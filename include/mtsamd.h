@@ -228,7 +228,7 @@ MTSAMD_API int mtsamd_scene_update_texture(mtsamd_scene *scene, uint32_t texture
 /* Mesh `vertex_positions_buf` (mesh.cpp:781-804) of shape `shape`, i.e. parameters_changed({"vertex_positions_buf"}) of that mesh: its
  * vertex and face counts and its face indices stay those of creation.  positions / normals: host OR device pointers (told apart as
  * mtsamd_scene_update_texture tells them apart) to 3 * vertex_count floats of that mesh; `normals` is required exactly when the mesh was
- * created with normals and an error otherwise (recompute_vertex_normals is left to the caller).  The accelerator keeps its topology and
+ * created with normals and an error otherwise (recompute_vertex_normals: mtsamd_scene_update_vertices below).  The accelerator keeps its topology and
  * gets new boxes (a refit: on the device for hierarchy scenes); the area distribution of an emitter shape, the scene's bounding box,
  * the bounding sphere in the constant / envmap / directional emitter records and the records of a flat scene follow.  Samples and
  * queries afterwards equal, bit for bit, those of a scene created from the moved vertices.  Refused with MTSAMD_ERR_INVALID before
@@ -236,6 +236,26 @@ MTSAMD_API int mtsamd_scene_update_texture(mtsamd_scene *scene, uint32_t texture
  * area ("DiscreteDistribution: no probability mass found!").  Every other setter's state is kept.  Waits for `stream` and returns when
  * the scene is consistent. */
 MTSAMD_API int mtsamd_scene_set_vertex_positions(mtsamd_scene *scene, uint32_t shape, const float *positions, const float *normals, void *stream);
+/* mtsamd_scene_set_vertex_positions with flags.  flags == 0: exactly that call (normals_out is not written).
+ * MTSAMD_VERTICES_RECOMPUTE_NORMALS: the other half of parameters_changed({"vertex_positions_buf"}), recompute_vertex_normals
+ * (mesh.cpp:199-276, called at mesh.cpp:797): `normals` must be NULL and the call behaves like mtsamd_scene_set_vertex_positions given
+ * the normals mtsamd_compute_vertex_normals computes from `positions` and the mesh's faces -- on the device for hierarchy scenes (no
+ * vertex data crosses to the host), bit for bit the same values.  normals_out (may be NULL): a host OR device pointer that receives
+ * those 3 * vertex_count floats.  Refused with MTSAMD_ERR_INVALID, beside the refusals of mtsamd_scene_set_vertex_positions and like
+ * them before anything is written: unknown flag bits; the flag together with `normals`; the flag on a mesh created without vertex
+ * normals (the reference Throws: "Storing new normals in a Mesh that didn't have normals at construction time is not implemented
+ * yet."). */
+enum {
+    MTSAMD_VERTICES_RECOMPUTE_NORMALS = 1
+};
+MTSAMD_API int mtsamd_scene_update_vertices(mtsamd_scene *scene, uint32_t shape, const float *positions, const float *normals, uint32_t flags,
+                                            float *normals_out, void *stream);
+/* recompute_vertex_normals (mesh.cpp:199-276) in single precision, on the host; needs no scene and no device.  Face normals weighted by
+ * the face's angle at each vertex (Thuermer & Wuethrich 1998), summed per vertex in the order of the faces; a face whose cross product
+ * or one of whose edges has a squared length that is zero or not finite in fp32 is skipped; a vertex without a valid normal gets
+ * (1, 0, 0).  positions: 3 * vertex_count floats; faces: 3 * face_count vertex indices; normals_out: 3 * vertex_count floats, always
+ * finite.  MTSAMD_ERR_INVALID: a null array or a face index out of range. */
+MTSAMD_API int mtsamd_compute_vertex_normals(uint32_t vertex_count, const float *positions, uint32_t face_count, const uint32_t *faces, float *normals_out);
 /* Test aid: copies one device array of the accelerator to the host.  MTSAMD_ERR_INVALID unless `bytes` is that array's size. */
 enum {
     MTSAMD_ACCEL_NODES = 0,      /* BVH2 nodes, 64 bytes each */

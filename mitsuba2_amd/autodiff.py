@@ -86,8 +86,11 @@ class ParameterMap:
     """Dictionary-like view of the differentiable scene parameters (util.py:16-130): torch tensors on the scene's GPU.
     Writes take effect in the scene after :meth:`update` (``parameters_changed``)."""
 
-    def __init__(self, scene, replay=False, geometry=False):
+    def __init__(self, scene, replay=False, geometry=False, normals=None):
         self._scene = scene
+        if normals not in (None, "recompute"):
+            raise RuntimeError("normals: None or \"recompute\", not %r" % (normals,))
+        self._normals = normals                      # how update() gets the vertex normals of a moved mesh that has them
         # spectral variant only: differentiate the reflectance family (constant srgb colours and bitmap texels of diffuse.reflectance /
         # (rough)plastic.diffuse_reflectance) by the spectral path replay, mtsamd_render_adjoint_spectral, instead of central differences,
         # and the emitter family (envmap texels; radiance / intensity / irradiance of every other emitter) by
@@ -201,7 +204,7 @@ class ParameterMap:
         for i, m in enumerate(scene._dict["meshes"] if geometry else []):
             key = m.get("id", "shape_%d" % i) + ".vertex_positions_buf"
             self.properties[key] = torch.as_tensor(np.ascontiguousarray(m["positions"], np.float32).reshape(-1), dtype=torch.float32, device=dev).clone()
-            self._kind[key] = ("vertices", i, i)
+            self._kind[key] = ("vertices", i, m.get("normals") is not None)
             # the scene was created from these positions: update() pushes the buffer only once it holds something else
             self.__dict__.setdefault("_pushed", {})[key] = (self.properties[key], self.properties[key]._version)
 
@@ -249,7 +252,7 @@ class ParameterMap:
                     v.clamp_(min=0.0)
             seen[k] = (v, v._version)
             if kind == "vertices":
-                self._scene.update_vertices(idx, v)
+                self._scene.update_vertices(idx, v, normals=self._normals if self._kind[k][2] else None)
             elif kind in ("texture", "param_texture"):
                 self._scene.update_texture(idx, v)
             elif kind == "emitter":
@@ -263,14 +266,15 @@ class ParameterMap:
                 self._scene.set_bsdf_reflectance(idx, v.detach().cpu().tolist())
 
 
-def traverse(scene, replay=False, geometry=False):
+def traverse(scene, replay=False, geometry=False, normals=None):
     """mitsuba.python.util.traverse (util.py:132-179) for the supported parameters.  ``replay=True`` (spectral scenes; ignored for RGB
     ones) adds the bitmap texels of the reflectance family and the emitted colour of shapeless emitters, and differentiates the reflectance
     family and the emitter family (envmap texels included) with one spectral path replay each per backward pass.  ``geometry=True`` adds
     '<shape id>.vertex_positions_buf' of every mesh (the flat 3N buffer of mesh.cpp:781-804); update() pushes it through
-    Scene.update_vertices.  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
+    Scene.update_vertices; ``normals="recompute"`` makes it pass that on for every mesh with vertex normals, so that a moved mesh's
+    normals are recomputed on the device and no vertex data visits the host.  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
     which is why they have to be asked for: render() raises on one that requires a gradient."""
-    return ParameterMap(scene, replay=replay, geometry=geometry)
+    return ParameterMap(scene, replay=replay, geometry=geometry, normals=normals)
 
 
 def _replayed(pmap, key):

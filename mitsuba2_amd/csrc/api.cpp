@@ -396,6 +396,10 @@ struct mtsamd_scene : SceneState {
     int32_t *d_node_child = nullptr, *d_wide_child = nullptr;
     float *d_boxes = nullptr, *d_stage_pos = nullptr, *d_stage_nrm = nullptr, *d_stage_area = nullptr;
     std::vector<uint32_t> class_start;      // height classes of d_order
+    // MTSAMD_VERTICES_RECOMPUTE_NORMALS, hierarchy scenes: per shape its vertex-to-corner table (build_corner_table), null until the first
+    // recompute of that shape; d_face_recs: 6 floats per face of the largest shape, allocated with the first table
+    std::vector<uint32_t *> d_corner_offsets, d_corners;
+    float *d_face_recs = nullptr;
     int32_t refit_root = 0;
     size_t n_tri_nrm = 0;                   // floats in d_tri_nrm
     uint32_t n_pairs = 0, n_clusters = 0;
@@ -602,6 +606,9 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
     for (auto &t : s->textures) (void) hipFree((void *) t.data);
     (void) hipFree(s->d_faces); (void) hipFree(s->d_prim_slot); (void) hipFree(s->d_slot_prim); (void) hipFree(s->d_order); (void) hipFree(s->d_refit_flag); (void) hipFree(s->d_kids);
     (void) hipFree(s->d_node_child); (void) hipFree(s->d_wide_child); (void) hipFree(s->d_boxes); (void) hipFree(s->d_stage_pos); (void) hipFree(s->d_stage_nrm); (void) hipFree(s->d_stage_area);
+    for (uint32_t *p : s->d_corner_offsets) (void) hipFree(p);
+    for (uint32_t *p : s->d_corners) (void) hipFree(p);
+    (void) hipFree(s->d_face_recs);
     (void) hipFree(s->d_textures); (void) hipFree(s->d_jac); (void) hipFree(s->d_cgrad); (void) hipFree(s->d_ejac); (void) hipFree(s->d_egrad);
     delete s;
 }
@@ -716,15 +723,22 @@ int mtsamd_scene_set_emitter_radiance(mtsamd_scene *s, uint32_t emitter, const f
 
 // ---- vertex updates ------------------------------------------------------------------------------------------------------------------
 // A flat scene: everything is rebuilt on the host by the code creation runs (set_vertex_positions) and uploaded again; then the frames.
-static int flat_vertex_update(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, hipStream_t stream) {
+// recompute: the normals are compute_vertex_normals' of the new positions, which are on the host here anyway.
+static int flat_vertex_update(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, bool recompute, float *normals_out,
+                              hipStream_t stream) {
     SceneGeometry &g = s->geometry;
     const size_t nv = 3 * (size_t) g.shape_vertices[shape];
-    std::vector<float> pos(nv), nrm(normals ? nv : 0);
+    const bool with_normals = normals || recompute;
+    std::vector<float> pos(nv), nrm(with_normals ? nv : 0);
     HIP_TRY(hipStreamSynchronize(stream));          // whatever writes the arrays, and the renders that read the old scene
     HIP_TRY(hipMemcpy(pos.data(), positions, nv * sizeof(float), hipMemcpyDefault));
     if (normals) HIP_TRY(hipMemcpy(nrm.data(), normals, nv * sizeof(float), hipMemcpyDefault));
+    if (recompute) {          // a non-finite coordinate is refused below before anything is written; the normals are finite whatever comes in
+        compute_vertex_normals(g.shape_vertices[shape], pos.data(), g.shape_faces[shape], g.faces.data() + 3 * (size_t) g.shapes[shape].first_prim, nrm.data());
+    }
     FlatRecords fr; fr.flat = true;
-    if (int rc = set_vertex_positions(*s, s->options, shape, pos.data(), normals ? nrm.data() : nullptr, g.tri_pos, g.tri_nrm, g.area_pmf, g.area_cdf, fr)) return rc;
+    if (int rc = set_vertex_positions(*s, s->options, shape, pos.data(), with_normals ? nrm.data() : nullptr, g.tri_pos, g.tri_nrm, g.area_pmf, g.area_cdf, fr)) return rc;
+    if (recompute && normals_out) HIP_TRY(hipMemcpy(normals_out, nrm.data(), nv * sizeof(float), hipMemcpyDefault));
     if (fr.n_pairs != s->n_pairs || fr.n_clusters != s->n_clusters) return fail(MTSAMD_ERR_DEVICE, "vertex update: the flat records changed their size");
     const BvhOutput &bvh = s->bvh;
     auto put = [](void *dst, const void *src, size_t bytes) { return bytes == 0 ? hipSuccess : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); };
@@ -758,16 +772,44 @@ static RefitView refit_view(const mtsamd_scene *s) {
     return rv;
 }
 
-int mtsamd_scene_set_vertex_positions(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, void *stream_) {
+// The vertex-to-corner table of `shape` on the device, built at the first recompute of that shape from the face indices the device
+// holds (the host copy was dropped at creation) and kept until the scene goes.
+static int corner_table(mtsamd_scene *s, uint32_t shape, hipStream_t stream) {
+    SceneGeometry &g = s->geometry;
+    if (s->d_corner_offsets.empty()) { s->d_corner_offsets.assign(g.shapes.size(), nullptr); s->d_corners.assign(g.shapes.size(), nullptr); }
+    if (!s->d_face_recs) {
+        uint32_t max_faces = 1;
+        for (uint32_t n : g.shape_faces) max_faces = std::max(max_faces, n);
+        HIP_TRY(hipMalloc((void **) &s->d_face_recs, 6 * sizeof(float) * (size_t) max_faces));
+    }
+    if (s->d_corner_offsets[shape]) return MTSAMD_OK;
+    const uint32_t n_faces = g.shape_faces[shape];
+    std::vector<uint32_t> faces(3 * (size_t) n_faces), offsets, corners;
+    if (n_faces) HIP_TRY(hipMemcpyAsync(faces.data(), s->d_faces + 3 * (size_t) g.shapes[shape].first_prim, faces.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    build_corner_table(g.shape_vertices[shape], n_faces, faces.data(), offsets, corners);
+    uint32_t *d_offsets = nullptr, *d_corners = nullptr;
+    if (int rc = upload(&d_offsets, offsets)) return rc;
+    if (int rc = upload(&d_corners, corners)) { (void) hipFree(d_offsets); return rc; }
+    s->d_corner_offsets[shape] = d_offsets; s->d_corners[shape] = d_corners;
+    return MTSAMD_OK;
+}
+
+static int vertex_update(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, uint32_t flags, float *normals_out, void *stream_) {
     if (!s) return fail(MTSAMD_ERR_INVALID, "null scene");
-    if (int rc = check_vertex_update(*s, shape, positions, normals)) return rc;
+    if (int rc = check_vertex_flags(*s, shape, normals, flags)) return rc;
+    const bool recompute = (flags & MTSAMD_VERTICES_RECOMPUTE_NORMALS) != 0u;
+    // with the flag the mesh has normals (check_vertex_flags) and the call computes them: what is left to check is the shape and the positions
+    if (int rc = check_vertex_update(*s, shape, positions, recompute ? positions : normals)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t) stream_;
     SceneGeometry &g = s->geometry;
-    if (g.flat) return flat_vertex_update(s, shape, positions, normals, stream);
+    if (g.flat) return flat_vertex_update(s, shape, positions, normals, recompute, normals_out, stream);
     const uint32_t nv = 3u * g.shape_vertices[shape], off = g.shapes[shape].first_prim, n_faces = g.shape_faces[shape];
     const int32_t em = g.shapes[shape].emitter;
     const RefitView rv = refit_view(s);
+    if (recompute)
+        if (int rc = corner_table(s, shape, stream)) return rc;
     // 1. stage the arrays (host or device pointers alike) and look before writing: finite coordinates, and the areas of an emitter shape
     HIP_TRY(hipMemcpyAsync(s->d_stage_pos, positions, nv * sizeof(float), hipMemcpyDefault, stream));
     if (normals) HIP_TRY(hipMemcpyAsync(s->d_stage_nrm, normals, nv * sizeof(float), hipMemcpyDefault, stream));
@@ -784,8 +826,14 @@ int mtsamd_scene_set_vertex_positions(mtsamd_scene *s, uint32_t shape, const flo
         e = s->emitters[em];
         if (int rc = area_distribution(pmf.data(), n_faces, cdf.data(), e)) return rc;
     }
+    // the normals of the staged positions into the staging buffer the gather reads: after the refusals, before the commit
+    if (recompute) {
+        HIP_TRY(launch_refit_normals(rv, s->d_stage_pos, off, n_faces, g.shape_vertices[shape], s->d_corner_offsets[shape], s->d_corners[shape],
+                                     s->d_face_recs, s->d_stage_nrm, stream));
+        if (normals_out) HIP_TRY(hipMemcpyAsync(normals_out, s->d_stage_nrm, nv * sizeof(float), hipMemcpyDefault, stream));
+    }
     // 2. commit: primitives and slots of the shape, then every box from the leaves up, one launch per height class
-    HIP_TRY(launch_refit_gather(rv, s->d_stage_pos, normals ? s->d_stage_nrm : nullptr, off, n_faces, stream));
+    HIP_TRY(launch_refit_gather(rv, s->d_stage_pos, normals || recompute ? s->d_stage_nrm : nullptr, off, n_faces, stream));
     for (size_t h = 0; h + 1 < s->class_start.size(); ++h)
         HIP_TRY(launch_refit_boxes(rv, s->class_start[h], s->class_start[h + 1] - s->class_start[h], h == 0, stream));
     // 3. the scene box: the root's.  Extent, grid, bounding sphere and the records that hold it are the host's arithmetic.
@@ -807,6 +855,23 @@ int mtsamd_scene_set_vertex_positions(mtsamd_scene *s, uint32_t shape, const flo
     }
     if (!s->emitters.empty()) HIP_TRY(hipMemcpyAsync(s->d_emitters, s->emitters.data(), s->emitters.size() * sizeof(DevEmitter), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    return MTSAMD_OK;
+}
+
+int mtsamd_scene_set_vertex_positions(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, void *stream) {
+    return vertex_update(s, shape, positions, normals, 0u, nullptr, stream);
+}
+
+int mtsamd_scene_update_vertices(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, uint32_t flags, float *normals_out,
+                                 void *stream) {
+    return vertex_update(s, shape, positions, normals, flags, normals_out, stream);
+}
+
+int mtsamd_compute_vertex_normals(uint32_t vertex_count, const float *positions, uint32_t face_count, const uint32_t *faces, float *normals_out) {
+    if ((vertex_count && (!positions || !normals_out)) || (face_count && !faces)) return fail(MTSAMD_ERR_INVALID, "null argument");
+    for (size_t c = 0; c < 3 * (size_t) face_count; ++c)
+        if (faces[c] >= vertex_count) return fail(MTSAMD_ERR_INVALID, "face %u: vertex index %u out of range (%u vertices)", (uint32_t) (c / 3), faces[c], vertex_count);
+    compute_vertex_normals(vertex_count, positions, face_count, faces, normals_out);
     return MTSAMD_OK;
 }
 

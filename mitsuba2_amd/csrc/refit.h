@@ -30,6 +30,11 @@ struct RefitView {
 // n_faces triangles of the shape whose faces start at primitive first_prim
 hipError_t launch_refit_check(const RefitView &rv, const float *positions, uint32_t n_floats, uint32_t first_prim, uint32_t n_faces, float *areas,
                               uint32_t *flag, hipStream_t s);
+// recompute_vertex_normals of one shape (vertex_normals.h): `normals` (3 per vertex) from the staged positions.  offsets (n_vertices + 1)
+// and corners (3 * n_faces, each 3 * face + corner with the face counted within the shape, ascending per vertex): the shape's
+// vertex-to-corner table; face_recs: 6 floats per face of scratch.  Two launches; reads nothing the refit writes.
+hipError_t launch_refit_normals(const RefitView &rv, const float *positions, uint32_t first_prim, uint32_t n_faces, uint32_t n_vertices,
+                                const uint32_t *offsets, const uint32_t *corners, float *face_recs, float *normals, hipStream_t s);
 // tri_pos, tri_nrm (normals not null) and the slot records of the shape's primitives
 hipError_t launch_refit_gather(const RefitView &rv, const float *positions, const float *normals, uint32_t first_prim, uint32_t n_faces, hipStream_t s);
 // boxes of the builder nodes order[first .. first + n): leaves from their triangles (height 0), inner nodes from their children.  One

@@ -1,8 +1,9 @@
-// refit.hip -- device BVH refit for gfx950 (refit.h).  Four small kernels; the kernel boundary is the only synchronisation: no thread
+// refit.hip -- device BVH refit for gfx950 (refit.h).  Four small kernels, and two that recompute vertex normals; the kernel boundary is the only synchronisation: no thread
 // waits on another, nothing is handed between workgroups inside a launch, and min / max are exact, so every result is order-free.
 // The arithmetic restates bvh.cpp's emission (refit_encode.h) and scene_build.cpp's triangle_area; the build has -ffp-contract=off.
 #include "refit.h"
 #include "device_scene.h"
+#include "vertex_normals.h"
 
 namespace mtsamd {
 namespace {
@@ -75,6 +76,38 @@ __global__ void __launch_bounds__(kRefitBlock) k_refit_level(RefitView rv, uint3
     for (int k = 0; k < 3; ++k) { bx[k] = enc_min(l[k], r[k]); bx[3 + k] = enc_max(l[3 + k], r[3 + k]); }
 }
 
+// Vertex normals recomputed from the staged positions (vertex_normals.h holds the arithmetic, the host's too).  One thread per face
+// writes the face's record: normal and corner angles, zeros for a skipped face.  `faces`: the shape's own, vertex indices below n_vertices.
+__global__ void __launch_bounds__(kRefitBlock) k_normals_faces(const uint32_t *__restrict__ faces, const float *__restrict__ positions, uint32_t n_faces,
+                                                               float *__restrict__ face_recs) {
+    const uint32_t f = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (f >= n_faces) return;
+    float p[9], rec[6];
+    for (int j = 0; j < 3; ++j) {
+        const uint32_t vi = faces[3 * (size_t) f + j];
+        for (int k = 0; k < 3; ++k) p[3 * j + k] = positions[3 * (size_t) vi + k];
+    }
+    vn_face(p, p + 3, p + 6, rec);
+    for (int k = 0; k < 6; ++k) face_recs[6 * (size_t) f + k] = rec[k];
+}
+
+// One thread per vertex gathers its corners (3 * face + corner) in the order of the table, which is the order of the host's loop over the
+// faces: no atomics, the sum of each vertex has one order.
+__global__ void __launch_bounds__(kRefitBlock) k_normals_vertices(const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ corners,
+                                                                  const float *__restrict__ face_recs, uint32_t n_vertices, float *__restrict__ normals) {
+    const uint32_t v = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (v >= n_vertices) return;
+    float acc[3] = { 0.0f, 0.0f, 0.0f }, out[3];
+    for (uint32_t c = offsets[v], end = offsets[v + 1]; c < end; ++c) {
+        const uint32_t corner = corners[c], f = corner / 3u;
+        float rec[6];
+        for (int k = 0; k < 6; ++k) rec[k] = face_recs[6 * (size_t) f + k];
+        vn_accumulate(acc, rec, corner - 3u * f);
+    }
+    vn_finish(acc, out);
+    for (int k = 0; k < 3; ++k) normals[3 * (size_t) v + k] = out[k];
+}
+
 // one thread per child box: 2 per BVH2 node, then 4 per wide node.  Child references and the words of absent children stay as creation
 // wrote them.
 __global__ void __launch_bounds__(kRefitBlock) k_refit_emit(RefitView rv, RefitGrid g) {
@@ -115,6 +148,13 @@ hipError_t launch_refit_check(const RefitView &rv, const float *positions, uint3
 hipError_t launch_refit_gather(const RefitView &rv, const float *positions, const float *normals, uint32_t first_prim, uint32_t n_faces, hipStream_t s) {
     if (n_faces == 0) return hipSuccess;
     hipLaunchKernelGGL(k_refit_gather, dim3(refit_blocks(n_faces)), dim3(kRefitBlock), 0, s, rv, positions, normals, first_prim, n_faces);
+    return hipGetLastError();
+}
+
+hipError_t launch_refit_normals(const RefitView &rv, const float *positions, uint32_t first_prim, uint32_t n_faces, uint32_t n_vertices,
+                                const uint32_t *offsets, const uint32_t *corners, float *face_recs, float *normals, hipStream_t s) {
+    if (n_faces) hipLaunchKernelGGL(k_normals_faces, dim3(refit_blocks(n_faces)), dim3(kRefitBlock), 0, s, rv.faces + 3 * (size_t) first_prim, positions, n_faces, face_recs);
+    if (n_vertices) hipLaunchKernelGGL(k_normals_vertices, dim3(refit_blocks(n_vertices)), dim3(kRefitBlock), 0, s, offsets, corners, face_recs, n_vertices, normals);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 // Reference call stack this replaces:
 //   Scene::Scene -> accel_init -> ShapeKDTree::build          src/librender/scene.cpp:22-98
 #include "scene_build.h"
+#include "vertex_normals.h"
 
 #include <algorithm>
 #include <cmath>
@@ -993,6 +994,37 @@ int check_vertex_update(const SceneState &st, uint32_t shape, const float *posit
     if (has && !normals) return fail(MTSAMD_ERR_INVALID, "shape %u was created with vertex normals: new normals are required with new positions", shape);
     if (!has && normals) return fail(MTSAMD_ERR_INVALID, "shape %u was created without vertex normals: none can be set", shape);
     return MTSAMD_OK;
+}
+
+int check_vertex_flags(const SceneState &st, uint32_t shape, const float *normals, uint32_t flags) {
+    const SceneGeometry &g = st.geometry;
+    if (flags & ~(uint32_t) MTSAMD_VERTICES_RECOMPUTE_NORMALS) return fail(MTSAMD_ERR_INVALID, "unknown vertex update flags 0x%x", flags & ~(uint32_t) MTSAMD_VERTICES_RECOMPUTE_NORMALS);
+    if (!(flags & MTSAMD_VERTICES_RECOMPUTE_NORMALS)) return MTSAMD_OK;
+    if (shape >= g.shapes.size()) return fail(MTSAMD_ERR_INVALID, "invalid shape index %u (the scene has %u shapes)", shape, (uint32_t) g.shapes.size());
+    if (normals) return fail(MTSAMD_ERR_INVALID, "shape %u: MTSAMD_VERTICES_RECOMPUTE_NORMALS computes the normals: none can be passed with it", shape);
+    if (!(g.shapes[shape].flags & kShapeHasNormals))      // recompute_vertex_normals' Throw (mesh.cpp:200-202)
+        return fail(MTSAMD_ERR_INVALID, "shape %u was created without vertex normals: storing new normals in such a mesh is not implemented", shape);
+    return MTSAMD_OK;
+}
+
+void compute_vertex_normals(uint32_t vertex_count, const float *positions, uint32_t face_count, const uint32_t *faces, float *normals_out) {
+    std::vector<float> acc(3 * (size_t) vertex_count, 0.0f);
+    for (uint32_t f = 0; f < face_count; ++f) {
+        const uint32_t *fi = faces + 3 * (size_t) f;
+        float rec[6];
+        if (!vn_face(positions + 3 * (size_t) fi[0], positions + 3 * (size_t) fi[1], positions + 3 * (size_t) fi[2], rec)) continue;
+        for (uint32_t j = 0; j < 3; ++j) vn_accumulate(&acc[3 * (size_t) fi[j]], rec, j);
+    }
+    for (uint32_t v = 0; v < vertex_count; ++v) vn_finish(&acc[3 * (size_t) v], normals_out + 3 * (size_t) v);
+}
+
+void build_corner_table(uint32_t vertex_count, uint32_t face_count, const uint32_t *faces, std::vector<uint32_t> &offsets, std::vector<uint32_t> &corners) {
+    offsets.assign((size_t) vertex_count + 1, 0u);
+    corners.assign(3 * (size_t) face_count, 0u);
+    for (size_t c = 0; c < corners.size(); ++c) ++offsets[(size_t) faces[c] + 1];
+    for (uint32_t v = 0; v < vertex_count; ++v) offsets[v + 1] += offsets[v];
+    std::vector<uint32_t> next(offsets.begin(), offsets.end() - 1);
+    for (size_t c = 0; c < corners.size(); ++c) corners[next[faces[c]]++] = (uint32_t) c;       // c = 3 * face + corner, met in ascending order
 }
 
 int check_finite(uint32_t shape, const float *positions, size_t n_floats) {

@@ -127,6 +127,15 @@ int check_vertex_update(const SceneState &st, uint32_t shape, const float *posit
 int check_finite(uint32_t shape, const float *positions, size_t n_floats);
 // per primitive of `shape`: 9 floats of positions (and normals) from its vertex arrays, in primitive order from 0
 void gather_shape(const SceneGeometry &g, uint32_t shape, const float *positions, const float *normals, float *tri_pos, float *tri_nrm);
+// Mesh::recompute_vertex_normals (mesh.cpp:199-276) in fp32, built from vertex_normals.h: the specification the device kernels of
+// refit.hip are held to, bit for bit, and what a flat scene uses.  faces: 3 vertex indices per face, each below vertex_count;
+// normals_out: 3 per vertex, always finite (a vertex without a valid normal gets (1, 0, 0)).
+void compute_vertex_normals(uint32_t vertex_count, const float *positions, uint32_t face_count, const uint32_t *faces, float *normals_out);
+// The vertex-to-corner table of one mesh in CSR form, as the device gathers through it: corners[offsets[v] .. offsets[v + 1]) are the
+// corners 3 * face + corner at which vertex v occurs, ascending, i.e. in the order compute_vertex_normals meets them.
+void build_corner_table(uint32_t vertex_count, uint32_t face_count, const uint32_t *faces, std::vector<uint32_t> &offsets, std::vector<uint32_t> &corners);
+// refusals of mtsamd_scene_update_vertices that concern its flags; what is left is check_vertex_update's with the normals the call will have
+int check_vertex_flags(const SceneState &st, uint32_t shape, const float *normals, uint32_t flags);
 // The whole update on the host: parameters_changed({"vertex_positions_buf"}) of one mesh over whole-scene arrays.  Flat scenes are
 // updated this way; for hierarchy scenes it is the specification the device refit (refit.hip) is held to.  Nothing is written on a refusal.
 int set_vertex_positions(SceneState &st, const BuildOptions &opt, uint32_t shape, const float *positions, const float *normals,

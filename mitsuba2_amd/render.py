@@ -637,6 +637,7 @@ class Scene:
         if not torch.cuda.is_available():
             raise RuntimeError("mitsuba2_amd requires a HIP device (torch.cuda.is_available() is False)")
         self._device_index = int(device)
+        self._pending_vertices = {}    # shape -> (positions, normals): device clones update_vertices(normals="recompute") has not mirrored yet
         self._dict = scene_dict
         self._sensors = [sensor] if sensor is not None else []
         self._integrator = integrator
@@ -826,15 +827,57 @@ class Scene:
                 if t == int(texture) and i < len(self._bsdf_records):
                     self._bsdf_records[i]["reflectance"]["data"] = np.clip(np.array(new, np.float32).reshape(shape), 0.0, 1.0)
 
+    @property
+    def _dict(self):
+        """The scene description.  It follows the device: vertex arrays that update_vertices(normals="recompute") left on the device are
+        copied into it before it is handed out, so every reader sees the scene as it is."""
+        for shape, (pos, nrm) in list(self._pending_vertices.items()):
+            mesh = self._description["meshes"][shape]
+            mesh["positions"] = pos.cpu().numpy().reshape(-1, 3)
+            mesh["normals"] = nrm.cpu().numpy().reshape(-1, 3)
+            del self._pending_vertices[shape]
+        return self._description
+
+    @_dict.setter
+    def _dict(self, value):
+        self._pending_vertices.clear()
+        self._description = value
+
+    def _recompute_vertices(self, shape, positions):
+        """update_vertices(normals="recompute"): mtsamd_scene_update_vertices with MTSAMD_VERTICES_RECOMPUTE_NORMALS"""
+        mesh = self._description["meshes"][shape]           # counts and the presence of normals never change: no need to flush for them
+        n_vertices = _f32(mesh["positions"]).reshape(-1, 3).shape[0]
+        dev = torch.device("cuda", self._device_index)
+        if isinstance(positions, torch.Tensor):
+            pos = positions.detach().to(device=dev, dtype=torch.float32).reshape(-1)
+        else:
+            pos = torch.from_numpy(_f32(positions).reshape(-1)).to(dev)
+        if pos.numel() != 3 * n_vertices:
+            raise RuntimeError("positions has %d values, expected 3 * %d" % (pos.numel(), n_vertices))
+        if mesh.get("normals") is None:
+            raise RuntimeError("shape %d was created without vertex normals: storing new normals in such a mesh is not implemented" % shape)
+        pos = pos.clone()                                    # the caller may overwrite theirs; the scene reads and keeps this one
+        nrm = torch.empty(3 * n_vertices, dtype=torch.float32, device=dev)
+        L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, _ptr(pos), None, 1, _ptr(nrm), _stream()))
+        self._pending_vertices[shape] = (pos, nrm.clone())
+        return nrm.reshape(-1, 3)
+
     def update_vertices(self, shape, positions, normals=None):
         """parameters_changed({"vertex_positions_buf"}) of mesh `shape` (mesh.cpp:781-804): new vertex positions, same vertex count and
         faces.  positions: (N, 3) or flat 3N, a numpy array or a torch tensor on the host or the device (a device tensor is read where it
         is).  A mesh with vertex normals gets `normals`, or -- None -- normals recomputed from the new positions with
-        loaders.compute_vertex_normals (recompute_vertex_normals), which runs on the host: a device tensor makes one round trip for it.
+        loaders.compute_vertex_normals (recompute_vertex_normals), which runs on the host in float64: a device tensor makes one round trip
+        for it.  normals="recompute" recomputes them in the library instead (mtsamd_compute_vertex_normals' fp32 arithmetic, on the device
+        for hierarchy scenes): with a device tensor no vertex data is copied to the host, the description is brought up to date when it is
+        next read, and the call returns the (N, 3) normals as a device tensor.
         The accelerator is refitted, not rebuilt; bbox(), the emitter tables and the scene description follow."""
         shape = int(shape)
         if not 0 <= shape < self._shape_count:
             raise RuntimeError("invalid shape index %d (the scene has %d shapes)" % (shape, self._shape_count))
+        if isinstance(normals, str):
+            if normals != "recompute":
+                raise RuntimeError("normals: an array, None or \"recompute\", not %r" % normals)
+            return self._recompute_vertices(shape, positions)
         mesh = self._dict["meshes"][shape]
         n_vertices = _f32(mesh["positions"]).reshape(-1, 3).shape[0]
         dev = torch.device("cuda", self._device_index)
