@@ -523,6 +523,46 @@ MTSAMD_API int mtsamd_scene_set_bsdf_param(mtsamd_scene *scene, uint32_t bsdf, i
 MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
                                 const float *film_dev, uint32_t bsdf, int32_t param, int32_t component, float h,
                                 float *grad1_dev, void *stream);
+/* Forward-mode derivative render: the image of d(image)/d(t) along ONE tangent direction t over the scene parameters -- what
+ * ek.set_gradient(param, t); ek.forward(param); ek.gradient(image) leaves behind in docs/examples/10_inverse_rendering/forward_diff.py
+ * (docs/src/inverse_rendering/diff_render.rst:332-398).  RGB variant, `path` integrator, plain BSDF records (no blendbsdf / mask, no
+ * textured BSDF parameters), any emitter mix, any max_depth.  Every camera sample is replayed with its PCG32 stream through the general
+ * path step with a dual part beside the path; one replay covers all four tangent families, whose contributions add up:
+ *   bsdf_tangents         bsdf_count * MTSAMD_BSDF_TANGENT_FLOATS floats on the host: tangent[18 * bsdf + 3 * param + component] for param =
+ *                         MTSAMD_PARAM_REFLECTANCE .. MTSAMD_PARAM_SPECULAR_TRANSMITTANCE (ALPHA: component 0 only).  A non-zero entry must
+ *                         name a parameter mtsamd_render_adjoint_param accepts for that record.  Differentiated by a central difference of
+ *                         the model code at the fixed directions between theta + eps t and theta - eps t, eps the largest step that moves
+ *                         no scalar by more than h (h <= 0: 1 % of max(|theta|, 0.05)), ALPHA and ETA kept above 1e-4;
+ *   emitter_tangents      emitter_count * 3 floats on the host: the colour of area, constant, point, spot and directional emitters
+ *                         (radiance is linear in them; exact).  The row of an envmap is ignored;
+ *   texture_tangents_dev  device, the layout of grad_textures_dev (mtsamd_scene_texture_info): texels of bitmaps used as
+ *                         diffuse.reflectance / (rough)plastic.diffuse_reflectance, in closed form as mtsamd_render_adjoint_textures;
+ *   envmap_tangent_dev    device, envmap height * width * 3: the texels of the envmap (the sampling hierarchy is not differentiated).
+ * Each may be NULL, not all four.  Sampling is detached as in the adjoints: directions, pdfs, lobe choices, MIS weights and the survival
+ * test are those of the primal path.  The Russian-roulette factor 1 / q (path.cpp:137-141) is differentiated as the reference and
+ * mtsamd_render_adjoint do; MTSAMD_FORWARD_DETACH_ROULETTE holds it fixed, the convention of mtsamd_render_adjoint_param. */
+enum { MTSAMD_FORWARD_DETACH_ROULETTE = 1 };
+#define MTSAMD_BSDF_TANGENT_FLOATS 18
+typedef struct {
+    const float *bsdf_tangents;        /* host, bsdf_count * 18, or NULL */
+    const float *emitter_tangents;     /* host, emitter_count * 3, or NULL (row of an envmap: ignored) */
+    const float *texture_tangents_dev; /* device, layout of grad_textures, or NULL */
+    const float *envmap_tangent_dev;   /* device, h * w * 3, or NULL */
+    float h;                           /* as mtsamd_render_adjoint_param; <= 0: default */
+    uint32_t flags;
+} mtsamd_tangent_desc;
+/* The derivative film of the whole crop window: film_dev (crop_height * crop_width * 5 channels dR, dG, dB, A, W) is ADDED into, through
+ * the film stage of mtsamd_render, in passes of whole rows (max_pass_log2 is respected); A and W equal those of the film mtsamd_render
+ * writes for the same desc with film_rgb = 1, so the derivative image is dvalues / (W + 1e-8).  desc->film_rgb must be 1, integrator 0,
+ * moment 0, no row window or tile partition, a reconstruction filter of at most 8 taps.  samples_per_pass, timeout and the scheduler
+ * knobs (paths_per_wave, pipeline, finish_kernel, profile) are ignored: one thread replays one sample.  Device scratch belongs to the
+ * scene; calls for one scene must be ordered on one stream.  Synchronises the stream. */
+MTSAMD_API int mtsamd_render_forward(mtsamd_scene *scene, const mtsamd_render_desc *desc, const mtsamd_tangent_desc *tangent, float *film_dev,
+                          void *stream);
+/* The counterpart of mtsamd_sample_radiance: (dR, dG, dB, alpha) of the camera samples [first, first + count) into rgba_dev (count * 4)
+ * and their film positions into pos_dev (count * 2, may be NULL). */
+MTSAMD_API int mtsamd_sample_forward(mtsamd_scene *scene, const mtsamd_render_desc *desc, const mtsamd_tangent_desc *tangent, uint64_t first,
+                          uint64_t count, float *rgba_dev, float *pos_dev, void *stream);
 /* The derivative with respect to bitmap texels ('bsdf.reflectance.data', src/textures/bitmap.cpp:295-299) in ANY RGB scene the path
  * integrator renders -- any emitter mix, any of the supported BSDFs -- of mitsuba.python.autodiff.render (autodiff.py:6-91): the texels of
  * bitmaps used as diffuse.reflectance or (rough)plastic.diffuse_reflectance (plain or inside `twosided`).  Every camera sample is replayed

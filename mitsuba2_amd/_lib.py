@@ -83,6 +83,15 @@ class RenderDesc(C.Structure):
                 ("max_pass_log2", C.c_int32), ("finish_kernel", C.c_int32)]
 
 
+class TangentDesc(C.Structure):
+    _fields_ = [("bsdf_tangents", f32p), ("emitter_tangents", f32p), ("texture_tangents_dev", vp), ("envmap_tangent_dev", vp),
+                ("h", C.c_float), ("flags", C.c_uint32)]
+
+
+FORWARD_DETACH_ROULETTE = 1
+BSDF_TANGENT_FLOATS = 18
+
+
 # every symbol include/mtsamd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mtsamd_abi_version": (C.c_int, []),
@@ -145,6 +154,8 @@ SYMBOLS = {
     "mtsamd_libm_eval": (C.c_int, [C.c_int32, C.c_uint64, vp, vp, vp, vp]),
     "mtsamd_scene_set_bsdf_param": (C.c_int, [vp, C.c_uint32, C.c_int32, f32p]),
     "mtsamd_render_adjoint_param": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, vp, vp]),
+    "mtsamd_render_forward": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(TangentDesc), vp, vp]),
+    "mtsamd_sample_forward": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(TangentDesc), C.c_uint64, C.c_uint64, vp, vp, vp]),
 }
 
 _lib = None

@@ -86,8 +86,9 @@ class ParameterMap:
     """Dictionary-like view of the differentiable scene parameters (util.py:16-130): torch tensors on the scene's GPU.
     Writes take effect in the scene after :meth:`update` (``parameters_changed``)."""
 
-    def __init__(self, scene, replay=False, geometry=False, normals=None):
+    def __init__(self, scene, replay=False, geometry=False, normals=None, emitters=False):
         self._scene = scene
+        want_emitters = bool(emitters) and not _is_spectral(scene)      # RGB scenes: the emitter-colour keys below, in any scene
         if normals not in (None, "recompute"):
             raise RuntimeError("normals: None or \"recompute\", not %r" % (normals,))
         self._normals = normals                      # how update() gets the vertex normals of a moved mesh that has them
@@ -199,6 +200,26 @@ class ParameterMap:
             self.properties[key] = torch.as_tensor(E.normalize(em)["radiance"], dtype=torch.float32, device=dev)
             self._kind[key] = ("emitter", e, e)
 
+        # RGB variant with `emitters`: the same emitter-colour keys in ANY scene -- area lights under their shape, `constant`, `point`, `spot`
+        # and `directional` under their own id.  Settable, and usable as tangents of render_forward (radiance is linear in them); the
+        # reverse pass covers them in diffuse area-lit scenes only (the keys above), so render() raises on one that requires a gradient
+        for i, m in enumerate(scene._dict["meshes"] if want_emitters and not diffuse_scene else []):
+            e = m.get("emitter", -1)
+            if e is None or e < 0 or scene._dict["emitters"][e].get("type", "area") != "area":
+                continue
+            key = m.get("id", "shape_%d" % i) + ".emitter.radiance.value"
+            rad = np.broadcast_to(np.asarray(E.normalize(scene._dict["emitters"][e])["radiance"], np.float32), (3,))
+            self.properties[key] = torch.as_tensor(rad.copy(), dtype=torch.float32, device=dev)
+            self._kind[key] = ("emitter", e, i)
+        for e, em in enumerate(emitters if want_emitters else []):
+            t = em.get("type", "area")
+            if t in ("envmap", "area"):
+                continue
+            key = "%s.%s.value" % (em.get("id", "emitter_%d" % e), E._VALUE_KEY[t])
+            rad = np.broadcast_to(np.asarray(E.normalize(em)["radiance"], np.float32), (3,))
+            self.properties[key] = torch.as_tensor(rad.copy(), dtype=torch.float32, device=dev)
+            self._kind[key] = ("emitter", e, e)
+
         # '<shape id>.vertex_positions_buf' of every mesh (mesh.cpp:781-804): the flat 3N buffer.  Settable, not differentiable: there is
         # no reparameterised integrator behind it (render() refuses a tensor that requires a gradient)
         for i, m in enumerate(scene._dict["meshes"] if geometry else []):
@@ -266,15 +287,18 @@ class ParameterMap:
                 self._scene.set_bsdf_reflectance(idx, v.detach().cpu().tolist())
 
 
-def traverse(scene, replay=False, geometry=False, normals=None):
+def traverse(scene, replay=False, geometry=False, normals=None, emitters=False):
     """mitsuba.python.util.traverse (util.py:132-179) for the supported parameters.  ``replay=True`` (spectral scenes; ignored for RGB
     ones) adds the bitmap texels of the reflectance family and the emitted colour of shapeless emitters, and differentiates the reflectance
     family and the emitter family (envmap texels included) with one spectral path replay each per backward pass.  ``geometry=True`` adds
     '<shape id>.vertex_positions_buf' of every mesh (the flat 3N buffer of mesh.cpp:781-804); update() pushes it through
     Scene.update_vertices; ``normals="recompute"`` makes it pass that on for every mesh with vertex normals, so that a moved mesh's
     normals are recomputed on the device and no vertex data visits the host.  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
-    which is why they have to be asked for: render() raises on one that requires a gradient."""
-    return ParameterMap(scene, replay=replay, geometry=geometry, normals=normals)
+    which is why they have to be asked for: render() raises on one that requires a gradient.  ``emitters=True`` (RGB scenes; ignored for
+    spectral ones) adds the emitter colours in any scene: '<shape id>.emitter.radiance.value' of area lights and
+    '<emitter id>.radiance|intensity|irradiance.value' of `constant`, `point`, `spot` and `directional` emitters.  They are settable and
+    serve as tangents of render_forward; outside diffuse area-lit scenes render() raises on one that requires a gradient."""
+    return ParameterMap(scene, replay=replay, geometry=geometry, normals=normals, emitters=emitters)
 
 
 def _replayed(pmap, key):
@@ -450,6 +474,82 @@ def _forget_scene(key):
     _render_tracked.discard(key)
 
 
+def _next_seed(scene, sensor):
+    """The seed of the next call for this scene: the call counter folded into the sampler's seed."""
+    if id(scene) not in _render_tracked:
+        _render_tracked.add(id(scene))
+        weakref.finalize(scene, _forget_scene, id(scene))
+    call = _render_counter.get(id(scene), 0)
+    _render_counter[id(scene)] = call + 1
+    return sensor.sampler().seed_value() + call * 0xD1B54A32D192ED03
+
+
+def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_roulette=False):
+    """Forward-mode derivative render: the flat ``H*W*3`` image of d(image)/d(t) along the tangent ``tangents`` -- what
+    ``ek.gradient(image)`` holds after ``ek.set_gradient(param, t); ek.forward(param)`` in
+    ``docs/examples/10_inverse_rendering/forward_diff.py`` (``diff_render.rst:332-398``).  ``tangents`` maps keys of ``params`` to tensors of
+    the parameters' shapes; the contributions of all keys add up in ONE replay (``mtsamd_render_forward``): BSDF constants, bitmap texels of
+    the reflectance family, emitter colours (``traverse(scene, emitters=True)``) and envmap texels.  Texels of parameter maps
+    (``'<bsdf>.alpha.data'``, ...) and vertex positions have no forward derivative here and raise.  ``params.update()`` runs first; the seed
+    comes from the call counter exactly as in :func:`render`, so resetting ``_render_counter[id(scene)]`` gives common random numbers with
+    it.  ``params.fd_step`` is the step of the central difference behind BSDF constants; ``detach_roulette=True`` holds the
+    Russian-roulette factor fixed (the convention of ``mtsamd_render_adjoint_param``); by default it is differentiated as the reference does."""
+    if _is_spectral(scene):
+        raise RuntimeError("render_forward is implemented for the RGB variant only")
+    sensor = scene.sensors()[sensor_index]
+    integrator = scene.integrator() if scene.integrator() is not None else PathIntegrator()
+    for k in tangents:
+        if k not in params:
+            raise KeyError(k)
+        kind = params._kind[k][0]
+        if kind in ("param_texture", "vertices"):
+            raise RuntimeError("%s has no forward-mode derivative: %s" % (k, "texels of BSDF parameter maps are differentiated by the reverse pass only"
+                                                                          if kind == "param_texture" else "there is no reparameterised integrator for vertex positions"))
+    if not tangents:
+        raise RuntimeError("render_forward needs a tangent on at least one parameter")
+    params.update()
+    d = _desc(scene, sensor, integrator, spp, _next_seed(scene, sensor))
+    dev = torch.device("cuda", scene._device_index)
+    n_bsdf = len(B.flatten(scene._bsdf_records))
+    n_em = len(scene._dict.get("emitters", []))
+    t_bsdf = np.zeros((max(n_bsdf, 1), L.BSDF_TANGENT_FLOATS), np.float32)
+    t_em = np.zeros((max(n_em, 1), 3), np.float32)
+    t_tex = t_env = None
+    used = set()
+    for k, t in tangents.items():
+        kind, idx, extra = params._kind[k]
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if t.numel() != params[k].numel():
+            raise RuntimeError("the tangent of %s has %d elements, the parameter %d" % (k, t.numel(), params[k].numel()))
+        used.add(kind)
+        if kind in ("bsdf", "bsdf_param"):
+            row = 0 if kind == "bsdf" else int(extra)
+            v = t.detach().cpu().reshape(-1).numpy()
+            t_bsdf[idx, 3 * row: 3 * row + len(v)] += v
+        elif kind == "emitter":
+            t_em[idx] += t.detach().cpu().reshape(3).numpy()
+        elif kind == "envmap":
+            t_env = t.detach().to(dev).reshape(params[k].shape).contiguous()
+        else:       # texture
+            if t_tex is None:
+                t_tex = torch.zeros(max(sum(h * w * 3 for (h, w, _) in scene._texture_shapes), 1), dtype=torch.float32, device=dev)
+            off, w, h = C.c_uint64(), C.c_int32(), C.c_int32()
+            L.check(L.lib().mtsamd_scene_texture_info(scene._handle, idx, C.byref(w), C.byref(h), C.byref(off)))
+            t_tex[off.value: off.value + 3 * w.value * h.value] = t.detach().to(dev).reshape(-1)
+    td = L.TangentDesc()
+    if used & {"bsdf", "bsdf_param"}:
+        td.bsdf_tangents = t_bsdf.ctypes.data_as(L.f32p)
+    if "emitter" in used:
+        td.emitter_tangents = t_em.ctypes.data_as(L.f32p)
+    td.texture_tangents_dev = _ptr(t_tex) if t_tex is not None else None
+    td.envmap_tangent_dev = _ptr(t_env) if t_env is not None else None
+    td.h = float(params.fd_step)
+    td.flags = L.FORWARD_DETACH_ROULETTE if detach_roulette else 0
+    film = torch.zeros((d.crop_height, d.crop_width, 5), dtype=torch.float32, device=dev)
+    L.check(L.lib().mtsamd_render_forward(scene._handle, C.byref(d), C.byref(td), _ptr(film), _stream()))
+    return _image_of(film)
+
+
 def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, params=None):
     """mitsuba.python.autodiff.render (autodiff.py:121-194): differentiable render returning the flattened RGB image
     (``len == H*W*3``).  ``params`` (or ``optimizer.params``) is the :class:`ParameterMap` whose tensors with
@@ -460,6 +560,11 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
     integrator = scene.integrator() if scene.integrator() is not None else PathIntegrator()
     if optimizer is not None and params is None:
         params = optimizer.params
+    if params is not None and not _is_spectral(scene) and not params._diffuse_scene:
+        for k, v in params.items():
+            if v.requires_grad and params._kind[k][0] == "emitter":
+                raise RuntimeError("%s has a reverse-mode gradient in diffuse scenes lit by area lights only; its derivative image in this "
+                                   "scene comes from render_forward (clear requires_grad on it)" % k)
     if unbiased:
         if optimizer is None and params is None:
             raise Exception("render(): unbiased=True requires that an optimizer is specified!")
@@ -467,12 +572,7 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
             spp = (spp, spp)
     elif isinstance(spp, tuple):
         raise Exception("render(): unbiased=False requires that spp is either an integer or None!")
-    if id(scene) not in _render_tracked:
-        _render_tracked.add(id(scene))
-        weakref.finalize(scene, _forget_scene, id(scene))
-    call = _render_counter.get(id(scene), 0)
-    _render_counter[id(scene)] = call + 1
-    base = sensor.sampler().seed_value() + call * 0xD1B54A32D192ED03
+    base = _next_seed(scene, sensor)
 
     def differentiable(spp_, seed):
         d = _desc(scene, sensor, integrator, spp_, seed)

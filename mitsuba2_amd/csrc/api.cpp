@@ -226,6 +226,10 @@ struct Workspace {
     float4 *aov_keep = nullptr;                                   // ... and, during a render of several passes, the streams + positions of all of them
     float *film_partials = nullptr; size_t film_partial_floats = 0;      // tiled film splat: one scratch tile per 16x16 source tile of a pass
     uint32_t *trace_spill = nullptr; size_t trace_spill_words = 0;      // k_trace: deep stack entries
+    // forward-mode render: the two perturbed BSDF tables, 1 / (2 eps) per record, the emitter tangent rows
+    DevBsdf *fw_plus = nullptr, *fw_minus = nullptr; size_t fw_records = 0;
+    float *fw_inv_2h = nullptr; size_t fw_inv_floats = 0;
+    float *fw_emitters = nullptr; size_t fw_emitter_floats = 0;
     uint32_t *h_counts = nullptr;        // pinned, 4 * n_waves
     uint64_t *h_cursor = nullptr;        // pinned, 2 * n_waves
     uint64_t *h_cursor_rb = nullptr;     // pinned, 2 slots x n_waves: cursors read back with the counts (pool-drain gathering)
@@ -251,6 +255,9 @@ struct Workspace {
         (void) hipFree(cursor); (void) hipFree(cursor_end); (void) hipFree(wave_stats);
         (void) hipFree(count_shadow); count_shadow = nullptr;
         (void) hipFree(trace_spill); trace_spill = nullptr; trace_spill_words = 0;
+        (void) hipFree(fw_plus); (void) hipFree(fw_minus); fw_plus = fw_minus = nullptr; fw_records = 0;
+        (void) hipFree(fw_inv_2h); fw_inv_2h = nullptr; fw_inv_floats = 0;
+        (void) hipFree(fw_emitters); fw_emitters = nullptr; fw_emitter_floats = 0;
         (void) hipFree(moment_film); moment_film = nullptr; moment_floats = 0;
         (void) hipFree(aov_stream); aov_stream = nullptr; aov_stream_slots = 0;
         (void) hipFree(aov_film); aov_film = nullptr; aov_film_floats = 0;
@@ -1812,6 +1819,121 @@ int mtsamd_render_adjoint_param(mtsamd_scene *s, const mtsamd_render_desc *d, co
     a.grad_param = grad1;
     a.rp.sv.general = std::max(a.rp.sv.general, 1u);
     HIP_TRY(launch_adjoint_param(a, (hipStream_t) stream_));
+    return MTSAMD_OK;
+}
+
+// ---- forward-mode derivative render (docs/examples/10_inverse_rendering/forward_diff.py) -------
+// What both entry points refuse before the device is touched, and the host half of the tangent: the perturbed record tables
+static int check_forward(const mtsamd_scene *s, const mtsamd_render_desc *d, const mtsamd_tangent_desc *t, const void *out, bool film,
+                         std::vector<DevBsdf> &plus, std::vector<DevBsdf> &minus, std::vector<float> &inv_2h) {
+    if (!s || !d || !t || !out) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (!t->bsdf_tangents && !t->emitter_tangents && !t->texture_tangents_dev && !t->envmap_tangent_dev)
+        return fail(MTSAMD_ERR_INVALID, "the tangent is empty: bsdf_tangents, emitter_tangents, texture_tangents_dev and envmap_tangent_dev are all null");
+    if (int rc = check_desc(d)) return rc;
+    if (t->flags & ~(uint32_t) MTSAMD_FORWARD_DETACH_ROULETTE) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the tangent descriptor", t->flags);
+    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render is implemented for the RGB variant only");
+    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
+    for (const DevBsdf &b : s->bsdfs)
+        if (b.type >= kBsdfBlend) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render does not handle blendbsdf / mask materials");
+    if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render differentiates the path integrator");
+    if (d->part_count > 1 || d->row_begin != 0 || d->row_end > 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render covers the whole crop window (no row window, no tile partition)");
+    if (film) {
+        if (d->moment) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render has no moment channels");
+        if (d->film_rgb != 1) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render writes an R, G, B, A, W film (film_rgb must be 1)");
+        FilterView filter;
+        if (int rc = make_filter(d->rfilter, d->rfilter_param, d->rfilter_param2, d->rfilter_analytic, filter)) return rc;
+        if (filter.taps > 8) return fail(MTSAMD_ERR_UNSUPPORTED, "reconstruction filter too wide for the forward-mode render");
+    }
+    if (t->envmap_tangent_dev && (s->environment < 0 || !s->d_envmap)) return fail(MTSAMD_ERR_UNSUPPORTED, "envmap_tangent_dev: the scene has no envmap emitter");
+    if (t->texture_tangents_dev) {
+        bool bitmaps = false;
+        for (const DevTexture &tx : s->textures) bitmaps = bitmaps || tx.kind == 0u;
+        if (!bitmaps) return fail(MTSAMD_ERR_UNSUPPORTED, "texture_tangents_dev: the scene has no bitmap textures");
+    }
+    if (t->emitter_tangents)
+        for (size_t i = 0; i < 3 * s->emitters.size(); ++i)
+            if (!std::isfinite(t->emitter_tangents[i])) return fail(MTSAMD_ERR_INVALID, "emitter %u: its tangent is not finite", (unsigned) (i / 3));
+    return build_tangent_records(*s, t->bsdf_tangents, t->h, plus, minus, inv_2h);
+}
+
+// The argument block of k_forward but for the samples of a launch; uploads the scene-owned scratch on `stream`.  The host arrays must
+// outlive the copies: both callers synchronise the stream before they return.
+static int fill_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mtsamd_tangent_desc *t, const Job &j, int store_xyz, hipStream_t stream,
+                        const std::vector<DevBsdf> &plus, const std::vector<DevBsdf> &minus, const std::vector<float> &inv_2h, ForwardParams &f) {
+    Workspace &w = s->ws;
+    f = ForwardParams{};
+    f.rp.sv = s->view; f.rp.cam = j.cam;
+    f.rp.sv.general = std::max(f.rp.sv.general, 1u);
+    f.rp.base_seed = d->seed; f.rp.spp = d->sample_count;
+    f.rp.crop_x = d->crop_x; f.rp.crop_y = d->crop_y; f.rp.crop_w = d->crop_width; f.rp.crop_h = d->crop_height;
+    f.rp.max_depth = d->max_depth; f.rp.rr_depth = d->rr_depth;
+    f.rp.rows = RowMap{ 0, d->crop_height, std::max(d->crop_height, 1), 0, 1 };
+    f.rp.store_xyz = store_xyz; f.rp.out_rgba = w.out_rgba; f.rp.out_pos = w.out_pos;
+    f.flags = t->flags;
+    if (t->bsdf_tangents && !plus.empty()) {
+        const size_t n = plus.size();
+        if (int rc = grow(w.fw_plus, w.fw_minus, w.fw_records, n)) return rc;
+        if (int rc = grow(w.fw_inv_2h, w.fw_inv_floats, n)) return rc;
+        HIP_TRY(hipMemcpyAsync(w.fw_plus, plus.data(), n * sizeof(DevBsdf), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(w.fw_minus, minus.data(), n * sizeof(DevBsdf), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(w.fw_inv_2h, inv_2h.data(), n * sizeof(float), hipMemcpyHostToDevice, stream));
+        f.plus = w.fw_plus; f.minus = w.fw_minus; f.inv_2h = w.fw_inv_2h;
+    }
+    if (t->emitter_tangents && !s->emitters.empty()) {
+        const size_t n = 3 * s->emitters.size();
+        if (int rc = grow(w.fw_emitters, w.fw_emitter_floats, n)) return rc;
+        HIP_TRY(hipMemcpyAsync(w.fw_emitters, t->emitter_tangents, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        f.em_tangent = w.fw_emitters;
+    }
+    if (f.plus || f.em_tangent) HIP_TRY(hipStreamSynchronize(stream));      // the host arrays are free again, whatever happens next
+    f.tex_tangent = t->texture_tangents_dev; f.env_tangent = t->envmap_tangent_dev;
+    return 0;
+}
+
+int mtsamd_render_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mtsamd_tangent_desc *t, float *film, void *stream_) {
+    std::vector<DevBsdf> plus, minus; std::vector<float> inv_2h;
+    if (int rc = check_forward(s, d, t, film, true, plus, minus, inv_2h)) return rc;
+    hipStream_t stream = (hipStream_t) stream_;
+    Job j;
+    if (int rc = open_render(j, s, d, stream, 0, 2)) return rc;      // the passes of mtsamd_render for this desc
+    FilmStage fs{ j };
+    if (int rc = fs.reserve(true)) return rc;
+    ForwardParams f;
+    if (int rc = fill_forward(s, d, t, j, 2, stream, plus, minus, inv_2h, f)) return rc;
+    for (uint64_t lr0 = 0; lr0 < (uint64_t) j.rows.local_rows; lr0 += j.fp.rows_per_pass) {
+        const Job::Pass p = j.pass(lr0);
+        f.rp.first_ordinal = p.a; f.n_samples = p.n;
+        HIP_TRY(launch_forward(f, stream));
+        j.passes += 1;
+        if (int rc = fs.begin(stream, p.lr0, p.nrows, j.fp.tile_h)) return rc;
+        if (int rc = fs.put(s->ws.out_rgba, s->ws.out_pos, film)) return rc;
+        if (int rc = fs.end()) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return fs.close(nullptr);
+}
+
+int mtsamd_sample_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mtsamd_tangent_desc *t, uint64_t first, uint64_t count, float *rgba,
+                          float *pos, void *stream_) {
+    std::vector<DevBsdf> plus, minus; std::vector<float> inv_2h;
+    if (int rc = check_forward(s, d, t, rgba, false, plus, minus, inv_2h)) return rc;
+    const uint64_t total = (uint64_t) d->crop_width * d->crop_height * (uint64_t) d->sample_count;
+    if (first + count > total) return fail(MTSAMD_ERR_INVALID, "sample range exceeds W*H*sample_count");
+    if (count == 0) return MTSAMD_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t) stream_;
+    Job j;
+    if (int rc = setup_job(j, s, d, stream, count)) return rc;
+    ForwardParams f;
+    if (int rc = fill_forward(s, d, t, j, 0, stream, plus, minus, inv_2h, f)) return rc;
+    for (uint64_t a = 0; a < count; a += j.pass_cap) {
+        const uint64_t n = std::min<uint64_t>(j.pass_cap, count - a);
+        f.rp.first_ordinal = first + a; f.n_samples = n;
+        HIP_TRY(launch_forward(f, stream));
+        HIP_TRY(hipMemcpyAsync(rgba + 4 * a, s->ws.out_rgba, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        if (pos) HIP_TRY(hipMemcpyAsync(pos + 2 * a, s->ws.out_pos, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
     return MTSAMD_OK;
 }
 

@@ -148,6 +148,24 @@ struct AdjointParams {
     // the hit); it adds into grad_tex
 };
 
+// k_forward: the forward-mode derivative render.  The camera samples [rp.first_ordinal, rp.first_ordinal + n_samples) of the whole crop
+// window are replayed; d(radiance) along ONE tangent direction over four parameter families goes to rp.out_rgba / rp.out_pos in the slot
+// layout of the sample stream (slot = ordinal - first_ordinal), ready for the film kernels.  An argument block of its own: AdjointParams,
+// and with it the argument block of every k_adjoint* kernel, stays what it was.
+constexpr uint32_t kForwardDetachRoulette = 1u;      // MTSAMD_FORWARD_DETACH_ROULETTE
+struct ForwardParams {
+    RenderParams rp;            // as AdjointParams::rp, with out_rgba / out_pos and store_xyz (0: plain alpha; else -1 marks a dropped sample)
+    uint64_t n_samples;
+    // BSDF constants: record b of the table at theta + eps t / theta - eps t and 1 / (2 eps); inv_2h[b] == 0: no tangent on record b.
+    // All three null: no BSDF tangents
+    const DevBsdf *plus, *minus; const float *inv_2h;
+    const float *tex_tangent;   // tangent texels of the reflectance family, layout of grad_textures (mtsamd_scene_texture_info), or null
+    const float *em_tangent;    // n_emitters * 3: tangent of the emitter colours (row of an envmap: not read), or null
+    const float *env_tangent;   // envmap height * width * 3, or null
+    uint32_t flags;             // kForwardDetachRoulette
+};
+hipError_t launch_forward(const ForwardParams &f, hipStream_t s);
+
 struct RayStreams {
     const float *ox, *oy, *oz, *dx, *dy, *dz, *mint, *maxt;
     const uint8_t *active;

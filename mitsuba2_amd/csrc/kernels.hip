@@ -1983,8 +1983,8 @@ MTS_DEV void scatter_texel_grad(float *grad_tex, const DevTexture &t, uint32_t t
 }
 
 // One workgroup per 256 samples, at most 2048 workgroups (the sample loop strides); the scene is staged like k_bounce's
-template <void (*K_FLAT)(const AdjointParams), void (*K_TREE)(const AdjointParams)>
-static hipError_t launch_adjoint_kernel(const AdjointParams &a, hipStream_t s) {
+template <auto K_FLAT, auto K_TREE, class A>
+static hipError_t launch_adjoint_kernel(const A &a, hipStream_t s) {
     if (a.n_samples == 0) return hipSuccess;
     uint64_t blocks = (a.n_samples + kBlock - 1) / kBlock;
     if (blocks > 2048) blocks = 2048;
@@ -2338,6 +2338,7 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_tex(const AdjointParams A) {
 }
 
 hipError_t launch_adjoint_tex(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_tex<true>, k_adjoint_tex<false>>(a, s); }
+
 
 // ---------------------------------------------------------------------------------------------
 // Spectral variant: derivative w.r.t. the reflectance family -- diffuse.reflectance and (rough)plastic.diffuse_reflectance, as a constant
@@ -3899,5 +3900,181 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_param_tex(const AdjointParam
 }
 
 hipError_t launch_adjoint_param_tex(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_param_tex<true>, k_adjoint_param_tex<false>>(a, s); }
+
+// ---------------------------------------------------------------------------------------------
+// Forward mode: the image of d(radiance)/d(t) along ONE tangent direction t over the scene parameters -- what ek.forward() leaves in
+// ek.gradient(image) (docs/examples/10_inverse_rendering/forward_diff.py, docs/src/inverse_rendering/diff_render.rst:332-398).  A tangent
+// is one direction, so one dual part (dthr = d throughput, dres = d radiance) beside the replayed path serves every parameter at once:
+//   BSDF constants     d f / d t at the fixed directions = the central difference of the model code between the records plus[b] and
+//                      minus[b] (theta +- eps t, built on the host: build_tangent_records), the rule of ParamGradProbe, discrete lobes included;
+//   reflectance texels d refl = the bilinear lookup of the tangent texels over the footprint the step reports, chained through the closed
+//                      forms of GeneralRecorder (bsdf_dvalue_drefl / bsdf_dweight_drefl);
+//   emitter colours    radiance is linear in them: emission picked up adds (ew thr) dLe, an unoccluded emitter sample mis thr bv em_geo dLe
+//                      with em_geo = spec / radiance from the factors r1, r2 and falloff (never a division by the radiance, which may be 0);
+//   envmap texels      dLe = scale * the bilinear lookup of the tangent image over the footprint of envmap_lookup, at the two uses
+//                      EnvGradProbe names; the sampling hierarchy is not differentiated.
+// Russian roulette (path.cpp:137-141): thr' = thr rq with rq = 1 / q, q = min(hmax(thr) eta^2, .95).  Attached (the default, as the
+// reference and k_adjoint / k_adjoint_tex): where q is not clamped, d rq = -rq^2 eta^2 d thr_c on the channel c that sets q -- the forward
+// form of the `corr` term of those sweeps.  kForwardDetachRoulette: dthr *= rq only (ParamGradProbe::roulette).  Everything else is
+// detached, as in the adjoints: directions, pdfs, lobe choices, MIS weights, the survival test.
+struct TangentProbe {
+    static constexpr bool kFactoredEmitter = true, kMirrorTwoSided = false, kSamples = true;
+    const ForwardParams &F;
+    f3 dthr, dres;
+    f3 thr0; float eta2;            // throughput and eta^2 on arrival (emission is picked up before roulette)
+    const DevBsdf *cur; f3 refl0;   // the record and reflectance of the surface of this step
+    int32_t rec; float inv_2h;      // its index; != 0: the record carries a BSDF tangent
+    bool tex; f3 drefl;             // a bitmap reflectance with a texel tangent was looked up: d refl
+    f3 dle;                         // d radiance of the emitter sample of this step (falloff, r1, r2 not applied)
+
+    MTS_DEV static float em_geo(const SceneView &sv, const NeeTerms &t) {       // spec / radiance of the emitter sample (EmitterGradProbeS::em_geo)
+        const float g = t.ds.delta ? t.ds.falloff * t.r1 : t.r1;
+        return sv.n_emitters > 1u ? g * t.r2 : g;
+    }
+    MTS_DEV f3 emitter_tangent(uint32_t e) const {
+        if (!F.em_tangent) return mk3(0.0f, 0.0f, 0.0f);
+        const float *row = F.em_tangent + 3u * (size_t) e;
+        return mk3(row[0], row[1], row[2]);
+    }
+    // envmap_lookup over the tangent image: the same footprint and arithmetic
+    MTS_DEV f3 env_tangent(const DevEnvmap &e, float u, float v) const {
+        if (!F.env_tangent) return mk3(0.0f, 0.0f, 0.0f);
+        u *= (float) (e.w - 1); v *= (float) (e.h - 1);
+        const uint32_t px = min((uint32_t) u, (uint32_t) (e.w - 2)), py = min((uint32_t) v, (uint32_t) (e.h - 2));
+        const float w1x = u - (float) px, w1y = v - (float) py, w0x = 1.0f - w1x, w0y = 1.0f - w1y;
+        const float *v00 = F.env_tangent + 3u * ((size_t) py * e.w + px), *v01 = v00 + 3u * (size_t) e.w;
+        f3 r;
+        { const float a = fmaf(w0x, v00[0], w1x * v00[3]), b = fmaf(w0x, v01[0], w1x * v01[3]); r.x = fmaf(w0y, a, w1y * b) * e.scale; }
+        { const float a = fmaf(w0x, v00[1], w1x * v00[4]), b = fmaf(w0x, v01[1], w1x * v01[4]); r.y = fmaf(w0y, a, w1y * b) * e.scale; }
+        { const float a = fmaf(w0x, v00[2], w1x * v00[5]), b = fmaf(w0x, v01[2], w1x * v01[5]); r.z = fmaf(w0y, a, w1y * b) * e.scale; }
+        return r;
+    }
+    MTS_DEV void perturbed_refl(const SceneView &sv, const SurfaceInteraction &si, const DevBsdf &bp, const DevBsdf &bm, f3 &rp, f3 &rm) const {
+        uint32_t tt; f2 tw;
+        rp = eval_reflectance(sv, bp, si.uv, tt, tw); rm = eval_reflectance(sv, bm, si.uv, tt, tw);
+    }
+    // d(value)/d(t) of the model at fixed directions: the central difference over the BSDF constants (ParamGradProbe::dvalue) ...
+    MTS_DEV f3 dvalue(const SceneView &sv, const SurfaceInteraction &si, f3 wo_l) const {
+        if (inv_2h == 0.0f) return mk3(0.0f, 0.0f, 0.0f);
+        const DevBsdf bp = F.plus[rec], bm = F.minus[rec];
+        f3 rp, rm, vp, vm; float pp, pm;
+        perturbed_refl(sv, si, bp, bm, rp, rm);
+        bsdf_eval_pdf(bp, rp, si.wi, wo_l, vp, pp);      // the model code itself (two-sided adapter included), no nesting
+        bsdf_eval_pdf(bm, rm, si.wi, wo_l, vm, pm);
+        return mk3((vp.x - vm.x) * inv_2h, (vp.y - vm.y) * inv_2h, (vp.z - vm.z) * inv_2h);
+    }
+    // ... + d: the chain through the textured reflectance, dr = d(value or weight)/d(refl) in closed form
+    MTS_DEV f3 chain(f3 d, f3 dr) const { return mk3(fmaf(dr.x, drefl.x, d.x), fmaf(dr.y, drefl.y, d.y), fmaf(dr.z, drefl.z, d.z)); }
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) {
+        static_assert(GENERAL && DEFER == 0 && !NEST, "the forward-mode derivative rides on the plain general fused step");
+        thr0 = s.thr; eta2 = s.eta * s.eta;
+        cur = nullptr; rec = -1; inv_2h = 0.0f; tex = false;
+        refl0 = drefl = dle = mk3(0.0f, 0.0f, 0.0f);
+    }
+    MTS_DEV void pick_up(float ew, f3 le, f3 d_le) {
+        dres = mk3(dres.x + ((ew * dthr.x) * le.x + (ew * thr0.x) * d_le.x), dres.y + ((ew * dthr.y) * le.y + (ew * thr0.y) * d_le.y),
+                   dres.z + ((ew * dthr.z) * le.z + (ew * thr0.z) * d_le.z));
+    }
+    MTS_DEV void emitted(float ew, int32_t emitter, f3 le) { pick_up(ew, le, emitter_tangent((uint32_t) emitter)); }
+    MTS_DEV void escaped(const SceneView &sv, const PathState &s, const DevEmitter &e, float ew, f3 le) {
+        f3 d_le;
+        if (e.pad0 == kEmitterEnvmap) {
+            float u, v;
+            env_dir_to_uv(mat3_apply(sv.envmap->to_local, s.d), u, v);
+            d_le = env_tangent(*sv.envmap, u, v);
+        } else d_le = emitter_tangent((uint32_t) sv.env_emitter);
+        pick_up(ew, le, d_le);
+    }
+    MTS_DEV void roulette(f3 thr, float hm, float rq, bool free) {
+        f3 d = dthr * rq;
+        if (free && !(F.flags & kForwardDetachRoulette)) {
+            const float dc = thr.x == hm ? dthr.x : (thr.y == hm ? dthr.y : dthr.z);
+            const float drq = -((rq * rq) * eta2) * dc;
+            d = mk3(fmaf(thr.x, drq, d.x), fmaf(thr.y, drq, d.y), fmaf(thr.z, drq, d.z));
+        }
+        dthr = d;
+    }
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, uint32_t texel, f2 tw1, f3) {
+        cur = &bsdf; refl0 = refl; rec = si.shape_rec.bsdf;
+        inv_2h = F.inv_2h ? F.inv_2h[rec] : 0.0f;
+        tex = F.tex_tangent != nullptr && texel != kNoPrim;
+        if (tex) {          // the weights scatter_texel_grad hands the four texels
+            const DevTexture t = F.rp.sv.textures[bsdf.texture];
+            const float *tt = F.tex_tangent + t.grad_offset + 3u * (size_t) texel;
+            const float w00 = (1.0f - tw1.y) * (1.0f - tw1.x), w10 = (1.0f - tw1.y) * tw1.x, w01 = tw1.y * (1.0f - tw1.x), w11 = tw1.y * tw1.x;
+            float d[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) d[ch] = fmaf(w11, tt[3 * t.w + 3 + ch], fmaf(w01, tt[3 * t.w + ch], fmaf(w10, tt[3 + ch], w00 * tt[ch])));
+            drefl = mk3(d[0], d[1], d[2]);
+        }
+    }
+    // the shadow ray is traced wherever the derivative may be non-zero, also where the radiance itself is 0
+    MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &, f3, const NeeTerms &t) {
+        dle = mk3(0.0f, 0.0f, 0.0f);
+        if (sv.n_emitters != 0u) dle = t.kind == kEmitterEnvmap ? env_tangent(*sv.envmap, t.ds.uv.x, t.ds.uv.y) : emitter_tangent(t.ds.emitter);
+        const bool lit = em_geo(sv, t) != 0.0f && (dle.x != 0.0f || dle.y != 0.0f || dle.z != 0.0f);
+        return lit || inv_2h != 0.0f || tex || dthr.x != 0.0f || dthr.y != 0.0f || dthr.z != 0.0f;
+    }
+    // d(mis thr bv spec) with mis fixed: (dthr bv + thr dbv) spec + thr bv em_geo dLe
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &si, f3 thr, const NeeTerms &t) {
+        f3 dbv = dvalue(sv, si, t.wo);
+        if (tex) dbv = chain(dbv, bsdf_dvalue_drefl(*cur, refl0, t.wi, t.wo));
+        const float g = em_geo(sv, t);
+        const f3 ds = mk3(g * dle.x, g * dle.y, g * dle.z);
+        dres = mk3(dres.x + ((t.mis * fmaf(dthr.x, t.bv.x, thr.x * dbv.x)) * t.spec.x + ((t.mis * thr.x) * t.bv.x) * ds.x),
+                   dres.y + ((t.mis * fmaf(dthr.y, t.bv.y, thr.y * dbv.y)) * t.spec.y + ((t.mis * thr.y) * t.bv.y) * ds.y),
+                   dres.z + ((t.mis * fmaf(dthr.z, t.bv.z, thr.z * dbv.z)) * t.spec.z + ((t.mis * thr.z) * t.bv.z) * ds.z));
+    }
+    // d(thr weight) = dthr weight + thr dweight;  dweight = d(value)/d(t) / pdf at the sampled direction (ParamGradProbe::bsdf_sampled)
+    MTS_DEV void bsdf_sampled(const SceneView &sv, const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, f3 thr, const BsdfSample &bs, f3 weight, float s1, f2 s2) {
+        f3 dw = mk3(0.0f, 0.0f, 0.0f);
+        if (inv_2h != 0.0f && !bs.delta && bs.pdf > 0.0f) {
+            const f3 dv = dvalue(sv, si, bs.wo);
+            const float ip = rcp(bs.pdf);
+            dw = mk3(dv.x * ip, dv.y * ip, dv.z * ip);
+        } else if (inv_2h != 0.0f && bs.delta) {
+            // a discrete lobe: re-sampled with the perturbed records and the same numbers; counts only if both land on the primal direction
+            const DevBsdf bp = F.plus[rec], bm = F.minus[rec];
+            f3 rp, rm, wp, wm; BsdfSample bp_, bm_;
+            perturbed_refl(sv, si, bp, bm, rp, rm);
+            const bool okp = bsdf_sample(bp, rp, si.wi, s1, s2, bp_, wp);
+            const bool okm = bsdf_sample(bm, rm, si.wi, s1, s2, bm_, wm);
+            if (okp && okm && bp_.delta && bm_.delta && bp_.wo.x == bs.wo.x && bp_.wo.y == bs.wo.y && bp_.wo.z == bs.wo.z &&
+                bm_.wo.x == bs.wo.x && bm_.wo.y == bs.wo.y && bm_.wo.z == bs.wo.z)
+                dw = mk3((wp.x - wm.x) * inv_2h, (wp.y - wm.y) * inv_2h, (wp.z - wm.z) * inv_2h);
+        }
+        if (tex) dw = chain(dw, bsdf_dweight_drefl(bsdf, refl, si.wi, bs));
+        dthr = mk3(fmaf(dthr.x, weight.x, thr.x * dw.x), fmaf(dthr.y, weight.y, thr.y * dw.y), fmaf(dthr.z, weight.z, thr.z * dw.z));
+    }
+};
+
+// One thread replays one camera sample with the PCG32 stream of the primal pass and writes (dR, dG, dB, a) and the film position into
+// its slot of the sample stream (generate_path / store_result), so that the film kernels splat the stream unchanged.  a = the primal
+// alpha, or -1 where the primal pass drops the sample (non-finite radiance: the store_xyz == 2 rule), so that the A and W channels of
+// the derivative film equal those of the primal film.  A derivative that is not finite while the radiance is finite is written as
+// zero and keeps its weight (the isfinite(g) rule of k_adjoint_param).
+template <bool FLAT>
+__global__ __launch_bounds__(kBlock) void k_forward(const ForwardParams F) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = F.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    const uint32_t spp = (uint32_t) P.spp;
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < F.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        const uint64_t ordinal = P.first_ordinal + k;
+        PathState s;
+        generate_path(P, ordinal, (uint32_t) (ordinal / spp), (uint32_t) (ordinal % spp), s);
+        TangentProbe tp = { F };
+        tp.dthr = tp.dres = mk3(0.0f, 0.0f, 0.0f);
+        Counters c = { 0u, 0u, 0u, 0u };
+        while (bounce_step<FLAT, 0, true>(P, lds, s, c, tp)) { }
+        float alpha = (s.flags & 1u) ? 1.0f : 0.0f;
+        if (P.store_xyz && !(isfinite(s.res.x) && isfinite(s.res.y) && isfinite(s.res.z))) alpha = -1.0f;
+        f3 d = tp.dres;
+        if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.z))) d = mk3(0.0f, 0.0f, 0.0f);
+        P.out_rgba[s.ordinal] = make_float4(d.x, d.y, d.z, alpha);
+    }
+}
+
+hipError_t launch_forward(const ForwardParams &f, hipStream_t s) { return launch_adjoint_kernel<k_forward<true>, k_forward<false>>(f, s); }
 
 } // namespace mtsamd

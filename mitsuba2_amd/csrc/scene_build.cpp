@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 
 namespace mtsamd {
@@ -841,6 +842,66 @@ bool bsdf_param_fields(const DevBsdf &b, int32_t kind, int32_t comp, float DevBs
         f0 = &DevBsdf::alpha_u; f1 = &DevBsdf::alpha_v; return true;
     default: return false;
     }
+}
+
+// The two perturbed copies of the BSDF table a forward-mode render differentiates between (k_forward): plus = theta + eps t, minus =
+// theta - eps t per record, eps the largest step that moves no scalar by more than its limit -- h, or with h <= 0 1 % of
+// max(|theta|, 0.05) -- shrunk so that ALPHA and ETA stay above 1e-4, as mtsamd_render_adjoint_param shrinks its step.  inv_2h[b] = 1 / (2 eps)
+// (0: record b has no tangent), taken from the scalar with the largest |t| as t / (plus - minus): for a tangent that is 1 on one scalar
+// and 0 elsewhere the three are bit for bit what mtsamd_render_adjoint_param builds for that scalar.
+int build_tangent_records(const SceneState &st, const float *bsdf_tangents, float h, std::vector<DevBsdf> &plus, std::vector<DevBsdf> &minus,
+                          std::vector<float> &inv_2h) {
+    const size_t n = st.bsdfs.size();
+    plus = st.bsdfs; minus = st.bsdfs; inv_2h.assign(n, 0.0f);
+    if (!bsdf_tangents) return MTSAMD_OK;
+    for (size_t i = 0; i < n * MTSAMD_BSDF_TANGENT_FLOATS; ++i)
+        if (!std::isfinite(bsdf_tangents[i]))
+            return fail(MTSAMD_ERR_INVALID, "bsdf %u: the tangent of parameter kind %d is not finite", (unsigned) (i / MTSAMD_BSDF_TANGENT_FLOATS), (int) (i % MTSAMD_BSDF_TANGENT_FLOATS) / 3);
+    for (size_t b = 0; b < n; ++b) {
+        const DevBsdf &rec = st.bsdfs[b];
+        const float *t = bsdf_tangents + MTSAMD_BSDF_TANGENT_FLOATS * b;
+        struct Scalar { float DevBsdf::*f0, DevBsdf::*f1; float t; int32_t kind; };
+        Scalar sc[MTSAMD_BSDF_TANGENT_FLOATS]; int n_sc = 0;
+        for (int32_t kind = MTSAMD_PARAM_REFLECTANCE; kind <= MTSAMD_PARAM_SPECULAR_TRANSMITTANCE; ++kind)
+            for (int32_t comp = 0; comp < 3; ++comp) {
+                if (t[3 * kind + comp] == 0.0f) continue;
+                Scalar &x = sc[n_sc];
+                if (!bsdf_param_fields(rec, kind, comp, x.f0, x.f1))
+                    return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u (type %d) has no differentiable parameter of kind %d (component %d of its tangent is not zero)",
+                                (unsigned) b, rec.type, kind, comp);
+                x.t = t[3 * kind + comp]; x.kind = kind; ++n_sc;
+            }
+        if (!n_sc) continue;
+        float eps = std::numeric_limits<float>::infinity();
+        for (int k = 0; k < n_sc; ++k) {
+            const float theta = rec.*sc[k].f0, at = std::fabs(sc[k].t);
+            float lim = h;
+            if (!(lim > 0.0f)) lim = 0.01f * std::max(std::fabs(theta), 0.05f);
+            eps = std::min(eps, lim / at);
+        }
+        for (int k = 0; k < n_sc; ++k) {          // the floor of ALPHA and ETA
+            const float theta = rec.*sc[k].f0, at = std::fabs(sc[k].t);
+            if ((sc[k].kind == MTSAMD_PARAM_ALPHA || sc[k].kind == MTSAMD_PARAM_ETA) && theta - eps * at <= 1e-4f) eps = std::min(eps, (0.5f * (theta - 1e-4f)) / at);
+        }
+        if (!(eps > 0.0f)) {
+            for (int k = 0; k < n_sc; ++k)
+                if ((sc[k].kind == MTSAMD_PARAM_ALPHA || sc[k].kind == MTSAMD_PARAM_ETA) && !(rec.*sc[k].f0 > 1e-4f))
+                    return fail(MTSAMD_ERR_INVALID, "bsdf %u: parameter value %g leaves no room for a central difference", (unsigned) b, rec.*sc[k].f0);
+            return fail(MTSAMD_ERR_INVALID, "bsdf %u: its tangent leaves no room for a central difference", (unsigned) b);
+        }
+        int lead = 0;
+        for (int k = 0; k < n_sc; ++k) {
+            const float theta = rec.*sc[k].f0, step = eps * sc[k].t;
+            plus[b].*sc[k].f0 = theta + step; minus[b].*sc[k].f0 = theta - step;
+            if (sc[k].f1) { plus[b].*sc[k].f1 = theta + step; minus[b].*sc[k].f1 = theta - step; }
+            if (std::fabs(sc[k].t) > std::fabs(sc[lead].t)) lead = k;
+        }
+        const float span = plus[b].*sc[lead].f0 - minus[b].*sc[lead].f0;
+        if (!(std::fabs(span) > 0.0f) || !std::isfinite(sc[lead].t / span))
+            return fail(MTSAMD_ERR_INVALID, "bsdf %u: parameter value %g leaves no room for a central difference", (unsigned) b, rec.*sc[lead].f0);
+        inv_2h[b] = sc[lead].t / span;
+    }
+    return MTSAMD_OK;
 }
 
 // parameters_changed() of a (rough)plastic whose colours were set: the weight from the means the scene holds now.  The specular mean is

@@ -144,6 +144,11 @@ int set_vertex_positions(SceneState &st, const BuildOptions &opt, uint32_t shape
 // ---- host half of the setters: they edit `st` and name what the device copy now lacks ------------------------------------------
 // One scalar parameter of a BSDF record: which float(s) of DevBsdf it is.  false: the model has no such (differentiable) parameter.
 bool bsdf_param_fields(const DevBsdf &b, int32_t kind, int32_t comp, float DevBsdf::*&f0, float DevBsdf::*&f1);
+// Forward-mode render: the BSDF table at theta + eps t and theta - eps t and 1 / (2 eps) per record (0: no tangent), from
+// bsdf_tangents[MTSAMD_BSDF_TANGENT_FLOATS * b + 3 * kind + comp] (null: no tangents, both tables are the scene's).  A non-zero entry must
+// name a field bsdf_param_fields accepts for its record; a refusal names record, type and kind through fail().
+int build_tangent_records(const SceneState &st, const float *bsdf_tangents, float h, std::vector<DevBsdf> &plus, std::vector<DevBsdf> &minus,
+                          std::vector<float> &inv_2h);
 // these three change record `bsdf` / `emitter` only (valid indices) and the Jacobians behind jac_dirty / ejac_dirty
 int set_bsdf_reflectance(SceneState &st, uint32_t bsdf, const float *rgb);
 int set_bsdf_param(SceneState &st, uint32_t bsdf, int32_t kind, const float *value3);
