@@ -563,6 +563,38 @@ MTSAMD_API int mtsamd_render_forward(mtsamd_scene *scene, const mtsamd_render_de
  * and their film positions into pos_dev (count * 2, may be NULL). */
 MTSAMD_API int mtsamd_sample_forward(mtsamd_scene *scene, const mtsamd_render_desc *desc, const mtsamd_tangent_desc *tangent, uint64_t first,
                           uint64_t count, float *rgba_dev, float *pos_dev, void *stream);
+/* Reverse-mode render: the transpose of mtsamd_render_forward -- what ek.backward(loss) leaves in ek.gradient(param) for every parameter
+ * at once (src/python/python/autodiff.py:6-91, docs/src/inverse_rendering/diff_render.rst:76-120).  ONE replay of every camera sample
+ * with its PCG32 stream and ONE dLoss/dImage (dloss_dimage_dev: crop_height * crop_width * 3; film_dev: the primal film of
+ * mtsamd_render with film_rgb = 1, whose weights normalise the image) give the gradient of every parameter the forward mode takes a
+ * tangent for, in the layouts of mtsamd_tangent_desc, so that a gradient dots with a tangent entry by entry:
+ *   bsdf_wanted / grad_bsdf_dev   wanted[18 * bsdf + 3 * param + component] != 0 marks a scalar mtsamd_render_adjoint_param accepts for that
+ *                                 record; its derivative -- the central difference mtsamd_render_adjoint_param takes, step h -- is ADDED to
+ *                                 the same entry of grad_bsdf_dev; the other entries are not touched.  Both or neither;
+ *   grad_emitters_dev             emitter_count * 3: the colour of area, constant, point, spot and directional emitters (exact; the row
+ *                                 of an envmap is not touched);
+ *   grad_textures_dev             the layout of mtsamd_render_adjoint's grad_textures_dev: texels of bitmaps used as diffuse.reflectance /
+ *                                 (rough)plastic.diffuse_reflectance, as mtsamd_render_adjoint_textures;
+ *   grad_envmap_dev               envmap height * width * 3, as mtsamd_render_adjoint_envmap.
+ * All are ACCUMULATED into; each may be NULL, not all four.  Scope and conventions are those of mtsamd_render_forward: RGB variant, `path`
+ * integrator, film_rgb = 1, plain BSDF records, any emitter mix; sampling is detached and the Russian-roulette factor is differentiated
+ * unless MTSAMD_REVERSE_DETACH_ROULETTE holds it fixed (the convention of mtsamd_render_adjoint_param).  Emitter and envmap gradients alone
+ * run at any max_depth; BSDF scalars and texels record the path's vertices and need 0 <= max_depth <= 16.  The isfinite rule holds per
+ * TERM, not per sample as in mtsamd_render_adjoint_param: a term (one vertex's contribution to one slot, one texel footprint, one emitter
+ * row or one envmap footprint) that is not finite adds nothing, and the finite terms of the same sample stay.  The slot table uploaded for the wanted scalars belongs to the scene: calls for one scene must be ordered on
+ * one stream.  Asynchronous on `stream` once the table is uploaded. */
+enum { MTSAMD_REVERSE_DETACH_ROULETTE = 1 };
+typedef struct {
+    const uint8_t *bsdf_wanted;   /* host, bsdf_count * MTSAMD_BSDF_TANGENT_FLOATS: non-zero = this scalar is wanted; or NULL */
+    float *grad_bsdf_dev;         /* device, bsdf_count * 18 floats, ACCUMULATED into at the wanted entries; NULL iff bsdf_wanted is NULL */
+    float *grad_emitters_dev;     /* device, emitter_count * 3, ACCUMULATED; or NULL */
+    float *grad_textures_dev;     /* device, layout of mtsamd_render_adjoint's grad_textures_dev, ACCUMULATED; or NULL */
+    float *grad_envmap_dev;       /* device, h * w * 3, ACCUMULATED; or NULL */
+    float h;                      /* central-difference step, as mtsamd_render_adjoint_param; <= 0: default */
+    uint32_t flags;
+} mtsamd_gradient_desc;
+MTSAMD_API int mtsamd_render_reverse(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
+                                     const float *film_dev, const mtsamd_gradient_desc *grad, void *stream);
 /* The derivative with respect to bitmap texels ('bsdf.reflectance.data', src/textures/bitmap.cpp:295-299) in ANY RGB scene the path
  * integrator renders -- any emitter mix, any of the supported BSDFs -- of mitsuba.python.autodiff.render (autodiff.py:6-91): the texels of
  * bitmaps used as diffuse.reflectance or (rough)plastic.diffuse_reflectance (plain or inside `twosided`).  Every camera sample is replayed

@@ -92,6 +92,14 @@ FORWARD_DETACH_ROULETTE = 1
 BSDF_TANGENT_FLOATS = 18
 
 
+class GradientDesc(C.Structure):
+    _fields_ = [("bsdf_wanted", C.POINTER(C.c_uint8)), ("grad_bsdf_dev", vp), ("grad_emitters_dev", vp), ("grad_textures_dev", vp),
+                ("grad_envmap_dev", vp), ("h", C.c_float), ("flags", C.c_uint32)]
+
+
+REVERSE_DETACH_ROULETTE = 1
+
+
 # every symbol include/mtsamd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mtsamd_abi_version": (C.c_int, []),
@@ -156,6 +164,7 @@ SYMBOLS = {
     "mtsamd_render_adjoint_param": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, vp, vp]),
     "mtsamd_render_forward": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(TangentDesc), vp, vp]),
     "mtsamd_sample_forward": (C.c_int, [vp, C.POINTER(RenderDesc), C.POINTER(TangentDesc), C.c_uint64, C.c_uint64, vp, vp, vp]),
+    "mtsamd_render_reverse": (C.c_int, [vp, C.POINTER(RenderDesc), vp, vp, C.POINTER(GradientDesc), vp]),
 }
 
 _lib = None

@@ -10,7 +10,8 @@ sample is replayed with the same PCG32 stream and its vertices are swept backwar
 ``mtsamd_render_adjoint_textures`` (``k_adjoint_tex``, the same sweep over the general path step), and the texels of bitmaps bound to
 ``alpha`` / ``alpha_u`` / ``alpha_v`` / ``specular_reflectance`` / ``specular_transmittance`` (``'<bsdf>.alpha.data'``, ...) through
 ``mtsamd_render_adjoint_param_textures`` (``k_adjoint_param_tex``: that sweep with a central difference of the model code, one replay per
-parameter slot).  PyTorch only provides the autograd plumbing (as ``render_torch`` does in the reference,
+parameter slot).  ``render(..., backward="fused")`` replaces these per-family replays of RGB scenes by ONE, ``mtsamd_render_reverse``
+(``k_reverse``, the transpose of ``render_forward``), which also differentiates emitter colours in any scene.  PyTorch only provides the autograd plumbing (as ``render_torch`` does in the reference,
 ``autodiff.py:380-482``).
 """
 import ctypes as C
@@ -202,7 +203,8 @@ class ParameterMap:
 
         # RGB variant with `emitters`: the same emitter-colour keys in ANY scene -- area lights under their shape, `constant`, `point`, `spot`
         # and `directional` under their own id.  Settable, and usable as tangents of render_forward (radiance is linear in them); the
-        # reverse pass covers them in diffuse area-lit scenes only (the keys above), so render() raises on one that requires a gradient
+        # default reverse pass covers them in diffuse area-lit scenes only (the keys above), so render() raises on one that requires a gradient
+        # unless backward="fused"
         for i, m in enumerate(scene._dict["meshes"] if want_emitters and not diffuse_scene else []):
             e = m.get("emitter", -1)
             if e is None or e < 0 or scene._dict["emitters"][e].get("type", "area") != "area":
@@ -297,7 +299,8 @@ def traverse(scene, replay=False, geometry=False, normals=None, emitters=False):
     which is why they have to be asked for: render() raises on one that requires a gradient.  ``emitters=True`` (RGB scenes; ignored for
     spectral ones) adds the emitter colours in any scene: '<shape id>.emitter.radiance.value' of area lights and
     '<emitter id>.radiance|intensity|irradiance.value' of `constant`, `point`, `spot` and `directional` emitters.  They are settable and
-    serve as tangents of render_forward; outside diffuse area-lit scenes render() raises on one that requires a gradient."""
+    serve as tangents of render_forward; outside diffuse area-lit scenes render() raises on one that requires a gradient unless it is
+    called with backward="fused"."""
     return ParameterMap(scene, replay=replay, geometry=geometry, normals=normals, emitters=emitters)
 
 
@@ -465,6 +468,71 @@ class _Render(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+class _RenderFused(torch.autograd.Function):
+    """render(backward="fused"): the primal pass of _Render, and ONE path replay (mtsamd_render_reverse, k_reverse) for every `bsdf`,
+    `bsdf_param`, `texture`, `emitter` and `envmap` key of the backward pass -- one estimator with one Russian-roulette convention.
+    `param_texture` keys keep their own replays (mtsamd_render_adjoint_param_textures)."""
+
+    @staticmethod
+    def forward(ctx, scene, d, pmap, keys, detach_roulette, *values):
+        pmap.update()
+        film = _render_film(scene, d)
+        ctx.scene, ctx.d, ctx.pmap, ctx.keys, ctx.detach_roulette = scene, d, pmap, keys, detach_roulette
+        ctx.save_for_backward(film)
+        return _image_of(film)
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        (film,) = ctx.saved_tensors
+        scene, d, pmap, keys = ctx.scene, ctx.d, ctx.pmap, ctx.keys
+        dev = film.device
+        gi = grad_image.to(dev, torch.float32).contiguous()
+        kinds = {pmap._kind[k][0] for k in keys}
+        n_bsdf = max(len(B.flatten(scene._bsdf_records)), 1)
+        wanted = np.zeros((n_bsdf, L.BSDF_TANGENT_FLOATS), np.uint8)
+        for k in keys:
+            kind, idx, extra = pmap._kind[k]
+            if kind in ("bsdf", "bsdf_param"):
+                row = 0 if kind == "bsdf" else int(extra)
+                wanted[idx, 3 * row: 3 * row + pmap[k].numel()] = 1
+        g_bsdf = torch.zeros((n_bsdf, L.BSDF_TANGENT_FLOATS), dtype=torch.float32, device=dev) if wanted.any() else None
+        g_em = torch.zeros((max(len(scene._dict.get("emitters", [])), 1), 3), dtype=torch.float32, device=dev) if "emitter" in kinds else None
+        tex_floats = sum(h * w * 3 for (h, w, _) in scene._texture_shapes)
+        g_tex = torch.zeros(max(tex_floats, 1), dtype=torch.float32, device=dev) if kinds & {"texture", "param_texture"} else None
+        g_env = torch.zeros_like(next(pmap[k] for k in keys if pmap._kind[k][0] == "envmap")) if "envmap" in kinds else None
+        if kinds - {"param_texture"}:
+            gd = L.GradientDesc()
+            if g_bsdf is not None:
+                gd.bsdf_wanted = wanted.ctypes.data_as(C.POINTER(C.c_uint8))
+                gd.grad_bsdf_dev = _ptr(g_bsdf)
+            gd.grad_emitters_dev = _ptr(g_em) if g_em is not None else None
+            gd.grad_textures_dev = _ptr(g_tex) if "texture" in kinds else None
+            gd.grad_envmap_dev = _ptr(g_env) if g_env is not None else None
+            gd.h = float(pmap.fd_step)
+            gd.flags = L.REVERSE_DETACH_ROULETTE if ctx.detach_roulette else 0
+            L.check(L.lib().mtsamd_render_reverse(scene._handle, C.byref(d), _ptr(gi), _ptr(film), C.byref(gd), _stream()))
+        g_slot = {}
+        for slot in sorted({s for k in keys if pmap._kind[k][0] == "param_texture" for s in pmap._kind[k][2]}):
+            g_slot[slot] = torch.zeros_like(g_tex)
+            L.check(L.lib().mtsamd_render_adjoint_param_textures(scene._handle, C.byref(d), _ptr(gi), _ptr(film), int(slot), float(pmap.fd_step),
+                                                                 _ptr(g_slot[slot]), _stream()))
+        grads = []
+        for k in keys:
+            kind, idx, extra = pmap._kind[k]
+            if kind == "param_texture":
+                grads.append(sum(_texture_slice(scene, g_slot[s], idx) for s in extra))
+            elif kind in ("bsdf", "bsdf_param"):
+                row = 0 if kind == "bsdf" else int(extra)
+                grads.append(g_bsdf[idx, 3 * row: 3 * row + pmap[k].numel()].clone().reshape(pmap[k].shape))
+            elif kind == "envmap":
+                grads.append(g_env)
+            elif kind == "emitter":
+                grads.append(g_em[idx].clone().reshape(pmap[k].shape))
+            else:
+                grads.append(_texture_slice(scene, g_tex, idx))
+        return (None, None, None, None, None) + tuple(grads)
+
+
 _render_counter = {}      # id(scene) -> number of render() calls so far
 _render_tracked = set()   # ids whose entry is dropped when their scene dies: id() values are reused, and a new scene must start at call 0
 
@@ -550,17 +618,28 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
     return _image_of(film)
 
 
-def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, params=None):
+def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, params=None, backward="families", detach_roulette=False):
     """mitsuba.python.autodiff.render (autodiff.py:121-194): differentiable render returning the flattened RGB image
     (``len == H*W*3``).  ``params`` (or ``optimizer.params``) is the :class:`ParameterMap` whose tensors with
     ``requires_grad`` receive gradients; without one the call is a plain render.  Every call draws new random numbers
     (the reference's sampler keeps advancing its streams between calls; here the call counter is folded into the seed).
+
+    ``backward`` picks the backward pass.  ``"families"`` (the default) is one entry point per parameter family: one replay per scalar of
+    a BSDF-model parameter, one for texels, one for the envmap; emitter colours only in diffuse area-lit scenes.  ``"fused"`` (RGB
+    scenes) serves every ``bsdf``, ``bsdf_param``, ``texture``, ``emitter`` and ``envmap`` key with ONE replay, ``mtsamd_render_reverse``,
+    the transpose of :func:`render_forward`: emitter keys of ``traverse(scene, emitters=True)`` are then differentiable in any scene, and
+    the whole gradient is that of one estimator -- Russian roulette differentiated as the reference does, or held fixed with
+    ``detach_roulette=True`` (the convention of ``mtsamd_render_adjoint_param``).  Texels of parameter maps keep their own replays.
     """
+    if backward not in ("families", "fused"):
+        raise RuntimeError("backward: \"families\" or \"fused\", not %r" % (backward,))
+    if backward == "fused" and _is_spectral(scene):
+        raise RuntimeError("backward=\"fused\" is implemented for the RGB variant only")
     sensor = scene.sensors()[sensor_index]
     integrator = scene.integrator() if scene.integrator() is not None else PathIntegrator()
     if optimizer is not None and params is None:
         params = optimizer.params
-    if params is not None and not _is_spectral(scene) and not params._diffuse_scene:
+    if params is not None and not _is_spectral(scene) and not params._diffuse_scene and backward != "fused":
         for k, v in params.items():
             if v.requires_grad and params._kind[k][0] == "emitter":
                 raise RuntimeError("%s has a reverse-mode gradient in diffuse scenes lit by area lights only; its derivative image in this "
@@ -585,6 +664,8 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
             if params is not None:
                 params.update()
             return _image_of(_render_film(scene, d))
+        if backward == "fused":
+            return _RenderFused.apply(scene, d, params, keys, bool(detach_roulette), *[params[k] for k in keys])
         return _Render.apply(scene, d, params, keys, *[params[k] for k in keys])
 
     if not unbiased:

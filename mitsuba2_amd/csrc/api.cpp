@@ -230,6 +230,9 @@ struct Workspace {
     DevBsdf *fw_plus = nullptr, *fw_minus = nullptr; size_t fw_records = 0;
     float *fw_inv_2h = nullptr; size_t fw_inv_floats = 0;
     float *fw_emitters = nullptr; size_t fw_emitter_floats = 0;
+    // reverse-mode render: the slot table of the wanted BSDF scalars and the slot range of every record
+    ReverseSlot *rv_slots = nullptr; size_t rv_slot_count = 0;
+    uint32_t *rv_range = nullptr; size_t rv_range_words = 0;
     uint32_t *h_counts = nullptr;        // pinned, 4 * n_waves
     uint64_t *h_cursor = nullptr;        // pinned, 2 * n_waves
     uint64_t *h_cursor_rb = nullptr;     // pinned, 2 slots x n_waves: cursors read back with the counts (pool-drain gathering)
@@ -258,6 +261,8 @@ struct Workspace {
         (void) hipFree(fw_plus); (void) hipFree(fw_minus); fw_plus = fw_minus = nullptr; fw_records = 0;
         (void) hipFree(fw_inv_2h); fw_inv_2h = nullptr; fw_inv_floats = 0;
         (void) hipFree(fw_emitters); fw_emitters = nullptr; fw_emitter_floats = 0;
+        (void) hipFree(rv_slots); rv_slots = nullptr; rv_slot_count = 0;
+        (void) hipFree(rv_range); rv_range = nullptr; rv_range_words = 0;
         (void) hipFree(moment_film); moment_film = nullptr; moment_floats = 0;
         (void) hipFree(aov_stream); aov_stream = nullptr; aov_stream_slots = 0;
         (void) hipFree(aov_film); aov_film = nullptr; aov_film_floats = 0;
@@ -1934,6 +1939,67 @@ int mtsamd_sample_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mt
         if (pos) HIP_TRY(hipMemcpyAsync(pos + 2 * a, s->ws.out_pos, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));
+    return MTSAMD_OK;
+}
+
+// ---- reverse-mode render: the transpose of mtsamd_render_forward (k_reverse) -------------------
+int mtsamd_render_reverse(mtsamd_scene *s, const mtsamd_render_desc *d, const float *dimage, const float *film, const mtsamd_gradient_desc *g,
+                          void *stream_) {
+    if (!s || !d || !dimage || !film || !g) return fail(MTSAMD_ERR_INVALID, "null argument");
+    if (!g->grad_bsdf_dev && !g->bsdf_wanted && !g->grad_emitters_dev && !g->grad_textures_dev && !g->grad_envmap_dev)
+        return fail(MTSAMD_ERR_INVALID, "the gradient is empty: grad_bsdf_dev, grad_emitters_dev, grad_textures_dev and grad_envmap_dev are all null");
+    if (!g->grad_bsdf_dev != !g->bsdf_wanted) return fail(MTSAMD_ERR_INVALID, "bsdf_wanted and grad_bsdf_dev go together: one of them is null");
+    if (int rc = check_desc(d)) return rc;
+    if (g->flags & ~(uint32_t) MTSAMD_REVERSE_DETACH_ROULETTE) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the gradient descriptor", g->flags);
+    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render is implemented for the RGB variant only");
+    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
+    for (const DevBsdf &b : s->bsdfs)
+        if (b.type >= kBsdfBlend) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render does not handle blendbsdf / mask materials");
+    if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render differentiates the path integrator");
+    if (d->part_count > 1 || d->row_begin != 0 || d->row_end > 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render covers the whole crop window (no row window, no tile partition)");
+    if (d->film_rgb != 1) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render differentiates an R, G, B, A, W film (film_rgb must be 1)");
+    ReverseParams r{};
+    if (int rc = make_filter(d->rfilter, d->rfilter_param, d->rfilter_param2, d->rfilter_analytic, r.filter)) return rc;
+    if (r.filter.taps > 8) return fail(MTSAMD_ERR_UNSUPPORTED, "reconstruction filter too wide for the reverse-mode render");
+    if (g->grad_envmap_dev && (s->environment < 0 || !s->d_envmap)) return fail(MTSAMD_ERR_UNSUPPORTED, "grad_envmap_dev: the scene has no envmap emitter");
+    if (g->grad_textures_dev) {
+        bool bitmaps = false;
+        for (const DevTexture &tx : s->textures) bitmaps = bitmaps || tx.kind == 0u;
+        if (!bitmaps) return fail(MTSAMD_ERR_UNSUPPORTED, "grad_textures_dev: the scene has no bitmap textures");
+    }
+    std::vector<ReverseSlot> slots; std::vector<uint32_t> range;
+    if (int rc = build_reverse_slots(*s, g->bsdf_wanted, g->h, slots, range)) return rc;
+    if (slots.empty() && !g->grad_emitters_dev && !g->grad_textures_dev && !g->grad_envmap_dev)
+        return fail(MTSAMD_ERR_INVALID, "the gradient is empty: no BSDF scalar is wanted and the other gradients are null");
+    const bool record = !slots.empty() || g->grad_textures_dev;
+    if (record && (d->max_depth < 0 || d->max_depth > 16))
+        return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render of BSDF scalars and texels needs a finite max_depth <= 16 (got %d)", d->max_depth);
+    if (int rc = make_camera(*d, r.rp.cam)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t) stream_;
+    r.rp.sv = s->view;
+    r.rp.sv.general = std::max(r.rp.sv.general, 1u);
+    r.rp.base_seed = d->seed; r.rp.spp = d->sample_count;
+    r.rp.crop_x = d->crop_x; r.rp.crop_y = d->crop_y; r.rp.crop_w = d->crop_width; r.rp.crop_h = d->crop_height;
+    r.rp.max_depth = d->max_depth; r.rp.rr_depth = d->rr_depth;
+    r.rp.rows = RowMap{ 0, d->crop_height, std::max(d->crop_height, 1), 0, 1 };
+    r.rp.store_xyz = 0; r.rp.out_pos = nullptr; r.rp.out_rgba = nullptr;
+    r.n_samples = (uint64_t) d->crop_width * d->crop_height * (uint64_t) d->sample_count;
+    r.dimage = dimage; r.film = film;
+    r.flags = g->flags;
+    r.grad_emitter = s->emitters.empty() ? nullptr : g->grad_emitters_dev;
+    r.grad_tex = g->grad_textures_dev; r.grad_env = g->grad_envmap_dev;
+    if (!slots.empty()) {
+        Workspace &w = s->ws;
+        if (int rc = grow(w.rv_slots, w.rv_slot_count, slots.size())) return rc;
+        if (int rc = grow(w.rv_range, w.rv_range_words, range.size())) return rc;
+        HIP_TRY(hipMemcpyAsync(w.rv_slots, slots.data(), slots.size() * sizeof(ReverseSlot), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(w.rv_range, range.data(), range.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));      // the host tables are free again
+        r.slots = w.rv_slots; r.slot_range = w.rv_range; r.n_slots = (uint32_t) slots.size(); r.grad_bsdf = g->grad_bsdf_dev;
+    }
+    if (!record && !r.grad_emitter && !r.grad_env) return MTSAMD_OK;      // emitter gradients of a scene without emitters
+    HIP_TRY(launch_reverse(r, record, stream));
     return MTSAMD_OK;
 }
 

@@ -166,6 +166,37 @@ struct ForwardParams {
 };
 hipError_t launch_forward(const ForwardParams &f, hipStream_t s);
 
+// k_reverse: the transpose of k_forward -- one replay of every camera sample, one dLoss/dImage, the gradient of every parameter the
+// forward mode knows.  An argument block of its own: AdjointParams and ForwardParams stay what they were.
+// One wanted BSDF scalar: record `record` with the floats f0 and f1 (offsets in floats into DevBsdf; f1 == f0 unless ALPHA moves both
+// roughnesses) set to `plus` / `minus` is the perturbed pair of its central difference, inv_2h = 1 / (plus - minus); the gradient is
+// added to grad_bsdf[out], out = 18 * record + 3 * kind + component (the layout of mtsamd_tangent_desc::bsdf_tangents).
+struct ReverseSlot { uint32_t record; uint16_t f0, f1; float plus, minus, inv_2h; uint32_t out; };
+static_assert(sizeof(ReverseSlot) == 24, "a slot is a 24-byte patch, not a pair of records");
+constexpr uint32_t kReverseDetachRoulette = 1u;      // MTSAMD_REVERSE_DETACH_ROULETTE
+// Per-workgroup LDS bins of k_reverse: the sums of the first kReverseSlotBins slots and of the first kReverseEmitterBins emitters are
+// kept in LDS (float atomics) and flushed with one global atomicAdd per non-zero bin; slots and emitters beyond go straight to global
+// atomics.  (64 + 3 * 32) * 4 = 640 bytes of static LDS beside a flat scene's kFlatLdsCap = 150 KiB of the CU's 160 KiB.
+constexpr uint32_t kReverseSlotBins = 64u, kReverseEmitterBins = 32u;
+struct ReverseParams {
+    RenderParams rp;            // as AdjointParams::rp
+    FilterView filter;
+    uint64_t n_samples;         // crop_w * crop_h * spp
+    const float *dimage;        // dLoss/dImage, crop_h * crop_w * 3
+    const float *film;          // primal film (5 channels; only the weight channel is read)
+    const ReverseSlot *slots;   // n_slots wanted scalars in record order; the slots of record b are slot_range[b] .. slot_range[b + 1]
+    const uint32_t *slot_range; // n_bsdfs + 1 (null with slots)
+    uint32_t n_slots;
+    float *grad_bsdf;           // n_bsdfs * 18, accumulated at the wanted entries (null iff there are no slots)
+    float *grad_emitter;        // n_emitters * 3, accumulated (row of an envmap untouched), or null
+    float *grad_tex;            // layout of AdjointParams::grad_tex, accumulated, or null
+    float *grad_env;            // envmap height * width * 3, accumulated, or null
+    uint32_t flags;             // kReverseDetachRoulette
+};
+// record = true: the replay keeps its vertices (at most 16, 0 <= max_depth <= 16) and sweeps them backwards -- BSDF scalars and texels;
+// false: emitter colours and envmap texels only, accumulated while the path runs, any max_depth
+hipError_t launch_reverse(const ReverseParams &r, bool record, hipStream_t s);
+
 struct RayStreams {
     const float *ox, *oy, *oz, *dx, *dy, *dz, *mint, *maxt;
     const uint8_t *active;

@@ -1932,7 +1932,8 @@ constexpr int kAdjointMaxDepth = 16;
 
 // dLoss/dRadiance of the camera sample at film position `pos`: the adjoint of ImageBlock::put (imageblock.cpp:117-169, block = the
 // crop window, no border) followed by Image = values / (weight + 1e-8) (autodiff.py:80-91)
-MTS_DEV f3 adjoint_delta(const AdjointParams &A, float2 pos) {
+template <class Params>      // AdjointParams or ReverseParams: rp, filter, dimage, film
+MTS_DEV f3 adjoint_delta(const Params &A, float2 pos) {
     const RenderParams &P = A.rp;
     const FilterView &f = A.filter;
     f3 delta = mk3(0.0f, 0.0f, 0.0f);
@@ -1964,7 +1965,8 @@ MTS_DEV f3 adjoint_delta(const AdjointParams &A, float2 pos) {
 // The camera samples of a launch are dealt to its threads grid-stride (the loop at the top of each kernel; launch_adjoint_kernel caps
 // the grid).  Sample k is regenerated with the PCG32 stream of the primal pass (`s`: the path state at its camera ray); returns
 // dLoss/dRadiance of the sample.
-MTS_DEV f3 adjoint_sample(const AdjointParams &A, uint64_t k, PathState &s) {
+template <class Params>
+MTS_DEV f3 adjoint_sample(const Params &A, uint64_t k, PathState &s) {
     const uint32_t spp = (uint32_t) A.rp.spp;
     float2 pos;
     generate_path(A.rp, k, (uint32_t) (k / spp), (uint32_t) (k % spp), s, &pos);
@@ -4076,5 +4078,253 @@ __global__ __launch_bounds__(kBlock) void k_forward(const ForwardParams F) {
 }
 
 hipError_t launch_forward(const ForwardParams &f, hipStream_t s) { return launch_adjoint_kernel<k_forward<true>, k_forward<false>>(f, s); }
+
+// ---------------------------------------------------------------------------------------------
+// Reverse mode: the transpose of k_forward.  One replay of every camera sample with one dLoss/dImage gives the gradient of every parameter
+// k_forward takes a tangent for, with k_forward's conventions term for term (everything detached but the Russian-roulette factor; the
+// detach flag holds that fixed too), so that <dL, J t> of a forward render equals <J^T dL, t> here up to the order of the sums:
+//   emitter colours    need no suffix of the path: emission picked up adds delta (ew T) to the emitter's row, an unoccluded emitter sample
+//                      delta (mis T' bv em_geo), em_geo from r1, r2 and the falloff as TangentProbe::em_geo forms it;
+//   envmap texels      scattered at the two sites of EnvGradProbe;
+//   reflectance texels the sweep of k_adjoint_tex over the recorded vertices, bsdf_dvalue_drefl / bsdf_dweight_drefl and scatter_texel_grad;
+//   BSDF constants     at a vertex whose record has wanted slots, slot j adds  g_j += sum_c T'_c (delta_c dNc_jc + a_c dW_jc)  with
+//                      dNc_j = (mis spec) dbv_j, dW_j = dv_j / pdf, both the central difference of bsdf_eval_pdf between the slot's pair
+//                      at the recorded directions; a discrete lobe is re-sampled with s1, s2 (ParamGradProbe::bsdf_sampled).
+// RECORD = false (no BSDF scalar, no texel wanted) keeps no vertices and runs at any depth.  RECORD = true is ONE replay with a wider
+// record than VertexRecG: besides T, invq, E, Nc, W and the texel terms it keeps what the slot differences need at the sweep -- wi, the two
+// wo, the pdf and delta flag, s1 / s2, the reflectance, mis spec and the record index (184 bytes per vertex, 16 vertices per lane).
+// Sums per slot and per emitter go to LDS bins of the workgroup (kReverseSlotBins, kReverseEmitterBins), flushed once at the end.
+struct VertexRecR {
+    f3 T; float invq;
+    f3 E; float eta2;
+    f3 Nc; int32_t rr_channel;      // channel that sets q (-1: none / q clamped / roulette detached)
+    f3 W; uint32_t texel;           // kNoPrim: no texel gradient at this vertex
+    f3 dNc; int32_t texture;        // d / d(refl), as VertexRecG
+    f3 dW; f2 w1;
+    f3 wi; int32_t rec;             // record of the surface if it has wanted slots, else -1
+    f3 wo_e; float pdf;             // local direction of the emitter sample; pdf of the BSDF sample
+    f3 wo_s; float s1;
+    f3 refl; uint32_t flags;        // 1: the emitter sample was unoccluded; 2: a BSDF sample was drawn; 4: from a discrete lobe
+    f3 ms; f2 s2;                   // mis * spec of the emitter sample
+};
+
+// the float of DevBsdf at offset `f` (in floats) set to v: a switch over the fields bsdf_param_fields can name, so the record stays in registers
+MTS_DEV void reverse_patch(DevBsdf &b, uint32_t f, float v) {
+    switch (f) {
+    case offsetof(DevBsdf, r) / 4: b.r = v; break; case offsetof(DevBsdf, g) / 4: b.g = v; break; case offsetof(DevBsdf, b) / 4: b.b = v; break;
+    case offsetof(DevBsdf, sr) / 4: b.sr = v; break; case offsetof(DevBsdf, sg) / 4: b.sg = v; break; case offsetof(DevBsdf, sb) / 4: b.sb = v; break;
+    case offsetof(DevBsdf, er) / 4: b.er = v; break; case offsetof(DevBsdf, eg) / 4: b.eg = v; break; case offsetof(DevBsdf, eb) / 4: b.eb = v; break;
+    case offsetof(DevBsdf, kr) / 4: b.kr = v; break; case offsetof(DevBsdf, kg) / 4: b.kg = v; break; case offsetof(DevBsdf, kb) / 4: b.kb = v; break;
+    case offsetof(DevBsdf, alpha_u) / 4: b.alpha_u = v; break; case offsetof(DevBsdf, alpha_v) / 4: b.alpha_v = v; break;
+    default: break;
+    }
+}
+
+// the workgroup's emitter bins: one __shared__ array that the probe and the kernel name directly, so that the sums are LDS float atomics
+// (a pointer kept in the probe reaches the step as a generic address)
+MTS_DEV float *reverse_emitter_bins() {
+    __shared__ float s_em[3 * kReverseEmitterBins];
+    return s_em;
+}
+
+template <bool RECORD>
+struct ReverseProbe {
+    static constexpr bool kFactoredEmitter = true, kMirrorTwoSided = false, kSamples = true;
+    const ReverseParams &R;
+    f3 delta;                       // dLoss/dRadiance of the sample
+    VertexRecR *r;                  // RECORD: the vertex of this step
+    f3 thr0;                        // throughput on arrival (emission is picked up before roulette)
+    const DevBsdf *cur; f3 refl0;   // the record and reflectance of the surface of this step
+    bool tex, slotted;              // a texel gradient / slots of the surface's record are wanted here
+
+    // delta * c added to the row of emitter e; a term that is not finite adds nothing
+    MTS_DEV void add_emitter(uint32_t e, f3 c) const {
+        const float v[3] = { delta.x * c.x, delta.y * c.y, delta.z * c.z };
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            if (v[ch] != 0.0f && isfinite(v[ch])) {
+                if (e < kReverseEmitterBins) atomicAdd(&reverse_emitter_bins()[3u * e + (uint32_t) ch], v[ch]);
+                else atomicAdd(R.grad_emitter + 3u * (size_t) e + ch, v[ch]);
+            }
+    }
+    // delta * coeff scattered over the footprint of envmap_lookup (EnvGradProbe::add), unless it is not finite
+    MTS_DEV void add_envmap(const DevEnvmap &e, float u, float v, f3 coeff) const {
+        if (isfinite(delta.x * coeff.x) && isfinite(delta.y * coeff.y) && isfinite(delta.z * coeff.z)) EnvGradProbe{ delta, R.grad_env }.add(e, u, v, coeff);
+    }
+    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) {
+        static_assert(GENERAL && DEFER == 0 && !NEST, "the reverse-mode derivative rides on the plain general fused step");
+        thr0 = s.thr; cur = nullptr; tex = slotted = false; refl0 = mk3(0.0f, 0.0f, 0.0f);
+        if (RECORD) {
+            r->T = s.thr; r->invq = 1.0f; r->eta2 = s.eta * s.eta; r->rr_channel = -1;
+            r->E = r->Nc = r->W = r->dNc = r->dW = mk3(0.0f, 0.0f, 0.0f);
+            r->texel = kNoPrim; r->texture = -1; r->w1.x = r->w1.y = 0.0f;
+            r->rec = -1; r->flags = 0u;
+        }
+    }
+    MTS_DEV void emitted(float ew, int32_t emitter, f3 le) {
+        if (R.grad_emitter) add_emitter((uint32_t) emitter, mk3(ew * thr0.x, ew * thr0.y, ew * thr0.z));
+        if (RECORD) r->E = mk3(ew * le.x, ew * le.y, ew * le.z);
+    }
+    MTS_DEV void escaped(const SceneView &sv, const PathState &s, const DevEmitter &e, float ew, f3 le) {
+        const f3 c = mk3(ew * s.thr.x, ew * s.thr.y, ew * s.thr.z);
+        if (e.pad0 == kEmitterEnvmap) {
+            if (R.grad_env) {
+                float u, v;
+                env_dir_to_uv(mat3_apply(sv.envmap->to_local, s.d), u, v);
+                add_envmap(*sv.envmap, u, v, c);
+            }
+        } else if (R.grad_emitter) add_emitter((uint32_t) sv.env_emitter, c);
+        if (RECORD) r->E = mk3(ew * le.x, ew * le.y, ew * le.z);
+    }
+    MTS_DEV void roulette(f3 thr, float hm, float rq, bool free) {
+        if (RECORD) {
+            r->invq = rq;
+            if (free && !(R.flags & kReverseDetachRoulette)) r->rr_channel = thr.x == hm ? 0 : (thr.y == hm ? 1 : 2);
+        }
+    }
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, uint32_t texel, f2 tw1, f3) {
+        cur = &bsdf; refl0 = refl;
+        if (RECORD) {
+            tex = R.grad_tex != nullptr && texel != kNoPrim;
+            if (tex) { r->texel = texel; r->w1 = tw1; r->texture = bsdf.texture; }
+            const int32_t b = si.shape_rec.bsdf;
+            slotted = R.slot_range != nullptr && R.slot_range[b + 1] > R.slot_range[b];
+            if (slotted) { r->rec = b; r->wi = si.wi; r->refl = refl; }
+        }
+    }
+    // the shadow ray is traced wherever a gradient may be non-zero, also where the radiance itself is 0
+    MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &, f3, const NeeTerms &t) {
+        const bool lit = TangentProbe::em_geo(sv, t) != 0.0f && (t.kind == kEmitterEnvmap ? R.grad_env != nullptr : R.grad_emitter != nullptr);
+        // RECORD: Nc feeds the suffix adjoint of EARLIER vertices, in channels where the throughput here may be 0 (GeneralRecorder)
+        const bool nc = (t.mis * t.bv.x) * t.spec.x != 0.0f || (t.mis * t.bv.y) * t.spec.y != 0.0f || (t.mis * t.bv.z) * t.spec.z != 0.0f;
+        return lit || (RECORD && (tex || slotted || nc));
+    }
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &, f3 thr, const NeeTerms &t) {
+        const float g = TangentProbe::em_geo(sv, t);
+        if (g != 0.0f) {
+            const f3 c = mk3(((t.mis * thr.x) * t.bv.x) * g, ((t.mis * thr.y) * t.bv.y) * g, ((t.mis * thr.z) * t.bv.z) * g);
+            if (t.kind == kEmitterEnvmap) { if (R.grad_env) add_envmap(*sv.envmap, t.ds.uv.x, t.ds.uv.y, c); }
+            else if (R.grad_emitter) add_emitter(t.ds.emitter, c);
+        }
+        if (RECORD) {
+            r->Nc = mk3((t.mis * t.bv.x) * t.spec.x, (t.mis * t.bv.y) * t.spec.y, (t.mis * t.bv.z) * t.spec.z);
+            if (tex) {
+                const f3 dbv = bsdf_dvalue_drefl(*cur, refl0, t.wi, t.wo);
+                r->dNc = mk3((t.mis * dbv.x) * t.spec.x, (t.mis * dbv.y) * t.spec.y, (t.mis * dbv.z) * t.spec.z);
+            }
+            if (slotted) { r->wo_e = t.wo; r->ms = mk3(t.mis * t.spec.x, t.mis * t.spec.y, t.mis * t.spec.z); r->flags |= 1u; }
+        }
+    }
+    MTS_DEV void bsdf_sampled(const SceneView &, const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, f3, const BsdfSample &bs, f3 weight, float s1, f2 s2) {
+        if (RECORD) {
+            r->W = weight;
+            if (tex) r->dW = bsdf_dweight_drefl(bsdf, refl, si.wi, bs);
+            if (slotted) { r->wo_s = bs.wo; r->pdf = bs.pdf; r->s1 = s1; r->s2 = s2; r->flags |= bs.delta ? 6u : 2u; }
+        }
+    }
+};
+
+// dNc and dW of one slot at a recorded vertex: the central difference of the model code between the slot's pair
+MTS_DEV void reverse_slot_terms(const DevBsdf &base, const ReverseSlot &sl, const VertexRecR &r, f3 &dnc, f3 &dw) {
+    DevBsdf bp = base, bm = base;
+    reverse_patch(bp, sl.f0, sl.plus); reverse_patch(bm, sl.f0, sl.minus);
+    if (sl.f1 != sl.f0) { reverse_patch(bp, sl.f1, sl.plus); reverse_patch(bm, sl.f1, sl.minus); }
+    // eval_reflectance of the perturbed records: their own constant, or the texel the primal record looked up
+    const f3 rp = base.texture < 0 ? mk3(bp.r, bp.g, bp.b) : r.refl, rm = base.texture < 0 ? mk3(bm.r, bm.g, bm.b) : r.refl;
+    dnc = dw = mk3(0.0f, 0.0f, 0.0f);
+    if (r.flags & 1u) {
+        f3 vp, vm; float pp, pm;
+        bsdf_eval_pdf(bp, rp, r.wi, r.wo_e, vp, pp);
+        bsdf_eval_pdf(bm, rm, r.wi, r.wo_e, vm, pm);
+        dnc = mk3(r.ms.x * ((vp.x - vm.x) * sl.inv_2h), r.ms.y * ((vp.y - vm.y) * sl.inv_2h), r.ms.z * ((vp.z - vm.z) * sl.inv_2h));
+    }
+    if ((r.flags & 6u) == 2u && r.pdf > 0.0f) {
+        f3 vp, vm; float pp, pm;
+        bsdf_eval_pdf(bp, rp, r.wi, r.wo_s, vp, pp);
+        bsdf_eval_pdf(bm, rm, r.wi, r.wo_s, vm, pm);
+        const float ip = rcp(r.pdf);
+        dw = mk3(((vp.x - vm.x) * sl.inv_2h) * ip, ((vp.y - vm.y) * sl.inv_2h) * ip, ((vp.z - vm.z) * sl.inv_2h) * ip);
+    } else if ((r.flags & 6u) == 6u) {
+        // a discrete lobe: re-sampled with the perturbed records and the same numbers; counts only if both land on the primal direction
+        f3 wp, wm; BsdfSample bp_, bm_;
+        const bool okp = bsdf_sample(bp, rp, r.wi, r.s1, r.s2, bp_, wp);
+        const bool okm = bsdf_sample(bm, rm, r.wi, r.s1, r.s2, bm_, wm);
+        if (okp && okm && bp_.delta && bm_.delta && bp_.wo.x == r.wo_s.x && bp_.wo.y == r.wo_s.y && bp_.wo.z == r.wo_s.z &&
+            bm_.wo.x == r.wo_s.x && bm_.wo.y == r.wo_s.y && bm_.wo.z == r.wo_s.z)
+            dw = mk3((wp.x - wm.x) * sl.inv_2h, (wp.y - wm.y) * sl.inv_2h, (wp.z - wm.z) * sl.inv_2h);
+    }
+}
+
+template <bool FLAT, bool RECORD>
+__global__ __launch_bounds__(kBlock) void k_reverse(const ReverseParams R) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = R.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    float *const s_em = reverse_emitter_bins();
+    __shared__ float s_slot[RECORD ? kReverseSlotBins : 1u];
+    for (uint32_t i = threadIdx.x; i < 3u * kReverseEmitterBins; i += kBlock) s_em[i] = 0.0f;
+    for (uint32_t i = threadIdx.x; i < (RECORD ? kReverseSlotBins : 1u); i += kBlock) s_slot[i] = 0.0f;
+    __syncthreads();
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < R.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        PathState s; const f3 delta = adjoint_sample(R, k, s);
+        if (delta.x == 0.0f && delta.y == 0.0f && delta.z == 0.0f) continue;       // every term below is proportional to delta
+        Counters c = { 0u, 0u, 0u, 0u };
+        ReverseProbe<RECORD> pr = { R, delta, nullptr };
+        if constexpr (!RECORD) {
+            while (bounce_step<FLAT, 0, true>(P, lds, s, c, pr)) { }
+        } else {
+        VertexRecR rec[kAdjointMaxDepth];
+        int n = 0;
+        bool alive = true;
+        while (alive && n < kAdjointMaxDepth) { pr.r = &rec[n]; alive = bounce_step<FLAT, 0, true>(P, lds, s, c, pr); ++n; }
+        const Geo<FLAT> geo{ P.sv, lds };
+        f3 a = mk3(0.0f, 0.0f, 0.0f);
+        for (int v = n - 1; v >= 0; --v) {
+            const VertexRecR &r = rec[v];
+            const f3 Tp = r.T * r.invq;
+            if (r.texel != kNoPrim) {
+                const float gg[3] = { Tp.x * fmaf(delta.x, r.dNc.x, a.x * r.dW.x), Tp.y * fmaf(delta.y, r.dNc.y, a.y * r.dW.y),
+                                      Tp.z * fmaf(delta.z, r.dNc.z, a.z * r.dW.z) };
+                if (isfinite(gg[0]) && isfinite(gg[1]) && isfinite(gg[2])) {
+                    const DevTexture t = P.sv.textures[r.texture];
+                    scatter_texel_grad(R.grad_tex, t, r.texel, r.w1, gg);
+                }
+            }
+            if (r.rec >= 0) {
+                const DevBsdf base = geo.bsdf((uint32_t) r.rec);
+                const uint32_t j1 = R.slot_range[r.rec + 1];
+                for (uint32_t j = R.slot_range[r.rec]; j < j1; ++j) {
+                    const ReverseSlot sl = R.slots[j];
+                    f3 dnc, dw;
+                    reverse_slot_terms(base, sl, r, dnc, dw);
+                    const float g = fmaf(Tp.z, fmaf(delta.z, dnc.z, a.z * dw.z), fmaf(Tp.y, fmaf(delta.y, dnc.y, a.y * dw.y), Tp.x * fmaf(delta.x, dnc.x, a.x * dw.x)));
+                    if (g != 0.0f && isfinite(g)) {
+                        if (j < kReverseSlotBins) atomicAdd(&s_slot[j], g);
+                        else atomicAdd(R.grad_bsdf + sl.out, g);
+                    }
+                }
+            }
+            const f3 b = mk3(fmaf(delta.x, r.Nc.x, r.W.x * a.x), fmaf(delta.y, r.Nc.y, r.W.y * a.y), fmaf(delta.z, r.Nc.z, r.W.z * a.z));
+            a = mk3(delta.x * r.E.x + r.invq * b.x, delta.y * r.E.y + r.invq * b.y, delta.z * r.E.z + r.invq * b.z);
+            if (r.rr_channel >= 0) {
+                const float corr = ((r.invq * r.invq) * r.eta2) * (b.x * r.T.x + b.y * r.T.y + b.z * r.T.z);
+                if (r.rr_channel == 0) a.x -= corr; else if (r.rr_channel == 1) a.y -= corr; else a.z -= corr;
+            }
+        }
+        }
+    }
+    __syncthreads();
+    if (R.grad_emitter)
+        for (uint32_t i = threadIdx.x; i < 3u * min(P.sv.n_emitters, kReverseEmitterBins); i += kBlock)
+            if (s_em[i] != 0.0f) atomicAdd(R.grad_emitter + i, s_em[i]);
+    if (RECORD && R.grad_bsdf)
+        for (uint32_t i = threadIdx.x; i < min(R.n_slots, kReverseSlotBins); i += kBlock)
+            if (s_slot[i] != 0.0f) atomicAdd(R.grad_bsdf + R.slots[i].out, s_slot[i]);
+}
+
+hipError_t launch_reverse(const ReverseParams &r, bool record, hipStream_t s) {
+    return record ? launch_adjoint_kernel<k_reverse<true, true>, k_reverse<false, true>>(r, s)
+                  : launch_adjoint_kernel<k_reverse<true, false>, k_reverse<false, false>>(r, s);
+}
 
 } // namespace mtsamd

@@ -904,6 +904,49 @@ int build_tangent_records(const SceneState &st, const float *bsdf_tangents, floa
     return MTSAMD_OK;
 }
 
+// The slot table of a reverse-mode render (k_reverse): per wanted scalar the patch that turns its record into the pair build_tangent_records
+// makes for the one-hot tangent on that scalar -- the arithmetic below is that function's with t = 1 (eps = lim / 1, step = eps * 1,
+// inv_2h = 1 / span), operation for operation, so the floats agree bit for bit.
+int build_reverse_slots(const SceneState &st, const uint8_t *wanted, float h, std::vector<ReverseSlot> &slots, std::vector<uint32_t> &range) {
+    const size_t n = st.bsdfs.size();
+    slots.clear(); range.assign(n + 1, 0u);
+    if (!wanted) return MTSAMD_OK;
+    for (size_t b = 0; b < n; ++b) {
+        const DevBsdf &rec = st.bsdfs[b];
+        range[b] = (uint32_t) slots.size();
+        for (int32_t kind = MTSAMD_PARAM_REFLECTANCE; kind <= MTSAMD_PARAM_SPECULAR_TRANSMITTANCE; ++kind)
+            for (int32_t comp = 0; comp < 3; ++comp) {
+                const uint32_t out = (uint32_t) (MTSAMD_BSDF_TANGENT_FLOATS * b) + (uint32_t) (3 * kind + comp);
+                if (!wanted[out]) continue;
+                float DevBsdf::*f0, DevBsdf::*f1;
+                if (!bsdf_param_fields(rec, kind, comp, f0, f1))
+                    return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u (type %d) has no differentiable parameter of kind %d (component %d is wanted)",
+                                (unsigned) b, rec.type, kind, comp);
+                const float theta = rec.*f0, at = 1.0f;
+                float lim = h;
+                if (!(lim > 0.0f)) lim = 0.01f * std::max(std::fabs(theta), 0.05f);
+                float eps = lim / at;
+                if ((kind == MTSAMD_PARAM_ALPHA || kind == MTSAMD_PARAM_ETA) && theta - eps * at <= 1e-4f) eps = std::min(eps, (0.5f * (theta - 1e-4f)) / at);
+                if (!(eps > 0.0f))
+                    return fail(MTSAMD_ERR_INVALID, "bsdf %u: parameter value %g leaves no room for a central difference", (unsigned) b, theta);
+                const float step = eps * at;
+                ReverseSlot s{};
+                s.plus = theta + step; s.minus = theta - step;
+                const float span = s.plus - s.minus;
+                if (!(std::fabs(span) > 0.0f) || !std::isfinite(at / span))
+                    return fail(MTSAMD_ERR_INVALID, "bsdf %u: parameter value %g leaves no room for a central difference", (unsigned) b, theta);
+                s.inv_2h = at / span;
+                s.record = (uint32_t) b; s.out = out;
+                const char *base = reinterpret_cast<const char *>(&rec);
+                s.f0 = (uint16_t) ((reinterpret_cast<const char *>(&(rec.*f0)) - base) / sizeof(float));
+                s.f1 = f1 ? (uint16_t) ((reinterpret_cast<const char *>(&(rec.*f1)) - base) / sizeof(float)) : s.f0;
+                slots.push_back(s);
+            }
+    }
+    range[n] = (uint32_t) slots.size();
+    return MTSAMD_OK;
+}
+
 // parameters_changed() of a (rough)plastic whose colours were set: the weight from the means the scene holds now.  The specular mean is
 // spec_mean[] in both variants, the one textured_lobe_weight reads: every setter of specular_reflectance keeps it current.
 static void constant_lobe_weight(SceneState &st, uint32_t bsdf) {

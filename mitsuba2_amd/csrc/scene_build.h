@@ -149,6 +149,11 @@ bool bsdf_param_fields(const DevBsdf &b, int32_t kind, int32_t comp, float DevBs
 // name a field bsdf_param_fields accepts for its record; a refusal names record, type and kind through fail().
 int build_tangent_records(const SceneState &st, const float *bsdf_tangents, float h, std::vector<DevBsdf> &plus, std::vector<DevBsdf> &minus,
                           std::vector<float> &inv_2h);
+// Reverse-mode render (k_reverse): one ReverseSlot (kernels.h) per wanted scalar, wanted[MTSAMD_BSDF_TANGENT_FLOATS * b + 3 * kind + comp] != 0,
+// in record order, and range[b] .. range[b + 1] = the slots of record b (range has bsdf_count + 1 entries).  The pair of a slot and its
+// inv_2h are bit for bit what build_tangent_records gives for the tangent that is 1 on that scalar and 0 elsewhere, stored as a patch
+// of the record: the float offsets it moves and their plus / minus values.  Refusals are those of build_tangent_records, by name.
+int build_reverse_slots(const SceneState &st, const uint8_t *wanted, float h, std::vector<ReverseSlot> &slots, std::vector<uint32_t> &range);
 // these three change record `bsdf` / `emitter` only (valid indices) and the Jacobians behind jac_dirty / ejac_dirty
 int set_bsdf_reflectance(SceneState &st, uint32_t bsdf, const float *rgb);
 int set_bsdf_param(SceneState &st, uint32_t bsdf, int32_t kind, const float *value3);
