@@ -246,7 +246,10 @@ MTSAMD_API int mtsamd_scene_set_vertex_positions(mtsamd_scene *scene, uint32_t s
  * normals (the reference Throws: "Storing new normals in a Mesh that didn't have normals at construction time is not implemented
  * yet."). */
 enum {
-    MTSAMD_VERTICES_RECOMPUTE_NORMALS = 1
+    MTSAMD_VERTICES_RECOMPUTE_NORMALS = 1,
+    /* the update, then mtsamd_scene_rebuild_accel(scene, 0, stream) in the same call; combinable with the flag above.  The refusals of
+     * the update come first and write nothing; a refused rebuild leaves the scene updated and refitted. */
+    MTSAMD_VERTICES_REBUILD_ACCEL = 2
 };
 MTSAMD_API int mtsamd_scene_update_vertices(mtsamd_scene *scene, uint32_t shape, const float *positions, const float *normals, uint32_t flags,
                                             float *normals_out, void *stream);
@@ -266,9 +269,32 @@ enum {
     MTSAMD_ACCEL_TRI_NRM = 5,    /* 36 bytes per primitive; empty if no mesh has normals */
     MTSAMD_ACCEL_AREA_PMF = 6,   /* 4 bytes per primitive */
     MTSAMD_ACCEL_AREA_CDF = 7,
-    MTSAMD_ACCEL_GRID = 8        /* q_lo[3], q_step[3] as the kernels receive them: 24 bytes */
+    MTSAMD_ACCEL_GRID = 8,       /* q_lo[3], q_step[3] as the kernels receive them: 24 bytes */
+    /* the refit table of a hierarchy scene (empty for a flat one); builder nodes are the nodes of the binary tree, leaves included */
+    MTSAMD_ACCEL_KIDS = 9,       /* per builder node (left, right), or (-1, leaf reference): 8 bytes */
+    MTSAMD_ACCEL_ORDER = 10,     /* builder nodes by height above the leaves: 4 bytes each */
+    MTSAMD_ACCEL_NODE_CHILD = 11,   /* per BVH2 node the builder nodes of its two children: 8 bytes */
+    MTSAMD_ACCEL_WIDE_CHILD = 12,   /* per BVH4 node the builder nodes of its four children, -1: absent: 16 bytes */
+    MTSAMD_ACCEL_BOXES = 13,     /* per builder node its exact box lo[3], hi[3]: 24 bytes */
+    MTSAMD_ACCEL_SLOT_PRIM = 14  /* per triangle slot its primitive: 4 bytes */
 };
 MTSAMD_API int mtsamd_scene_read_accel(const mtsamd_scene *scene, int32_t which, void *host_dst, uint64_t bytes);
+/* Rebuilds the topology of the accelerator on the device from the positions the scene holds now: after large vertex moves a refitted
+ * tree keeps correctness, not quality (the reference rebuilds its acceleration structure on every parameters_changed,
+ * src/librender/scene_optix.inl:260-411).  The new tree is an LBVH: Morton order of the triangle centres, the radix tree of Karras 2012,
+ * leaves of the builder's leaf size, the BVH4 collapse of creation (the host function build_lbvh of csrc/bvh.h is its specification and
+ * the device writes the same bytes).  flags must be 0 (MTSAMD_ERR_INVALID otherwise).  A flat scene (at most 64 primitives, no tree)
+ * is left alone: MTSAMD_OK.  The hit of a ray does not depend on the tree, so queries and samples afterwards equal those before, bit for
+ * bit; every setter's state is kept, and later vertex updates refit the new topology.  Refused with the scene exactly as it was:
+ * MTSAMD_ERR_NOMEM, and MTSAMD_ERR_UNSUPPORTED for a tree too deep for the LDS traversal stack.  Waits for `stream` and returns when the
+ * scene is consistent. */
+MTSAMD_API int mtsamd_scene_rebuild_accel(mtsamd_scene *scene, uint32_t flags, void *stream);
+/* The accelerator a scene holds now.  out8: BVH2 nodes, BVH4 nodes, triangle slots, depth of the binary tree, depth of the BVH4,
+ * entries of the traversal stack per lane, builder (0: the binned-SAH build of creation, 1: the LBVH of a rebuild), rebuilds so far.
+ * sah_cost (may be NULL): the sum over the inner nodes of the binary tree of area / area(root) plus 1.5 times the sum over its leaves of
+ * count * area / area(root), from the exact boxes the scene holds (computed on the device in double, in a fixed order): the number that
+ * tells when a refitted tree has degraded enough to rebuild.  0 for a flat scene. */
+MTSAMD_API int mtsamd_scene_accel_info(const mtsamd_scene *scene, uint32_t *out8, double *sah_cost);
 
 /* ---- scene queries on SoA ray streams --------------------------------------
  * The stream layout follows the reference's device-stream precedent OptixParams

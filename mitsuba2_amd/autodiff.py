@@ -87,8 +87,11 @@ class ParameterMap:
     """Dictionary-like view of the differentiable scene parameters (util.py:16-130): torch tensors on the scene's GPU.
     Writes take effect in the scene after :meth:`update` (``parameters_changed``)."""
 
-    def __init__(self, scene, replay=False, geometry=False, normals=None, emitters=False):
+    def __init__(self, scene, replay=False, geometry=False, normals=None, emitters=False, accel="refit"):
         self._scene = scene
+        if accel not in ("refit", "rebuild"):
+            raise RuntimeError("accel: \"refit\" or \"rebuild\", not %r" % (accel,))
+        self._accel = accel                          # what update() does to the accelerator when it moves a mesh
         want_emitters = bool(emitters) and not _is_spectral(scene)      # RGB scenes: the emitter-colour keys below, in any scene
         if normals not in (None, "recompute"):
             raise RuntimeError("normals: None or \"recompute\", not %r" % (normals,))
@@ -275,7 +278,7 @@ class ParameterMap:
                     v.clamp_(min=0.0)
             seen[k] = (v, v._version)
             if kind == "vertices":
-                self._scene.update_vertices(idx, v, normals=self._normals if self._kind[k][2] else None)
+                self._scene.update_vertices(idx, v, normals=self._normals if self._kind[k][2] else None, accel=self._accel)
             elif kind in ("texture", "param_texture"):
                 self._scene.update_texture(idx, v)
             elif kind == "emitter":
@@ -289,19 +292,20 @@ class ParameterMap:
                 self._scene.set_bsdf_reflectance(idx, v.detach().cpu().tolist())
 
 
-def traverse(scene, replay=False, geometry=False, normals=None, emitters=False):
+def traverse(scene, replay=False, geometry=False, normals=None, emitters=False, accel="refit"):
     """mitsuba.python.util.traverse (util.py:132-179) for the supported parameters.  ``replay=True`` (spectral scenes; ignored for RGB
     ones) adds the bitmap texels of the reflectance family and the emitted colour of shapeless emitters, and differentiates the reflectance
     family and the emitter family (envmap texels included) with one spectral path replay each per backward pass.  ``geometry=True`` adds
     '<shape id>.vertex_positions_buf' of every mesh (the flat 3N buffer of mesh.cpp:781-804); update() pushes it through
     Scene.update_vertices; ``normals="recompute"`` makes it pass that on for every mesh with vertex normals, so that a moved mesh's
-    normals are recomputed on the device and no vertex data visits the host.  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
+    normals are recomputed on the device and no vertex data visits the host; ``accel="rebuild"`` makes every such update rebuild the
+    accelerator's topology instead of only refitting it (Scene.update_vertices).  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
     which is why they have to be asked for: render() raises on one that requires a gradient.  ``emitters=True`` (RGB scenes; ignored for
     spectral ones) adds the emitter colours in any scene: '<shape id>.emitter.radiance.value' of area lights and
     '<emitter id>.radiance|intensity|irradiance.value' of `constant`, `point`, `spot` and `directional` emitters.  They are settable and
     serve as tangents of render_forward; outside diffuse area-lit scenes render() raises on one that requires a gradient unless it is
     called with backward="fused"."""
-    return ParameterMap(scene, replay=replay, geometry=geometry, normals=normals, emitters=emitters)
+    return ParameterMap(scene, replay=replay, geometry=geometry, normals=normals, emitters=emitters, accel=accel)
 
 
 def _replayed(pmap, key):

@@ -15,6 +15,8 @@
 #include "kernels.h"
 #include "scene_build.h"
 #include "refit.h"
+#include "lbvh.h"
+#include "lbvh_keys.h"
 #include "schedule.h"
 #include "spectral_upsampling.h"
 #include "cie_data.h"
@@ -414,6 +416,15 @@ struct mtsamd_scene : SceneState {
     float *d_face_recs = nullptr;
     int32_t refit_root = 0;
     size_t n_tri_nrm = 0;                   // floats in d_tri_nrm
+    // accelerator rebuilds (mtsamd_scene_rebuild_accel), hierarchy scenes: the scratch of the device build and a second set of every
+    // array a build writes, sized for the worst case, both allocated at the first rebuild and kept.  A build goes into `spare`; accepted,
+    // it becomes the live set and the former live set the spare (the set of creation, sized for its own tree, is freed instead).
+    LbvhScratch *lbvh_scratch = nullptr;
+    LbvhTarget spare{};
+    bool accel_worst_case = false;          // the live set is sized for the worst case
+    uint32_t n_builder = 0, builder = 0, rebuilds = 0;      // builder nodes; 0 = binned SAH (creation), 1 = LBVH; rebuilds so far
+    size_t walk_spill_entries = 0;          // entries in d_walk_spill
+    double *d_sah_partial = nullptr; size_t sah_partial_cap = 0;      // mtsamd_scene_accel_info: per-block sums of the SAH cost
     uint32_t n_pairs = 0, n_clusters = 0;
     BuildOptions options;
     SceneView view{};
@@ -510,7 +521,7 @@ int upload_refit_table(mtsamd_scene *s, HostScene &hs) {
     HIP_TRY(hipMalloc((void **) &s->d_stage_nrm, sizeof(float) * 3 * (size_t) std::max(max_vertices, 1u)));
     HIP_TRY(hipMalloc((void **) &s->d_stage_area, sizeof(float) * (size_t) std::max(max_faces, 1u)));
     HIP_TRY(hipMalloc((void **) &s->d_refit_flag, sizeof(uint32_t)));
-    s->class_start = rt.class_start; s->refit_root = rt.root;
+    s->class_start = rt.class_start; s->refit_root = rt.root; s->n_builder = (uint32_t) kids.size();
     // the device owns these now; the counts (n_nodes, n_wnodes, n_slots), roots, bbox and grid stay
     bvh.nodes = {}; bvh.qnodes = {}; bvh.wnodes = {}; bvh.wnodes_h = {}; bvh.wnodes_p = {}; bvh.tris = {};
     rt = RefitTable{};
@@ -572,6 +583,7 @@ int fill_scene_view(mtsamd_scene *s, const HostScene &hs) {
     if (!hs.flat && v.stack_depth > v.walk_lds_depth) {
         const size_t entries = (size_t) v.walk_blocks * (v.stack_depth - v.walk_lds_depth) * 256u;
         if (ws_alloc((void **) &s->d_walk_spill, entries * sizeof(StackEntry))) return fail(MTSAMD_ERR_NOMEM, "traversal spill area");
+        s->walk_spill_entries = entries;
     }
     v.walk_spill = s->d_walk_spill;
     v.tri_pos = s->d_tri_pos; v.tri_nrm = hs.tri_nrm.empty() ? nullptr : s->d_tri_nrm; v.tri_uv = hs.tri_uv.empty() ? nullptr : s->d_tri_uv;
@@ -586,7 +598,8 @@ int fill_scene_view(mtsamd_scene *s, const HostScene &hs) {
     v.flat_pairs = s->d_pairs; v.n_pairs = hs.n_pairs; v.n_clusters = hs.n_clusters;
     v.n_spectra = hs.n_spectra;
     // hierarchy scenes only: a flat scene is within kFlatLdsCap in every launch, or build_host_scene would not have kept it flat
-    if (bounce_lds_bytes(v) > kFlatLdsCap) return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", v.stack_depth);
+    static_assert(kStackLdsCap == kFlatLdsCap, "bvh.h restates the LDS cap of kernels.h");
+    if (bounce_lds_bytes(v) > kFlatLdsCap || (!hs.flat && !bvh_stack_fits(v.stack_depth, sizeof(StackEntry)))) return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", v.stack_depth);
     return MTSAMD_OK;
 }
 
@@ -607,6 +620,12 @@ int mtsamd_device_count(void) {
     return n;
 }
 
+static void free_target(LbvhTarget &t) {
+    (void) hipFree(t.prim_slot); (void) hipFree(t.slot_prim); (void) hipFree(t.order); (void) hipFree(t.kids); (void) hipFree(t.node_child); (void) hipFree(t.wide_child);
+    (void) hipFree(t.boxes); (void) hipFree(t.tris); (void) hipFree(t.nodes); (void) hipFree(t.qnodes); (void) hipFree(t.wnodes);
+    t = LbvhTarget{};
+}
+
 void mtsamd_scene_destroy(mtsamd_scene *s) {
     if (!s) return;
     (void) hipSetDevice(s->device);
@@ -621,6 +640,9 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
     for (uint32_t *p : s->d_corner_offsets) (void) hipFree(p);
     for (uint32_t *p : s->d_corners) (void) hipFree(p);
     (void) hipFree(s->d_face_recs);
+    lbvh_scratch_destroy(s->lbvh_scratch);
+    free_target(s->spare);
+    (void) hipFree(s->d_sah_partial);
     (void) hipFree(s->d_textures); (void) hipFree(s->d_jac); (void) hipFree(s->d_cgrad); (void) hipFree(s->d_ejac); (void) hipFree(s->d_egrad);
     delete s;
 }
@@ -809,7 +831,7 @@ static int corner_table(mtsamd_scene *s, uint32_t shape, hipStream_t stream) {
 
 static int vertex_update(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, uint32_t flags, float *normals_out, void *stream_) {
     if (!s) return fail(MTSAMD_ERR_INVALID, "null scene");
-    if (int rc = check_vertex_flags(*s, shape, normals, flags)) return rc;
+    if (int rc = check_vertex_flags(*s, shape, normals, flags)) return rc;       // MTSAMD_VERTICES_REBUILD_ACCEL: the caller's, after the update
     const bool recompute = (flags & MTSAMD_VERTICES_RECOMPUTE_NORMALS) != 0u;
     // with the flag the mesh has normals (check_vertex_flags) and the call computes them: what is left to check is the shape and the positions
     if (int rc = check_vertex_update(*s, shape, positions, recompute ? positions : normals)) return rc;
@@ -874,9 +896,110 @@ int mtsamd_scene_set_vertex_positions(mtsamd_scene *s, uint32_t shape, const flo
     return vertex_update(s, shape, positions, normals, 0u, nullptr, stream);
 }
 
+// ---- accelerator rebuild ---------------------------------------------------------------------------------------------------------------
+static LbvhTarget live_target(const mtsamd_scene *s) {
+    LbvhTarget t{};
+    t.prim_slot = s->d_prim_slot; t.slot_prim = s->d_slot_prim; t.order = s->d_order; t.kids = s->d_kids; t.node_child = s->d_node_child;
+    t.wide_child = s->d_wide_child; t.boxes = s->d_boxes; t.tris = s->d_tris; t.nodes = s->d_nodes; t.qnodes = s->d_qnodes; t.wnodes = s->d_wnodes;
+    return t;
+}
+
+static int alloc_target(uint32_t n, LbvhTarget &t) {       // the worst case of n primitives (lbvh.h)
+    const size_t nb = 2 * (size_t) n - 1, ni = std::max<size_t>(n - 1, 1);
+    t = LbvhTarget{};
+    auto get = [](auto **p, size_t count) { return hipMalloc((void **) p, sizeof(**p) * count); };
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    ok(get(&t.prim_slot, n)); ok(get(&t.slot_prim, n)); ok(get(&t.order, nb)); ok(get(&t.kids, nb)); ok(get(&t.node_child, 2 * ni)); ok(get(&t.wide_child, 4 * ni));
+    ok(get(&t.boxes, 6 * nb)); ok(get(&t.tris, 3 * (size_t) n)); ok(get(&t.nodes, 4 * ni)); ok(get(&t.qnodes, 2 * ni)); ok(get(&t.wnodes, 4 * ni));
+    if (e == hipSuccess) return MTSAMD_OK;
+    (void) hipGetLastError();
+    free_target(t);
+    return fail(MTSAMD_ERR_NOMEM, "accelerator rebuild: out of device memory (%u primitives)", n);
+}
+
+// The device build (lbvh.h) from the positions the scene holds, into the spare set; then look before writing: the tree must fit the
+// traversal stack and the spill area must be there before a single pointer of the scene changes.
+static int rebuild_accel(mtsamd_scene *s, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->geometry.flat || s->n_prims == 0) return MTSAMD_OK;
+    const uint32_t n = s->n_prims;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (!s->lbvh_scratch) {
+        const hipError_t e = lbvh_scratch_create(n, &s->lbvh_scratch);
+        if (e == hipErrorOutOfMemory) { (void) hipGetLastError(); return fail(MTSAMD_ERR_NOMEM, "accelerator rebuild: out of device memory (%u primitives)", n); }
+        HIP_TRY(e);
+    }
+    if (!s->spare.kids)
+        if (int rc = alloc_target(n, s->spare)) return rc;
+    RefitGrid grid{};
+    float q_lo[3], q_step[3];
+    scene_grid(s->bvh.bbox, &grid.extent, q_lo, q_step);          // the box is unchanged by a rebuild, and so is the grid
+    for (int k = 0; k < 3; ++k) { grid.glo[k] = (double) q_lo[k]; grid.gstep[k] = (double) q_step[k]; }
+    LbvhResult r;
+    HIP_TRY(lbvh_build(s->lbvh_scratch, s->d_tri_pos, n, s->options.max_leaf, s->bvh.bbox, grid, s->spare, r, stream));
+    SceneView &v = s->view;
+    const uint32_t stack_depth = bvh_stack_depth(r.depth, r.wdepth, MTS_BVH4 != 0);
+    if (!bvh_stack_fits(stack_depth, sizeof(StackEntry))) return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", stack_depth);
+    const uint32_t walk_lds_depth = std::min<uint32_t>(stack_depth, MTS_BVH4 ? 8u : 16u);
+    const size_t entries = stack_depth > walk_lds_depth ? (size_t) v.walk_blocks * (stack_depth - walk_lds_depth) * 256u : 0u;
+    StackEntry *spill = nullptr;
+    if (entries > s->walk_spill_entries)
+        if (ws_alloc((void **) &spill, entries * sizeof(StackEntry))) return fail(MTSAMD_ERR_NOMEM, "traversal spill area");
+    // accepted: swap
+    LbvhTarget old = live_target(s);
+    const LbvhTarget &t = s->spare;
+    s->d_prim_slot = t.prim_slot; s->d_slot_prim = t.slot_prim; s->d_order = t.order; s->d_kids = t.kids; s->d_node_child = t.node_child;
+    s->d_wide_child = t.wide_child; s->d_boxes = t.boxes; s->d_tris = t.tris; s->d_nodes = t.nodes; s->d_qnodes = t.qnodes; s->d_wnodes = t.wnodes;
+    if (s->accel_worst_case) s->spare = old;
+    else { free_target(old); s->spare = LbvhTarget{}; s->accel_worst_case = true; }
+    if (spill) { (void) hipFree(s->d_walk_spill); s->d_walk_spill = spill; s->walk_spill_entries = entries; }
+    BvhOutput &b = s->bvh;
+    b.n_nodes = r.n_nodes; b.n_wnodes = r.n_wide; b.n_slots = r.n_slots; b.depth = r.depth; b.wdepth = r.wdepth; b.root = r.root; b.wroot = r.wroot;
+    s->class_start = r.class_start; s->refit_root = 0; s->n_builder = r.n_builder;
+    v.nodes = s->d_nodes; v.qnodes = s->d_qnodes; v.wnodes = s->d_wnodes; v.tris = s->d_tris; v.root = b.root; v.wroot = b.wroot;
+    v.n_nodes = b.n_nodes; v.n_wnodes = b.n_wnodes; v.n_slots = b.n_slots;
+    v.stack_depth = stack_depth; v.walk_lds_depth = walk_lds_depth; v.walk_spill = s->d_walk_spill;
+    s->builder = 1u; ++s->rebuilds;
+    return MTSAMD_OK;
+}
+
 int mtsamd_scene_update_vertices(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, uint32_t flags, float *normals_out,
                                  void *stream) {
-    return vertex_update(s, shape, positions, normals, flags, normals_out, stream);
+    if (int rc = vertex_update(s, shape, positions, normals, flags, normals_out, stream)) return rc;
+    if (flags & MTSAMD_VERTICES_REBUILD_ACCEL) return rebuild_accel(s, (hipStream_t) stream);
+    return MTSAMD_OK;
+}
+
+int mtsamd_scene_rebuild_accel(mtsamd_scene *s, uint32_t flags, void *stream) {
+    if (!s) return fail(MTSAMD_ERR_INVALID, "null scene");
+    if (flags) return fail(MTSAMD_ERR_INVALID, "unknown accelerator rebuild flags 0x%x", flags);
+    return rebuild_accel(s, (hipStream_t) stream);
+}
+
+int mtsamd_scene_accel_info(const mtsamd_scene *s_, uint32_t *out8, double *sah_cost) {
+    if (!s_ || !out8) return fail(MTSAMD_ERR_INVALID, "null argument");
+    mtsamd_scene *s = const_cast<mtsamd_scene *>(s_);          // the scratch of the sum is the scene's
+    out8[0] = s->bvh.n_nodes; out8[1] = s->bvh.n_wnodes; out8[2] = s->bvh.n_slots; out8[3] = s->bvh.depth; out8[4] = s->bvh.wdepth;
+    out8[5] = s->view.stack_depth; out8[6] = s->builder; out8[7] = s->rebuilds;
+    if (!sah_cost) return MTSAMD_OK;
+    *sah_cost = 0.0;
+    if (s->geometry.flat || s->n_prims == 0 || s->n_builder == 0) return MTSAMD_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t blocks = ((size_t) s->n_builder + kSahBlock - 1) / kSahBlock;
+    if (blocks > s->sah_partial_cap) {
+        (void) hipFree(s->d_sah_partial); s->d_sah_partial = nullptr; s->sah_partial_cap = 0;
+        HIP_TRY(hipMalloc((void **) &s->d_sah_partial, blocks * sizeof(double)));
+        s->sah_partial_cap = blocks;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(launch_sah_partials(s->d_kids, s->d_boxes, s->n_builder, s->refit_root, s->d_sah_partial, nullptr));
+    std::vector<double> partial(blocks);
+    HIP_TRY(hipMemcpy(partial.data(), s->d_sah_partial, blocks * sizeof(double), hipMemcpyDeviceToHost));
+    double total = 0.0;
+    for (double p : partial) total += p;
+    *sah_cost = total;
+    return MTSAMD_OK;
 }
 
 int mtsamd_compute_vertex_normals(uint32_t vertex_count, const float *positions, uint32_t face_count, const uint32_t *faces, float *normals_out) {
@@ -901,6 +1024,12 @@ int mtsamd_scene_read_accel(const mtsamd_scene *s, int32_t which, void *host_dst
     case MTSAMD_ACCEL_AREA_PMF: src = s->d_area_pmf; size = 4ull * s->n_prims; break;
     case MTSAMD_ACCEL_AREA_CDF: src = s->d_area_cdf; size = 4ull * s->n_prims; break;
     case MTSAMD_ACCEL_GRID: size = 24; break;
+    case MTSAMD_ACCEL_KIDS: src = s->d_kids; size = 8ull * s->n_builder; break;
+    case MTSAMD_ACCEL_ORDER: src = s->d_order; size = 4ull * s->n_builder; break;
+    case MTSAMD_ACCEL_NODE_CHILD: src = s->d_node_child; size = 8ull * s->bvh.n_nodes; break;
+    case MTSAMD_ACCEL_WIDE_CHILD: src = s->d_wide_child; size = 16ull * s->bvh.n_wnodes; break;
+    case MTSAMD_ACCEL_BOXES: src = s->d_boxes; size = 24ull * s->n_builder; break;
+    case MTSAMD_ACCEL_SLOT_PRIM: src = s->d_slot_prim; size = 4ull * (s->n_builder ? s->bvh.n_slots : 0u); break;
     default: return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_read_accel: unknown array %d", which);
     }
     if (bytes != size) return fail(MTSAMD_ERR_INVALID, "mtsamd_scene_read_accel: array %d holds %llu bytes, not %llu", which, (unsigned long long) size, (unsigned long long) bytes);

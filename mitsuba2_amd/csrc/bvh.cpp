@@ -1,6 +1,7 @@
 // bvh.cpp -- binned-SAH BVH2 builder (host).  See bvh.h.
 #include "bvh.h"
 #include "refit_encode.h"
+#include "lbvh_keys.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -440,6 +441,148 @@ void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOut
     out.n_nodes = (uint32_t) bfs.size();
     out.n_slots = slot;
     out.depth = b.max_depth + 1;
+}
+
+// ---- build_lbvh: the specification of the device build (bvh.h).  Every step is a loop over independent elements, or a scan; the
+// element functions are lbvh_keys.h's, which csrc/lbvh.hip calls too.
+namespace { struct Kid { int32_t x, y; }; }
+
+void build_lbvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out) {
+    max_leaf = std::min<uint32_t>(std::max<uint32_t>(max_leaf, 1), 15);
+    const int n = (int) n_prims;
+    RefitTable &rt = out.refit;
+    rt = RefitTable{};
+    // keys: the scene box is the exact union of all vertices; then one code per primitive and the stable order
+    float bbox[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+    for (size_t p = 0; p < n_prims; ++p) {
+        float lo[3], hi[3];
+        lbvh_prim_box(tri_pos + 9 * p, lo, hi);
+        for (int k = 0; k < 3; ++k) { bbox[k] = enc_min(bbox[k], lo[k]); bbox[3 + k] = enc_max(bbox[3 + k], hi[k]); }
+    }
+    std::vector<uint64_t> keys(n_prims);
+    for (size_t p = 0; p < n_prims; ++p) keys[p] = ((uint64_t) lbvh_code(tri_pos + 9 * p, bbox) << 32) | p;
+    std::sort(keys.begin(), keys.end());
+    std::vector<uint32_t> codes(n_prims);
+    rt.slot_prim.resize(n_prims);
+    for (size_t s = 0; s < n_prims; ++s) { codes[s] = (uint32_t) (keys[s] >> 32); rt.slot_prim[s] = (uint32_t) keys[s]; }
+    // radix tree: ids [0, n - 1) are the inner nodes, n - 1 + s the leaf at position s.  Each inner node states what its children are:
+    // 0 = below a leaf (dropped), 1 = leaf, 2 = inner
+    const size_t n_radix = 2 * (size_t) n_prims - 1;
+    std::vector<uint32_t> state(n_radix, 0u), first(n_radix, 0u), count(n_radix, 0u);
+    std::vector<int32_t> rl(n_prims - 1), rr(n_prims - 1);
+    state[0] = n_prims > max_leaf ? 2u : 1u; first[0] = 0u; count[0] = n_prims;
+    for (int i = 0; i + 1 < n; ++i) {
+        int f, l, split;
+        lbvh_radix_node(codes.data(), n, i, &f, &l, &split);
+        const int32_t c[2] = { split == f ? n - 1 + split : split, split + 1 == l ? n - 1 + split + 1 : split + 1 };
+        const uint32_t cf[2] = { (uint32_t) f, (uint32_t) split + 1u }, cc[2] = { (uint32_t) (split - f + 1), (uint32_t) (l - split) };
+        rl[i] = c[0]; rr[i] = c[1];
+        const bool open = (uint32_t) (l - f + 1) > max_leaf;
+        for (int k = 0; k < 2; ++k) { state[c[k]] = !open ? 0u : (cc[k] > max_leaf ? 2u : 1u); first[c[k]] = cf[k]; count[c[k]] = cc[k]; }
+    }
+    // compaction: builder ids and BVH2 ids are exclusive scans of the survivors
+    std::vector<int32_t> bid(n_radix, -1), iid(n_radix, -1);
+    size_t n_tmp = 0, n_inner = 0;
+    for (size_t x = 0; x < n_radix; ++x) {
+        if (state[x]) bid[x] = (int32_t) n_tmp++;
+        if (state[x] == 2u) iid[x] = (int32_t) n_inner++;
+    }
+    rt.root = 0;
+    rt.left.assign(n_tmp, -1); rt.right.assign(n_tmp, -1); rt.ref2.assign(n_tmp, 0u); rt.ref4.assign(n_tmp, 0xffffffffu);
+    rt.boxes.assign(6 * n_tmp, 0.0f); rt.node_child.resize(2 * n_inner);
+    for (size_t x = 0; x < n_radix; ++x) {
+        if (!state[x]) continue;
+        const int32_t t = bid[x];
+        if (state[x] == 2u) {
+            rt.left[t] = bid[rl[x]]; rt.right[t] = bid[rr[x]];
+            rt.ref2[t] = (uint32_t) iid[x];
+            rt.node_child[2 * (size_t) iid[x]] = rt.left[t]; rt.node_child[2 * (size_t) iid[x] + 1] = rt.right[t];
+        } else {
+            rt.ref2[t] = rt.ref4[t] = kLeafFlag | (count[x] << kLeafCountShift) | first[x];
+        }
+    }
+    // heights: a node's is known once both children's are; rounds of that rule, as many as the tree is high
+    rt.height.assign(n_tmp, kLbvhNoHeight);
+    for (size_t t = 0; t < n_tmp; ++t) if (rt.left[t] < 0) rt.height[t] = 0u;
+    for (bool again = true; again;) {
+        again = false;
+        std::vector<uint32_t> next(rt.height);
+        for (size_t t = 0; t < n_tmp; ++t) {
+            if (rt.height[t] != kLbvhNoHeight) continue;
+            const uint32_t a = rt.height[rt.left[t]], b = rt.height[rt.right[t]];
+            if (a != kLbvhNoHeight && b != kLbvhNoHeight) next[t] = 1u + std::max(a, b); else again = true;
+        }
+        rt.height.swap(next);
+    }
+    const uint32_t top = rt.height[0];
+    rt.class_start.assign(top + 2, 0u);
+    for (size_t t = 0; t < n_tmp; ++t) rt.class_start[rt.height[t] + 1]++;
+    for (uint32_t h = 0; h <= top; ++h) rt.class_start[h + 1] += rt.class_start[h];
+    rt.order.resize(n_tmp);
+    { std::vector<uint32_t> at(rt.class_start.begin(), rt.class_start.end() - 1);
+      for (size_t t = 0; t < n_tmp; ++t) rt.order[at[rt.height[t]]++] = (uint32_t) t; }
+    // exact boxes, as a refit computes them
+    std::vector<Kid> kids(n_tmp);
+    for (size_t t = 0; t < n_tmp; ++t) kids[t] = rt.left[t] >= 0 ? Kid{ rt.left[t], rt.right[t] } : Kid{ -1, (int32_t) rt.ref2[t] };
+    for (size_t i = 0; i < n_tmp; ++i) {
+        const uint32_t t = rt.order[i];
+        float *bx = &rt.boxes[6 * (size_t) t];
+        if (kids[t].x < 0) {
+            const uint32_t ref = rt.ref2[t], s0 = ref & ((1u << kLeafCountShift) - 1u), cnt = (ref >> kLeafCountShift) & 15u;
+            for (int k = 0; k < 3; ++k) { bx[k] = INFINITY; bx[3 + k] = -INFINITY; }
+            for (uint32_t s = s0; s < s0 + cnt; ++s) {
+                const float *tp = tri_pos + 9 * (size_t) rt.slot_prim[s];
+                for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) { bx[k] = enc_min(bx[k], tp[3 * j + k]); bx[3 + k] = enc_max(bx[3 + k], tp[3 * j + k]); }
+            }
+        } else {
+            const float *l = &rt.boxes[6 * (size_t) kids[t].x], *r = &rt.boxes[6 * (size_t) kids[t].y];
+            for (int k = 0; k < 3; ++k) { bx[k] = enc_min(l[k], r[k]); bx[3 + k] = enc_max(l[3 + k], r[3 + k]); }
+        }
+    }
+    // BVH4: one wide level after the other; the inner children of a level, by parent and child position, are the next
+    out.root = out.wroot = n_inner ? 0u : rt.ref2[0];
+    out.n_wnodes = 0; out.wdepth = 1;
+    if (n_inner) {
+        std::vector<int32_t> level(1, 0), wide_child;
+        uint32_t levels = 0;
+        while (!level.empty()) {
+            ++levels;
+            const size_t start = wide_child.size() / 4, next_start = start + level.size();
+            std::vector<int32_t> next;
+            for (size_t j = 0; j < level.size(); ++j) {
+                int32_t c[4];
+                lbvh_collapse(kids.data(), rt.boxes.data(), level[j], c);
+                for (int k = 0; k < 4; ++k) {
+                    wide_child.push_back(c[k]);
+                    if (c[k] >= 0 && kids[c[k]].x >= 0) { rt.ref4[c[k]] = (uint32_t) (next_start + next.size()); next.push_back(c[k]); }
+                }
+            }
+            level.swap(next);
+        }
+        rt.ref4[0] = 0u;
+        rt.wide_child = wide_child;
+        out.n_wnodes = (uint32_t) (wide_child.size() / 4); out.wdepth = levels;
+    }
+    emit_bvh(tri_pos, out);
+    out.n_nodes = (uint32_t) n_inner;
+    out.n_slots = n_prims;
+    out.depth = top + 1;
+}
+
+double sah_cost_blocked(const int32_t *kids, const float *boxes, size_t n_builder, int32_t root) {
+    const double root_area = lbvh_area(boxes + 6 * (size_t) root);
+    double total = 0.0;
+    for (size_t base = 0; base < n_builder; base += kSahBlock) {
+        double v[kSahBlock];
+        for (size_t j = 0; j < kSahBlock; ++j) {
+            const size_t t = base + j;
+            v[j] = t < n_builder ? lbvh_sah_term(Kid{ kids[2 * t], kids[2 * t + 1] }, boxes + 6 * t, root_area) : 0.0;
+        }
+        for (uint32_t stride = kSahBlock / 2; stride > 0; stride /= 2)
+            for (uint32_t j = 0; j < stride; ++j) v[j] += v[j + stride];
+        total += v[0];
+    }
+    return total;
 }
 
 } // namespace mtsamd

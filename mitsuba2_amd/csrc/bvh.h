@@ -6,6 +6,7 @@
 // lane fetches with four 16-byte loads (LDS or L2), leaves of at most 4 triangles stored as
 // 48-byte pre-subtracted (p0, e1, e2) records in leaf order.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -65,4 +66,25 @@ namespace mtsamd {
 void refit_bvh(const float *tri_pos, BvhOutput &out);
 // What the emission derives from the scene box (6 floats: lo, hi): `extent` of the box padding and the quantisation grid
 void scene_grid(const float bbox[6], double *extent, float q_lo[3], float q_step[3]);
+
+// The topology a device can build (csrc/lbvh.hip does, and is held to these bytes): primitives in the order of (30-bit Morton code of
+// the centre of their exact box over the scene box, primitive index); the binary radix tree of Karras 2012 over those keys, equal codes
+// split on the bits of the sorted position; a radix-tree node that covers at most max_leaf primitives while its parent covers more is
+// a leaf (a root that covers at most max_leaf: the whole scene is one leaf); the BVH4 collapse of build_bvh per wide level.  Numbering:
+// triangle slots in sorted order; builder nodes = surviving radix-tree nodes in radix index order (inner nodes, then positions), BVH2
+// nodes = surviving inner nodes in the same order; wide nodes level by level, within a level by parent and child position.  Fills
+// everything build_bvh fills and ends in the same emission; refit_bvh refits it.  The binary depth is at most 31 + ceil(log2 n).
+void build_lbvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out);
+
+// The traversal stack of a hierarchy scene: entries per lane for a tree of these depths, and whether the stack of a 256-lane workgroup
+// fits the LDS a launch may ask for (kernels.h: bounce_lds_bytes(v) <= kFlatLdsCap; api.cpp asserts that the constants agree).  An entry
+// of the BVH4 walk has 8 bytes, one of the BVH2 walk 4.
+constexpr uint32_t kStackEntryBytes = 8u, kStackBlock = 256u, kStackLdsCap = 150u * 1024u;
+inline uint32_t bvh_stack_depth(uint32_t depth, uint32_t wdepth, bool bvh4) { return bvh4 ? 3u * wdepth + 2u : (depth > 2u ? depth : 2u); }
+inline bool bvh_stack_fits(uint32_t stack_depth, uint32_t entry_bytes = kStackEntryBytes) { return (uint64_t) entry_bytes * stack_depth * kStackBlock <= kStackLdsCap; }
+
+// SAH cost of the tree a refit table describes, from its exact boxes: the sum over inner builder nodes of area / area(root) plus 1.5 times
+// the sum over leaves of count * area / area(root), in double, in the blocked order lbvh_keys.h fixes (the device's).  kids: 2 per
+// builder node, (left, right) or (-1, leaf reference); boxes: 6 per builder node.
+double sah_cost_blocked(const int32_t *kids, const float *boxes, size_t n_builder, int32_t root);
 } // namespace mtsamd

@@ -1102,7 +1102,9 @@ int check_vertex_update(const SceneState &st, uint32_t shape, const float *posit
 
 int check_vertex_flags(const SceneState &st, uint32_t shape, const float *normals, uint32_t flags) {
     const SceneGeometry &g = st.geometry;
-    if (flags & ~(uint32_t) MTSAMD_VERTICES_RECOMPUTE_NORMALS) return fail(MTSAMD_ERR_INVALID, "unknown vertex update flags 0x%x", flags & ~(uint32_t) MTSAMD_VERTICES_RECOMPUTE_NORMALS);
+    // the text of this refusal is what it was before MTSAMD_VERTICES_REBUILD_ACCEL existed: every bit beside the recompute flag
+    const uint32_t known = MTSAMD_VERTICES_RECOMPUTE_NORMALS | MTSAMD_VERTICES_REBUILD_ACCEL;
+    if (flags & ~known) return fail(MTSAMD_ERR_INVALID, "unknown vertex update flags 0x%x", flags & ~(uint32_t) MTSAMD_VERTICES_RECOMPUTE_NORMALS);
     if (!(flags & MTSAMD_VERTICES_RECOMPUTE_NORMALS)) return MTSAMD_OK;
     if (shape >= g.shapes.size()) return fail(MTSAMD_ERR_INVALID, "invalid shape index %u (the scene has %u shapes)", shape, (uint32_t) g.shapes.size());
     if (normals) return fail(MTSAMD_ERR_INVALID, "shape %u: MTSAMD_VERTICES_RECOMPUTE_NORMALS computes the normals: none can be passed with it", shape);

@@ -843,7 +843,7 @@ class Scene:
         self._pending_vertices.clear()
         self._description = value
 
-    def _recompute_vertices(self, shape, positions):
+    def _recompute_vertices(self, shape, positions, rebuild=False):
         """update_vertices(normals="recompute"): mtsamd_scene_update_vertices with MTSAMD_VERTICES_RECOMPUTE_NORMALS"""
         mesh = self._description["meshes"][shape]           # counts and the presence of normals never change: no need to flush for them
         n_vertices = _f32(mesh["positions"]).reshape(-1, 3).shape[0]
@@ -858,11 +858,30 @@ class Scene:
             raise RuntimeError("shape %d was created without vertex normals: storing new normals in such a mesh is not implemented" % shape)
         pos = pos.clone()                                    # the caller may overwrite theirs; the scene reads and keeps this one
         nrm = torch.empty(3 * n_vertices, dtype=torch.float32, device=dev)
-        L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, _ptr(pos), None, 1, _ptr(nrm), _stream()))
+        L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, _ptr(pos), None, 1 | (2 if rebuild else 0), _ptr(nrm), _stream()))
         self._pending_vertices[shape] = (pos, nrm.clone())
         return nrm.reshape(-1, 3)
 
-    def update_vertices(self, shape, positions, normals=None):
+    def rebuild_accel(self):
+        """mtsamd_scene_rebuild_accel: a new topology of the accelerator (an LBVH built on the device) from the positions the scene
+        holds now -- what a tree refitted through large vertex moves needs once accel_info(sah_cost=True) says it has degraded.  Samples
+        and queries are the same bits before and after; every setter's state is kept; a flat scene is left alone."""
+        L.check(L.lib().mtsamd_scene_rebuild_accel(self._handle, 0, _stream()))
+
+    def accel_info(self, sah_cost=False):
+        """mtsamd_scene_accel_info: counts and depths of the accelerator, its builder ("sah": creation, "lbvh": a rebuild), the number of
+        rebuilds, and with sah_cost=True the SAH cost of the tree as it is now (0.0 for a flat scene)."""
+        out = (C.c_uint32 * 8)()
+        cost = C.c_double(0.0)
+        L.check(L.lib().mtsamd_scene_accel_info(self._handle, out, C.byref(cost) if sah_cost else None))
+        info = dict(zip(("bvh_nodes", "wide_nodes", "slots", "depth", "wdepth", "stack_depth"), [int(x) for x in out[:6]]))
+        info["builder"] = ("sah", "lbvh")[int(out[6])]
+        info["rebuilds"] = int(out[7])
+        if sah_cost:
+            info["sah_cost"] = float(cost.value)
+        return info
+
+    def update_vertices(self, shape, positions, normals=None, accel="refit"):
         """parameters_changed({"vertex_positions_buf"}) of mesh `shape` (mesh.cpp:781-804): new vertex positions, same vertex count and
         faces.  positions: (N, 3) or flat 3N, a numpy array or a torch tensor on the host or the device (a device tensor is read where it
         is).  A mesh with vertex normals gets `normals`, or -- None -- normals recomputed from the new positions with
@@ -870,14 +889,18 @@ class Scene:
         for it.  normals="recompute" recomputes them in the library instead (mtsamd_compute_vertex_normals' fp32 arithmetic, on the device
         for hierarchy scenes): with a device tensor no vertex data is copied to the host, the description is brought up to date when it is
         next read, and the call returns the (N, 3) normals as a device tensor.
-        The accelerator is refitted, not rebuilt; bbox(), the emitter tables and the scene description follow."""
+        The accelerator is refitted (accel="refit") or, after the update, rebuilt in the same call (accel="rebuild": rebuild_accel);
+        bbox(), the emitter tables and the scene description follow."""
         shape = int(shape)
+        if accel not in ("refit", "rebuild"):
+            raise RuntimeError("accel: \"refit\" or \"rebuild\", not %r" % (accel,))
+        rebuild = accel == "rebuild"
         if not 0 <= shape < self._shape_count:
             raise RuntimeError("invalid shape index %d (the scene has %d shapes)" % (shape, self._shape_count))
         if isinstance(normals, str):
             if normals != "recompute":
                 raise RuntimeError("normals: an array, None or \"recompute\", not %r" % normals)
-            return self._recompute_vertices(shape, positions)
+            return self._recompute_vertices(shape, positions, rebuild)
         mesh = self._dict["meshes"][shape]
         n_vertices = _f32(mesh["positions"]).reshape(-1, 3).shape[0]
         dev = torch.device("cuda", self._device_index)
@@ -908,7 +931,10 @@ class Scene:
             n_arg, n_keep, n_host = as_arg(normals, "normals")
         elif normals is not None:
             raise RuntimeError("shape %d was created without vertex normals: none can be set" % shape)
-        L.check(L.lib().mtsamd_scene_set_vertex_positions(self._handle, shape, p_arg, n_arg, _stream()))
+        if rebuild:
+            L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, p_arg, n_arg, 2, None, _stream()))
+        else:
+            L.check(L.lib().mtsamd_scene_set_vertex_positions(self._handle, shape, p_arg, n_arg, _stream()))
         # the scene description follows the device, as for the other setters
         if p_host is None:
             p_host = p_keep.cpu().numpy()
@@ -920,14 +946,20 @@ class Scene:
 
     def read_accel(self, which, words=None):
         """Test aid (mtsamd_scene_read_accel): one device array of the accelerator as a flat numpy array of 32-bit words.  which:
-        "nodes", "qnodes", "wnodes", "tris", "tri_pos", "tri_nrm", "area_pmf", "area_cdf" or "grid".  `words`: the array's length where
-        info() does not give it (the wide nodes); a wrong length is an error."""
-        names = ("nodes", "qnodes", "wnodes", "tris", "tri_pos", "tri_nrm", "area_pmf", "area_cdf", "grid")
+        "nodes", "qnodes", "wnodes", "tris", "tri_pos", "tri_nrm", "area_pmf", "area_cdf", "grid", or an array of the refit table of a
+        hierarchy scene: "kids", "order", "node_child", "wide_child", "boxes", "slot_prim".  `words`: the array's length where info() and
+        accel_info() do not give it; a wrong length is an error."""
+        names = ("nodes", "qnodes", "wnodes", "tris", "tri_pos", "tri_nrm", "area_pmf", "area_cdf", "grid",
+                 "kids", "order", "node_child", "wide_child", "boxes", "slot_prim")
         info = self.info()
         n_prims, n_nodes = info["primitives"], info["bvh_nodes"]
         has_normals = any(m.get("normals") is not None for m in self._dict["meshes"])
         sizes = dict(nodes=16 * n_nodes, qnodes=8 * n_nodes, tris=12 * n_prims, tri_pos=9 * n_prims, tri_nrm=9 * n_prims if has_normals else 0,
-                     area_pmf=n_prims, area_cdf=n_prims, grid=6)
+                     area_pmf=n_prims, area_cdf=n_prims, grid=6, node_child=2 * n_nodes)
+        n_builder = 2 * n_nodes + 1                 # the binary tree of a hierarchy scene: one more leaf than inner nodes
+        sizes.update(kids=2 * n_builder, order=n_builder, boxes=6 * n_builder, slot_prim=n_prims)
+        if words is None and which in ("wnodes", "wide_child"):
+            words = (16 if which == "wnodes" else 4) * self.accel_info()["wide_nodes"]
         if words is None:
             words = sizes[which]
         out = np.zeros(max(int(words), 1), np.uint32)
