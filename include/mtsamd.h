@@ -249,7 +249,10 @@ enum {
     MTSAMD_VERTICES_RECOMPUTE_NORMALS = 1,
     /* the update, then mtsamd_scene_rebuild_accel(scene, 0, stream) in the same call; combinable with the flag above.  The refusals of
      * the update come first and write nothing; a refused rebuild leaves the scene updated and refitted. */
-    MTSAMD_VERTICES_REBUILD_ACCEL = 2
+    MTSAMD_VERTICES_REBUILD_ACCEL = 2,
+    /* valid only together with MTSAMD_VERTICES_REBUILD_ACCEL (alone it is refused as an unknown flag): that rebuild is
+     * mtsamd_scene_rebuild_accel_with(scene, MTSAMD_BUILDER_SAH, 0, stream).  Bit 2 (value 4) is not assigned. */
+    MTSAMD_VERTICES_ACCEL_SAH = 8
 };
 MTSAMD_API int mtsamd_scene_update_vertices(mtsamd_scene *scene, uint32_t shape, const float *positions, const float *normals, uint32_t flags,
                                             float *normals_out, void *stream);
@@ -289,8 +292,22 @@ MTSAMD_API int mtsamd_scene_read_accel(const mtsamd_scene *scene, int32_t which,
  * MTSAMD_ERR_NOMEM, and MTSAMD_ERR_UNSUPPORTED for a tree too deep for the LDS traversal stack.  Waits for `stream` and returns when the
  * scene is consistent. */
 MTSAMD_API int mtsamd_scene_rebuild_accel(mtsamd_scene *scene, uint32_t flags, void *stream);
+/* mtsamd_scene_rebuild_accel with the builder named; the values are those mtsamd_scene_accel_info reports.  MTSAMD_BUILDER_LBVH: exactly
+ * that call.  MTSAMD_BUILDER_SAH: the binned-SAH tree of creation, built level by level on the device (the host function
+ * build_sah_levels of csrc/bvh.h is its specification and the device writes the same bytes): BVH2 and BVH4 nodes and the grid come out
+ * byte for byte as those of a scene created from the positions the scene holds now, every leaf holds the same triangles (in ascending
+ * primitive order), and mtsamd_scene_accel_info reports builder 0 afterwards.  One documented difference to creation: from depth 40 on a
+ * node is split in the middle of its primitives' order, where creation takes an object median; only pathological sets reach it.
+ * flags must be 0; an unknown builder is MTSAMD_ERR_INVALID.  Commit protocol, refusals (MTSAMD_ERR_NOMEM, MTSAMD_ERR_UNSUPPORTED: the
+ * scene stays as it was), flat scenes (left alone, MTSAMD_OK) and later refits are those of mtsamd_scene_rebuild_accel. */
+enum { MTSAMD_BUILDER_SAH = 0, MTSAMD_BUILDER_LBVH = 1 };
+MTSAMD_API int mtsamd_scene_rebuild_accel_with(mtsamd_scene *scene, uint32_t builder, uint32_t flags, void *stream);
+/* Measurement aid: the levels of the scene's last MTSAMD_BUILDER_SAH build.  *levels: their number (0: none yet); the first `capacity`
+ * of them get nodes[i], the nodes of level i, and ms[i], the host's wall time for it (launches, scan and the wait for its count). */
+MTSAMD_API int mtsamd_scene_rebuild_levels(const mtsamd_scene *scene, uint32_t capacity, uint32_t *nodes, float *ms, uint32_t *levels);
 /* The accelerator a scene holds now.  out8: BVH2 nodes, BVH4 nodes, triangle slots, depth of the binary tree, depth of the BVH4,
- * entries of the traversal stack per lane, builder (0: the binned-SAH build of creation, 1: the LBVH of a rebuild), rebuilds so far.
+ * entries of the traversal stack per lane, builder (0: the binned-SAH build of creation or of a MTSAMD_BUILDER_SAH rebuild, 1: the LBVH
+ * of a rebuild), rebuilds so far.
  * sah_cost (may be NULL): the sum over the inner nodes of the binary tree of area / area(root) plus 1.5 times the sum over its leaves of
  * count * area / area(root), from the exact boxes the scene holds (computed on the device in double, in a fixed order): the number that
  * tells when a refitted tree has degraded enough to rebuild.  0 for a flat scene. */

@@ -124,6 +124,8 @@ SYMBOLS = {
     "mtsamd_compute_vertex_normals": (C.c_int, [C.c_uint32, vp, C.c_uint32, vp, vp]),
     "mtsamd_scene_read_accel": (C.c_int, [vp, C.c_int32, vp, C.c_uint64]),
     "mtsamd_scene_rebuild_accel": (C.c_int, [vp, C.c_uint32, vp]),
+    "mtsamd_scene_rebuild_accel_with": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+    "mtsamd_scene_rebuild_levels": (C.c_int, [vp, C.c_uint32, vp, vp, vp]),
     "mtsamd_scene_accel_info": (C.c_int, [vp, u32p, C.POINTER(C.c_double)]),
     "mtsamd_ray_intersect": (C.c_int, [vp, C.c_uint64, C.POINTER(Rays), vp, vp, vp, vp, vp, vp]),
     "mtsamd_ray_intersect_naive": (C.c_int, [vp, C.c_uint64, C.POINTER(Rays), vp, vp, vp, vp, vp, vp]),

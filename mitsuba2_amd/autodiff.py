@@ -89,8 +89,8 @@ class ParameterMap:
 
     def __init__(self, scene, replay=False, geometry=False, normals=None, emitters=False, accel="refit"):
         self._scene = scene
-        if accel not in ("refit", "rebuild"):
-            raise RuntimeError("accel: \"refit\" or \"rebuild\", not %r" % (accel,))
+        if accel not in ("refit", "rebuild", "rebuild-sah"):
+            raise RuntimeError("accel: \"refit\", \"rebuild\" or \"rebuild-sah\", not %r" % (accel,))
         self._accel = accel                          # what update() does to the accelerator when it moves a mesh
         want_emitters = bool(emitters) and not _is_spectral(scene)      # RGB scenes: the emitter-colour keys below, in any scene
         if normals not in (None, "recompute"):
@@ -299,7 +299,7 @@ def traverse(scene, replay=False, geometry=False, normals=None, emitters=False, 
     '<shape id>.vertex_positions_buf' of every mesh (the flat 3N buffer of mesh.cpp:781-804); update() pushes it through
     Scene.update_vertices; ``normals="recompute"`` makes it pass that on for every mesh with vertex normals, so that a moved mesh's
     normals are recomputed on the device and no vertex data visits the host; ``accel="rebuild"`` makes every such update rebuild the
-    accelerator's topology instead of only refitting it (Scene.update_vertices).  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
+    accelerator's topology instead of only refitting it, ``accel="rebuild-sah"`` with the SAH builder (Scene.update_vertices).  These keys are settable, not differentiable -- an optimiser marks every key of its map as requiring a gradient,
     which is why they have to be asked for: render() raises on one that requires a gradient.  ``emitters=True`` (RGB scenes; ignored for
     spectral ones) adds the emitter colours in any scene: '<shape id>.emitter.radiance.value' of area lights and
     '<emitter id>.radiance|intensity|irradiance.value' of `constant`, `point`, `spot` and `directional` emitters.  They are settable and

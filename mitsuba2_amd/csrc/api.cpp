@@ -17,6 +17,7 @@
 #include "refit.h"
 #include "lbvh.h"
 #include "lbvh_keys.h"
+#include "sah_build.h"
 #include "schedule.h"
 #include "spectral_upsampling.h"
 #include "cie_data.h"
@@ -420,6 +421,7 @@ struct mtsamd_scene : SceneState {
     // array a build writes, sized for the worst case, both allocated at the first rebuild and kept.  A build goes into `spare`; accepted,
     // it becomes the live set and the former live set the spare (the set of creation, sized for its own tree, is freed instead).
     LbvhScratch *lbvh_scratch = nullptr;
+    SahScratch *sah_scratch = nullptr;      // of the SAH builder (sah_build.h), allocated at its first use
     LbvhTarget spare{};
     bool accel_worst_case = false;          // the live set is sized for the worst case
     uint32_t n_builder = 0, builder = 0, rebuilds = 0;      // builder nodes; 0 = binned SAH (creation), 1 = LBVH; rebuilds so far
@@ -641,6 +643,7 @@ void mtsamd_scene_destroy(mtsamd_scene *s) {
     for (uint32_t *p : s->d_corners) (void) hipFree(p);
     (void) hipFree(s->d_face_recs);
     lbvh_scratch_destroy(s->lbvh_scratch);
+    sah_scratch_destroy(s->sah_scratch);
     free_target(s->spare);
     (void) hipFree(s->d_sah_partial);
     (void) hipFree(s->d_textures); (void) hipFree(s->d_jac); (void) hipFree(s->d_cgrad); (void) hipFree(s->d_ejac); (void) hipFree(s->d_egrad);
@@ -918,15 +921,20 @@ static int alloc_target(uint32_t n, LbvhTarget &t) {       // the worst case of 
     return fail(MTSAMD_ERR_NOMEM, "accelerator rebuild: out of device memory (%u primitives)", n);
 }
 
-// The device build (lbvh.h) from the positions the scene holds, into the spare set; then look before writing: the tree must fit the
+// The device build (lbvh.h, or sah_build.h: creation's tree) from the positions the scene holds, into the spare set; then look before writing: the tree must fit the
 // traversal stack and the spill area must be there before a single pointer of the scene changes.
-static int rebuild_accel(mtsamd_scene *s, hipStream_t stream) {
+static int rebuild_accel(mtsamd_scene *s, uint32_t builder, hipStream_t stream) {
     HIP_TRY(hipSetDevice(s->device));
     if (s->geometry.flat || s->n_prims == 0) return MTSAMD_OK;
     const uint32_t n = s->n_prims;
     HIP_TRY(hipStreamSynchronize(stream));
     if (!s->lbvh_scratch) {
         const hipError_t e = lbvh_scratch_create(n, &s->lbvh_scratch);
+        if (e == hipErrorOutOfMemory) { (void) hipGetLastError(); return fail(MTSAMD_ERR_NOMEM, "accelerator rebuild: out of device memory (%u primitives)", n); }
+        HIP_TRY(e);
+    }
+    if (builder == MTSAMD_BUILDER_SAH && !s->sah_scratch) {
+        const hipError_t e = sah_scratch_create(n, &s->sah_scratch);
         if (e == hipErrorOutOfMemory) { (void) hipGetLastError(); return fail(MTSAMD_ERR_NOMEM, "accelerator rebuild: out of device memory (%u primitives)", n); }
         HIP_TRY(e);
     }
@@ -937,7 +945,8 @@ static int rebuild_accel(mtsamd_scene *s, hipStream_t stream) {
     scene_grid(s->bvh.bbox, &grid.extent, q_lo, q_step);          // the box is unchanged by a rebuild, and so is the grid
     for (int k = 0; k < 3; ++k) { grid.glo[k] = (double) q_lo[k]; grid.gstep[k] = (double) q_step[k]; }
     LbvhResult r;
-    HIP_TRY(lbvh_build(s->lbvh_scratch, s->d_tri_pos, n, s->options.max_leaf, s->bvh.bbox, grid, s->spare, r, stream));
+    if (builder == MTSAMD_BUILDER_SAH) HIP_TRY(sah_build(s->sah_scratch, s->lbvh_scratch, s->d_tri_pos, n, s->options.max_leaf, grid, s->spare, r, stream));
+    else HIP_TRY(lbvh_build(s->lbvh_scratch, s->d_tri_pos, n, s->options.max_leaf, s->bvh.bbox, grid, s->spare, r, stream));
     SceneView &v = s->view;
     const uint32_t stack_depth = bvh_stack_depth(r.depth, r.wdepth, MTS_BVH4 != 0);
     if (!bvh_stack_fits(stack_depth, sizeof(StackEntry))) return fail(MTSAMD_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack (depth %u)", stack_depth);
@@ -960,21 +969,39 @@ static int rebuild_accel(mtsamd_scene *s, hipStream_t stream) {
     v.nodes = s->d_nodes; v.qnodes = s->d_qnodes; v.wnodes = s->d_wnodes; v.tris = s->d_tris; v.root = b.root; v.wroot = b.wroot;
     v.n_nodes = b.n_nodes; v.n_wnodes = b.n_wnodes; v.n_slots = b.n_slots;
     v.stack_depth = stack_depth; v.walk_lds_depth = walk_lds_depth; v.walk_spill = s->d_walk_spill;
-    s->builder = 1u; ++s->rebuilds;
+    s->builder = builder; ++s->rebuilds;
     return MTSAMD_OK;
 }
 
 int mtsamd_scene_update_vertices(mtsamd_scene *s, uint32_t shape, const float *positions, const float *normals, uint32_t flags, float *normals_out,
                                  void *stream) {
     if (int rc = vertex_update(s, shape, positions, normals, flags, normals_out, stream)) return rc;
-    if (flags & MTSAMD_VERTICES_REBUILD_ACCEL) return rebuild_accel(s, (hipStream_t) stream);
+    if (flags & MTSAMD_VERTICES_REBUILD_ACCEL) return rebuild_accel(s, (flags & MTSAMD_VERTICES_ACCEL_SAH) ? MTSAMD_BUILDER_SAH : MTSAMD_BUILDER_LBVH, (hipStream_t) stream);
     return MTSAMD_OK;
 }
 
 int mtsamd_scene_rebuild_accel(mtsamd_scene *s, uint32_t flags, void *stream) {
     if (!s) return fail(MTSAMD_ERR_INVALID, "null scene");
     if (flags) return fail(MTSAMD_ERR_INVALID, "unknown accelerator rebuild flags 0x%x", flags);
-    return rebuild_accel(s, (hipStream_t) stream);
+    return rebuild_accel(s, MTSAMD_BUILDER_LBVH, (hipStream_t) stream);
+}
+
+int mtsamd_scene_rebuild_accel_with(mtsamd_scene *s, uint32_t builder, uint32_t flags, void *stream) {
+    if (!s) return fail(MTSAMD_ERR_INVALID, "null scene");
+    if (builder != MTSAMD_BUILDER_SAH && builder != MTSAMD_BUILDER_LBVH) return fail(MTSAMD_ERR_INVALID, "unknown accelerator builder %u", builder);
+    if (flags) return fail(MTSAMD_ERR_INVALID, "unknown accelerator rebuild flags 0x%x", flags);
+    return rebuild_accel(s, builder, (hipStream_t) stream);
+}
+
+int mtsamd_scene_rebuild_levels(const mtsamd_scene *s, uint32_t capacity, uint32_t *nodes, float *ms, uint32_t *levels) {
+    if (!s || !levels || (capacity && (!nodes || !ms))) return fail(MTSAMD_ERR_INVALID, "null argument");
+    *levels = 0;
+    if (!s->sah_scratch) return MTSAMD_OK;
+    const std::vector<float> &t = sah_level_ms(s->sah_scratch);
+    const std::vector<uint32_t> &m = sah_level_nodes(s->sah_scratch);
+    *levels = (uint32_t) t.size();
+    for (size_t i = 0; i < t.size() && i < capacity; ++i) { nodes[i] = m[i]; ms[i] = t[i]; }
+    return MTSAMD_OK;
 }
 
 int mtsamd_scene_accel_info(const mtsamd_scene *s_, uint32_t *out8, double *sah_cost) {

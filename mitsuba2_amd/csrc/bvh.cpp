@@ -2,6 +2,7 @@
 #include "bvh.h"
 #include "refit_encode.h"
 #include "lbvh_keys.h"
+#include "sah_keys.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -443,64 +444,14 @@ void build_bvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOut
     out.depth = b.max_depth + 1;
 }
 
-// ---- build_lbvh: the specification of the device build (bvh.h).  Every step is a loop over independent elements, or a scan; the
-// element functions are lbvh_keys.h's, which csrc/lbvh.hip calls too.
 namespace { struct Kid { int32_t x, y; }; }
 
-void build_lbvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out) {
-    max_leaf = std::min<uint32_t>(std::max<uint32_t>(max_leaf, 1), 15);
-    const int n = (int) n_prims;
+// ---- what build_lbvh and build_sah_levels share, from the heights on: the table holds left / right, ref2 (and ref4 of the leaves),
+// node_child and slot_prim, builder node 0 is the root; heights, order / class_start, exact boxes with the refit's arithmetic, the BVH4
+// collapse per wide level, the emission.
+static void finish_levels(const float *tri_pos, BvhOutput &out) {
     RefitTable &rt = out.refit;
-    rt = RefitTable{};
-    // keys: the scene box is the exact union of all vertices; then one code per primitive and the stable order
-    float bbox[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
-    for (size_t p = 0; p < n_prims; ++p) {
-        float lo[3], hi[3];
-        lbvh_prim_box(tri_pos + 9 * p, lo, hi);
-        for (int k = 0; k < 3; ++k) { bbox[k] = enc_min(bbox[k], lo[k]); bbox[3 + k] = enc_max(bbox[3 + k], hi[k]); }
-    }
-    std::vector<uint64_t> keys(n_prims);
-    for (size_t p = 0; p < n_prims; ++p) keys[p] = ((uint64_t) lbvh_code(tri_pos + 9 * p, bbox) << 32) | p;
-    std::sort(keys.begin(), keys.end());
-    std::vector<uint32_t> codes(n_prims);
-    rt.slot_prim.resize(n_prims);
-    for (size_t s = 0; s < n_prims; ++s) { codes[s] = (uint32_t) (keys[s] >> 32); rt.slot_prim[s] = (uint32_t) keys[s]; }
-    // radix tree: ids [0, n - 1) are the inner nodes, n - 1 + s the leaf at position s.  Each inner node states what its children are:
-    // 0 = below a leaf (dropped), 1 = leaf, 2 = inner
-    const size_t n_radix = 2 * (size_t) n_prims - 1;
-    std::vector<uint32_t> state(n_radix, 0u), first(n_radix, 0u), count(n_radix, 0u);
-    std::vector<int32_t> rl(n_prims - 1), rr(n_prims - 1);
-    state[0] = n_prims > max_leaf ? 2u : 1u; first[0] = 0u; count[0] = n_prims;
-    for (int i = 0; i + 1 < n; ++i) {
-        int f, l, split;
-        lbvh_radix_node(codes.data(), n, i, &f, &l, &split);
-        const int32_t c[2] = { split == f ? n - 1 + split : split, split + 1 == l ? n - 1 + split + 1 : split + 1 };
-        const uint32_t cf[2] = { (uint32_t) f, (uint32_t) split + 1u }, cc[2] = { (uint32_t) (split - f + 1), (uint32_t) (l - split) };
-        rl[i] = c[0]; rr[i] = c[1];
-        const bool open = (uint32_t) (l - f + 1) > max_leaf;
-        for (int k = 0; k < 2; ++k) { state[c[k]] = !open ? 0u : (cc[k] > max_leaf ? 2u : 1u); first[c[k]] = cf[k]; count[c[k]] = cc[k]; }
-    }
-    // compaction: builder ids and BVH2 ids are exclusive scans of the survivors
-    std::vector<int32_t> bid(n_radix, -1), iid(n_radix, -1);
-    size_t n_tmp = 0, n_inner = 0;
-    for (size_t x = 0; x < n_radix; ++x) {
-        if (state[x]) bid[x] = (int32_t) n_tmp++;
-        if (state[x] == 2u) iid[x] = (int32_t) n_inner++;
-    }
-    rt.root = 0;
-    rt.left.assign(n_tmp, -1); rt.right.assign(n_tmp, -1); rt.ref2.assign(n_tmp, 0u); rt.ref4.assign(n_tmp, 0xffffffffu);
-    rt.boxes.assign(6 * n_tmp, 0.0f); rt.node_child.resize(2 * n_inner);
-    for (size_t x = 0; x < n_radix; ++x) {
-        if (!state[x]) continue;
-        const int32_t t = bid[x];
-        if (state[x] == 2u) {
-            rt.left[t] = bid[rl[x]]; rt.right[t] = bid[rr[x]];
-            rt.ref2[t] = (uint32_t) iid[x];
-            rt.node_child[2 * (size_t) iid[x]] = rt.left[t]; rt.node_child[2 * (size_t) iid[x] + 1] = rt.right[t];
-        } else {
-            rt.ref2[t] = rt.ref4[t] = kLeafFlag | (count[x] << kLeafCountShift) | first[x];
-        }
-    }
+    const size_t n_tmp = rt.left.size(), n_inner = rt.node_child.size() / 2;
     // heights: a node's is known once both children's are; rounds of that rule, as many as the tree is high
     rt.height.assign(n_tmp, kLbvhNoHeight);
     for (size_t t = 0; t < n_tmp; ++t) if (rt.left[t] < 0) rt.height[t] = 0u;
@@ -565,8 +516,182 @@ void build_lbvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOu
     }
     emit_bvh(tri_pos, out);
     out.n_nodes = (uint32_t) n_inner;
-    out.n_slots = n_prims;
+    out.n_slots = (uint32_t) rt.slot_prim.size();
     out.depth = top + 1;
+}
+
+// ---- build_lbvh: the specification of the device build (bvh.h).  Every step is a loop over independent elements, or a scan; the
+// element functions are lbvh_keys.h's, which csrc/lbvh.hip calls too.
+void build_lbvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out) {
+    max_leaf = std::min<uint32_t>(std::max<uint32_t>(max_leaf, 1), 15);
+    const int n = (int) n_prims;
+    RefitTable &rt = out.refit;
+    rt = RefitTable{};
+    // keys: the scene box is the exact union of all vertices; then one code per primitive and the stable order
+    float bbox[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+    for (size_t p = 0; p < n_prims; ++p) {
+        float lo[3], hi[3];
+        lbvh_prim_box(tri_pos + 9 * p, lo, hi);
+        for (int k = 0; k < 3; ++k) { bbox[k] = enc_min(bbox[k], lo[k]); bbox[3 + k] = enc_max(bbox[3 + k], hi[k]); }
+    }
+    std::vector<uint64_t> keys(n_prims);
+    for (size_t p = 0; p < n_prims; ++p) keys[p] = ((uint64_t) lbvh_code(tri_pos + 9 * p, bbox) << 32) | p;
+    std::sort(keys.begin(), keys.end());
+    std::vector<uint32_t> codes(n_prims);
+    rt.slot_prim.resize(n_prims);
+    for (size_t s = 0; s < n_prims; ++s) { codes[s] = (uint32_t) (keys[s] >> 32); rt.slot_prim[s] = (uint32_t) keys[s]; }
+    // radix tree: ids [0, n - 1) are the inner nodes, n - 1 + s the leaf at position s.  Each inner node states what its children are:
+    // 0 = below a leaf (dropped), 1 = leaf, 2 = inner
+    const size_t n_radix = 2 * (size_t) n_prims - 1;
+    std::vector<uint32_t> state(n_radix, 0u), first(n_radix, 0u), count(n_radix, 0u);
+    std::vector<int32_t> rl(n_prims - 1), rr(n_prims - 1);
+    state[0] = n_prims > max_leaf ? 2u : 1u; first[0] = 0u; count[0] = n_prims;
+    for (int i = 0; i + 1 < n; ++i) {
+        int f, l, split;
+        lbvh_radix_node(codes.data(), n, i, &f, &l, &split);
+        const int32_t c[2] = { split == f ? n - 1 + split : split, split + 1 == l ? n - 1 + split + 1 : split + 1 };
+        const uint32_t cf[2] = { (uint32_t) f, (uint32_t) split + 1u }, cc[2] = { (uint32_t) (split - f + 1), (uint32_t) (l - split) };
+        rl[i] = c[0]; rr[i] = c[1];
+        const bool open = (uint32_t) (l - f + 1) > max_leaf;
+        for (int k = 0; k < 2; ++k) { state[c[k]] = !open ? 0u : (cc[k] > max_leaf ? 2u : 1u); first[c[k]] = cf[k]; count[c[k]] = cc[k]; }
+    }
+    // compaction: builder ids and BVH2 ids are exclusive scans of the survivors
+    std::vector<int32_t> bid(n_radix, -1), iid(n_radix, -1);
+    size_t n_tmp = 0, n_inner = 0;
+    for (size_t x = 0; x < n_radix; ++x) {
+        if (state[x]) bid[x] = (int32_t) n_tmp++;
+        if (state[x] == 2u) iid[x] = (int32_t) n_inner++;
+    }
+    rt.root = 0;
+    rt.left.assign(n_tmp, -1); rt.right.assign(n_tmp, -1); rt.ref2.assign(n_tmp, 0u); rt.ref4.assign(n_tmp, 0xffffffffu);
+    rt.boxes.assign(6 * n_tmp, 0.0f); rt.node_child.resize(2 * n_inner);
+    for (size_t x = 0; x < n_radix; ++x) {
+        if (!state[x]) continue;
+        const int32_t t = bid[x];
+        if (state[x] == 2u) {
+            rt.left[t] = bid[rl[x]]; rt.right[t] = bid[rr[x]];
+            rt.ref2[t] = (uint32_t) iid[x];
+            rt.node_child[2 * (size_t) iid[x]] = rt.left[t]; rt.node_child[2 * (size_t) iid[x] + 1] = rt.right[t];
+        } else {
+            rt.ref2[t] = rt.ref4[t] = kLeafFlag | (count[x] << kLeafCountShift) | first[x];
+        }
+    }
+    finish_levels(tri_pos, out);
+}
+
+// ---- build_sah_levels: the specification of the device SAH build (bvh.h).  A level is three loops: decide every node (independent), number
+// what they made (a scan), write children and leaf slots (independent).  The element functions are sah_keys.h's, which
+// csrc/sah_build.hip calls too.
+void build_sah_levels(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out, SahLevelsTrace *trace) {
+    max_leaf = std::min<uint32_t>(std::max<uint32_t>(max_leaf, 1), 15);
+    RefitTable &rt = out.refit;
+    rt = RefitTable{};
+    std::vector<float> pbox(6 * (size_t) n_prims);
+    std::vector<double> cen(3 * (size_t) n_prims);
+    std::vector<uint32_t> perm(n_prims), perm_next(n_prims);
+    for (size_t p = 0; p < n_prims; ++p) {
+        sah_prim(tri_pos + 9 * p, &pbox[6 * p], &pbox[6 * p + 3], &cen[3 * p]);
+        perm[p] = (uint32_t) p;
+    }
+    struct Active { uint32_t first, count; };
+    struct Decision { uint32_t mode, left; int axis, bin; double lo, scale, cost; };
+    std::vector<Active> level(1, Active{ 0u, n_prims }), next_level;
+    size_t level_base = 0, n_inner = 0, n_slots = 0;
+    rt.root = 0;
+    rt.slot_prim.resize(n_prims);
+    for (uint32_t depth = 0; !level.empty(); ++depth) {
+        const size_t m = level.size(), next_base = level_base + m;
+        // decide
+        std::vector<Decision> dec(m);
+        for (size_t j = 0; j < m; ++j) {
+            const uint32_t first = level[j].first, count = level[j].count;
+            Decision &d = dec[j];
+            d = Decision{ kSahLeaf, 0u, -1, -1, 0.0, 0.0, DBL_MAX };
+            SahBins bins;
+            if (count > 1u) {
+                float nb[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+                double cb_lo[3] = { DBL_MAX, DBL_MAX, DBL_MAX }, cb_hi[3] = { -DBL_MAX, -DBL_MAX, -DBL_MAX };
+                for (uint32_t i = 0; i < count; ++i) {
+                    const size_t p = perm[first + i];
+                    for (int k = 0; k < 3; ++k) {
+                        nb[k] = std::min(nb[k], pbox[6 * p + k]); nb[3 + k] = std::max(nb[3 + k], pbox[6 * p + 3 + k]);
+                        cb_lo[k] = std::min(cb_lo[k], cen[3 * p + k]); cb_hi[k] = std::max(cb_hi[k], cen[3 * p + k]);
+                    }
+                }
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < kSahBins; ++b) { for (int k = 0; k < 3; ++k) { bins.lo[a][b][k] = 0xffffffffu; bins.hi[a][b][k] = 0u; } bins.cnt[a][b] = 0u; }
+                for (int a = 0; a < 3; ++a) {
+                    const double ext = cb_hi[a] - cb_lo[a];
+                    if (!(ext > 0.0)) continue;
+                    const double scale = sah_scale(ext);
+                    for (uint32_t i = 0; i < count; ++i) {
+                        const size_t p = perm[first + i];
+                        const int b = sah_bin(cen[3 * p + a], cb_lo[a], scale);
+                        for (int k = 0; k < 3; ++k) {
+                            bins.lo[a][b][k] = std::min(bins.lo[a][b][k], sah_ord(pbox[6 * p + k]));
+                            bins.hi[a][b][k] = std::max(bins.hi[a][b][k], sah_ord(pbox[6 * p + 3 + k]));
+                        }
+                        bins.cnt[a][b]++;
+                    }
+                }
+                sah_choose(bins, cb_lo, cb_hi, lbvh_area(nb), &d.axis, &d.bin, &d.cost);
+                d.mode = sah_decide(count, max_leaf, depth, d.axis, d.cost);
+                if (d.mode != kSahLeaf) d.left = sah_left_count(bins, count, &d.mode, d.axis, d.bin);
+                if (d.mode == kSahSplitBin) { d.lo = cb_lo[d.axis]; d.scale = sah_scale(cb_hi[d.axis] - cb_lo[d.axis]); }
+            }
+            if (trace) {
+                trace->first.push_back(first); trace->count.push_back(count); trace->depth.push_back(depth); trace->mode.push_back(d.mode);
+                trace->left_count.push_back(d.left); trace->axis.push_back(d.axis); trace->bin.push_back(d.bin); trace->cost.push_back(d.cost);
+                if (count > 1u && trace->bins_node.size() < trace->bins_of) {
+                    trace->bins_node.push_back((uint32_t) (level_base + j));
+                    const uint32_t *w = reinterpret_cast<const uint32_t *>(&bins);
+                    trace->bins.insert(trace->bins.end(), w, w + kSahBinWords);
+                }
+            }
+        }
+        // number: the children and the BVH2 id of every split node, the first slot of every leaf
+        std::vector<uint32_t> split_rank(m), leaf_slot(m);
+        size_t n_split = 0;
+        for (size_t j = 0; j < m; ++j) {
+            split_rank[j] = (uint32_t) n_split; leaf_slot[j] = (uint32_t) n_slots;
+            if (dec[j].mode != kSahLeaf) ++n_split; else n_slots += level[j].count;
+        }
+        // write
+        rt.left.resize(next_base, -1); rt.right.resize(next_base, -1); rt.ref2.resize(next_base, 0u); rt.ref4.resize(next_base, 0xffffffffu);
+        rt.node_child.resize(2 * (n_inner + n_split));
+        next_level.assign(2 * n_split, Active{ 0u, 0u });
+        for (size_t j = 0; j < m; ++j) {
+            const size_t t = level_base + j;
+            const uint32_t first = level[j].first, count = level[j].count;
+            const Decision &d = dec[j];
+            if (d.mode == kSahLeaf) {
+                rt.ref2[t] = rt.ref4[t] = kLeafFlag | (count << kLeafCountShift) | leaf_slot[j];
+                for (uint32_t i = 0; i < count; ++i) rt.slot_prim[leaf_slot[j] + i] = perm[first + i];
+                continue;
+            }
+            const size_t r = split_rank[j], iid = n_inner + r;
+            const int32_t l = (int32_t) (next_base + 2 * r);
+            rt.left[t] = l; rt.right[t] = l + 1; rt.ref2[t] = (uint32_t) iid;
+            rt.node_child[2 * iid] = l; rt.node_child[2 * iid + 1] = l + 1;
+            next_level[2 * r] = Active{ first, d.left }; next_level[2 * r + 1] = Active{ first + d.left, count - d.left };
+            if (d.mode == kSahSplitBin) {                     // the stable partition
+                uint32_t nl = 0, nr = 0;
+                for (uint32_t i = 0; i < count; ++i) {
+                    const uint32_t p = perm[first + i];
+                    if (sah_bin(cen[3 * (size_t) p + d.axis], d.lo, d.scale) <= d.bin) perm_next[first + nl++] = p;
+                    else perm_next[first + d.left + nr++] = p;
+                }
+            } else {
+                for (uint32_t i = 0; i < count; ++i) perm_next[first + i] = perm[first + i];
+            }
+        }
+        n_inner += n_split;
+        level_base = next_base;
+        level.swap(next_level);
+        perm.swap(perm_next);
+    }
+    rt.boxes.assign(6 * rt.left.size(), 0.0f);
+    finish_levels(tri_pos, out);
 }
 
 double sah_cost_blocked(const int32_t *kids, const float *boxes, size_t n_builder, int32_t root) {

@@ -76,6 +76,26 @@ void scene_grid(const float bbox[6], double *extent, float q_lo[3], float q_step
 // everything build_bvh fills and ends in the same emission; refit_bvh refits it.  The binary depth is at most 31 + ceil(log2 n).
 void build_lbvh(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out);
 
+// build_bvh with the shipped BvhOptions (16 bins, intersect cost 1.5, no sweep, BFS layout; the experiment knobs of the environment are not
+// honoured), restated level by level so that a device can build it (csrc/sah_build.hip does, and is held to these bytes).  Every decision
+// of build_bvh depends only on the set of primitives of a node, so a level is a loop over independent nodes: node box and centroid box,
+// 16 bins per axis of positive centroid extent, the search and the leaf rule of sah_keys.h, then a stable partition of the node's part of
+// `perm` (identity at the root) by bin, or its middle when no candidate exists.  The one difference: from depth 40 on (root = 0) a split
+// is the middle of the present order, whatever the search said, where build_bvh takes an object median by nth_element, whose order among
+// equals is the library's; the depth bound 40 + ceil(log2 n) stays.  Numbering: builder nodes level by level (root 0; the children of a
+// level's split nodes follow in parent order, left then right); BVH2 nodes = split nodes in that order (build_bvh's BFS order); triangle
+// slots leaf by leaf in ascending builder id, inside a leaf in perm order, which is ascending primitive index (build_bvh's leaf-reach
+// order); wide nodes as build_lbvh.  From the heights on it is build_lbvh's tail.  nodes, qnodes, wnodes* and the grid come out byte for
+// byte as build_bvh's, tris / slot_prim with the same set in every leaf.  trace (may be null): what was decided, for the tests.
+struct SahLevelsTrace {
+    std::vector<uint32_t> first, count, depth, mode, left_count;      // per builder node; mode: sah_keys.h (kSahLeaf, ..)
+    std::vector<int32_t> axis, bin;                                   // the search's result (-1: no candidate), whatever the mode
+    std::vector<double> cost;
+    uint32_t bins_of = 0;                                             // in: keep the bins of the first so many nodes of more than one primitive
+    std::vector<uint32_t> bins_node, bins;                            // their builder ids, and kSahBinWords words each
+};
+void build_sah_levels(const float *tri_pos, uint32_t n_prims, uint32_t max_leaf, BvhOutput &out, SahLevelsTrace *trace = nullptr);
+
 // The traversal stack of a hierarchy scene: entries per lane for a tree of these depths, and whether the stack of a 256-lane workgroup
 // fits the LDS a launch may ask for (kernels.h: bounce_lds_bytes(v) <= kFlatLdsCap; api.cpp asserts that the constants agree).  An entry
 // of the BVH4 walk has 8 bytes, one of the BVH2 walk 4.

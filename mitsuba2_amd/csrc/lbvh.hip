@@ -13,19 +13,6 @@
 
 namespace mtsamd {
 
-struct LbvhScratch {
-    uint32_t n = 0;                          // primitives the arrays are sized for; R = 2n - 1 radix-tree nodes
-    uint32_t *codes = nullptr, *codes_sorted = nullptr, *iota = nullptr;        // n, n, R
-    uint32_t *state = nullptr, *rfirst = nullptr, *rcount = nullptr;            // R each: what a radix-tree node becomes, and its range
-    int32_t *rl = nullptr, *rr = nullptr;                                       // n each: children of the inner radix-tree nodes
-    uint32_t *any_flag = nullptr, *bid = nullptr, *inner_flag = nullptr, *iid = nullptr;      // R + 1, R + 1, n + 1, n + 1
-    uint32_t *ref2 = nullptr, *ref4 = nullptr;                                  // R each, per builder node
-    uint32_t *h_a = nullptr, *h_b = nullptr, *h_sorted = nullptr, *hist = nullptr;             // R, R, R, 128
-    int32_t *wide_builder = nullptr;                                            // n: the builder node a wide node replaces
-    uint32_t *cnt = nullptr, *offs = nullptr;                                   // n + 1 each: inner children per wide node of a level
-    void *tmp = nullptr; size_t tmp_bytes = 0;                                  // rocPRIM's
-};
-
 namespace {
 
 constexpr uint32_t kLbvhBlock = 256u;
@@ -278,9 +265,18 @@ hipError_t lbvh_build(LbvhScratch *sc, const float *tri_pos, uint32_t n, uint32_
     if (nb != 2u * n_nodes + 1u || nb > R) return hipErrorUnknown;       // a binary tree has one more leaf than inner nodes
     hipLaunchKernelGGL(k_lbvh_compact, dim3(lbvh_blocks(R)), dim3(kLbvhBlock), 0, s, *sc, R, tg.kids, tg.node_child);
     LBVH_TRY(hipGetLastError());
-    // 5. heights: as many rounds as a tree over n keys of 30 + ceil(log2 n) bits can be high; then the nodes in the order of their height
+    // 5 - 8. as many rounds of the heights as a tree over n keys of 30 + ceil(log2 n) bits can be high
     uint32_t rounds = 32u;
     while ((1ull << (rounds - 32u)) < n) ++rounds;
+    return lbvh_finish(sc, tri_pos, n, nb, n_nodes, rounds, grid, tg, res, s);
+}
+
+// The tail of a build, from the heights on (lbvh.h): kids, node_child, slot_prim / prim_slot / tris are written, sc->ref2 / ref4 hold the
+// references of the builder nodes and sc->h_a their heights as far as known (leaves 0, inner nodes kLbvhNoHeight).
+hipError_t lbvh_finish(LbvhScratch *sc, const float *tri_pos, uint32_t n, uint32_t nb, uint32_t n_nodes, uint32_t rounds, const RefitGrid &grid, const LbvhTarget &tg,
+                       LbvhResult &res, hipStream_t s) {
+    if (!sc || n == 0 || n > sc->n || nb != 2u * n_nodes + 1u || nb > 2u * n - 1u) return hipErrorInvalidValue;
+    // 5. heights: `rounds` rounds; then the nodes in the order of their height
     uint32_t *h_in = sc->h_a, *h_out = sc->h_b;
     for (uint32_t r = 0; r < rounds; ++r) {
         hipLaunchKernelGGL(k_lbvh_height, dim3(lbvh_blocks(nb)), dim3(kLbvhBlock), 0, s, tg.kids, h_in, h_out, nb);
@@ -341,6 +337,11 @@ hipError_t lbvh_build(LbvhScratch *sc, const float *tri_pos, uint32_t n, uint32_
     res.n_builder = nb; res.n_nodes = n_nodes; res.n_wide = n_wide; res.n_slots = n; res.depth = top + 1u; res.wdepth = wdepth;
     res.root = res.wroot = n_nodes ? 0u : (kLbvhLeafFlag | (n << 27));
     return hipSuccess;
+}
+
+hipError_t launch_lbvh_slots(const float *tri_pos, const uint32_t *slot_prim, uint32_t n, uint32_t *prim_slot, float4 *tris, hipStream_t s) {
+    hipLaunchKernelGGL(k_lbvh_slots, dim3(lbvh_blocks(n)), dim3(kLbvhBlock), 0, s, tri_pos, slot_prim, n, prim_slot, tris);
+    return hipGetLastError();
 }
 
 hipError_t launch_sah_partials(const int2 *kids, const float *boxes, uint32_t n_builder, int32_t root, double *partial, hipStream_t s) {

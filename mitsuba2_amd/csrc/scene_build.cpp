@@ -1103,7 +1103,8 @@ int check_vertex_update(const SceneState &st, uint32_t shape, const float *posit
 int check_vertex_flags(const SceneState &st, uint32_t shape, const float *normals, uint32_t flags) {
     const SceneGeometry &g = st.geometry;
     // the text of this refusal is what it was before MTSAMD_VERTICES_REBUILD_ACCEL existed: every bit beside the recompute flag
-    const uint32_t known = MTSAMD_VERTICES_RECOMPUTE_NORMALS | MTSAMD_VERTICES_REBUILD_ACCEL;
+    // MTSAMD_VERTICES_ACCEL_SAH chooses the builder of a rebuild: without one it is an unknown bit
+    const uint32_t known = MTSAMD_VERTICES_RECOMPUTE_NORMALS | MTSAMD_VERTICES_REBUILD_ACCEL | ((flags & MTSAMD_VERTICES_REBUILD_ACCEL) ? MTSAMD_VERTICES_ACCEL_SAH : 0u);
     if (flags & ~known) return fail(MTSAMD_ERR_INVALID, "unknown vertex update flags 0x%x", flags & ~(uint32_t) MTSAMD_VERTICES_RECOMPUTE_NORMALS);
     if (!(flags & MTSAMD_VERTICES_RECOMPUTE_NORMALS)) return MTSAMD_OK;
     if (shape >= g.shapes.size()) return fail(MTSAMD_ERR_INVALID, "invalid shape index %u (the scene has %u shapes)", shape, (uint32_t) g.shapes.size());

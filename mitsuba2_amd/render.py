@@ -843,7 +843,7 @@ class Scene:
         self._pending_vertices.clear()
         self._description = value
 
-    def _recompute_vertices(self, shape, positions, rebuild=False):
+    def _recompute_vertices(self, shape, positions, rebuild=0):
         """update_vertices(normals="recompute"): mtsamd_scene_update_vertices with MTSAMD_VERTICES_RECOMPUTE_NORMALS"""
         mesh = self._description["meshes"][shape]           # counts and the presence of normals never change: no need to flush for them
         n_vertices = _f32(mesh["positions"]).reshape(-1, 3).shape[0]
@@ -858,15 +858,26 @@ class Scene:
             raise RuntimeError("shape %d was created without vertex normals: storing new normals in such a mesh is not implemented" % shape)
         pos = pos.clone()                                    # the caller may overwrite theirs; the scene reads and keeps this one
         nrm = torch.empty(3 * n_vertices, dtype=torch.float32, device=dev)
-        L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, _ptr(pos), None, 1 | (2 if rebuild else 0), _ptr(nrm), _stream()))
+        L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, _ptr(pos), None, 1 | rebuild, _ptr(nrm), _stream()))
         self._pending_vertices[shape] = (pos, nrm.clone())
         return nrm.reshape(-1, 3)
 
-    def rebuild_accel(self):
-        """mtsamd_scene_rebuild_accel: a new topology of the accelerator (an LBVH built on the device) from the positions the scene
-        holds now -- what a tree refitted through large vertex moves needs once accel_info(sah_cost=True) says it has degraded.  Samples
-        and queries are the same bits before and after; every setter's state is kept; a flat scene is left alone."""
-        L.check(L.lib().mtsamd_scene_rebuild_accel(self._handle, 0, _stream()))
+    def rebuild_accel(self, builder="lbvh"):
+        """mtsamd_scene_rebuild_accel_with: a new topology of the accelerator, built on the device from the positions the scene holds
+        now -- what a tree refitted through large vertex moves needs once accel_info(sah_cost=True) says it has degraded.  builder:
+        "lbvh" (the fast one), or "sah": the binned-SAH tree a scene created from these positions would get, node for node.  Samples and
+        queries are the same bits before and after; every setter's state is kept; a flat scene is left alone."""
+        if builder not in ("sah", "lbvh"):
+            raise RuntimeError("builder: \"sah\" or \"lbvh\", not %r" % (builder,))
+        L.check(L.lib().mtsamd_scene_rebuild_accel_with(self._handle, ("sah", "lbvh").index(builder), 0, _stream()))
+
+    def rebuild_levels(self):
+        """Measurement aid (mtsamd_scene_rebuild_levels): [(nodes, milliseconds)] per level of the last rebuild_accel(builder="sah")"""
+        n = C.c_uint32(0)
+        L.check(L.lib().mtsamd_scene_rebuild_levels(self._handle, 0, None, None, C.byref(n)))
+        nodes, ms = (C.c_uint32 * max(n.value, 1))(), (C.c_float * max(n.value, 1))()
+        L.check(L.lib().mtsamd_scene_rebuild_levels(self._handle, n.value, nodes, ms, C.byref(n)))
+        return [(int(nodes[i]), float(ms[i])) for i in range(n.value)]
 
     def accel_info(self, sah_cost=False):
         """mtsamd_scene_accel_info: counts and depths of the accelerator, its builder ("sah": creation, "lbvh": a rebuild), the number of
@@ -889,12 +900,13 @@ class Scene:
         for it.  normals="recompute" recomputes them in the library instead (mtsamd_compute_vertex_normals' fp32 arithmetic, on the device
         for hierarchy scenes): with a device tensor no vertex data is copied to the host, the description is brought up to date when it is
         next read, and the call returns the (N, 3) normals as a device tensor.
-        The accelerator is refitted (accel="refit") or, after the update, rebuilt in the same call (accel="rebuild": rebuild_accel);
+        The accelerator is refitted (accel="refit") or, after the update, rebuilt in the same call (accel="rebuild": rebuild_accel();
+        accel="rebuild-sah": rebuild_accel(builder="sah"));
         bbox(), the emitter tables and the scene description follow."""
         shape = int(shape)
-        if accel not in ("refit", "rebuild"):
-            raise RuntimeError("accel: \"refit\" or \"rebuild\", not %r" % (accel,))
-        rebuild = accel == "rebuild"
+        if accel not in ("refit", "rebuild", "rebuild-sah"):
+            raise RuntimeError("accel: \"refit\", \"rebuild\" or \"rebuild-sah\", not %r" % (accel,))
+        rebuild = {"refit": 0, "rebuild": 2, "rebuild-sah": 2 | 8}[accel]          # MTSAMD_VERTICES_REBUILD_ACCEL, .._ACCEL_SAH
         if not 0 <= shape < self._shape_count:
             raise RuntimeError("invalid shape index %d (the scene has %d shapes)" % (shape, self._shape_count))
         if isinstance(normals, str):
@@ -932,7 +944,7 @@ class Scene:
         elif normals is not None:
             raise RuntimeError("shape %d was created without vertex normals: none can be set" % shape)
         if rebuild:
-            L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, p_arg, n_arg, 2, None, _stream()))
+            L.check(L.lib().mtsamd_scene_update_vertices(self._handle, shape, p_arg, n_arg, rebuild, None, _stream()))
         else:
             L.check(L.lib().mtsamd_scene_set_vertex_positions(self._handle, shape, p_arg, n_arg, _stream()))
         # the scene description follows the device, as for the other setters

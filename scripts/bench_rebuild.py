@@ -2,12 +2,13 @@
 """What an accelerator rebuild costs and what the rebuilt tree is worth, on scenes.matpreview() (a displaced sphere of ~262 k triangles,
 a ground plane, an area light, an envmap).
 
-(a) `rebuild`: Scene.rebuild_accel() end to end, synchronised wall clock per call; beside it `refit` (mtsamd_scene_set_vertex_positions
+(a) `rebuild`: Scene.rebuild_accel(builder=...) end to end per --builder (`lbvh`, `sah` or `both`; the figure carries the builder),
+    synchronised wall clock per call, and for the SAH builder the host's wall time per level of the last build; beside it `refit` (mtsamd_scene_set_vertex_positions
     with arrays on the device) and `create` (render.Scene of the same description: the only alternative without the rebuild).  Run the
     script with --lib on a build of the parent commit to time creation there (--create-only implied).  The split by stage comes from a
     kernel trace of `--no-renders`, taken in a run of its own.
 (b) tree quality: triangle tests per closest-hit query, the time of one 256x192x16 render and accel_info's SAH cost for four trees --
-    the SAH tree of a fresh scene, that tree refitted, the LBVH of a rebuild -- without a move, after each of bench_vertex_update.py's
+    the SAH tree of a fresh scene, that tree refitted, the LBVH of a rebuild, the SAH tree of a rebuild -- without a move, after each of bench_vertex_update.py's
     three moves, and after one large deformation (squash to a tenth of the height plus a jitter of 0.2).
 One JSON line per figure: the median and the range of --rounds timings after --warmup.  No threshold: these are first measurements."""
 import argparse
@@ -61,13 +62,15 @@ def main():
     ap.add_argument("--theta", type=int, default=256)
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--spp", type=int, default=16)
+    ap.add_argument("--builder", choices=("lbvh", "sah", "both"), default="both", help="the builder(s) of the rebuilds that are timed and rendered")
+    ap.add_argument("--moves", default=None, help="comma-separated subset of the deformations of (b)")
     ap.add_argument("--lib", default=None, help="time scene creation with this libmtsamd.so (a build of another commit)")
     ap.add_argument("--create-only", action="store_true")
     ap.add_argument("--no-renders", action="store_true", help="stop after the timings of (a) (the run under the kernel trace)")
     a = ap.parse_args()
     if a.lib:
         L.LIB_PATH = os.path.abspath(a.lib)
-        for name in ("mtsamd_scene_rebuild_accel", "mtsamd_scene_accel_info"):
+        for name in ("mtsamd_scene_rebuild_accel", "mtsamd_scene_accel_info", "mtsamd_scene_rebuild_accel_with", "mtsamd_scene_rebuild_levels"):
             L.SYMBOLS.pop(name, None)
         a.create_only = True
     assert torch.cuda.is_available(), "this benchmark needs a HIP device"
@@ -96,17 +99,27 @@ def main():
         p, n = sets[(k + 1) % 2]
         L.check(lib.mtsamd_scene_set_vertex_positions(scene._handle, SPHERE, C.c_void_p(p.data_ptr()), C.c_void_p(n.data_ptr()), stream))
     report("refit", timed(refit, a.rounds, a.warmup), triangles=n_tris)
-    report("rebuild", timed(lambda k: scene.rebuild_accel(), a.rounds, a.warmup), triangles=n_tris, info=scene.accel_info(sah_cost=True))
+    builders = ("lbvh", "sah") if a.builder == "both" else (a.builder,)
+    for builder in builders:
+        report("rebuild", timed(lambda k: scene.rebuild_accel(builder=builder), a.rounds, a.warmup), builder=builder, triangles=n_tris,
+               info=scene.accel_info(sah_cost=True))
+        if builder == "sah":
+            levels = scene.rebuild_levels()
+            print(json.dumps(dict(figure="rebuild-levels", builder=builder, levels=len(levels), total_ms=sum(ms for _, ms in levels),
+                                  nodes=[m for m, _ in levels], ms=[round(ms, 4) for _, ms in levels])), flush=True)
 
-    def both(k):
-        p, n = sets[(k + 1) % 2]
-        L.check(lib.mtsamd_scene_update_vertices(scene._handle, SPHERE, C.c_void_p(p.data_ptr()), C.c_void_p(n.data_ptr()), 2, None, stream))
-    report("update-and-rebuild", timed(both, a.rounds, a.warmup), triangles=n_tris)
+        def both(k):
+            p, n = sets[(k + 1) % 2]
+            L.check(lib.mtsamd_scene_update_vertices(scene._handle, SPHERE, C.c_void_p(p.data_ptr()), C.c_void_p(n.data_ptr()), 2 | (8 if builder == "sah" else 0),
+                                                     None, stream))
+        report("update-and-rebuild", timed(both, a.rounds, a.warmup), builder=builder, triangles=n_tris)
     if a.no_renders:
         return
 
     sp = scenes.bumpy_sphere_sensor(a.width, a.width * 3 // 4, a.spp, seed=1, max_depth=6)
     for name, p in moves(pos).items():
+        if a.moves and name not in a.moves.split(","):
+            continue
         p32 = np.ascontiguousarray(p, np.float32)
         new = copy.deepcopy(sd)
         new["meshes"][SPHERE] = dict(new["meshes"][SPHERE], positions=p32, normals=normals(p32))
@@ -114,8 +127,9 @@ def main():
         if name != "none":
             trees["refitted-sah"] = render.Scene(copy.deepcopy(sd))
             trees["refitted-sah"].update_vertices(SPHERE, torch.from_numpy(p32).cuda())
-        trees["rebuilt-lbvh"] = render.Scene(copy.deepcopy(sd))
-        trees["rebuilt-lbvh"].update_vertices(SPHERE, torch.from_numpy(p32).cuda(), accel="rebuild")
+        for builder in builders:
+            trees["rebuilt-" + builder] = render.Scene(copy.deepcopy(sd))
+            trees["rebuilt-" + builder].update_vertices(SPHERE, torch.from_numpy(p32).cuda(), accel="rebuild" if builder == "lbvh" else "rebuild-sah")
         films = {}
         for label, s in trees.items():
             integ, sensor = render.PathIntegrator(max_depth=6), render.make_sensor(sp)
