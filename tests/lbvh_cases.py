@@ -97,8 +97,14 @@ class Driver:
             elif key.endswith(".message"):
                 out[key] = rest
             else:
-                out[key] = np.array([int(w, 16) for w in rest.split()], np.uint32)
+                out[key] = hex_words(rest)
         return out
+
+
+def hex_words(text):
+    """the words of one dumped line: every word is printed as %08x, so the digits without the blanks are the big-endian bytes (a
+    32 769-triangle dump holds millions of words: int(w, 16) word by word takes seconds)"""
+    return np.frombuffer(bytes.fromhex(text.replace(" ", "")), dtype=">u4").astype(np.uint32)
 
 
 COUNTS = ("root", "wroot", "wdepth", "n_nodes", "n_wnodes", "n_slots", "depth", "stack_depth")
