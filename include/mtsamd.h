@@ -568,8 +568,8 @@ MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_ren
                                 float *grad1_dev, void *stream);
 /* Forward-mode derivative render: the image of d(image)/d(t) along ONE tangent direction t over the scene parameters -- what
  * ek.set_gradient(param, t); ek.forward(param); ek.gradient(image) leaves behind in docs/examples/10_inverse_rendering/forward_diff.py
- * (docs/src/inverse_rendering/diff_render.rst:332-398).  RGB variant, `path` integrator, plain BSDF records (no blendbsdf / mask, no
- * textured BSDF parameters), any emitter mix, any max_depth.  Every camera sample is replayed with its PCG32 stream through the general
+ * (docs/src/inverse_rendering/diff_render.rst:332-398).  RGB variant, `path` integrator, plain BSDF records (no blendbsdf / mask;
+ * textured BSDF parameters under MTSAMD_FORWARD_PARAM_TEXTURES only), any emitter mix, any max_depth.  Every camera sample is replayed with its PCG32 stream through the general
  * path step with a dual part beside the path; one replay covers all four tangent families, whose contributions add up:
  *   bsdf_tangents         bsdf_count * MTSAMD_BSDF_TANGENT_FLOATS floats on the host: tangent[18 * bsdf + 3 * param + component] for param =
  *                         MTSAMD_PARAM_REFLECTANCE .. MTSAMD_PARAM_SPECULAR_TRANSMITTANCE (ALPHA: component 0 only).  A non-zero entry must
@@ -583,16 +583,29 @@ MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_ren
  *   envmap_tangent_dev    device, envmap height * width * 3: the texels of the envmap (the sampling hierarchy is not differentiated).
  * Each may be NULL, not all four.  Sampling is detached as in the adjoints: directions, pdfs, lobe choices, MIS weights and the survival
  * test are those of the primal path.  The Russian-roulette factor 1 / q (path.cpp:137-141) is differentiated as the reference and
- * mtsamd_render_adjoint do; MTSAMD_FORWARD_DETACH_ROULETTE holds it fixed, the convention of mtsamd_render_adjoint_param. */
-enum { MTSAMD_FORWARD_DETACH_ROULETTE = 1 };
+ * mtsamd_render_adjoint do; MTSAMD_FORWARD_DETACH_ROULETTE holds it fixed, the convention of mtsamd_render_adjoint_param.
+ * MTSAMD_FORWARD_PARAM_TEXTURES (opt-in; without it a scene with textured BSDF parameters is refused; in a scene without them the bit has
+ * no meaning and stays refused with the unknown flag bits, so nothing such a scene is answered today changes) accepts scenes whose records read alpha / alpha_u / alpha_v / specular_reflectance / specular_transmittance from a
+ * texture (mtsamd_texture_binding).  All four families then work as above, the untextured constants of a record with a map included
+ * (eta / k beside an alpha map: plus / minus carry the looked-up values in the textured fields); a non-zero bsdf_tangents entry on a
+ * parameter that its record reads from a texture is refused by name (ALPHA if either roughness is bound), and texture_tangents_dev also
+ * carries the texels of bitmaps bound to BSDF parameters, at the same offsets: at a hit, every bound slot adds its central difference --
+ * that of mtsamd_render_adjoint_param_textures, operation for operation: the two working records perturbed after the lookup, step h
+ * absolute (<= 0: 1 % of the looked-up value, of at least 0.05; h MUST STAY BELOW THE SMALLEST ROUGHNESS OF A MAP), a colour's channels
+ * moved together, one bitmap behind alpha_u and alpha_v moved as one parameter, a discrete lobe counted where both records re-sample the
+ * primal direction -- times the bilinear lookup of the tangent texels over the slot's footprint (per channel for a colour; through the
+ * luminance weights, or channel 0, for a roughness).  A bitmap that serves two bindings thus receives its total derivative.  Checkerboards
+ * have no texels.  The Russian-roulette factor is differentiated for the map texels as for every other family (detached by the detach
+ * bit), which mtsamd_render_adjoint_param_textures never does. */
+enum { MTSAMD_FORWARD_DETACH_ROULETTE = 1, MTSAMD_FORWARD_PARAM_TEXTURES = 2 };
 #define MTSAMD_BSDF_TANGENT_FLOATS 18
 typedef struct {
     const float *bsdf_tangents;        /* host, bsdf_count * 18, or NULL */
     const float *emitter_tangents;     /* host, emitter_count * 3, or NULL (row of an envmap: ignored) */
     const float *texture_tangents_dev; /* device, layout of grad_textures, or NULL */
     const float *envmap_tangent_dev;   /* device, h * w * 3, or NULL */
-    float h;                           /* as mtsamd_render_adjoint_param; <= 0: default */
-    uint32_t flags;
+    float h;                           /* as mtsamd_render_adjoint_param; <= 0: default.  Also the absolute step of the map slots (PARAM_TEXTURES) */
+    uint32_t flags;                    /* MTSAMD_FORWARD_DETACH_ROULETTE | MTSAMD_FORWARD_PARAM_TEXTURES */
 } mtsamd_tangent_desc;
 /* The derivative film of the whole crop window: film_dev (crop_height * crop_width * 5 channels dR, dG, dB, A, W) is ADDED into, through
  * the film stage of mtsamd_render, in passes of whole rows (max_pass_log2 is respected); A and W equal those of the film mtsamd_render
@@ -625,16 +638,24 @@ MTSAMD_API int mtsamd_sample_forward(mtsamd_scene *scene, const mtsamd_render_de
  * run at any max_depth; BSDF scalars and texels record the path's vertices and need 0 <= max_depth <= 16.  The isfinite rule holds per
  * TERM, not per sample as in mtsamd_render_adjoint_param: a term (one vertex's contribution to one slot, one texel footprint, one emitter
  * row or one envmap footprint) that is not finite adds nothing, and the finite terms of the same sample stay.  The slot table uploaded for the wanted scalars belongs to the scene: calls for one scene must be ordered on
- * one stream.  Asynchronous on `stream` once the table is uploaded. */
-enum { MTSAMD_REVERSE_DETACH_ROULETTE = 1 };
+ * one stream.  Asynchronous on `stream` once the table is uploaded.
+ * MTSAMD_REVERSE_PARAM_TEXTURES (opt-in, as MTSAMD_FORWARD_PARAM_TEXTURES: without it, and in scenes without textured BSDF parameters
+ * with it, every refusal and result is what it was)
+ * is the transpose of the forward render with that bit in a scene with textured BSDF parameters: wanted constants of every record (a
+ * wanted flag on a parameter its record reads from a texture is refused by name), reflectance texels, emitter colours and envmap texels
+ * as above, and grad_textures_dev additionally collects, for every bound slot of every recorded vertex, T' (delta dNc + a dW) of the
+ * slot's central difference over the footprint of the slot's lookup -- the texel gradients of mtsamd_render_adjoint_param_textures for
+ * all slots in this one replay, in the same layout, with the Russian-roulette term attached unless the detach bit is set.  In such a
+ * scene any texel gradient records the vertices (8 more bytes each, the uv of the hit) and needs 0 <= max_depth <= 16. */
+enum { MTSAMD_REVERSE_DETACH_ROULETTE = 1, MTSAMD_REVERSE_PARAM_TEXTURES = 2 };
 typedef struct {
     const uint8_t *bsdf_wanted;   /* host, bsdf_count * MTSAMD_BSDF_TANGENT_FLOATS: non-zero = this scalar is wanted; or NULL */
     float *grad_bsdf_dev;         /* device, bsdf_count * 18 floats, ACCUMULATED into at the wanted entries; NULL iff bsdf_wanted is NULL */
     float *grad_emitters_dev;     /* device, emitter_count * 3, ACCUMULATED; or NULL */
     float *grad_textures_dev;     /* device, layout of mtsamd_render_adjoint's grad_textures_dev, ACCUMULATED; or NULL */
     float *grad_envmap_dev;       /* device, h * w * 3, ACCUMULATED; or NULL */
-    float h;                      /* central-difference step, as mtsamd_render_adjoint_param; <= 0: default */
-    uint32_t flags;
+    float h;                      /* central-difference step, as mtsamd_render_adjoint_param; <= 0: default.  Also the step of the map slots */
+    uint32_t flags;               /* MTSAMD_REVERSE_DETACH_ROULETTE | MTSAMD_REVERSE_PARAM_TEXTURES */
 } mtsamd_gradient_desc;
 MTSAMD_API int mtsamd_render_reverse(mtsamd_scene *scene, const mtsamd_render_desc *desc, const float *dloss_dimage_dev,
                                      const float *film_dev, const mtsamd_gradient_desc *grad, void *stream);

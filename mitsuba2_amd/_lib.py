@@ -89,6 +89,7 @@ class TangentDesc(C.Structure):
 
 
 FORWARD_DETACH_ROULETTE = 1
+FORWARD_PARAM_TEXTURES = 2
 BSDF_TANGENT_FLOATS = 18
 
 
@@ -98,6 +99,7 @@ class GradientDesc(C.Structure):
 
 
 REVERSE_DETACH_ROULETTE = 1
+REVERSE_PARAM_TEXTURES = 2
 
 
 # every symbol include/mtsamd.h declares: name -> (restype, argtypes)

@@ -475,10 +475,12 @@ class _Render(torch.autograd.Function):
 class _RenderFused(torch.autograd.Function):
     """render(backward="fused"): the primal pass of _Render, and ONE path replay (mtsamd_render_reverse, k_reverse) for every `bsdf`,
     `bsdf_param`, `texture`, `emitter` and `envmap` key of the backward pass -- one estimator with one Russian-roulette convention.
-    `param_texture` keys keep their own replays (mtsamd_render_adjoint_param_textures)."""
+    `param_texture` keys keep their own replays (mtsamd_render_adjoint_param_textures) unless `param_maps` is set: then they come from
+    that same call (MTSAMD_REVERSE_PARAM_TEXTURES), beside every other key of a scene with textured BSDF parameters."""
 
     @staticmethod
-    def forward(ctx, scene, d, pmap, keys, detach_roulette, *values):
+    def forward(ctx, scene, d, pmap, keys, flags, *values):
+        detach_roulette, ctx.param_maps = bool(flags & 1), bool(flags & 2)
         pmap.update()
         film = _render_film(scene, d)
         ctx.scene, ctx.d, ctx.pmap, ctx.keys, ctx.detach_roulette = scene, d, pmap, keys, detach_roulette
@@ -504,26 +506,28 @@ class _RenderFused(torch.autograd.Function):
         tex_floats = sum(h * w * 3 for (h, w, _) in scene._texture_shapes)
         g_tex = torch.zeros(max(tex_floats, 1), dtype=torch.float32, device=dev) if kinds & {"texture", "param_texture"} else None
         g_env = torch.zeros_like(next(pmap[k] for k in keys if pmap._kind[k][0] == "envmap")) if "envmap" in kinds else None
-        if kinds - {"param_texture"}:
+        fused_kinds = kinds if ctx.param_maps else kinds - {"param_texture"}
+        if fused_kinds:
             gd = L.GradientDesc()
             if g_bsdf is not None:
                 gd.bsdf_wanted = wanted.ctypes.data_as(C.POINTER(C.c_uint8))
                 gd.grad_bsdf_dev = _ptr(g_bsdf)
             gd.grad_emitters_dev = _ptr(g_em) if g_em is not None else None
-            gd.grad_textures_dev = _ptr(g_tex) if "texture" in kinds else None
+            gd.grad_textures_dev = _ptr(g_tex) if fused_kinds & {"texture", "param_texture"} else None
             gd.grad_envmap_dev = _ptr(g_env) if g_env is not None else None
             gd.h = float(pmap.fd_step)
-            gd.flags = L.REVERSE_DETACH_ROULETTE if ctx.detach_roulette else 0
+            gd.flags = (L.REVERSE_DETACH_ROULETTE if ctx.detach_roulette else 0) | \
+                       (L.REVERSE_PARAM_TEXTURES if ctx.param_maps and getattr(scene, "_param_texture", None) else 0)
             L.check(L.lib().mtsamd_render_reverse(scene._handle, C.byref(d), _ptr(gi), _ptr(film), C.byref(gd), _stream()))
         g_slot = {}
-        for slot in sorted({s for k in keys if pmap._kind[k][0] == "param_texture" for s in pmap._kind[k][2]}):
+        for slot in sorted({s for k in keys if pmap._kind[k][0] == "param_texture" and not ctx.param_maps for s in pmap._kind[k][2]}):
             g_slot[slot] = torch.zeros_like(g_tex)
             L.check(L.lib().mtsamd_render_adjoint_param_textures(scene._handle, C.byref(d), _ptr(gi), _ptr(film), int(slot), float(pmap.fd_step),
                                                                  _ptr(g_slot[slot]), _stream()))
         grads = []
         for k in keys:
             kind, idx, extra = pmap._kind[k]
-            if kind == "param_texture":
+            if kind == "param_texture" and not ctx.param_maps:
                 grads.append(sum(_texture_slice(scene, g_slot[s], idx) for s in extra))
             elif kind in ("bsdf", "bsdf_param"):
                 row = 0 if kind == "bsdf" else int(extra)
@@ -556,7 +560,7 @@ def _next_seed(scene, sensor):
     return sensor.sampler().seed_value() + call * 0xD1B54A32D192ED03
 
 
-def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_roulette=False):
+def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_roulette=False, param_maps=False):
     """Forward-mode derivative render: the flat ``H*W*3`` image of d(image)/d(t) along the tangent ``tangents`` -- what
     ``ek.gradient(image)`` holds after ``ek.set_gradient(param, t); ek.forward(param)`` in
     ``docs/examples/10_inverse_rendering/forward_diff.py`` (``diff_render.rst:332-398``).  ``tangents`` maps keys of ``params`` to tensors of
@@ -565,7 +569,10 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
     (``'<bsdf>.alpha.data'``, ...) and vertex positions have no forward derivative here and raise.  ``params.update()`` runs first; the seed
     comes from the call counter exactly as in :func:`render`, so resetting ``_render_counter[id(scene)]`` gives common random numbers with
     it.  ``params.fd_step`` is the step of the central difference behind BSDF constants; ``detach_roulette=True`` holds the
-    Russian-roulette factor fixed (the convention of ``mtsamd_render_adjoint_param``); by default it is differentiated as the reference does."""
+    Russian-roulette factor fixed (the convention of ``mtsamd_render_adjoint_param``); by default it is differentiated as the reference does.
+    ``param_maps=True`` (``MTSAMD_FORWARD_PARAM_TEXTURES``) opens scenes with textured BSDF parameters: every key above works there, and the
+    texels of parameter maps (``'<bsdf>.alpha.data'``, ...) take tangents too, with the step ``params.fd_step`` of
+    ``mtsamd_render_adjoint_param_textures``."""
     if _is_spectral(scene):
         raise RuntimeError("render_forward is implemented for the RGB variant only")
     sensor = scene.sensors()[sensor_index]
@@ -574,7 +581,7 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
         if k not in params:
             raise KeyError(k)
         kind = params._kind[k][0]
-        if kind in ("param_texture", "vertices"):
+        if kind == "vertices" or (kind == "param_texture" and not param_maps):
             raise RuntimeError("%s has no forward-mode derivative: %s" % (k, "texels of BSDF parameter maps are differentiated by the reverse pass only"
                                                                           if kind == "param_texture" else "there is no reparameterised integrator for vertex positions"))
     if not tangents:
@@ -602,7 +609,7 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
             t_em[idx] += t.detach().cpu().reshape(3).numpy()
         elif kind == "envmap":
             t_env = t.detach().to(dev).reshape(params[k].shape).contiguous()
-        else:       # texture
+        else:       # texture, param_texture: the texture buffer at the bitmap's slice
             if t_tex is None:
                 t_tex = torch.zeros(max(sum(h * w * 3 for (h, w, _) in scene._texture_shapes), 1), dtype=torch.float32, device=dev)
             off, w, h = C.c_uint64(), C.c_int32(), C.c_int32()
@@ -616,13 +623,15 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
     td.texture_tangents_dev = _ptr(t_tex) if t_tex is not None else None
     td.envmap_tangent_dev = _ptr(t_env) if t_env is not None else None
     td.h = float(params.fd_step)
-    td.flags = L.FORWARD_DETACH_ROULETTE if detach_roulette else 0
+    # the C interface knows the bit in scenes with textured BSDF parameters only; in any other scene param_maps changes nothing
+    td.flags = (L.FORWARD_DETACH_ROULETTE if detach_roulette else 0) | (L.FORWARD_PARAM_TEXTURES if param_maps and getattr(scene, "_param_texture", None) else 0)
     film = torch.zeros((d.crop_height, d.crop_width, 5), dtype=torch.float32, device=dev)
     L.check(L.lib().mtsamd_render_forward(scene._handle, C.byref(d), C.byref(td), _ptr(film), _stream()))
     return _image_of(film)
 
 
-def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, params=None, backward="families", detach_roulette=False):
+def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, params=None, backward="families", detach_roulette=False,
+           param_maps=False):
     """mitsuba.python.autodiff.render (autodiff.py:121-194): differentiable render returning the flattened RGB image
     (``len == H*W*3``).  ``params`` (or ``optimizer.params``) is the :class:`ParameterMap` whose tensors with
     ``requires_grad`` receive gradients; without one the call is a plain render.  Every call draws new random numbers
@@ -633,7 +642,10 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
     scenes) serves every ``bsdf``, ``bsdf_param``, ``texture``, ``emitter`` and ``envmap`` key with ONE replay, ``mtsamd_render_reverse``,
     the transpose of :func:`render_forward`: emitter keys of ``traverse(scene, emitters=True)`` are then differentiable in any scene, and
     the whole gradient is that of one estimator -- Russian roulette differentiated as the reference does, or held fixed with
-    ``detach_roulette=True`` (the convention of ``mtsamd_render_adjoint_param``).  Texels of parameter maps keep their own replays.
+    ``detach_roulette=True`` (the convention of ``mtsamd_render_adjoint_param``).  Texels of parameter maps keep their own replays, and
+    no other key of a scene with such maps is differentiable, unless ``param_maps=True`` (``MTSAMD_REVERSE_PARAM_TEXTURES``): then that one
+    ``mtsamd_render_reverse`` call serves the maps' texels and every other key of the scene alike, mixed key sets such as (``eta``,
+    ``alpha.data``, a lamp colour) included.  ``backward="families"`` ignores ``param_maps``.
     """
     if backward not in ("families", "fused"):
         raise RuntimeError("backward: \"families\" or \"fused\", not %r" % (backward,))
@@ -669,7 +681,7 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
                 params.update()
             return _image_of(_render_film(scene, d))
         if backward == "fused":
-            return _RenderFused.apply(scene, d, params, keys, bool(detach_roulette), *[params[k] for k in keys])
+            return _RenderFused.apply(scene, d, params, keys, (1 if detach_roulette else 0) | (2 if param_maps else 0), *[params[k] for k in keys])
         return _Render.apply(scene, d, params, keys, *[params[k] for k in keys])
 
     if not unbiased:

@@ -1991,9 +1991,10 @@ static int check_forward(const mtsamd_scene *s, const mtsamd_render_desc *d, con
     if (!t->bsdf_tangents && !t->emitter_tangents && !t->texture_tangents_dev && !t->envmap_tangent_dev)
         return fail(MTSAMD_ERR_INVALID, "the tangent is empty: bsdf_tangents, emitter_tangents, texture_tangents_dev and envmap_tangent_dev are all null");
     if (int rc = check_desc(d)) return rc;
-    if (t->flags & ~(uint32_t) MTSAMD_FORWARD_DETACH_ROULETTE) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the tangent descriptor", t->flags);
+    // the PARAM_TEXTURES bit is known where it means something, in a scene with textured BSDF parameters; elsewhere it stays refused
+    if (t->flags & ~(uint32_t) (MTSAMD_FORWARD_DETACH_ROULETTE | (s->textured_params ? MTSAMD_FORWARD_PARAM_TEXTURES : 0))) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the tangent descriptor", t->flags);
     if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render is implemented for the RGB variant only");
-    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
+    if (s->textured_params && !(t->flags & MTSAMD_FORWARD_PARAM_TEXTURES)) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
     for (const DevBsdf &b : s->bsdfs)
         if (b.type >= kBsdfBlend) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render does not handle blendbsdf / mask materials");
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render differentiates the path integrator");
@@ -2030,7 +2031,7 @@ static int fill_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mtsa
     f.rp.max_depth = d->max_depth; f.rp.rr_depth = d->rr_depth;
     f.rp.rows = RowMap{ 0, d->crop_height, std::max(d->crop_height, 1), 0, 1 };
     f.rp.store_xyz = store_xyz; f.rp.out_rgba = w.out_rgba; f.rp.out_pos = w.out_pos;
-    f.flags = t->flags;
+    f.flags = t->flags; f.map_h = t->h;
     if (t->bsdf_tangents && !plus.empty()) {
         const size_t n = plus.size();
         if (int rc = grow(w.fw_plus, w.fw_minus, w.fw_records, n)) return rc;
@@ -2064,7 +2065,7 @@ int mtsamd_render_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mt
     for (uint64_t lr0 = 0; lr0 < (uint64_t) j.rows.local_rows; lr0 += j.fp.rows_per_pass) {
         const Job::Pass p = j.pass(lr0);
         f.rp.first_ordinal = p.a; f.n_samples = p.n;
-        HIP_TRY(launch_forward(f, stream));
+        HIP_TRY(launch_forward(f, s->textured_params, stream));
         j.passes += 1;
         if (int rc = fs.begin(stream, p.lr0, p.nrows, j.fp.tile_h)) return rc;
         if (int rc = fs.put(s->ws.out_rgba, s->ws.out_pos, film)) return rc;
@@ -2090,7 +2091,7 @@ int mtsamd_sample_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mt
     for (uint64_t a = 0; a < count; a += j.pass_cap) {
         const uint64_t n = std::min<uint64_t>(j.pass_cap, count - a);
         f.rp.first_ordinal = first + a; f.n_samples = n;
-        HIP_TRY(launch_forward(f, stream));
+        HIP_TRY(launch_forward(f, s->textured_params, stream));
         HIP_TRY(hipMemcpyAsync(rgba + 4 * a, s->ws.out_rgba, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
         if (pos) HIP_TRY(hipMemcpyAsync(pos + 2 * a, s->ws.out_pos, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
     }
@@ -2106,9 +2107,10 @@ int mtsamd_render_reverse(mtsamd_scene *s, const mtsamd_render_desc *d, const fl
         return fail(MTSAMD_ERR_INVALID, "the gradient is empty: grad_bsdf_dev, grad_emitters_dev, grad_textures_dev and grad_envmap_dev are all null");
     if (!g->grad_bsdf_dev != !g->bsdf_wanted) return fail(MTSAMD_ERR_INVALID, "bsdf_wanted and grad_bsdf_dev go together: one of them is null");
     if (int rc = check_desc(d)) return rc;
-    if (g->flags & ~(uint32_t) MTSAMD_REVERSE_DETACH_ROULETTE) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the gradient descriptor", g->flags);
+    // the PARAM_TEXTURES bit is known where it means something, in a scene with textured BSDF parameters; elsewhere it stays refused
+    if (g->flags & ~(uint32_t) (MTSAMD_REVERSE_DETACH_ROULETTE | (s->textured_params ? MTSAMD_REVERSE_PARAM_TEXTURES : 0))) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the gradient descriptor", g->flags);
     if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render is implemented for the RGB variant only");
-    if (s->textured_params) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
+    if (s->textured_params && !(g->flags & MTSAMD_REVERSE_PARAM_TEXTURES)) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
     for (const DevBsdf &b : s->bsdfs)
         if (b.type >= kBsdfBlend) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render does not handle blendbsdf / mask materials");
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render differentiates the path integrator");
@@ -2142,7 +2144,7 @@ int mtsamd_render_reverse(mtsamd_scene *s, const mtsamd_render_desc *d, const fl
     r.rp.store_xyz = 0; r.rp.out_pos = nullptr; r.rp.out_rgba = nullptr;
     r.n_samples = (uint64_t) d->crop_width * d->crop_height * (uint64_t) d->sample_count;
     r.dimage = dimage; r.film = film;
-    r.flags = g->flags;
+    r.flags = g->flags; r.map_h = g->h;
     r.grad_emitter = s->emitters.empty() ? nullptr : g->grad_emitters_dev;
     r.grad_tex = g->grad_textures_dev; r.grad_env = g->grad_envmap_dev;
     if (!slots.empty()) {
@@ -2155,7 +2157,7 @@ int mtsamd_render_reverse(mtsamd_scene *s, const mtsamd_render_desc *d, const fl
         r.slots = w.rv_slots; r.slot_range = w.rv_range; r.n_slots = (uint32_t) slots.size(); r.grad_bsdf = g->grad_bsdf_dev;
     }
     if (!record && !r.grad_emitter && !r.grad_env) return MTSAMD_OK;      // emitter gradients of a scene without emitters
-    HIP_TRY(launch_reverse(r, record, stream));
+    HIP_TRY(launch_reverse(r, record, s->textured_params, stream));
     return MTSAMD_OK;
 }
 

@@ -163,8 +163,11 @@ struct ForwardParams {
     const float *em_tangent;    // n_emitters * 3: tangent of the emitter colours (row of an envmap: not read), or null
     const float *env_tangent;   // envmap height * width * 3, or null
     uint32_t flags;             // kForwardDetachRoulette
+    float map_h;                // nest launches: the absolute step of the map slots' central differences (<= 0: 1 % of the value at the hit);
+                                // it sits in what was the struct's tail padding, so the argument block keeps its size
 };
-hipError_t launch_forward(const ForwardParams &f, hipStream_t s);
+// nest: the scene has textured BSDF parameters (k_forward<FLAT, true>: the step that resolves them, and tangents on the maps' texels)
+hipError_t launch_forward(const ForwardParams &f, bool nest, hipStream_t s);
 
 // k_reverse: the transpose of k_forward -- one replay of every camera sample, one dLoss/dImage, the gradient of every parameter the
 // forward mode knows.  An argument block of its own: AdjointParams and ForwardParams stay what they were.
@@ -192,10 +195,12 @@ struct ReverseParams {
     float *grad_tex;            // layout of AdjointParams::grad_tex, accumulated, or null
     float *grad_env;            // envmap height * width * 3, accumulated, or null
     uint32_t flags;             // kReverseDetachRoulette
+    float map_h;                // nest launches: as ForwardParams::map_h (tail padding as well)
 };
 // record = true: the replay keeps its vertices (at most 16, 0 <= max_depth <= 16) and sweeps them backwards -- BSDF scalars and texels;
 // false: emitter colours and envmap texels only, accumulated while the path runs, any max_depth
-hipError_t launch_reverse(const ReverseParams &r, bool record, hipStream_t s);
+// nest: the scene has textured BSDF parameters (k_reverse<FLAT, RECORD, true>); grad_tex then also collects the texels of the maps
+hipError_t launch_reverse(const ReverseParams &r, bool record, bool nest, hipStream_t s);
 
 struct RayStreams {
     const float *ox, *oy, *oz, *dx, *dy, *dz, *mint, *maxt;

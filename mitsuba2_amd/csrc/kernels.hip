@@ -3903,6 +3903,34 @@ __global__ __launch_bounds__(kBlock) void k_adjoint_param_tex(const AdjointParam
 
 hipError_t launch_adjoint_param_tex(const AdjointParams &a, hipStream_t s) { return launch_adjoint_kernel<k_adjoint_param_tex<true>, k_adjoint_param_tex<false>>(a, s); }
 
+// One map slot at one hit outside k_adjoint_param_tex -- the NEST forms of TangentProbe / ReverseProbe, which visit EVERY bound slot of a
+// record in one replay -- is ParamTexRecorder itself on a vertex record of its own: its footprint and step rules (surface), its central
+// difference (dvalue) and its rule for the sampled direction (bsdf_sampled) are called, not restated.
+// Does the record `bsdf` (after resolve_textured) read q.slot from a bitmap at uv?  Fills q.r.texel / w1 / texture / lum and the step
+MTS_DEV bool param_tex_hit(ParamTexRecorder &q, const DevBsdf &bsdf, f2 uv) {
+    SurfaceInteraction si; si.uv = uv;
+    q.r.texel = kNoPrim;
+    q.surface(si, bsdf, mk3(0.0f, 0.0f, 0.0f), kNoPrim, uv, mk3(0.0f, 0.0f, 0.0f));
+    return q.here;
+}
+// d(weight)/d(parameter) at the sampled direction: d(value) / pdf of a smooth lobe, the re-sampled difference of a discrete one
+MTS_DEV f3 param_tex_dweight(ParamTexRecorder &q, const DevBsdf &bsdf, f3 refl, f3 wi, f3 wo, float pdf, bool delta, float s1, f2 s2) {
+    SurfaceInteraction si; si.wi = wi;
+    BsdfSample bs; bs.wo = wo; bs.pdf = pdf; bs.delta = delta;
+    q.r.dW = mk3(0.0f, 0.0f, 0.0f);
+    q.bsdf_sampled(q.sv, si, bsdf, refl, mk3(0.0f, 0.0f, 0.0f), bs, mk3(0.0f, 0.0f, 0.0f), s1, s2);
+    return q.r.dW;
+}
+// A roughness reaches the RGB texel through what resolve_textured applied (the sweep of k_adjoint_param_tex): the luminance weights where
+// the kBsdfAlpha?Lum flag is set, else channel 0.  gg: the per-channel gradient with respect to the slot's parameter
+MTS_DEV void param_tex_chain(int slot, uint32_t lum, float gg[3]) {
+    if (slot == kTexAlphaU || slot == kTexAlphaV) {
+        const float g = (gg[0] + gg[1]) + gg[2];
+        gg[0] = lum ? 0.212671f * g : g; gg[1] = lum ? 0.715160f * g : 0.0f; gg[2] = lum ? 0.072169f * g : 0.0f;
+    }
+}
+
+
 // ---------------------------------------------------------------------------------------------
 // Forward mode: the image of d(radiance)/d(t) along ONE tangent direction t over the scene parameters -- what ek.forward() leaves in
 // ek.gradient(image) (docs/examples/10_inverse_rendering/forward_diff.py, docs/src/inverse_rendering/diff_render.rst:332-398).  A tangent
@@ -3919,6 +3947,16 @@ hipError_t launch_adjoint_param_tex(const AdjointParams &a, hipStream_t s) { ret
 // reference and k_adjoint / k_adjoint_tex): where q is not clamped, d rq = -rq^2 eta^2 d thr_c on the channel c that sets q -- the forward
 // form of the `corr` term of those sweeps.  kForwardDetachRoulette: dthr *= rq only (ParamGradProbe::roulette).  Everything else is
 // detached, as in the adjoints: directions, pdfs, lobe choices, MIS weights, the survival test.
+// the fields of `cur` (after resolve_textured) that a texture wrote, copied into another copy of the same record
+MTS_DEV void copy_textured(const DevBsdf &cur, DevBsdf &b) {
+    if (!(cur.flags & kBsdfTexParams)) return;
+    if (bsdf_param_texture(cur, kTexAlphaU)) b.alpha_u = cur.alpha_u;
+    if (bsdf_param_texture(cur, kTexAlphaV)) b.alpha_v = cur.alpha_v;
+    if (bsdf_param_texture(cur, kTexSpec)) { b.sr = cur.sr; b.sg = cur.sg; b.sb = cur.sb; }
+    if (bsdf_param_texture(cur, kTexTrans)) { b.kr = cur.kr; b.kg = cur.kg; b.kb = cur.kb; }
+}
+
+template <bool NEST = false>
 struct TangentProbe {
     static constexpr bool kFactoredEmitter = true, kMirrorTwoSided = false, kSamples = true;
     const ForwardParams &F;
@@ -3928,6 +3966,7 @@ struct TangentProbe {
     int32_t rec; float inv_2h;      // its index; != 0: the record carries a BSDF tangent
     bool tex; f3 drefl;             // a bitmap reflectance with a texel tangent was looked up: d refl
     f3 dle;                         // d radiance of the emitter sample of this step (falloff, r1, r2 not applied)
+    bool maps;                      // NEST: the record reads parameters from textures and there are texel tangents
 
     MTS_DEV static float em_geo(const SceneView &sv, const NeeTerms &t) {       // spec / radiance of the emitter sample (EmitterGradProbeS::em_geo)
         const float g = t.ds.delta ? t.ds.falloff * t.r1 : t.r1;
@@ -3955,10 +3994,45 @@ struct TangentProbe {
         uint32_t tt; f2 tw;
         rp = eval_reflectance(sv, bp, si.uv, tt, tw); rm = eval_reflectance(sv, bm, si.uv, tt, tw);
     }
+    // the record of this step in a perturbed table; NEST: its textured fields carry what resolve_textured looked up at the hit, bit for bit
+    MTS_DEV DevBsdf side(const DevBsdf *table) const {
+        DevBsdf b = table[rec];
+        if constexpr (NEST) copy_textured(*cur, b);
+        return b;
+    }
+    // NEST, slot `slot` of the record of this step: its footprint and step, and the tangent of its parameter -- the bilinear lookup of the
+    // tangent texels over that footprint, per channel for a colour, through the luminance / channel-0 rule for a roughness
+    MTS_DEV bool map_slot(const SurfaceInteraction &si, ParamTexRecorder &q, f3 &dt) const {
+        if (!param_tex_hit(q, *cur, si.uv)) return false;
+        const VertexRecP &m = q.r;
+        const DevTexture t = q.sv.textures[m.texture];
+        const float *tt = F.tex_tangent + t.grad_offset + 3u * (size_t) m.texel;
+        const float w00 = (1.0f - m.w1.y) * (1.0f - m.w1.x), w10 = (1.0f - m.w1.y) * m.w1.x, w01 = m.w1.y * (1.0f - m.w1.x), w11 = m.w1.y * m.w1.x;
+        float d[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) d[ch] = fmaf(w11, tt[3 * t.w + 3 + ch], fmaf(w01, tt[3 * t.w + ch], fmaf(w10, tt[3 + ch], w00 * tt[ch])));
+        if (q.slot <= kTexAlphaV) d[0] = d[1] = d[2] = m.lum ? fmaf(0.072169f, d[2], fmaf(0.715160f, d[1], 0.212671f * d[0])) : d[0];
+        dt = mk3(d[0], d[1], d[2]);
+        return true;
+    }
+    // NEST: the map texels' part of d(value)/d(t) at wo_l (bs: of d(weight)/d(t) at the sampled direction instead): over every bound slot,
+    // the slot's central difference (ParamTexRecorder's) times the tangent of its parameter
+    MTS_DEV f3 map_dvalue(const SceneView &sv, const SurfaceInteraction &si, f3 wo_l, const BsdfSample *bs, float s1, f2 s2) const {
+        f3 sum = mk3(0.0f, 0.0f, 0.0f);
+#pragma unroll 1
+        for (int slot = kTexAlphaU; slot <= kTexTrans; ++slot) {
+            VertexRecP v; ParamTexRecorder q = { v, sv, slot, F.map_h };
+            f3 dt;
+            if (!map_slot(si, q, dt)) continue;
+            const f3 dv = bs ? param_tex_dweight(q, *cur, refl0, si.wi, bs->wo, bs->pdf, bs->delta, s1, s2) : q.dvalue(*cur, refl0, si.wi, wo_l);
+            sum = mk3(fmaf(dv.x, dt.x, sum.x), fmaf(dv.y, dt.y, sum.y), fmaf(dv.z, dt.z, sum.z));
+        }
+        return sum;
+    }
     // d(value)/d(t) of the model at fixed directions: the central difference over the BSDF constants (ParamGradProbe::dvalue) ...
     MTS_DEV f3 dvalue(const SceneView &sv, const SurfaceInteraction &si, f3 wo_l) const {
         if (inv_2h == 0.0f) return mk3(0.0f, 0.0f, 0.0f);
-        const DevBsdf bp = F.plus[rec], bm = F.minus[rec];
+        const DevBsdf bp = side(F.plus), bm = side(F.minus);
         f3 rp, rm, vp, vm; float pp, pm;
         perturbed_refl(sv, si, bp, bm, rp, rm);
         bsdf_eval_pdf(bp, rp, si.wi, wo_l, vp, pp);      // the model code itself (two-sided adapter included), no nesting
@@ -3967,10 +4041,11 @@ struct TangentProbe {
     }
     // ... + d: the chain through the textured reflectance, dr = d(value or weight)/d(refl) in closed form
     MTS_DEV f3 chain(f3 d, f3 dr) const { return mk3(fmaf(dr.x, drefl.x, d.x), fmaf(dr.y, drefl.y, d.y), fmaf(dr.z, drefl.z, d.z)); }
-    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) {
-        static_assert(GENERAL && DEFER == 0 && !NEST, "the forward-mode derivative rides on the plain general fused step");
+    template <int DEFER, bool GENERAL, bool NEST_> MTS_DEV void begin(const PathState &s) {
+        static_assert(GENERAL && DEFER == 0 && NEST_ == NEST, "the forward-mode derivative rides on the general fused step of its scene");
         thr0 = s.thr; eta2 = s.eta * s.eta;
         cur = nullptr; rec = -1; inv_2h = 0.0f; tex = false;
+        if constexpr (NEST) maps = false;
         refl0 = drefl = dle = mk3(0.0f, 0.0f, 0.0f);
     }
     MTS_DEV void pick_up(float ew, f3 le, f3 d_le) {
@@ -4009,18 +4084,21 @@ struct TangentProbe {
             for (int ch = 0; ch < 3; ++ch) d[ch] = fmaf(w11, tt[3 * t.w + 3 + ch], fmaf(w01, tt[3 * t.w + ch], fmaf(w10, tt[3 + ch], w00 * tt[ch])));
             drefl = mk3(d[0], d[1], d[2]);
         }
+        if constexpr (NEST) maps = F.tex_tangent != nullptr && (bsdf.flags & kBsdfTexParams) != 0u;
     }
     // the shadow ray is traced wherever the derivative may be non-zero, also where the radiance itself is 0
     MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &, f3, const NeeTerms &t) {
         dle = mk3(0.0f, 0.0f, 0.0f);
         if (sv.n_emitters != 0u) dle = t.kind == kEmitterEnvmap ? env_tangent(*sv.envmap, t.ds.uv.x, t.ds.uv.y) : emitter_tangent(t.ds.emitter);
         const bool lit = em_geo(sv, t) != 0.0f && (dle.x != 0.0f || dle.y != 0.0f || dle.z != 0.0f);
+        if constexpr (NEST) if (maps) return true;
         return lit || inv_2h != 0.0f || tex || dthr.x != 0.0f || dthr.y != 0.0f || dthr.z != 0.0f;
     }
     // d(mis thr bv spec) with mis fixed: (dthr bv + thr dbv) spec + thr bv em_geo dLe
     MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &si, f3 thr, const NeeTerms &t) {
         f3 dbv = dvalue(sv, si, t.wo);
         if (tex) dbv = chain(dbv, bsdf_dvalue_drefl(*cur, refl0, t.wi, t.wo));
+        if constexpr (NEST) if (maps) dbv = dbv + map_dvalue(sv, si, t.wo, nullptr, 0.0f, f2{ 0.0f, 0.0f });
         const float g = em_geo(sv, t);
         const f3 ds = mk3(g * dle.x, g * dle.y, g * dle.z);
         dres = mk3(dres.x + ((t.mis * fmaf(dthr.x, t.bv.x, thr.x * dbv.x)) * t.spec.x + ((t.mis * thr.x) * t.bv.x) * ds.x),
@@ -4036,7 +4114,7 @@ struct TangentProbe {
             dw = mk3(dv.x * ip, dv.y * ip, dv.z * ip);
         } else if (inv_2h != 0.0f && bs.delta) {
             // a discrete lobe: re-sampled with the perturbed records and the same numbers; counts only if both land on the primal direction
-            const DevBsdf bp = F.plus[rec], bm = F.minus[rec];
+            const DevBsdf bp = side(F.plus), bm = side(F.minus);
             f3 rp, rm, wp, wm; BsdfSample bp_, bm_;
             perturbed_refl(sv, si, bp, bm, rp, rm);
             const bool okp = bsdf_sample(bp, rp, si.wi, s1, s2, bp_, wp);
@@ -4046,6 +4124,7 @@ struct TangentProbe {
                 dw = mk3((wp.x - wm.x) * inv_2h, (wp.y - wm.y) * inv_2h, (wp.z - wm.z) * inv_2h);
         }
         if (tex) dw = chain(dw, bsdf_dweight_drefl(bsdf, refl, si.wi, bs));
+        if constexpr (NEST) if (maps) dw = dw + map_dvalue(sv, si, bs.wo, &bs, s1, s2);
         dthr = mk3(fmaf(dthr.x, weight.x, thr.x * dw.x), fmaf(dthr.y, weight.y, thr.y * dw.y), fmaf(dthr.z, weight.z, thr.z * dw.z));
     }
 };
@@ -4055,7 +4134,7 @@ struct TangentProbe {
 // alpha, or -1 where the primal pass drops the sample (non-finite radiance: the store_xyz == 2 rule), so that the A and W channels of
 // the derivative film equal those of the primal film.  A derivative that is not finite while the radiance is finite is written as
 // zero and keeps its weight (the isfinite(g) rule of k_adjoint_param).
-template <bool FLAT>
+template <bool FLAT, bool NEST = false>
 __global__ __launch_bounds__(kBlock) void k_forward(const ForwardParams F) {
     extern __shared__ float4 smem[];
     const RenderParams &P = F.rp;
@@ -4065,10 +4144,10 @@ __global__ __launch_bounds__(kBlock) void k_forward(const ForwardParams F) {
         const uint64_t ordinal = P.first_ordinal + k;
         PathState s;
         generate_path(P, ordinal, (uint32_t) (ordinal / spp), (uint32_t) (ordinal % spp), s);
-        TangentProbe tp = { F };
+        TangentProbe<NEST> tp = { F };
         tp.dthr = tp.dres = mk3(0.0f, 0.0f, 0.0f);
         Counters c = { 0u, 0u, 0u, 0u };
-        while (bounce_step<FLAT, 0, true>(P, lds, s, c, tp)) { }
+        while (bounce_step<FLAT, 0, true, NEST>(P, lds, s, c, tp)) { }
         float alpha = (s.flags & 1u) ? 1.0f : 0.0f;
         if (P.store_xyz && !(isfinite(s.res.x) && isfinite(s.res.y) && isfinite(s.res.z))) alpha = -1.0f;
         f3 d = tp.dres;
@@ -4077,7 +4156,10 @@ __global__ __launch_bounds__(kBlock) void k_forward(const ForwardParams F) {
     }
 }
 
-hipError_t launch_forward(const ForwardParams &f, hipStream_t s) { return launch_adjoint_kernel<k_forward<true>, k_forward<false>>(f, s); }
+static hipError_t launch_forward_nest(const ForwardParams &f, hipStream_t s);      // at the end of the file, with the kernels it instantiates
+hipError_t launch_forward(const ForwardParams &f, bool nest, hipStream_t s) {
+    return nest ? launch_forward_nest(f, s) : launch_adjoint_kernel<k_forward<true, false>, k_forward<false, false>>(f, s);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Reverse mode: the transpose of k_forward.  One replay of every camera sample with one dLoss/dImage gives the gradient of every parameter
@@ -4108,6 +4190,9 @@ struct VertexRecR {
     f3 ms; f2 s2;                   // mis * spec of the emitter sample
 };
 
+// NEST (textured BSDF parameters): the sweep re-resolves the record and recomputes the footprints of its maps from the uv of the hit
+struct VertexRecRN : VertexRecR { f2 uv; };
+
 // the float of DevBsdf at offset `f` (in floats) set to v: a switch over the fields bsdf_param_fields can name, so the record stays in registers
 MTS_DEV void reverse_patch(DevBsdf &b, uint32_t f, float v) {
     switch (f) {
@@ -4127,12 +4212,13 @@ MTS_DEV float *reverse_emitter_bins() {
     return s_em;
 }
 
-template <bool RECORD>
+template <bool RECORD, bool NEST = false>
 struct ReverseProbe {
     static constexpr bool kFactoredEmitter = true, kMirrorTwoSided = false, kSamples = true;
+    using Rec = std::conditional_t<NEST, VertexRecRN, VertexRecR>;
     const ReverseParams &R;
     f3 delta;                       // dLoss/dRadiance of the sample
-    VertexRecR *r;                  // RECORD: the vertex of this step
+    Rec *r;                         // RECORD: the vertex of this step
     f3 thr0;                        // throughput on arrival (emission is picked up before roulette)
     const DevBsdf *cur; f3 refl0;   // the record and reflectance of the surface of this step
     bool tex, slotted;              // a texel gradient / slots of the surface's record are wanted here
@@ -4151,8 +4237,8 @@ struct ReverseProbe {
     MTS_DEV void add_envmap(const DevEnvmap &e, float u, float v, f3 coeff) const {
         if (isfinite(delta.x * coeff.x) && isfinite(delta.y * coeff.y) && isfinite(delta.z * coeff.z)) EnvGradProbe{ delta, R.grad_env }.add(e, u, v, coeff);
     }
-    template <int DEFER, bool GENERAL, bool NEST> MTS_DEV void begin(const PathState &s) {
-        static_assert(GENERAL && DEFER == 0 && !NEST, "the reverse-mode derivative rides on the plain general fused step");
+    template <int DEFER, bool GENERAL, bool NEST_> MTS_DEV void begin(const PathState &s) {
+        static_assert(GENERAL && DEFER == 0 && NEST_ == NEST, "the reverse-mode derivative rides on the general fused step of its scene");
         thr0 = s.thr; cur = nullptr; tex = slotted = false; refl0 = mk3(0.0f, 0.0f, 0.0f);
         if (RECORD) {
             r->T = s.thr; r->invq = 1.0f; r->eta2 = s.eta * s.eta; r->rr_channel = -1;
@@ -4189,18 +4275,20 @@ struct ReverseProbe {
             if (tex) { r->texel = texel; r->w1 = tw1; r->texture = bsdf.texture; }
             const int32_t b = si.shape_rec.bsdf;
             slotted = R.slot_range != nullptr && R.slot_range[b + 1] > R.slot_range[b];
+            // NEST: the texels of the record's maps are wanted -- the vertex keeps what their central differences need, as for a slot
+            if constexpr (NEST) { slotted = slotted || (R.grad_tex != nullptr && (bsdf.flags & kBsdfTexParams) != 0u); r->uv = si.uv; }
             if (slotted) { r->rec = b; r->wi = si.wi; r->refl = refl; }
         }
     }
     // the shadow ray is traced wherever a gradient may be non-zero, also where the radiance itself is 0
     MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &, f3, const NeeTerms &t) {
-        const bool lit = TangentProbe::em_geo(sv, t) != 0.0f && (t.kind == kEmitterEnvmap ? R.grad_env != nullptr : R.grad_emitter != nullptr);
+        const bool lit = TangentProbe<>::em_geo(sv, t) != 0.0f && (t.kind == kEmitterEnvmap ? R.grad_env != nullptr : R.grad_emitter != nullptr);
         // RECORD: Nc feeds the suffix adjoint of EARLIER vertices, in channels where the throughput here may be 0 (GeneralRecorder)
         const bool nc = (t.mis * t.bv.x) * t.spec.x != 0.0f || (t.mis * t.bv.y) * t.spec.y != 0.0f || (t.mis * t.bv.z) * t.spec.z != 0.0f;
         return lit || (RECORD && (tex || slotted || nc));
     }
     MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &, f3 thr, const NeeTerms &t) {
-        const float g = TangentProbe::em_geo(sv, t);
+        const float g = TangentProbe<>::em_geo(sv, t);
         if (g != 0.0f) {
             const f3 c = mk3(((t.mis * thr.x) * t.bv.x) * g, ((t.mis * thr.y) * t.bv.y) * g, ((t.mis * thr.z) * t.bv.z) * g);
             if (t.kind == kEmitterEnvmap) { if (R.grad_env) add_envmap(*sv.envmap, t.ds.uv.x, t.ds.uv.y, c); }
@@ -4255,7 +4343,18 @@ MTS_DEV void reverse_slot_terms(const DevBsdf &base, const ReverseSlot &sl, cons
     }
 }
 
-template <bool FLAT, bool RECORD>
+// dNc and dW of one map slot at a recorded vertex of a NEST replay: the slot's central difference (ParamTexRecorder's) at the recorded
+// directions.  `base` is the record re-resolved at the vertex's uv, q the recorder after param_tex_hit
+MTS_DEV void reverse_map_terms(const DevBsdf &base, ParamTexRecorder &q, const VertexRecR &r, f3 &dnc, f3 &dw) {
+    dnc = dw = mk3(0.0f, 0.0f, 0.0f);
+    if (r.flags & 1u) {
+        const f3 dv = q.dvalue(base, r.refl, r.wi, r.wo_e);
+        dnc = mk3(r.ms.x * dv.x, r.ms.y * dv.y, r.ms.z * dv.z);
+    }
+    if (r.flags & 2u) dw = param_tex_dweight(q, base, r.refl, r.wi, r.wo_s, r.pdf, (r.flags & 4u) != 0u, r.s1, r.s2);
+}
+
+template <bool FLAT, bool RECORD, bool NEST = false>
 __global__ __launch_bounds__(kBlock) void k_reverse(const ReverseParams R) {
     extern __shared__ float4 smem[];
     const RenderParams &P = R.rp;
@@ -4269,18 +4368,18 @@ __global__ __launch_bounds__(kBlock) void k_reverse(const ReverseParams R) {
         PathState s; const f3 delta = adjoint_sample(R, k, s);
         if (delta.x == 0.0f && delta.y == 0.0f && delta.z == 0.0f) continue;       // every term below is proportional to delta
         Counters c = { 0u, 0u, 0u, 0u };
-        ReverseProbe<RECORD> pr = { R, delta, nullptr };
+        ReverseProbe<RECORD, NEST> pr = { R, delta, nullptr };
         if constexpr (!RECORD) {
-            while (bounce_step<FLAT, 0, true>(P, lds, s, c, pr)) { }
+            while (bounce_step<FLAT, 0, true, NEST>(P, lds, s, c, pr)) { }
         } else {
-        VertexRecR rec[kAdjointMaxDepth];
+        typename ReverseProbe<RECORD, NEST>::Rec rec[kAdjointMaxDepth];
         int n = 0;
         bool alive = true;
-        while (alive && n < kAdjointMaxDepth) { pr.r = &rec[n]; alive = bounce_step<FLAT, 0, true>(P, lds, s, c, pr); ++n; }
+        while (alive && n < kAdjointMaxDepth) { pr.r = &rec[n]; alive = bounce_step<FLAT, 0, true, NEST>(P, lds, s, c, pr); ++n; }
         const Geo<FLAT> geo{ P.sv, lds };
         f3 a = mk3(0.0f, 0.0f, 0.0f);
         for (int v = n - 1; v >= 0; --v) {
-            const VertexRecR &r = rec[v];
+            const auto &r = rec[v];
             const f3 Tp = r.T * r.invq;
             if (r.texel != kNoPrim) {
                 const float gg[3] = { Tp.x * fmaf(delta.x, r.dNc.x, a.x * r.dW.x), Tp.y * fmaf(delta.y, r.dNc.y, a.y * r.dW.y),
@@ -4291,9 +4390,31 @@ __global__ __launch_bounds__(kBlock) void k_reverse(const ReverseParams R) {
                 }
             }
             if (r.rec >= 0) {
-                const DevBsdf base = geo.bsdf((uint32_t) r.rec);
-                const uint32_t j1 = R.slot_range[r.rec + 1];
-                for (uint32_t j = R.slot_range[r.rec]; j < j1; ++j) {
+                DevBsdf base = geo.bsdf((uint32_t) r.rec);
+                uint32_t j0, j1;
+                if constexpr (NEST) {
+                    // the working record of the hit, bit for bit: the slots' pairs carry the looked-up values in their textured fields
+                    resolve_textured(P.sv, base, r.uv);
+                    j0 = R.slot_range ? R.slot_range[r.rec] : 0u; j1 = R.slot_range ? R.slot_range[r.rec + 1] : 0u;
+                    // every bound slot's T' (delta dNc + a dW) goes to the texels of its map
+                    if (R.grad_tex && (base.flags & kBsdfTexParams)) {
+#pragma unroll 1
+                        for (int slot = kTexAlphaU; slot <= kTexTrans; ++slot) {
+                            VertexRecP m; ParamTexRecorder q = { m, P.sv, slot, R.map_h };
+                            if (!param_tex_hit(q, base, r.uv)) continue;
+                            f3 dnc, dw;
+                            reverse_map_terms(base, q, r, dnc, dw);
+                            float gg[3] = { Tp.x * fmaf(delta.x, dnc.x, a.x * dw.x), Tp.y * fmaf(delta.y, dnc.y, a.y * dw.y),
+                                            Tp.z * fmaf(delta.z, dnc.z, a.z * dw.z) };
+                            param_tex_chain(slot, m.lum, gg);
+                            if (isfinite(gg[0]) && isfinite(gg[1]) && isfinite(gg[2])) {
+                                const DevTexture t = P.sv.textures[m.texture];
+                                scatter_texel_grad(R.grad_tex, t, m.texel, m.w1, gg);
+                            }
+                        }
+                    }
+                } else { j0 = R.slot_range[r.rec]; j1 = R.slot_range[r.rec + 1]; }
+                for (uint32_t j = j0; j < j1; ++j) {
                     const ReverseSlot sl = R.slots[j];
                     f3 dnc, dw;
                     reverse_slot_terms(base, sl, r, dnc, dw);
@@ -4322,9 +4443,25 @@ __global__ __launch_bounds__(kBlock) void k_reverse(const ReverseParams R) {
             if (s_slot[i] != 0.0f) atomicAdd(R.grad_bsdf + R.slots[i].out, s_slot[i]);
 }
 
-hipError_t launch_reverse(const ReverseParams &r, bool record, hipStream_t s) {
-    return record ? launch_adjoint_kernel<k_reverse<true, true>, k_reverse<false, true>>(r, s)
-                  : launch_adjoint_kernel<k_reverse<true, false>, k_reverse<false, false>>(r, s);
+static hipError_t launch_reverse_nest(const ReverseParams &r, bool record, hipStream_t s);
+hipError_t launch_reverse(const ReverseParams &r, bool record, bool nest, hipStream_t s) {
+    if (nest) return launch_reverse_nest(r, record, s);
+    return record ? launch_adjoint_kernel<k_reverse<true, true, false>, k_reverse<false, true, false>>(r, s)
+                  : launch_adjoint_kernel<k_reverse<true, false, false>, k_reverse<false, false, false>>(r, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// (Last in the file, as k_adjoint_param_tex once was and for the same reason: the six kernels below are instantiated here, after every
+// other kernel of the file, so that the assembler's function and long-branch label numbers of all the others stay what they were.)
+// Scenes with textured BSDF parameters (MTSAMD_FORWARD_PARAM_TEXTURES / MTSAMD_REVERSE_PARAM_TEXTURES): the forward and reverse renders
+// on the fused step that resolves the maps at the hit, NEST = true.  Constants: plus / minus / the slots' pairs carry the looked-up values
+// in their textured fields (TangentProbe::side, the re-resolved `base` of the sweep).  Map texels: every bound slot of the record of a hit
+// is one ParamTexRecorder -- its footprint, step, central difference and discrete-lobe rule -- times the tangent texels looked up over
+// the slot's footprint (forward), or scattered over it (reverse); the roulette factor is attached as for every other family.
+static hipError_t launch_forward_nest(const ForwardParams &f, hipStream_t s) { return launch_adjoint_kernel<k_forward<true, true>, k_forward<false, true>>(f, s); }
+static hipError_t launch_reverse_nest(const ReverseParams &r, bool record, hipStream_t s) {
+    return record ? launch_adjoint_kernel<k_reverse<true, true, true>, k_reverse<false, true, true>>(r, s)
+                  : launch_adjoint_kernel<k_reverse<true, false, true>, k_reverse<false, false, true>>(r, s);
 }
 
 } // namespace mtsamd

@@ -844,11 +844,27 @@ bool bsdf_param_fields(const DevBsdf &b, int32_t kind, int32_t comp, float DevBs
     }
 }
 
+// Does record d read parameter `kind` from a texture (mtsamd_texture_binding)?  Such a parameter has no constant to differentiate: its
+// texels carry the tangent / gradient.  Returns the name of the bound parameter, or null; ALPHA counts if either roughness is bound
+static const char *textured_param(const DevBsdf &d, int32_t kind) {
+    if (!(d.flags & kBsdfTexParams)) return nullptr;
+    if (kind == MTSAMD_PARAM_ALPHA) {
+        const uint32_t tu = bsdf_param_texture(d, kTexAlphaU), tv = bsdf_param_texture(d, kTexAlphaV);
+        if (!tu && !tv) return nullptr;
+        return texture_param_name(tu && tv ? MTSAMD_PARAM_ALPHA : (tu ? MTSAMD_PARAM_ALPHA_U : MTSAMD_PARAM_ALPHA_V));
+    }
+    if (kind == MTSAMD_PARAM_SPECULAR_REFLECTANCE && bsdf_param_texture(d, kTexSpec)) return texture_param_name(kind);
+    if (kind == MTSAMD_PARAM_SPECULAR_TRANSMITTANCE && bsdf_param_texture(d, kTexTrans)) return texture_param_name(kind);
+    return nullptr;
+}
+
 // The two perturbed copies of the BSDF table a forward-mode render differentiates between (k_forward): plus = theta + eps t, minus =
 // theta - eps t per record, eps the largest step that moves no scalar by more than its limit -- h, or with h <= 0 1 % of
 // max(|theta|, 0.05) -- shrunk so that ALPHA and ETA stay above 1e-4, as mtsamd_render_adjoint_param shrinks its step.  inv_2h[b] = 1 / (2 eps)
 // (0: record b has no tangent), taken from the scalar with the largest |t| as t / (plus - minus): for a tangent that is 1 on one scalar
-// and 0 elsewhere the three are bit for bit what mtsamd_render_adjoint_param builds for that scalar.
+// and 0 elsewhere the three are bit for bit what mtsamd_render_adjoint_param builds for that scalar.  A tangent on a parameter the record
+// reads from a texture is refused by name, so a field a texture overwrites at the hit never enters the eps rule, and the pairs of the
+// untextured fields of a record with a map are those of the same record without it.
 int build_tangent_records(const SceneState &st, const float *bsdf_tangents, float h, std::vector<DevBsdf> &plus, std::vector<DevBsdf> &minus,
                           std::vector<float> &inv_2h) {
     const size_t n = st.bsdfs.size();
@@ -866,6 +882,9 @@ int build_tangent_records(const SceneState &st, const float *bsdf_tangents, floa
             for (int32_t comp = 0; comp < 3; ++comp) {
                 if (t[3 * kind + comp] == 0.0f) continue;
                 Scalar &x = sc[n_sc];
+                if (const char *name = textured_param(rec, kind))
+                    return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: %s holds a texture; its texels carry the tangent (texture_tangents_dev), not a constant",
+                                (unsigned) b, name);
                 if (!bsdf_param_fields(rec, kind, comp, x.f0, x.f1))
                     return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u (type %d) has no differentiable parameter of kind %d (component %d of its tangent is not zero)",
                                 (unsigned) b, rec.type, kind, comp);
@@ -919,6 +938,9 @@ int build_reverse_slots(const SceneState &st, const uint8_t *wanted, float h, st
                 const uint32_t out = (uint32_t) (MTSAMD_BSDF_TANGENT_FLOATS * b) + (uint32_t) (3 * kind + comp);
                 if (!wanted[out]) continue;
                 float DevBsdf::*f0, DevBsdf::*f1;
+                if (const char *name = textured_param(rec, kind))
+                    return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: %s holds a texture; its texels carry the gradient (grad_textures_dev), not a constant",
+                                (unsigned) b, name);
                 if (!bsdf_param_fields(rec, kind, comp, f0, f1))
                     return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u (type %d) has no differentiable parameter of kind %d (component %d is wanted)",
                                 (unsigned) b, rec.type, kind, comp);
