@@ -853,15 +853,17 @@ static int vertex_update(mtsamd_scene *s, uint32_t shape, const float *positions
     HIP_TRY(hipMemsetAsync(s->d_refit_flag, 0, sizeof(uint32_t), stream));
     HIP_TRY(launch_refit_check(rv, s->d_stage_pos, nv, off, n_faces, em >= 0 ? s->d_stage_area : nullptr, s->d_refit_flag, stream));
     uint32_t flag = 0;
-    std::vector<float> pmf(em >= 0 ? n_faces : 0), cdf(pmf.size());
+    std::vector<float> pmf(em >= 0 ? n_faces : 0), cdf(pmf.size()), em_pos(em >= 0 ? nv : 0);
     HIP_TRY(hipMemcpyAsync(&flag, s->d_refit_flag, sizeof(flag), hipMemcpyDeviceToHost, stream));
     if (em >= 0 && n_faces) HIP_TRY(hipMemcpyAsync(pmf.data(), s->d_stage_area, n_faces * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (em >= 0 && nv) HIP_TRY(hipMemcpyAsync(em_pos.data(), s->d_stage_pos, nv * sizeof(float), hipMemcpyDeviceToHost, stream));      // an emitter's vertices: its box (fated.h)
     HIP_TRY(hipStreamSynchronize(stream));
     if (flag) return fail(MTSAMD_ERR_INVALID, "shape %u: a vertex has a non-finite coordinate", shape);
     DevEmitter e{};
     if (em >= 0) {       // the cdf is a sequential double sum: the host's, not a scan that rounds differently
         e = s->emitters[em];
         if (int rc = area_distribution(pmf.data(), n_faces, cdf.data(), e)) return rc;
+        emitter_exact_box(em_pos.data(), nv / 3u, e);      // over every vertex of the mesh: at least its triangles; padded by set_scene_bounds
     }
     // the normals of the staged positions into the staging buffer the gather reads: after the refusals, before the commit
     if (recompute) {

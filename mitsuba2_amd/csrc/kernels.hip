@@ -15,6 +15,7 @@
 // owns `seg_cap` slots and a private range of sample ordinals; no atomics and no inter-workgroup
 // traffic are needed, so the result is independent of dispatch order.
 #include "kernels.h"
+#include "fated.h"
 
 namespace mtsamd {
 
@@ -117,9 +118,33 @@ template <bool FLAT> struct BsdfTable<true, FLAT> {
     MTS_DEV DevBsdf operator()(uint32_t i) const { DevBsdf rec = geo.bsdf(i); resolve_textured(geo.sv, rec, uv); return rec; }
 };
 
+// Fated paths (fated.h): called by the render steps (NoProbe / NoProbeS) on the state they hand to the next step -- the ray
+// just spawned, depth already incremented, hm = hmax(thr).  true: that step would end the path whatever it finds (max_depth, or a
+// roulette that is already decided) and the ray cannot reach the triangles of any area emitter, so it could not add emission either.
+// The query is then counted as the step that ran it would have counted it, and the caller ends the path.  Off, wave-uniformly, where
+// the scene's list is empty (an environment emitter, no area emitter, more than kFatedMaxBoxes of them: set_emitter_boxes).
+template <bool FLAT>
+MTS_DEV bool fated_elide(const RenderParams &P, const LdsView &lds, const f3 &o, const f3 &d, float mint, float maxt, float hm, float eta, uint32_t depth,
+                         uint64_t rng_state, Counters &c) {
+    const SceneView &sv = P.sv;
+    if (sv.env_emitter >= 0 || sv.n_emitters == 0u) return false;
+    const DevEmitter *em = FLAT ? lds.emitters : sv.emitters;
+    const uint32_t list = __float_as_uint(em[0].aux[kFatedList]);
+    if (list == 0u) return false;
+    if (!fated_decide(depth, P.max_depth, P.rr_depth, hm, eta, rng_state)) return false;
+    const CullLean q = cull_ray<CullLean>(o.x, o.y, o.z, d.x, d.y, d.z);
+    for (uint32_t l = list; l != 0u; l >>= 8)
+        if (fated_reach(q, em[(l & 0xffu) - 1u].aux, mint, maxt)) return false;
+    if (!MTS_FATED_STATS) ++c.closest;
+    ++c.segments;
+    if (FLAT && !(MTS_CULL_STATS & 1)) c.tri_tests += sv.n_prims;      // the nominal count of the flat closest-hit loops (device_scene.h)
+    return true;
+}
+
 // DEFER: 0 = both ray queries inline (fused kernel); 1 = closest hit precomputed + shadow ray queued (split pipeline of
 // hierarchy scenes); 2 = closest hit inline, shadow ray queued (flat scenes: the any-hit loop then runs on dense batches)
-template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false, class Probe = NoProbe>
+// ELIDE = false: without the fated-path rule (k_mega on diffuse RGB hierarchy scenes, where its registers cost an occupancy step)
+template <bool FLAT, int DEFER = 0, bool GENERAL = false, bool NEST = false, class Probe = NoProbe, bool ELIDE = true>
 MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c, Probe &&probe = Probe{}, Deferred *df = nullptr) {
     using Pr = std::remove_reference_t<Probe>;
     static_assert(!NEST || (GENERAL && DEFER == 0), "blendbsdf / mask run the general fused step");
@@ -270,6 +295,8 @@ MTS_DEV bool bounce_step(const RenderParams &P, const LdsView &lds, PathState &s
     s.maxt = __builtin_inff();
     s.bs_pdf = pdf;
     s.depth += 1u;
+    if constexpr (MTS_FATED_ELIDE && ELIDE && std::is_same_v<Pr, NoProbe>)        // render kernels only: a probe sees every step
+        if (fated_elide<FLAT>(P, lds, s.o, s.d, s.mint, s.maxt, fmaxf(fmaxf(s.thr.x, s.thr.y), s.thr.z), s.eta, s.depth, s.rng.state, c)) return false;
     return true;
 }
 
@@ -779,6 +806,9 @@ MTS_DEV bool bounce_step_spectral(const RenderParams &P, const LdsView &lds, Pat
     s.maxt = __builtin_inff();
     s.bs_pdf = pdf;
     s.depth += 1u;
+    if constexpr (MTS_FATED_ELIDE && MTS_FATED_ELIDE_SPECTRAL && !kWatch)      // as bounce_step; shipped off (fated.h)
+        if (fated_elide<FLAT>(P, lds, s.o, s.d, s.mint, s.maxt, fmaxf(fmaxf(s.thr.v[0], s.thr.v[1]), fmaxf(s.thr.v[2], s.thr.v[3])), s.eta, s.depth,
+                              s.rng.state, c)) return false;
     return true;
 }
 
@@ -1188,6 +1218,23 @@ template <> struct ShadowRing<PathState> {
 };
 static_assert(ShadowRing<PathState>::kFloat4 * 16u == 48u * kShadowRing && ShadowRing<PathStateS>::kFloat4 * 16u == 52u * kShadowRing,
               "ring sizes of shadow_ring_bytes()");
+// RGB ring: a path that dies with its shadow ray pending is not kept a launch as a zombie.  Its entry carries the sample's ordinal and
+// kRingFinal in the slot word (slots and ordinals of a pass stay below 2^31: cursor_sample), and the drain finishes the path.
+constexpr uint32_t kRingFinal = 0x80000000u;
+template <typename State> constexpr bool kRingFinishes = MTS_FATED_ELIDE != 0 && ShadowRing<State>::kSlotInNee;
+// The drain's half: an entry with kRingFinal ends its path here (true).  The slot word holds the sample's ordinal, whose place in the
+// sample stream holds (res.xyz, valid_ray) meanwhile (k_shade); res + nee as for a stored path, then store_result as for any other.
+MTS_DEV bool finish_ring_entry(const RenderParams &P, const float4 &e, bool occluded) {
+    const uint32_t w = __float_as_uint(e.w);
+    if (!(w & kRingFinal)) return false;
+    PathState t;
+    t.ordinal = w & ~kRingFinal;
+    const float4 r = P.out_rgba[t.ordinal];
+    t.res = occluded ? mk3(r.x, r.y, r.z) : mk3(r.x + e.x, r.y + e.y, r.z + e.z);
+    t.flags = r.w != 0.0f ? 1u : 0u;
+    store_result(P, t);
+    return true;
+}
 
 template <typename State, bool GENERAL>
 MTS_DEV void drain_shadow_ring(const RenderParams &P, const LdsView &lds, const ShadowRing<State> &q, uint32_t head, uint32_t count,
@@ -1199,7 +1246,10 @@ MTS_DEV void drain_shadow_ring(const RenderParams &P, const LdsView &lds, const 
         const uint32_t k = (head + lane) & (kShadowRing - 1u);
         const float4 o = q.o[k], d = q.d[k];
         Hit h;
-        if (!traverse<true, true>(P.sv, lds, mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), o.w, d.w, h, c.tri_tests)) {
+        const bool occluded = traverse<true, true>(P.sv, lds, mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), o.w, d.w, h, c.tri_tests);
+        bool finished = false;
+        if constexpr (kRingFinishes<State>) finished = finish_ring_entry(P, q.nee[k], occluded);
+        if (!finished && !occluded) {
             const float4 e = q.nee[k];
             const size_t slot = base + (ShadowRing<State>::kSlotInNee ? __float_as_uint(e.w) : q.slot[k]);
             float4 r = P.out.res[slot];
@@ -1365,8 +1415,17 @@ void k_shade(const RenderParams P) {
                 if (zombie_now) { s.flags &= ~kFlagZombie; finish_path(P, s); alive = false; }
             }
         }
+        // RGB ring: a path that died with its shadow ray pending leaves the pool now.  Its radiance and valid_ray wait in its place of the
+        // sample stream, its ring entry (below) tells the drain to finish it; the workgroup fence ahead of the drain orders write and read.
+        bool final_now = false;
+        if constexpr (INLINE && kRingFinishes<State>) {
+            if (zombie_now && df.pending) {          // (not pending: the camera-path chunk above has finished it)
+                P.out_rgba[s.ordinal] = make_float4(s.res.x, s.res.y, s.res.z, (s.flags & 1u) ? 1.0f : 0.0f);
+                alive = false; final_now = true;
+            }
+        }
         // survivors are compacted to the front of the output segment, their shadow rays into a dense queue of their own
-        const uint64_t m = __ballot(alive), ms = __ballot(alive && df.pending);
+        const uint64_t m = __ballot(alive), ms = __ballot((alive || final_now) && df.pending);
         if (alive) {
             const uint32_t slot = n_out + mask_rank(m);
             // gathering: the segment of wave + 4 q takes the slots [q seg_cap, (q + 1) seg_cap) of this hardware wave
@@ -1391,6 +1450,14 @@ void k_shade(const RenderParams P) {
                     st_stream<kNT>(P.out.nee + q, make_float4(df.nee[0], df.nee[1], df.nee[2], df.nee[3]));
                     st_stream<kNT>(P.out.sh_slot + q, slot);
                 }
+            }
+        }
+        if constexpr (INLINE && kRingFinishes<State>) {
+            if (final_now) {
+                const uint32_t k = (q_head + q_count + mask_rank(ms)) & (kShadowRing - 1u);
+                ring.o[k] = make_float4(df.so.x, df.so.y, df.so.z, df.smint);
+                ring.d[k] = make_float4(df.sd.x, df.sd.y, df.sd.z, df.smaxt);
+                ring.nee[k] = make_float4(df.nee[0], df.nee[1], df.nee[2], __uint_as_float(s.ordinal | kRingFinal));
             }
         }
         n_out += (uint32_t) __popcll(m);
@@ -1451,11 +1518,11 @@ void k_shade(const RenderParams P) {
 // the next one of the workgroup's list at once, every loop trip is one path.cpp iteration (both ray queries inline, as in k_bounce:
 // the floating-point operations on a sample and their order are those of the other schedules, the film is unchanged).
 constexpr uint32_t kFinishMaxPer = 1024u, kFinishLdsDepth = 8u;      // the spill area is sized for k_trace AND for this depth (trace_spill_words)
-template <bool GENERAL, bool FLAT>
-MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c) { return bounce_step<FLAT, 0, GENERAL>(P, lds, s, c); }
-template <bool GENERAL, bool FLAT>
+template <bool GENERAL, bool FLAT, bool ELIDE = true>
+MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathState &s, Counters &c) { return bounce_step<FLAT, 0, GENERAL, false, NoProbe, ELIDE>(P, lds, s, c); }
+template <bool GENERAL, bool FLAT, bool ELIDE = true>
 MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathStateS &s, Counters &c) { return bounce_step_spectral<FLAT, false, GENERAL>(P, lds, s, c); }
-template <bool GENERAL, bool FLAT>
+template <bool GENERAL, bool FLAT, bool ELIDE = true>
 MTS_DEV bool step_fused(const RenderParams &P, const LdsView &lds, PathStateT &s, Counters &c) { return bounce_step_spectral<FLAT, 0, GENERAL, false, NoProbeS, true>(P, lds, s, c); }
 
 template <typename State, bool GENERAL, bool FLAT>
@@ -1558,7 +1625,9 @@ __global__ __launch_bounds__(64) void k_mega(const RenderParams P) {
             if (cursor >= end) break;
             continue;
         }
-        if (busy && !step_fused<GENERAL, FLAT>(P, lds, s, c)) { finish_path(P, s); busy = false; }
+        // diffuse RGB hierarchy scenes: the fated-path rule would cost this kernel its fourth wave per SIMD (126 -> 134 VGPRs), measured
+        // as -6 % on a 261 k-triangle mesh (profiles/r27_ab_fated_elide.txt); the spectral states ignore the flag
+        if (busy && !step_fused<GENERAL, FLAT, FLAT || GENERAL>(P, lds, s, c)) { finish_path(P, s); busy = false; }
     }
     uint32_t tot[4] = { c.closest, c.any, c.segments, c.tri_tests };
 #pragma unroll

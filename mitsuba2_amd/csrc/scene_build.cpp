@@ -4,6 +4,7 @@
 // Reference call stack this replaces:
 //   Scene::Scene -> accel_init -> ShapeKDTree::build          src/librender/scene.cpp:22-98
 #include "scene_build.h"
+#include "fated.h"
 #include "vertex_normals.h"
 
 #include <algorithm>
@@ -390,6 +391,7 @@ int area_emitter(const mtsamd_emitter_desc &ed, uint32_t shape, uint32_t off, ui
     std::memset(&e, 0, sizeof(e));
     e.r = ed.radiance[0]; e.g = ed.radiance[1]; e.b = ed.radiance[2];
     e.shape = shape; e.first_prim = off; e.n_prims = face_count;
+    emitter_exact_box(&hs.tri_pos[9 * (size_t) off], 3 * (size_t) face_count, e);      // padded and listed by set_scene_bounds (stage 6)
     return area_distribution(&hs.area_pmf[off], face_count, &hs.area_cdf[off], e);
 }
 
@@ -1110,6 +1112,38 @@ void set_scene_bounds(SceneState &st) {
     }
     for (DevEmitter &e : st.emitters)           // DirectionalEmitter::set_scene (directional.cpp:65-70)
         if (e.pad0 == kEmitterDirectional) e.radius = radius;
+    set_emitter_boxes(st);
+}
+
+void emitter_exact_box(const float *xyz, size_t n_points, DevEmitter &e) {
+    float lo[3] = { 3e38f, 3e38f, 3e38f }, hi[3] = { -3e38f, -3e38f, -3e38f };
+    for (size_t i = 0; i < n_points; ++i)
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], xyz[3 * i + a]); hi[a] = std::max(hi[a], xyz[3 * i + a]); }
+    for (int a = 0; a < 3; ++a) { e.aux[kFatedExact + a] = lo[a]; e.aux[kFatedExact + 3 + a] = hi[a]; }
+}
+
+// The padded boxes of the area emitters and the scene's list of them (fated.h), with the pad rule of the cluster boxes (stage 7) on the
+// scene box: the largest coordinate magnitude of a box corner is that of a vertex.
+void set_emitter_boxes(SceneState &st) {
+    if (st.emitters.empty()) return;
+    float ext = 0.0f;
+    for (int k = 0; k < 6; ++k) ext = std::max(ext, std::fabs(st.bvh.bbox[k]));
+    const float pad = 1e-4f * std::max(ext, 1e-3f);
+    uint32_t list = 0u, n = 0u;
+    bool off = st.environment >= 0;             // an escaped ray adds radiance
+    for (size_t i = 0; i < st.emitters.size(); ++i) {
+        DevEmitter &e = st.emitters[i];
+        if (e.pad0 != 0u) continue;             // environment and delta emitters own no triangle
+        const float lo[3] = { e.aux[kFatedExact], e.aux[kFatedExact + 1], e.aux[kFatedExact + 2] };
+        const float hi[3] = { e.aux[kFatedExact + 3], e.aux[kFatedExact + 4], e.aux[kFatedExact + 5] };
+        if (std::isfinite(pad)) fated_encode(lo, hi, pad, e.aux);
+        else fated_invalidate(e.aux);
+        if (n < kFatedMaxBoxes && i < 255u) list |= (uint32_t) (i + 1u) << (8u * n);
+        else off = true;
+        ++n;
+    }
+    if (off || n == 0u) list = 0u;
+    std::memcpy(&st.emitters[0].aux[kFatedList], &list, 4);
 }
 
 int check_vertex_update(const SceneState &st, uint32_t shape, const float *positions, const float *normals) {
@@ -1188,6 +1222,7 @@ int set_vertex_positions(SceneState &st, const BuildOptions &opt, uint32_t shape
         e = st.emitters[em];
         for (uint32_t f = 0; f < n; ++f) pmf[f] = triangle_area(&pos[9 * (size_t) f]);
         if (int rc = area_distribution(pmf.data(), n, cdf.data(), e)) return rc;
+        emitter_exact_box(pos.data(), 3 * (size_t) n, e);
     }
     std::copy(pos.begin(), pos.end(), tri_pos.begin() + 9 * (size_t) off);
     if (normals) std::copy(nrm.begin(), nrm.end(), tri_nrm.begin() + 9 * (size_t) off);

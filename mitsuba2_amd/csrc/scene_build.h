@@ -120,7 +120,12 @@ int build_host_scene(const mtsamd_scene_desc *desc, const mtsamd_spectrum_desc *
 float triangle_area(const float *tri_pos9);
 // cdf and emitter fields (area_sum, area_norm, valid_lo / hi) of `face_count` areas; an emitter without area is refused with the reference's text
 int area_distribution(const float *areas, uint32_t face_count, float *cdf, DevEmitter &e);
-void set_scene_bounds(SceneState &st);       // bounding sphere of st.bvh.bbox into the records of the constant, envmap and directional emitters
+// bounding sphere of st.bvh.bbox into the records of the constant, envmap and directional emitters; then set_emitter_boxes
+void set_scene_bounds(SceneState &st);
+// Fated paths (fated.h): the exact box of an area emitter over `n_points` xyz triples that hold all its vertices (creation and every
+// vertex update of its shape), and from these and st.bvh.bbox the padded boxes the device tests and the scene's list of them
+void emitter_exact_box(const float *xyz, size_t n_points, DevEmitter &e);
+void set_emitter_boxes(SceneState &st);
 void build_flat_records(const BuildOptions &opt, const SceneState &st, const std::vector<float> &tri_pos, FlatRecords &out);
 // refusals of a vertex update that need no look at the data, and the one that needs the (host) data
 int check_vertex_update(const SceneState &st, uint32_t shape, const float *positions, const float *normals);
