@@ -568,8 +568,8 @@ MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_ren
                                 float *grad1_dev, void *stream);
 /* Forward-mode derivative render: the image of d(image)/d(t) along ONE tangent direction t over the scene parameters -- what
  * ek.set_gradient(param, t); ek.forward(param); ek.gradient(image) leaves behind in docs/examples/10_inverse_rendering/forward_diff.py
- * (docs/src/inverse_rendering/diff_render.rst:332-398).  RGB variant, `path` integrator, plain BSDF records (no blendbsdf / mask;
- * textured BSDF parameters under MTSAMD_FORWARD_PARAM_TEXTURES only), any emitter mix, any max_depth.  Every camera sample is replayed with its PCG32 stream through the general
+ * (docs/src/inverse_rendering/diff_render.rst:332-398).  RGB variant, `path` integrator, plain BSDF records (blendbsdf / mask under
+ * MTSAMD_FORWARD_NESTED only; textured BSDF parameters under MTSAMD_FORWARD_PARAM_TEXTURES only), any emitter mix, any max_depth.  Every camera sample is replayed with its PCG32 stream through the general
  * path step with a dual part beside the path; one replay covers all four tangent families, whose contributions add up:
  *   bsdf_tangents         bsdf_count * MTSAMD_BSDF_TANGENT_FLOATS floats on the host: tangent[18 * bsdf + 3 * param + component] for param =
  *                         MTSAMD_PARAM_REFLECTANCE .. MTSAMD_PARAM_SPECULAR_TRANSMITTANCE (ALPHA: component 0 only).  A non-zero entry must
@@ -596,8 +596,22 @@ MTSAMD_API int mtsamd_render_adjoint_param(mtsamd_scene *scene, const mtsamd_ren
  * primal direction -- times the bilinear lookup of the tangent texels over the slot's footprint (per channel for a colour; through the
  * luminance weights, or channel 0, for a roughness).  A bitmap that serves two bindings thus receives its total derivative.  Checkerboards
  * have no texels.  The Russian-roulette factor is differentiated for the map texels as for every other family (detached by the detach
- * bit), which mtsamd_render_adjoint_param_textures never does. */
-enum { MTSAMD_FORWARD_DETACH_ROULETTE = 1, MTSAMD_FORWARD_PARAM_TEXTURES = 2 };
+ * bit), which mtsamd_render_adjoint_param_textures never does.
+ * MTSAMD_FORWARD_NESTED (opt-in, under the same rule: known only in an RGB scene with at least one blendbsdf / mask record, the unknown bit
+ * everywhere else; without it such a scene is refused as before) opens scenes with blendbsdf / mask records.  Children are ordinary records:
+ * their constants use their own rows of bsdf_tangents, their reflectance texels texture_tangents_dev.  The weight / opacity of nested
+ * record b is entry 18 * b + 0 (MTSAMD_PARAM_REFLECTANCE, component 0: the field the record keeps it in); every other entry of such a row
+ * is refused by name, and so is entry 0 where the weight holds a texture -- the texels of a bitmap weight take their tangent in
+ * texture_tangents_dev (luminance weights, or channel 0), a checkerboard has none.  With w the clamped weight at the hit and dw the
+ * tangent of the raw value where 0 <= raw <= 1 (0 elsewhere):  blendbsdf, evaluated: df = (1 - w) df0 + w df1 + dw (f1 - f0); sampled,
+ * child i chosen: dW = dW_i + W_i dw s, s = +1 / w for bsdf_1, -1 / (1 - w) for bsdf_0.  mask, evaluated: df = w df_c + dw f_c; child lobe
+ * dW = dW_c + W_c dw / w, null lobe dW = -dw / (1 - w).  The s term is the derivative of the selection probability over itself -- the
+ * probability is detached in the denominator and attached in the integrand, as plastic's lobe choice is here -- so the result is the
+ * derivative of the EXPECTED image; the reference's automatic differentiation has no such term (its comparison masks carry no
+ * derivative) and sees the weight through the emitter-sampling evaluation only.  MIS weights stay detached; the primal returns the
+ * child's pdf after a child lobe but w * pdf in the evaluation, so with area lights or envmaps the weight derivative is that at frozen
+ * MIS weights.  A scene with both nested records and textured BSDF parameters is refused. */
+enum { MTSAMD_FORWARD_DETACH_ROULETTE = 1, MTSAMD_FORWARD_PARAM_TEXTURES = 2, MTSAMD_FORWARD_NESTED = 4 };
 #define MTSAMD_BSDF_TANGENT_FLOATS 18
 typedef struct {
     const float *bsdf_tangents;        /* host, bsdf_count * 18, or NULL */
@@ -646,8 +660,14 @@ MTSAMD_API int mtsamd_sample_forward(mtsamd_scene *scene, const mtsamd_render_de
  * as above, and grad_textures_dev additionally collects, for every bound slot of every recorded vertex, T' (delta dNc + a dW) of the
  * slot's central difference over the footprint of the slot's lookup -- the texel gradients of mtsamd_render_adjoint_param_textures for
  * all slots in this one replay, in the same layout, with the Russian-roulette term attached unless the detach bit is set.  In such a
- * scene any texel gradient records the vertices (8 more bytes each, the uv of the hit) and needs 0 <= max_depth <= 16. */
-enum { MTSAMD_REVERSE_DETACH_ROULETTE = 1, MTSAMD_REVERSE_PARAM_TEXTURES = 2 };
+ * scene any texel gradient records the vertices (8 more bytes each, the uv of the hit) and needs 0 <= max_depth <= 16.
+ * MTSAMD_REVERSE_NESTED (opt-in, as MTSAMD_FORWARD_NESTED: known only in an RGB scene with a blendbsdf / mask record) is the transpose of
+ * the forward render with that bit: a blend vertex scatters into the wanted slots and reflectance texels of both children, scaled by
+ * 1 - w and w (a mask: of its child, by w), and into grad_bsdf_dev[18 * b] of the nested record b -- its weight / opacity, wanted through
+ * bsdf_wanted[18 * b] -- or, for a bitmap weight, into its texels in grad_textures_dev.  Any other wanted entry of a nested record, and
+ * entry 0 of a textured weight, is refused by name.  A wanted BSDF scalar (weights included) or any texel gradient records the vertices:
+ * 0 <= max_depth <= 16; emitter and envmap gradients alone run at any depth.  The per-family adjoints keep refusing nested scenes. */
+enum { MTSAMD_REVERSE_DETACH_ROULETTE = 1, MTSAMD_REVERSE_PARAM_TEXTURES = 2, MTSAMD_REVERSE_NESTED = 4 };
 typedef struct {
     const uint8_t *bsdf_wanted;   /* host, bsdf_count * MTSAMD_BSDF_TANGENT_FLOATS: non-zero = this scalar is wanted; or NULL */
     float *grad_bsdf_dev;         /* device, bsdf_count * 18 floats, ACCUMULATED into at the wanted entries; NULL iff bsdf_wanted is NULL */

@@ -90,6 +90,7 @@ class TangentDesc(C.Structure):
 
 FORWARD_DETACH_ROULETTE = 1
 FORWARD_PARAM_TEXTURES = 2
+FORWARD_NESTED = 4
 BSDF_TANGENT_FLOATS = 18
 
 
@@ -100,6 +101,7 @@ class GradientDesc(C.Structure):
 
 REVERSE_DETACH_ROULETTE = 1
 REVERSE_PARAM_TEXTURES = 2
+REVERSE_NESTED = 4
 
 
 # every symbol include/mtsamd.h declares: name -> (restype, argtypes)

@@ -177,6 +177,27 @@ class ParameterMap:
         for key, t, slots, data in (_parameter_texture_parameters(scene) if not _is_spectral(scene) else []):
             self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
             self._kind[key] = ("param_texture", t, slots)
+        # blendbsdf / mask records of RGB scenes, under the names of the reference's traverse() (blendbsdf.cpp:165-169, mask.cpp:167-170):
+        # '<id>.weight.value|data' / '<id>.opacity.value|data' and the children's parameters under '<id>.bsdf_0.' / '.bsdf_1.' /
+        # '.nested_bsdf.'.  Settable through the setters above; differentiable by render(backward="fused", nested=True) and render_forward(nested=True) only
+        self._nested_scene = not _is_spectral(scene) and any(b["type"] in (B.BLEND, B.MASK) for b in scene._bsdf_records)
+        for i, b in enumerate(scene._bsdf_records if self._nested_scene else []):
+            if b["type"] not in (B.BLEND, B.MASK):
+                continue
+            name = b.get("id", "bsdf_%d" % i)
+            wname = "weight" if b["type"] == B.BLEND else "opacity"
+            w = b["reflectance"]
+            if isinstance(w, dict):
+                if w.get("type") == "bitmap":         # (a checkerboard weight renders but has no texels)
+                    key = "%s.%s.data" % (name, wname)
+                    self.properties[key] = torch.as_tensor(np.ascontiguousarray(w["data"], np.float32), dtype=torch.float32, device=dev).clone()
+                    self._kind[key] = ("texture", scene.texture_index(i), i)
+            else:
+                key = "%s.%s.value" % (name, wname)
+                self.properties[key] = torch.as_tensor([float(w[0])], dtype=torch.float32, device=dev)
+                self._kind[key] = ("nest_weight", i, 0)
+            for c, child in enumerate(b["children"]):
+                self._add_child_keys(scene, child, name + (".bsdf_%d" % c if b["type"] == B.BLEND else ".nested_bsdf"), b["nested"][c], dev)
         # spectral variant with `replay`: the same texel keys, in diffuse and general scenes alike (mtsamd_render_adjoint_spectral)
         for key, i, data in (_texture_parameters(scene._bsdf_records) if self._replay else []):
             self.properties[key] = torch.as_tensor(np.ascontiguousarray(data, np.float32), dtype=torch.float32, device=dev).clone()
@@ -234,6 +255,33 @@ class ParameterMap:
             # the scene was created from these positions: update() pushes the buffer only once it holds something else
             self.__dict__.setdefault("_pushed", {})[key] = (self.properties[key], self.properties[key]._version)
 
+    def _add_child_keys(self, scene, b, prefix, flat_index, dev):
+        """The keys of a plain record that is a child of a blendbsdf / mask (record `flat_index` of the flattened table): what the loops
+        over the top-level records of a general scene add, under `prefix`."""
+        name = prefix + (".brdf_0" if b.get("twosided") and b["type"] != B.DIFFUSE else "")
+        for pname, kind, types in (("reflectance", 0, (B.DIFFUSE,)), ("diffuse_reflectance", 0, (B.PLASTIC, B.ROUGHPLASTIC)),
+                                   ("specular_reflectance", 1, (B.CONDUCTOR, B.ROUGHCONDUCTOR, B.PLASTIC, B.ROUGHPLASTIC, B.DIELECTRIC, B.ROUGHDIELECTRIC, B.THINDIELECTRIC)),
+                                   ("specular_transmittance", 5, (B.DIELECTRIC, B.ROUGHDIELECTRIC, B.THINDIELECTRIC)),
+                                   ("eta", 2, (B.CONDUCTOR, B.ROUGHCONDUCTOR)), ("k", 3, (B.CONDUCTOR, B.ROUGHCONDUCTOR))):
+            if b["type"] not in types:
+                continue
+            src = b["reflectance"] if kind == 0 else b[pname]
+            if pname in b.get("textures", {}):
+                continue
+            if isinstance(src, dict):
+                if kind == 0 and src.get("type") == "bitmap":
+                    key = "%s.%s.data" % (prefix + (".brdf_0" if b.get("twosided") else ""), pname)
+                    self.properties[key] = torch.as_tensor(np.ascontiguousarray(src["data"], np.float32), dtype=torch.float32, device=dev).clone()
+                    self._kind[key] = ("texture", scene.texture_index(flat_index), flat_index)
+                continue
+            key = "%s.%s.value" % (name, pname)
+            self.properties[key] = torch.as_tensor([float(x) for x in src], dtype=torch.float32, device=dev)
+            self._kind[key] = ("bsdf_param", flat_index, kind)
+        if b["type"] in (B.ROUGHCONDUCTOR, B.ROUGHDIELECTRIC) and b["alpha_u"] == b["alpha_v"] and not {"alpha_u", "alpha_v"} & set(b.get("textures", {})):
+            key = name + ".alpha.value"
+            self.properties[key] = torch.as_tensor([float(b["alpha_u"])], dtype=torch.float32, device=dev)
+            self._kind[key] = ("bsdf_param", flat_index, 4)
+
     def __getitem__(self, k): return self.properties[k]
     def __contains__(self, k): return k in self.properties
     def __len__(self): return len(self.properties)
@@ -288,6 +336,8 @@ class ParameterMap:
             elif kind == "bsdf_param":
                 vals = [float(x) for x in v.detach().cpu().reshape(-1).tolist()]
                 self._scene.set_bsdf_param(idx, self._kind[k][2], vals)
+            elif kind == "nest_weight":      # the record keeps its weight / opacity in the reflectance field, all three components
+                self._scene.set_bsdf_reflectance(idx, [float(v.detach().cpu().reshape(-1)[0])] * 3)
             else:
                 self._scene.set_bsdf_reflectance(idx, v.detach().cpu().tolist())
 
@@ -480,7 +530,7 @@ class _RenderFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, scene, d, pmap, keys, flags, *values):
-        detach_roulette, ctx.param_maps = bool(flags & 1), bool(flags & 2)
+        detach_roulette, ctx.param_maps, ctx.nested = bool(flags & 1), bool(flags & 2), bool(flags & 4)
         pmap.update()
         film = _render_film(scene, d)
         ctx.scene, ctx.d, ctx.pmap, ctx.keys, ctx.detach_roulette = scene, d, pmap, keys, detach_roulette
@@ -498,8 +548,8 @@ class _RenderFused(torch.autograd.Function):
         wanted = np.zeros((n_bsdf, L.BSDF_TANGENT_FLOATS), np.uint8)
         for k in keys:
             kind, idx, extra = pmap._kind[k]
-            if kind in ("bsdf", "bsdf_param"):
-                row = 0 if kind == "bsdf" else int(extra)
+            if kind in ("bsdf", "bsdf_param", "nest_weight"):
+                row = int(extra) if kind == "bsdf_param" else 0      # a weight / opacity: entry 18 * record + 0
                 wanted[idx, 3 * row: 3 * row + pmap[k].numel()] = 1
         g_bsdf = torch.zeros((n_bsdf, L.BSDF_TANGENT_FLOATS), dtype=torch.float32, device=dev) if wanted.any() else None
         g_em = torch.zeros((max(len(scene._dict.get("emitters", [])), 1), 3), dtype=torch.float32, device=dev) if "emitter" in kinds else None
@@ -517,7 +567,8 @@ class _RenderFused(torch.autograd.Function):
             gd.grad_envmap_dev = _ptr(g_env) if g_env is not None else None
             gd.h = float(pmap.fd_step)
             gd.flags = (L.REVERSE_DETACH_ROULETTE if ctx.detach_roulette else 0) | \
-                       (L.REVERSE_PARAM_TEXTURES if ctx.param_maps and getattr(scene, "_param_texture", None) else 0)
+                       (L.REVERSE_PARAM_TEXTURES if ctx.param_maps and getattr(scene, "_param_texture", None) else 0) | \
+                       (L.REVERSE_NESTED if ctx.nested and _has_nested_records(scene) else 0)
             L.check(L.lib().mtsamd_render_reverse(scene._handle, C.byref(d), _ptr(gi), _ptr(film), C.byref(gd), _stream()))
         g_slot = {}
         for slot in sorted({s for k in keys if pmap._kind[k][0] == "param_texture" and not ctx.param_maps for s in pmap._kind[k][2]}):
@@ -529,8 +580,8 @@ class _RenderFused(torch.autograd.Function):
             kind, idx, extra = pmap._kind[k]
             if kind == "param_texture" and not ctx.param_maps:
                 grads.append(sum(_texture_slice(scene, g_slot[s], idx) for s in extra))
-            elif kind in ("bsdf", "bsdf_param"):
-                row = 0 if kind == "bsdf" else int(extra)
+            elif kind in ("bsdf", "bsdf_param", "nest_weight"):
+                row = int(extra) if kind == "bsdf_param" else 0
                 grads.append(g_bsdf[idx, 3 * row: 3 * row + pmap[k].numel()].clone().reshape(pmap[k].shape))
             elif kind == "envmap":
                 grads.append(g_env)
@@ -560,7 +611,11 @@ def _next_seed(scene, sensor):
     return sensor.sampler().seed_value() + call * 0xD1B54A32D192ED03
 
 
-def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_roulette=False, param_maps=False):
+def _has_nested_records(scene):
+    return not _is_spectral(scene) and any(b["type"] in (B.BLEND, B.MASK) for b in scene._bsdf_records)
+
+
+def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_roulette=False, param_maps=False, nested=False):
     """Forward-mode derivative render: the flat ``H*W*3`` image of d(image)/d(t) along the tangent ``tangents`` -- what
     ``ek.gradient(image)`` holds after ``ek.set_gradient(param, t); ek.forward(param)`` in
     ``docs/examples/10_inverse_rendering/forward_diff.py`` (``diff_render.rst:332-398``).  ``tangents`` maps keys of ``params`` to tensors of
@@ -572,9 +627,14 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
     Russian-roulette factor fixed (the convention of ``mtsamd_render_adjoint_param``); by default it is differentiated as the reference does.
     ``param_maps=True`` (``MTSAMD_FORWARD_PARAM_TEXTURES``) opens scenes with textured BSDF parameters: every key above works there, and the
     texels of parameter maps (``'<bsdf>.alpha.data'``, ...) take tangents too, with the step ``params.fd_step`` of
-    ``mtsamd_render_adjoint_param_textures``."""
+    ``mtsamd_render_adjoint_param_textures``.  ``nested=True`` (``MTSAMD_FORWARD_NESTED``) opens scenes with blendbsdf / mask records: the
+    children's keys, ``'<id>.weight.value'`` / ``'<id>.opacity.value'`` and the texels of a bitmap weight take tangents; the weight's
+    derivative includes the derivative of the child-selection probability, so the image is the derivative of the expected image
+    (``include/mtsamd.h``).  The keyword is inert in scenes without such records."""
     if _is_spectral(scene):
         raise RuntimeError("render_forward is implemented for the RGB variant only")
+    if _has_nested_records(scene) and not nested:
+        raise RuntimeError("this scene has blendbsdf / mask materials: render_forward differentiates it with nested=True only")
     sensor = scene.sensors()[sensor_index]
     integrator = scene.integrator() if scene.integrator() is not None else PathIntegrator()
     for k in tangents:
@@ -601,8 +661,8 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
         if t.numel() != params[k].numel():
             raise RuntimeError("the tangent of %s has %d elements, the parameter %d" % (k, t.numel(), params[k].numel()))
         used.add(kind)
-        if kind in ("bsdf", "bsdf_param"):
-            row = 0 if kind == "bsdf" else int(extra)
+        if kind in ("bsdf", "bsdf_param", "nest_weight"):
+            row = int(extra) if kind == "bsdf_param" else 0      # a weight / opacity: entry 18 * record + 0
             v = t.detach().cpu().reshape(-1).numpy()
             t_bsdf[idx, 3 * row: 3 * row + len(v)] += v
         elif kind == "emitter":
@@ -616,7 +676,7 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
             L.check(L.lib().mtsamd_scene_texture_info(scene._handle, idx, C.byref(w), C.byref(h), C.byref(off)))
             t_tex[off.value: off.value + 3 * w.value * h.value] = t.detach().to(dev).reshape(-1)
     td = L.TangentDesc()
-    if used & {"bsdf", "bsdf_param"}:
+    if used & {"bsdf", "bsdf_param", "nest_weight"}:
         td.bsdf_tangents = t_bsdf.ctypes.data_as(L.f32p)
     if "emitter" in used:
         td.emitter_tangents = t_em.ctypes.data_as(L.f32p)
@@ -624,14 +684,15 @@ def render_forward(scene, params, tangents, spp=None, sensor_index=0, detach_rou
     td.envmap_tangent_dev = _ptr(t_env) if t_env is not None else None
     td.h = float(params.fd_step)
     # the C interface knows the bit in scenes with textured BSDF parameters only; in any other scene param_maps changes nothing
-    td.flags = (L.FORWARD_DETACH_ROULETTE if detach_roulette else 0) | (L.FORWARD_PARAM_TEXTURES if param_maps and getattr(scene, "_param_texture", None) else 0)
+    td.flags = (L.FORWARD_DETACH_ROULETTE if detach_roulette else 0) | (L.FORWARD_PARAM_TEXTURES if param_maps and getattr(scene, "_param_texture", None) else 0) | \
+               (L.FORWARD_NESTED if nested and _has_nested_records(scene) else 0)      # likewise: the bit exists in scenes with blend / mask records only
     film = torch.zeros((d.crop_height, d.crop_width, 5), dtype=torch.float32, device=dev)
     L.check(L.lib().mtsamd_render_forward(scene._handle, C.byref(d), C.byref(td), _ptr(film), _stream()))
     return _image_of(film)
 
 
 def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, params=None, backward="families", detach_roulette=False,
-           param_maps=False):
+           param_maps=False, nested=False):
     """mitsuba.python.autodiff.render (autodiff.py:121-194): differentiable render returning the flattened RGB image
     (``len == H*W*3``).  ``params`` (or ``optimizer.params``) is the :class:`ParameterMap` whose tensors with
     ``requires_grad`` receive gradients; without one the call is a plain render.  Every call draws new random numbers
@@ -645,7 +706,10 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
     ``detach_roulette=True`` (the convention of ``mtsamd_render_adjoint_param``).  Texels of parameter maps keep their own replays, and
     no other key of a scene with such maps is differentiable, unless ``param_maps=True`` (``MTSAMD_REVERSE_PARAM_TEXTURES``): then that one
     ``mtsamd_render_reverse`` call serves the maps' texels and every other key of the scene alike, mixed key sets such as (``eta``,
-    ``alpha.data``, a lamp colour) included.  ``backward="families"`` ignores ``param_maps``.
+    ``alpha.data``, a lamp colour) included.  ``backward="families"`` ignores ``param_maps``.  A scene with blendbsdf / mask materials is
+    differentiable with ``backward="fused", nested=True`` only (``MTSAMD_REVERSE_NESTED``): the weight / opacity, the children's
+    parameters, the texels of a bitmap weight and every other key of the scene come from that one call; without the keyword a key of such
+    a scene that requires a gradient raises.  ``nested`` is inert in scenes without such materials.
     """
     if backward not in ("families", "fused"):
         raise RuntimeError("backward: \"families\" or \"fused\", not %r" % (backward,))
@@ -680,8 +744,12 @@ def render(scene, spp=None, unbiased=False, optimizer=None, sensor_index=0, para
             if params is not None:
                 params.update()
             return _image_of(_render_film(scene, d))
+        if _has_nested_records(scene) and not (backward == "fused" and nested):
+            raise RuntimeError("%s requires a gradient in a scene with blendbsdf / mask materials: such a scene is differentiated by "
+                               "render(..., backward=\"fused\", nested=True) only" % keys[0])
         if backward == "fused":
-            return _RenderFused.apply(scene, d, params, keys, (1 if detach_roulette else 0) | (2 if param_maps else 0), *[params[k] for k in keys])
+            return _RenderFused.apply(scene, d, params, keys, (1 if detach_roulette else 0) | (2 if param_maps else 0) | (4 if nested else 0),
+                                      *[params[k] for k in keys])
         return _Render.apply(scene, d, params, keys, *[params[k] for k in keys])
 
     if not unbiased:

@@ -1988,17 +1988,14 @@ int mtsamd_render_adjoint_param(mtsamd_scene *s, const mtsamd_render_desc *d, co
 // ---- forward-mode derivative render (docs/examples/10_inverse_rendering/forward_diff.py) -------
 // What both entry points refuse before the device is touched, and the host half of the tangent: the perturbed record tables
 static int check_forward(const mtsamd_scene *s, const mtsamd_render_desc *d, const mtsamd_tangent_desc *t, const void *out, bool film,
-                         std::vector<DevBsdf> &plus, std::vector<DevBsdf> &minus, std::vector<float> &inv_2h) {
+                         std::vector<DevBsdf> &plus, std::vector<DevBsdf> &minus, std::vector<float> &inv_2h, bool &nested) {
+    nested = false;
     if (!s || !d || !t || !out) return fail(MTSAMD_ERR_INVALID, "null argument");
     if (!t->bsdf_tangents && !t->emitter_tangents && !t->texture_tangents_dev && !t->envmap_tangent_dev)
         return fail(MTSAMD_ERR_INVALID, "the tangent is empty: bsdf_tangents, emitter_tangents, texture_tangents_dev and envmap_tangent_dev are all null");
     if (int rc = check_desc(d)) return rc;
-    // the PARAM_TEXTURES bit is known where it means something, in a scene with textured BSDF parameters; elsewhere it stays refused
-    if (t->flags & ~(uint32_t) (MTSAMD_FORWARD_DETACH_ROULETTE | (s->textured_params ? MTSAMD_FORWARD_PARAM_TEXTURES : 0))) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the tangent descriptor", t->flags);
-    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render is implemented for the RGB variant only");
-    if (s->textured_params && !(t->flags & MTSAMD_FORWARD_PARAM_TEXTURES)) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
-    for (const DevBsdf &b : s->bsdfs)
-        if (b.type >= kBsdfBlend) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render does not handle blendbsdf / mask materials");
+    // a flag bit is known where it means something (PARAM_TEXTURES: textured BSDF parameters; NESTED: blend / mask records); elsewhere it stays refused
+    if (int rc = check_derivative_flags(*s, t->flags, false, nested)) return rc;
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render differentiates the path integrator");
     if (d->part_count > 1 || d->row_begin != 0 || d->row_end > 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the forward-mode render covers the whole crop window (no row window, no tile partition)");
     if (film) {
@@ -2017,7 +2014,14 @@ static int check_forward(const mtsamd_scene *s, const mtsamd_render_desc *d, con
     if (t->emitter_tangents)
         for (size_t i = 0; i < 3 * s->emitters.size(); ++i)
             if (!std::isfinite(t->emitter_tangents[i])) return fail(MTSAMD_ERR_INVALID, "emitter %u: its tangent is not finite", (unsigned) (i / 3));
-    return build_tangent_records(*s, t->bsdf_tangents, t->h, plus, minus, inv_2h);
+    if (!nested) return build_tangent_records(*s, t->bsdf_tangents, t->h, plus, minus, inv_2h);
+    // NESTED: the rows of blend / mask records are taken out first; inv_2h of such a record then carries the tangent of its constant weight
+    std::vector<float> rest, weight; std::vector<uint8_t> none_r, none_w;
+    if (int rc = split_nested_rows(*s, t->bsdf_tangents, nullptr, rest, weight, none_r, none_w)) return rc;
+    if (int rc = build_tangent_records(*s, t->bsdf_tangents ? rest.data() : nullptr, t->h, plus, minus, inv_2h)) return rc;
+    for (size_t b = 0; b < s->bsdfs.size(); ++b)
+        if (s->bsdfs[b].type >= kBsdfBlend) inv_2h[b] = weight[b];
+    return MTSAMD_OK;
 }
 
 // The argument block of k_forward but for the samples of a launch; uploads the scene-owned scratch on `stream`.  The host arrays must
@@ -2055,8 +2059,8 @@ static int fill_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mtsa
 }
 
 int mtsamd_render_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mtsamd_tangent_desc *t, float *film, void *stream_) {
-    std::vector<DevBsdf> plus, minus; std::vector<float> inv_2h;
-    if (int rc = check_forward(s, d, t, film, true, plus, minus, inv_2h)) return rc;
+    std::vector<DevBsdf> plus, minus; std::vector<float> inv_2h; bool nested;
+    if (int rc = check_forward(s, d, t, film, true, plus, minus, inv_2h, nested)) return rc;
     hipStream_t stream = (hipStream_t) stream_;
     Job j;
     if (int rc = open_render(j, s, d, stream, 0, 2)) return rc;      // the passes of mtsamd_render for this desc
@@ -2067,7 +2071,7 @@ int mtsamd_render_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mt
     for (uint64_t lr0 = 0; lr0 < (uint64_t) j.rows.local_rows; lr0 += j.fp.rows_per_pass) {
         const Job::Pass p = j.pass(lr0);
         f.rp.first_ordinal = p.a; f.n_samples = p.n;
-        HIP_TRY(launch_forward(f, s->textured_params, stream));
+        HIP_TRY(nested ? launch_forward_nested(f, stream) : launch_forward(f, s->textured_params, stream));
         j.passes += 1;
         if (int rc = fs.begin(stream, p.lr0, p.nrows, j.fp.tile_h)) return rc;
         if (int rc = fs.put(s->ws.out_rgba, s->ws.out_pos, film)) return rc;
@@ -2079,8 +2083,8 @@ int mtsamd_render_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mt
 
 int mtsamd_sample_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mtsamd_tangent_desc *t, uint64_t first, uint64_t count, float *rgba,
                           float *pos, void *stream_) {
-    std::vector<DevBsdf> plus, minus; std::vector<float> inv_2h;
-    if (int rc = check_forward(s, d, t, rgba, false, plus, minus, inv_2h)) return rc;
+    std::vector<DevBsdf> plus, minus; std::vector<float> inv_2h; bool nested;
+    if (int rc = check_forward(s, d, t, rgba, false, plus, minus, inv_2h, nested)) return rc;
     const uint64_t total = (uint64_t) d->crop_width * d->crop_height * (uint64_t) d->sample_count;
     if (first + count > total) return fail(MTSAMD_ERR_INVALID, "sample range exceeds W*H*sample_count");
     if (count == 0) return MTSAMD_OK;
@@ -2093,7 +2097,7 @@ int mtsamd_sample_forward(mtsamd_scene *s, const mtsamd_render_desc *d, const mt
     for (uint64_t a = 0; a < count; a += j.pass_cap) {
         const uint64_t n = std::min<uint64_t>(j.pass_cap, count - a);
         f.rp.first_ordinal = first + a; f.n_samples = n;
-        HIP_TRY(launch_forward(f, s->textured_params, stream));
+        HIP_TRY(nested ? launch_forward_nested(f, stream) : launch_forward(f, s->textured_params, stream));
         HIP_TRY(hipMemcpyAsync(rgba + 4 * a, s->ws.out_rgba, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
         if (pos) HIP_TRY(hipMemcpyAsync(pos + 2 * a, s->ws.out_pos, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
     }
@@ -2109,12 +2113,9 @@ int mtsamd_render_reverse(mtsamd_scene *s, const mtsamd_render_desc *d, const fl
         return fail(MTSAMD_ERR_INVALID, "the gradient is empty: grad_bsdf_dev, grad_emitters_dev, grad_textures_dev and grad_envmap_dev are all null");
     if (!g->grad_bsdf_dev != !g->bsdf_wanted) return fail(MTSAMD_ERR_INVALID, "bsdf_wanted and grad_bsdf_dev go together: one of them is null");
     if (int rc = check_desc(d)) return rc;
-    // the PARAM_TEXTURES bit is known where it means something, in a scene with textured BSDF parameters; elsewhere it stays refused
-    if (g->flags & ~(uint32_t) (MTSAMD_REVERSE_DETACH_ROULETTE | (s->textured_params ? MTSAMD_REVERSE_PARAM_TEXTURES : 0))) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the gradient descriptor", g->flags);
-    if (s->spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render is implemented for the RGB variant only");
-    if (s->textured_params && !(g->flags & MTSAMD_REVERSE_PARAM_TEXTURES)) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)");
-    for (const DevBsdf &b : s->bsdfs)
-        if (b.type >= kBsdfBlend) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render does not handle blendbsdf / mask materials");
+    // a flag bit is known where it means something (PARAM_TEXTURES: textured BSDF parameters; NESTED: blend / mask records); elsewhere it stays refused
+    bool nested = false;
+    if (int rc = check_derivative_flags(*s, g->flags, true, nested)) return rc;
     if (d->integrator != 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render differentiates the path integrator");
     if (d->part_count > 1 || d->row_begin != 0 || d->row_end > 0) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render covers the whole crop window (no row window, no tile partition)");
     if (d->film_rgb != 1) return fail(MTSAMD_ERR_UNSUPPORTED, "the reverse-mode render differentiates an R, G, B, A, W film (film_rgb must be 1)");
@@ -2128,7 +2129,13 @@ int mtsamd_render_reverse(mtsamd_scene *s, const mtsamd_render_desc *d, const fl
         if (!bitmaps) return fail(MTSAMD_ERR_UNSUPPORTED, "grad_textures_dev: the scene has no bitmap textures");
     }
     std::vector<ReverseSlot> slots; std::vector<uint32_t> range;
-    if (int rc = build_reverse_slots(*s, g->bsdf_wanted, g->h, slots, range)) return rc;
+    if (!nested) { if (int rc = build_reverse_slots(*s, g->bsdf_wanted, g->h, slots, range)) return rc; }
+    else {      // NESTED: the rows of blend / mask records are taken out first; a wanted constant weight becomes a slot without a pair
+        std::vector<float> none_r, none_w; std::vector<uint8_t> rest, weight;
+        if (int rc = split_nested_rows(*s, nullptr, g->bsdf_wanted, none_r, none_w, rest, weight)) return rc;
+        if (int rc = build_reverse_slots(*s, g->bsdf_wanted ? rest.data() : nullptr, g->h, slots, range)) return rc;
+        add_weight_slots(weight, slots, range);
+    }
     if (slots.empty() && !g->grad_emitters_dev && !g->grad_textures_dev && !g->grad_envmap_dev)
         return fail(MTSAMD_ERR_INVALID, "the gradient is empty: no BSDF scalar is wanted and the other gradients are null");
     const bool record = !slots.empty() || g->grad_textures_dev;
@@ -2159,7 +2166,7 @@ int mtsamd_render_reverse(mtsamd_scene *s, const mtsamd_render_desc *d, const fl
         r.slots = w.rv_slots; r.slot_range = w.rv_range; r.n_slots = (uint32_t) slots.size(); r.grad_bsdf = g->grad_bsdf_dev;
     }
     if (!record && !r.grad_emitter && !r.grad_env) return MTSAMD_OK;      // emitter gradients of a scene without emitters
-    HIP_TRY(launch_reverse(r, record, s->textured_params, stream));
+    HIP_TRY(nested ? launch_reverse_nested(r, record, stream) : launch_reverse(r, record, s->textured_params, stream));
     return MTSAMD_OK;
 }
 

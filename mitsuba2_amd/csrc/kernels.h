@@ -202,6 +202,15 @@ struct ReverseParams {
 // nest: the scene has textured BSDF parameters (k_reverse<FLAT, RECORD, true>); grad_tex then also collects the texels of the maps
 hipError_t launch_reverse(const ReverseParams &r, bool record, bool nest, hipStream_t s);
 
+// Scenes with blendbsdf / mask records (MTSAMD_FORWARD_NESTED / MTSAMD_REVERSE_NESTED): k_forward_nested<FLAT> / k_reverse_nested<FLAT,
+// RECORD>, on the same argument blocks.  The weight / opacity of a nested record has a closed-form derivative, so it needs no +- pair:
+// forward, inv_2h[b] of a nested record b carries the TANGENT of its constant weight (no plain rule ever reads that entry); reverse, a
+// wanted constant weight is a slot of its record with f0 = f1 = kWeightSlot and out = 18 * b.  Texels of a bitmap weight use tex_tangent /
+// grad_tex like every other bitmap.
+constexpr uint16_t kWeightSlot = 0xffffu;
+hipError_t launch_forward_nested(const ForwardParams &f, hipStream_t s);
+hipError_t launch_reverse_nested(const ReverseParams &r, bool record, hipStream_t s);
+
 struct RayStreams {
     const float *ox, *oy, *oz, *dx, *dy, *dz, *mint, *maxt;
     const uint8_t *active;

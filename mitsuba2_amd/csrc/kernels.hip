@@ -4533,4 +4533,351 @@ static hipError_t launch_reverse_nest(const ReverseParams &r, bool record, hipSt
                   : launch_adjoint_kernel<k_reverse<true, false, true>, k_reverse<false, false, true>>(r, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Scenes with blendbsdf / mask records (MTSAMD_FORWARD_NESTED / MTSAMD_REVERSE_NESTED), after everything else for the reason above.  The
+// probes derive from the NEST = true probes (such a scene has no textured parameters, so their map code is idle) and ride on
+// bounce_step<FLAT, 0, true, true>, the step that resolves the nest in the primal render; at a plain record they ARE their base.  At a
+// blend / mask record, with w the clamped weight of the hit and dw the tangent of the raw value where 0 <= raw <= 1 (else 0):
+//   blendbsdf, evaluated       df = (1 - w) df0 + w df1 + dw (f1 - f0)
+//   ... sampled, child i       dW = dW_i + W_i dw s,   s = +1 / w for bsdf_1, -1 / (1 - w) for bsdf_0
+//   mask, evaluated            df = w df_c + dw f_c
+//   ... sampled                child lobe dW = dW_c + W_c dw / w;   null lobe (W = 1) dW = -dw / (1 - w)
+// df_i / dW_i are the child's existing rules on ITS row of the tables: the central difference between plus[i] and minus[i] (a discrete
+// lobe re-sampled with the rescaled sample1 the primal handed the child), and the texel chain of a bitmap reflectance.  s is the
+// derivative of the selection probability over itself: the probability is a pdf, detached in the denominator and attached in the
+// integrand, as plastic's lobe choice is.  Detached as everywhere: directions, lobe and child choices, pdfs, MIS weights, the rescaled
+// sample1.  A lobe of probability 0 is reached at sample1 == 0 only; s is infinite there and the isfinite rule drops the term.
+struct NestAt { int kind; uint32_t n0, n1; bool two, lum, open; float w; };      // open: 0 <= raw weight <= 1, where d(clamp) = 1
+// nest_info's arithmetic on the value the record's weight reads
+MTS_DEV NestAt nest_at(const DevBsdf &b, f3 v) {
+    NestAt n;
+    n.kind = b.type; n.n0 = b.nested0; n.n1 = b.nested1; n.two = (b.flags & kBsdfTwoSided) != 0u; n.lum = (b.flags & kBsdfWeightLum) != 0u;
+    const float raw = n.lum ? fmaf(0.072169f, v.z, fmaf(0.715160f, v.y, 0.212671f * v.x)) : v.x;
+    n.open = raw >= 0.0f && raw <= 1.0f;
+    n.w = fminf(fmaxf(raw, 0.0f), 1.0f);
+    return n;
+}
+// The lobe surface_bsdf_sample took with sample1: k = 0 / 1: child n0 / n1, with the sample1 it was handed; k = 2: the null lobe of a
+// mask; k = -1: none (a NaN sample).  s = d(selection probability) / d(w) / (selection probability)
+struct NestLobe { int k; float s1, s; };
+MTS_DEV NestLobe nest_lobe(const NestAt &n, float sample1) {
+    NestLobe l = { -1, sample1, 0.0f };
+    const float w = n.w;
+    if (n.kind == kBsdfBlend) {
+        if (sample1 > w) { l.k = 0; l.s1 = (sample1 - w) / (1.0f - w); l.s = -1.0f / (1.0f - w); }
+        else if (sample1 <= w) { l.k = 1; l.s1 = sample1 / w; l.s = 1.0f / w; }
+    } else if (sample1 < w) { l.k = 0; l.s1 = sample1 / w; l.s = 1.0f / w; }
+    else { l.k = 2; l.s = -1.0f / (1.0f - w); }
+    return l;
+}
+// the bilinear lookup of the tangent texels over a footprint (TangentProbe::surface)
+MTS_DEV f3 texel_tangent(const float *tex_tangent, const DevTexture &t, uint32_t texel, f2 tw1) {
+    const float *tt = tex_tangent + t.grad_offset + 3u * (size_t) texel;
+    const float w00 = (1.0f - tw1.y) * (1.0f - tw1.x), w10 = (1.0f - tw1.y) * tw1.x, w01 = tw1.y * (1.0f - tw1.x), w11 = tw1.y * tw1.x;
+    float d[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) d[ch] = fmaf(w11, tt[3 * t.w + 3 + ch], fmaf(w01, tt[3 * t.w + ch], fmaf(w10, tt[3 + ch], w00 * tt[ch])));
+    return mk3(d[0], d[1], d[2]);
+}
+
+struct NestedTangentProbe : TangentProbe<true> {
+    using Base = TangentProbe<true>;
+    NestAt nh;          // kind 0: the record of this step is a plain one
+    f2 uv; float dwt;   // the hit's uv; the tangent of the weight at the hit
+
+    // central difference of child record c at (wi, wo) between its pair, d(value)/d(t) of the constants
+    MTS_DEV f3 child_dvalue(const SceneView &sv, uint32_t c, f3 wi, f3 wo) const {
+        const float i2h = F.inv_2h ? F.inv_2h[c] : 0.0f;
+        if (i2h == 0.0f) return mk3(0.0f, 0.0f, 0.0f);
+        const DevBsdf bp = F.plus[c], bm = F.minus[c];
+        uint32_t tt; f2 tw; f3 vp, vm; float pp, pm;
+        const f3 rp = eval_reflectance(sv, bp, uv, tt, tw), rm = eval_reflectance(sv, bm, uv, tt, tw);
+        bsdf_eval_pdf(bp, rp, wi, wo, vp, pp);
+        bsdf_eval_pdf(bm, rm, wi, wo, vm, pm);
+        return mk3((vp.x - vm.x) * i2h, (vp.y - vm.y) * i2h, (vp.z - vm.z) * i2h);
+    }
+    // d(value)/d(t) of the nest at (wi, wo): its children's rules and the weight's closed form
+    MTS_DEV f3 nest_dvalue(const SceneView &sv, f3 wi, f3 wo) const {
+        f3 sum = mk3(0.0f, 0.0f, 0.0f);
+        if (nh.two) {
+            if (wi.z == 0.0f) return sum;
+            if (wi.z < 0.0f) { wi.z = -wi.z; wo.z = -wo.z; }
+        }
+        const bool blend = nh.kind == kBsdfBlend;
+#pragma unroll 1
+        for (uint32_t k = 0; k < (blend ? 2u : 1u); ++k) {
+            const uint32_t c = k == 0u ? nh.n0 : nh.n1;
+            const DevBsdf b = sv.bsdfs[c];
+            uint32_t tx; f2 tw; f3 v; float p;
+            const f3 rc = eval_reflectance(sv, b, uv, tx, tw);
+            bsdf_eval_pdf(b, rc, wi, wo, v, p);
+            f3 dv = child_dvalue(sv, c, wi, wo);
+            if (F.tex_tangent && tx != kNoPrim) {
+                const f3 dr = bsdf_dvalue_drefl(b, rc, wi, wo), dt = texel_tangent(F.tex_tangent, sv.textures[b.texture], tx, tw);
+                dv = mk3(fmaf(dr.x, dt.x, dv.x), fmaf(dr.y, dt.y, dv.y), fmaf(dr.z, dt.z, dv.z));
+            }
+            const float coef = blend ? (k == 0u ? 1.0f - nh.w : nh.w) : nh.w, dc = blend && k == 0u ? -dwt : dwt;
+            sum = mk3(fmaf(dc, v.x, fmaf(coef, dv.x, sum.x)), fmaf(dc, v.y, fmaf(coef, dv.y, sum.y)), fmaf(dc, v.z, fmaf(coef, dv.z, sum.z)));
+        }
+        return sum;
+    }
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, uint32_t texel, f2 tw1, f3 thr) {
+        nh.kind = 0;
+        if (bsdf.type < kBsdfBlend) { Base::surface(si, bsdf, refl, texel, tw1, thr); return; }
+        cur = &bsdf; refl0 = refl; rec = si.shape_rec.bsdf; inv_2h = 0.0f; tex = false; maps = false;
+        nh = nest_at(bsdf, refl); uv = si.uv; dwt = 0.0f;
+        if (nh.open) {
+            if (texel != kNoPrim) {         // a bitmap weight: the functional of nest_info over the tangent texels
+                if (F.tex_tangent) {
+                    const f3 d = texel_tangent(F.tex_tangent, F.rp.sv.textures[bsdf.texture], texel, tw1);
+                    dwt = nh.lum ? fmaf(0.072169f, d.z, fmaf(0.715160f, d.y, 0.212671f * d.x)) : d.x;
+                }
+            } else if (bsdf.texture < 0 && F.inv_2h) dwt = F.inv_2h[rec];      // a constant weight: its tangent rides in inv_2h (kernels.h)
+        }
+    }
+    MTS_DEV bool emitter_sample(const SceneView &sv, const DevBsdf &bsdf, f3 refl, const NeeTerms &t) {
+        const bool base = Base::emitter_sample(sv, bsdf, refl, t);      // (sets dle)
+        return base || nh.kind != 0;
+    }
+    MTS_DEV void unoccluded(const SceneView &sv, const SurfaceInteraction &si, f3 thr, const NeeTerms &t) {
+        if (nh.kind == 0) { Base::unoccluded(sv, si, thr, t); return; }
+        const f3 dbv = nest_dvalue(sv, t.wi, t.wo);
+        const float g = em_geo(sv, t);
+        const f3 ds = mk3(g * dle.x, g * dle.y, g * dle.z);
+        dres = mk3(dres.x + ((t.mis * fmaf(dthr.x, t.bv.x, thr.x * dbv.x)) * t.spec.x + ((t.mis * thr.x) * t.bv.x) * ds.x),
+                   dres.y + ((t.mis * fmaf(dthr.y, t.bv.y, thr.y * dbv.y)) * t.spec.y + ((t.mis * thr.y) * t.bv.y) * ds.y),
+                   dres.z + ((t.mis * fmaf(dthr.z, t.bv.z, thr.z * dbv.z)) * t.spec.z + ((t.mis * thr.z) * t.bv.z) * ds.z));
+    }
+    // `bsdf` is the working record of the step: after surface_bsdf_sample, the child that was sampled
+    MTS_DEV void bsdf_sampled(const SceneView &sv, const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, f3 thr, const BsdfSample &bs, f3 weight, float s1, f2 s2) {
+        if (nh.kind == 0) { Base::bsdf_sampled(sv, si, bsdf, refl, thr, bs, weight, s1, s2); return; }
+        f3 wi = si.wi, wo = bs.wo;
+        if (nh.two && wi.z < 0.0f) { wi.z = -wi.z; wo.z = -wo.z; }
+        const NestLobe l = nest_lobe(nh, s1);
+        f3 dw = mk3(0.0f, 0.0f, 0.0f);
+        if (l.k == 0 || l.k == 1) {
+            const uint32_t c = l.k == 0 ? nh.n0 : nh.n1;
+            const float i2h = F.inv_2h ? F.inv_2h[c] : 0.0f;
+            uint32_t tx; f2 tw;
+            const f3 rc = eval_reflectance(sv, bsdf, uv, tx, tw);
+            if (i2h != 0.0f && !bs.delta && bs.pdf > 0.0f) {
+                const f3 dv = child_dvalue(sv, c, wi, wo);
+                const float ip = rcp(bs.pdf);
+                dw = mk3(dv.x * ip, dv.y * ip, dv.z * ip);
+            } else if (i2h != 0.0f && bs.delta) {        // TangentProbe::bsdf_sampled's rule for a discrete lobe, with the child's sample1
+                const DevBsdf bp = F.plus[c], bm = F.minus[c];
+                uint32_t tt; f2 t2; f3 wp, wm; BsdfSample bp_, bm_;
+                const f3 rp = eval_reflectance(sv, bp, uv, tt, t2), rm = eval_reflectance(sv, bm, uv, tt, t2);
+                const bool okp = bsdf_sample(bp, rp, wi, l.s1, s2, bp_, wp);
+                const bool okm = bsdf_sample(bm, rm, wi, l.s1, s2, bm_, wm);
+                if (okp && okm && bp_.delta && bm_.delta && bp_.wo.x == wo.x && bp_.wo.y == wo.y && bp_.wo.z == wo.z &&
+                    bm_.wo.x == wo.x && bm_.wo.y == wo.y && bm_.wo.z == wo.z)
+                    dw = mk3((wp.x - wm.x) * i2h, (wp.y - wm.y) * i2h, (wp.z - wm.z) * i2h);
+            }
+            if (F.tex_tangent && tx != kNoPrim) {
+                BsdfSample bl = bs; bl.wo = wo;
+                const f3 dr = bsdf_dweight_drefl(bsdf, rc, wi, bl), dt = texel_tangent(F.tex_tangent, sv.textures[bsdf.texture], tx, tw);
+                dw = mk3(fmaf(dr.x, dt.x, dw.x), fmaf(dr.y, dt.y, dw.y), fmaf(dr.z, dt.z, dw.z));
+            }
+        }
+        if (dwt != 0.0f && l.k >= 0) {          // the selection probability, attached in the integrand (weight = 1 at the null lobe)
+            const float ds = dwt * l.s;
+            dw = mk3(fmaf(weight.x, ds, dw.x), fmaf(weight.y, ds, dw.y), fmaf(weight.z, ds, dw.z));
+        }
+        dthr = mk3(fmaf(dthr.x, weight.x, thr.x * dw.x), fmaf(dthr.y, weight.y, thr.y * dw.y), fmaf(dthr.z, weight.z, thr.z * dw.z));
+    }
+};
+
+// k_forward on a scene with blend / mask records
+template <bool FLAT>
+__global__ __launch_bounds__(kBlock) void k_forward_nested(const ForwardParams F) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = F.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    const uint32_t spp = (uint32_t) P.spp;
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < F.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        const uint64_t ordinal = P.first_ordinal + k;
+        PathState s;
+        generate_path(P, ordinal, (uint32_t) (ordinal / spp), (uint32_t) (ordinal % spp), s);
+        NestedTangentProbe tp = { { F } };
+        tp.dthr = tp.dres = mk3(0.0f, 0.0f, 0.0f);
+        tp.nh.kind = 0;
+        Counters c = { 0u, 0u, 0u, 0u };
+        while (bounce_step<FLAT, 0, true, true>(P, lds, s, c, tp)) { }
+        float alpha = (s.flags & 1u) ? 1.0f : 0.0f;
+        if (P.store_xyz && !(isfinite(s.res.x) && isfinite(s.res.y) && isfinite(s.res.z))) alpha = -1.0f;
+        f3 d = tp.dres;
+        if (!(isfinite(d.x) && isfinite(d.y) && isfinite(d.z))) d = mk3(0.0f, 0.0f, 0.0f);
+        P.out_rgba[s.ordinal] = make_float4(d.x, d.y, d.z, alpha);
+    }
+}
+hipError_t launch_forward_nested(const ForwardParams &f, hipStream_t s) { return launch_adjoint_kernel<k_forward_nested<true>, k_forward_nested<false>>(f, s); }
+
+// The transpose.  The probe records a nest vertex as ReverseProbe<RECORD, true> records a vertex with wanted slots -- directions, pdf,
+// sample numbers, mis * spec, the uv of the hit; r.refl is what the weight reads -- and the sweep rebuilds the rest from these: the
+// children's records and reflectances, the lobe the primal took, w and s.
+template <bool RECORD>
+struct NestedReverseProbe : ReverseProbe<RECORD, true> {
+    using Base = ReverseProbe<RECORD, true>;
+    bool nest;
+    MTS_DEV void surface(const SurfaceInteraction &si, const DevBsdf &bsdf, f3 refl, uint32_t texel, f2 tw1, f3 thr) {
+        nest = bsdf.type >= kBsdfBlend;
+        if (!nest) { Base::surface(si, bsdf, refl, texel, tw1, thr); return; }
+        this->cur = &bsdf; this->refl0 = refl; this->tex = false; this->slotted = RECORD;
+        if (RECORD) { this->r->rec = si.shape_rec.bsdf; this->r->wi = si.wi; this->r->refl = refl; this->r->uv = si.uv; }
+    }
+};
+
+// One blend / mask vertex of the sweep: T' (delta dNc + a dW) of the weight, of the wanted slots of the children and of their reflectance
+// texels.  Tp = T invq; a: the suffix adjoint behind the vertex; s_slot: the workgroup's slot bins
+template <bool FLAT>
+MTS_DEV void reverse_nest_vertex(const ReverseParams &R, const Geo<FLAT> &geo, const DevBsdf &nrec, const VertexRecRN &r, f3 delta, f3 a, f3 Tp, float *s_slot) {
+    const SceneView &sv = R.rp.sv;
+    const NestAt nh = nest_at(nrec, r.refl);
+    f3 wi = r.wi, wo_e = r.wo_e, wo_s = r.wo_s;
+    if (nh.two) {
+        if (wi.z == 0.0f) return;
+        if (wi.z < 0.0f) { wi.z = -wi.z; wo_e.z = -wo_e.z; wo_s.z = -wo_s.z; }
+    }
+    const bool blend = nh.kind == kBsdfBlend;
+    NestLobe l = { -1, 0.0f, 0.0f };
+    if (r.flags & 2u) l = nest_lobe(nh, r.s1);
+    float gw = 0.0f;        // d / d(w)
+#pragma unroll 1
+    for (uint32_t k = 0; k < (blend ? 2u : 1u); ++k) {
+        const uint32_t c = k == 0u ? nh.n0 : nh.n1;
+        const DevBsdf b = geo.bsdf(c);
+        uint32_t tx; f2 tw;
+        const f3 rc = eval_reflectance(sv, b, r.uv, tx, tw);
+        const float coef = blend ? (k == 0u ? 1.0f - nh.w : nh.w) : nh.w;
+        const bool chosen = l.k == (int) k;
+        if (r.flags & 1u) {         // the evaluation: d / d(w) of (1 - w) f0 + w f1, or of w f_c
+            f3 v; float p;
+            bsdf_eval_pdf(b, rc, wi, wo_e, v, p);
+            const float sg = blend && k == 0u ? -1.0f : 1.0f;
+            gw += sg * fmaf(Tp.z * delta.z, r.ms.z * v.z, fmaf(Tp.y * delta.y, r.ms.y * v.y, (Tp.x * delta.x) * (r.ms.x * v.x)));
+        }
+        if (chosen) gw += l.s * fmaf(Tp.z * a.z, r.W.z, fmaf(Tp.y * a.y, r.W.y, (Tp.x * a.x) * r.W.x));
+        // the child at this vertex as the sweep sees a plain vertex: its share of the evaluation, the sample if it drew it
+        VertexRecR q;
+        q.wi = wi; q.wo_e = wo_e; q.wo_s = wo_s; q.pdf = r.pdf; q.s1 = l.s1; q.s2 = r.s2; q.refl = rc;
+        q.ms = mk3(coef * r.ms.x, coef * r.ms.y, coef * r.ms.z);
+        q.flags = (r.flags & 1u) | (chosen ? (r.flags & 6u) : 0u);
+        if (R.grad_tex && tx != kNoPrim) {
+            f3 dnc = mk3(0.0f, 0.0f, 0.0f), dw = dnc;
+            if (q.flags & 1u) { const f3 dv = bsdf_dvalue_drefl(b, rc, wi, wo_e); dnc = mk3(q.ms.x * dv.x, q.ms.y * dv.y, q.ms.z * dv.z); }
+            if (q.flags & 2u) { BsdfSample bs; bs.wo = wo_s; bs.pdf = r.pdf; bs.delta = (q.flags & 4u) != 0u; dw = bsdf_dweight_drefl(b, rc, wi, bs); }
+            const float gg[3] = { Tp.x * fmaf(delta.x, dnc.x, a.x * dw.x), Tp.y * fmaf(delta.y, dnc.y, a.y * dw.y), Tp.z * fmaf(delta.z, dnc.z, a.z * dw.z) };
+            if (isfinite(gg[0]) && isfinite(gg[1]) && isfinite(gg[2])) {
+                const DevTexture t = sv.textures[b.texture];
+                scatter_texel_grad(R.grad_tex, t, tx, tw, gg);
+            }
+        }
+        const uint32_t j0 = R.slot_range ? R.slot_range[c] : 0u, j1 = R.slot_range ? R.slot_range[c + 1] : 0u;
+        for (uint32_t j = j0; j < j1; ++j) {
+            const ReverseSlot sl = R.slots[j];
+            f3 dnc, dw;
+            reverse_slot_terms(b, sl, q, dnc, dw);
+            const float g = fmaf(Tp.z, fmaf(delta.z, dnc.z, a.z * dw.z), fmaf(Tp.y, fmaf(delta.y, dnc.y, a.y * dw.y), Tp.x * fmaf(delta.x, dnc.x, a.x * dw.x)));
+            if (g != 0.0f && isfinite(g)) {
+                if (j < kReverseSlotBins) atomicAdd(&s_slot[j], g);
+                else atomicAdd(R.grad_bsdf + sl.out, g);
+            }
+        }
+    }
+    if (l.k == 2) gw += l.s * fmaf(Tp.z, a.z, fmaf(Tp.y, a.y, Tp.x * a.x));       // the null lobe: W = 1
+    if (!nh.open || gw == 0.0f || !isfinite(gw)) return;
+    uint32_t tx; f2 tw;
+    (void) eval_reflectance(sv, nrec, r.uv, tx, tw);      // the footprint of a bitmap weight
+    if (tx != kNoPrim) {
+        if (R.grad_tex) {
+            const float gg[3] = { nh.lum ? 0.212671f * gw : gw, nh.lum ? 0.715160f * gw : 0.0f, nh.lum ? 0.072169f * gw : 0.0f };
+            const DevTexture t = sv.textures[nrec.texture];
+            scatter_texel_grad(R.grad_tex, t, tx, tw, gg);
+        }
+    } else if (nrec.texture < 0 && R.slot_range) {
+        for (uint32_t j = R.slot_range[r.rec]; j < R.slot_range[r.rec + 1]; ++j)
+            if (R.slots[j].f0 == kWeightSlot) {
+                if (j < kReverseSlotBins) atomicAdd(&s_slot[j], gw);
+                else atomicAdd(R.grad_bsdf + R.slots[j].out, gw);
+            }
+    }
+}
+
+// k_reverse on a scene with blend / mask records: its replay and sweep, and reverse_nest_vertex at the nest vertices
+template <bool FLAT, bool RECORD>
+__global__ __launch_bounds__(kBlock) void k_reverse_nested(const ReverseParams R) {
+    extern __shared__ float4 smem[];
+    const RenderParams &P = R.rp;
+    const LdsView lds = lds_stage<FLAT>(P.sv, smem);
+    float *const s_em = reverse_emitter_bins();
+    __shared__ float s_slot[RECORD ? kReverseSlotBins : 1u];
+    for (uint32_t i = threadIdx.x; i < 3u * kReverseEmitterBins; i += kBlock) s_em[i] = 0.0f;
+    for (uint32_t i = threadIdx.x; i < (RECORD ? kReverseSlotBins : 1u); i += kBlock) s_slot[i] = 0.0f;
+    __syncthreads();
+    for (uint64_t k = (uint64_t) blockIdx.x * kBlock + threadIdx.x; k < R.n_samples; k += (uint64_t) gridDim.x * kBlock) {
+        PathState s; const f3 delta = adjoint_sample(R, k, s);
+        if (delta.x == 0.0f && delta.y == 0.0f && delta.z == 0.0f) continue;
+        Counters c = { 0u, 0u, 0u, 0u };
+        NestedReverseProbe<RECORD> pr = { { R, delta, nullptr } };
+        pr.nest = false;
+        if constexpr (!RECORD) {
+            while (bounce_step<FLAT, 0, true, true>(P, lds, s, c, pr)) { }
+        } else {
+        VertexRecRN rec[kAdjointMaxDepth];
+        int n = 0;
+        bool alive = true;
+        while (alive && n < kAdjointMaxDepth) { pr.r = &rec[n]; alive = bounce_step<FLAT, 0, true, true>(P, lds, s, c, pr); ++n; }
+        const Geo<FLAT> geo{ P.sv, lds };
+        f3 a = mk3(0.0f, 0.0f, 0.0f);
+        for (int v = n - 1; v >= 0; --v) {
+            const VertexRecRN &r = rec[v];
+            const f3 Tp = r.T * r.invq;
+            if (r.texel != kNoPrim) {
+                const float gg[3] = { Tp.x * fmaf(delta.x, r.dNc.x, a.x * r.dW.x), Tp.y * fmaf(delta.y, r.dNc.y, a.y * r.dW.y),
+                                      Tp.z * fmaf(delta.z, r.dNc.z, a.z * r.dW.z) };
+                if (isfinite(gg[0]) && isfinite(gg[1]) && isfinite(gg[2])) {
+                    const DevTexture t = P.sv.textures[r.texture];
+                    scatter_texel_grad(R.grad_tex, t, r.texel, r.w1, gg);
+                }
+            }
+            if (r.rec >= 0) {
+                const DevBsdf base = geo.bsdf((uint32_t) r.rec);
+                if (base.type >= kBsdfBlend) reverse_nest_vertex<FLAT>(R, geo, base, r, delta, a, Tp, s_slot);
+                else {
+                    const uint32_t j0 = R.slot_range ? R.slot_range[r.rec] : 0u, j1 = R.slot_range ? R.slot_range[r.rec + 1] : 0u;
+                    for (uint32_t j = j0; j < j1; ++j) {
+                        const ReverseSlot sl = R.slots[j];
+                        f3 dnc, dw;
+                        reverse_slot_terms(base, sl, r, dnc, dw);
+                        const float g = fmaf(Tp.z, fmaf(delta.z, dnc.z, a.z * dw.z), fmaf(Tp.y, fmaf(delta.y, dnc.y, a.y * dw.y), Tp.x * fmaf(delta.x, dnc.x, a.x * dw.x)));
+                        if (g != 0.0f && isfinite(g)) {
+                            if (j < kReverseSlotBins) atomicAdd(&s_slot[j], g);
+                            else atomicAdd(R.grad_bsdf + sl.out, g);
+                        }
+                    }
+                }
+            }
+            const f3 b = mk3(fmaf(delta.x, r.Nc.x, r.W.x * a.x), fmaf(delta.y, r.Nc.y, r.W.y * a.y), fmaf(delta.z, r.Nc.z, r.W.z * a.z));
+            a = mk3(delta.x * r.E.x + r.invq * b.x, delta.y * r.E.y + r.invq * b.y, delta.z * r.E.z + r.invq * b.z);
+            if (r.rr_channel >= 0) {
+                const float corr = ((r.invq * r.invq) * r.eta2) * (b.x * r.T.x + b.y * r.T.y + b.z * r.T.z);
+                if (r.rr_channel == 0) a.x -= corr; else if (r.rr_channel == 1) a.y -= corr; else a.z -= corr;
+            }
+        }
+        }
+    }
+    __syncthreads();
+    if (R.grad_emitter)
+        for (uint32_t i = threadIdx.x; i < 3u * min(P.sv.n_emitters, kReverseEmitterBins); i += kBlock)
+            if (s_em[i] != 0.0f) atomicAdd(R.grad_emitter + i, s_em[i]);
+    if (RECORD && R.grad_bsdf)
+        for (uint32_t i = threadIdx.x; i < min(R.n_slots, kReverseSlotBins); i += kBlock)
+            if (s_slot[i] != 0.0f) atomicAdd(R.grad_bsdf + R.slots[i].out, s_slot[i]);
+}
+hipError_t launch_reverse_nested(const ReverseParams &r, bool record, hipStream_t s) {
+    return record ? launch_adjoint_kernel<k_reverse_nested<true, true>, k_reverse_nested<false, true>>(r, s)
+                  : launch_adjoint_kernel<k_reverse_nested<true, false>, k_reverse_nested<false, false>>(r, s);
+}
+
 } // namespace mtsamd

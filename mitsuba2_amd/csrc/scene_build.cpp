@@ -971,6 +971,87 @@ int build_reverse_slots(const SceneState &st, const uint8_t *wanted, float h, st
     return MTSAMD_OK;
 }
 
+// ---- blendbsdf / mask records in the forward and reverse renders (MTSAMD_FORWARD_NESTED / MTSAMD_REVERSE_NESTED) ---------------------
+bool has_nested_records(const SceneState &st) {
+    for (const DevBsdf &b : st.bsdfs)
+        if (b.type >= kBsdfBlend) return true;
+    return false;
+}
+
+// Every bit is known only where it means something: PARAM_TEXTURES (2) in a scene with textured BSDF parameters, NESTED (4) in an RGB scene
+// with a blend / mask record.  Without bit 4 each refusal is, word for word, what it was before the bit existed.
+int check_derivative_flags(const SceneState &st, uint32_t flags, bool reverse, bool &nested) {
+    const char *mode = reverse ? "reverse-mode" : "forward-mode";
+    const bool nests = has_nested_records(st);
+    nested = false;
+    const uint32_t known = 1u | (st.textured_params ? 2u : 0u) | (nests && !st.spectral ? 4u : 0u);
+    if (flags & ~known) return fail(MTSAMD_ERR_INVALID, "unknown flag bits 0x%x in the %s descriptor", flags, reverse ? "gradient" : "tangent");
+    if (st.spectral) return fail(MTSAMD_ERR_UNSUPPORTED, "the %s render is implemented for the RGB variant only", mode);
+    if ((flags & 4u) && st.textured_params)
+        return fail(MTSAMD_ERR_UNSUPPORTED, "the %s render does not handle blendbsdf / mask materials together with textured BSDF parameters "
+                                            "(alpha, specular_reflectance, specular_transmittance) in one scene", mode);
+    if (st.textured_params && !(flags & 2u))
+        return fail(MTSAMD_ERR_UNSUPPORTED, "the %s render does not handle textured BSDF parameters (alpha, specular_reflectance, specular_transmittance)", mode);
+    if (nests && !(flags & 4u)) return fail(MTSAMD_ERR_UNSUPPORTED, "the %s render does not handle blendbsdf / mask materials", mode);
+    nested = nests;
+    return MTSAMD_OK;
+}
+
+// The rows of blend / mask records taken out of a tangent (bsdf_tangents) or of a wanted list (bsdf_wanted); either may be null.  The
+// weight / opacity of nested record b is entry 18 * b + 0 -- MTSAMD_PARAM_REFLECTANCE, component 0, the field the record keeps it in: it
+// goes to weight_tangent[b] / weight_wanted[b] (bsdf_count entries each, 0 for every other record).  Every other non-zero entry of such a
+// row is refused by name, and so is entry 0 where the record reads its weight from a texture (a bitmap's texels carry the tangent /
+// gradient; a checkerboard has none).  rest_tangents / rest_wanted are the inputs with the nested rows zeroed: what build_tangent_records
+// and build_reverse_slots are then called on, so the rows of every plain record, children included, reach them bit for bit.
+int split_nested_rows(const SceneState &st, const float *bsdf_tangents, const uint8_t *bsdf_wanted, std::vector<float> &rest_tangents,
+                      std::vector<float> &weight_tangent, std::vector<uint8_t> &rest_wanted, std::vector<uint8_t> &weight_wanted) {
+    const size_t n = st.bsdfs.size(), row = MTSAMD_BSDF_TANGENT_FLOATS;
+    rest_tangents.clear(); rest_wanted.clear();
+    weight_tangent.assign(n, 0.0f); weight_wanted.assign(n, 0);
+    if (bsdf_tangents) rest_tangents.assign(bsdf_tangents, bsdf_tangents + n * row);
+    if (bsdf_wanted) rest_wanted.assign(bsdf_wanted, bsdf_wanted + n * row);
+    for (size_t b = 0; b < n; ++b) {
+        const DevBsdf &rec = st.bsdfs[b];
+        if (rec.type < kBsdfBlend) continue;
+        const char *name = rec.type == kBsdfBlend ? "weight" : "opacity";
+        for (size_t i = 0; i < row; ++i) {
+            const float t = bsdf_tangents ? bsdf_tangents[row * b + i] : 0.0f;
+            const bool want = bsdf_wanted && bsdf_wanted[row * b + i] != 0;
+            if (bsdf_tangents && !std::isfinite(t))
+                return fail(MTSAMD_ERR_INVALID, "bsdf %u: the tangent of parameter kind %d is not finite", (unsigned) b, (int) i / 3);
+            if (t == 0.0f && !want) continue;
+            if (i != 0)
+                return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: a %s record has one differentiable scalar, its %s (parameter kind 0, component 0); kind %d, "
+                                                    "component %d %s", (unsigned) b, rec.type == kBsdfBlend ? "blendbsdf" : "mask", name, (int) i / 3, (int) i % 3,
+                            want ? "is wanted" : "of its tangent is not zero");
+            if (rec.texture >= 0)
+                return fail(MTSAMD_ERR_UNSUPPORTED, "bsdf %u: %s holds a texture; its texels carry the %s, not a constant", (unsigned) b, name,
+                            want ? "gradient (grad_textures_dev)" : "tangent (texture_tangents_dev)");
+            weight_tangent[b] = t; weight_wanted[b] = want ? 1 : 0;
+        }
+        if (bsdf_tangents) std::fill(rest_tangents.begin() + row * b, rest_tangents.begin() + row * (b + 1), 0.0f);
+        if (bsdf_wanted) std::fill(rest_wanted.begin() + row * b, rest_wanted.begin() + row * (b + 1), (uint8_t) 0);
+    }
+    return MTSAMD_OK;
+}
+
+// The slot table of build_reverse_slots with one more slot per wanted weight, in record order: a slot with f0 = f1 = kWeightSlot names
+// no field of the record -- the weight's derivative is closed-form, so it has no +- pair -- and out = 18 * record.
+void add_weight_slots(const std::vector<uint8_t> &weight_wanted, std::vector<ReverseSlot> &slots, std::vector<uint32_t> &range) {
+    std::vector<ReverseSlot> merged; std::vector<uint32_t> r(range.size(), 0u);
+    for (size_t b = 0; b + 1 < range.size(); ++b) {
+        r[b] = (uint32_t) merged.size();
+        merged.insert(merged.end(), slots.begin() + range[b], slots.begin() + range[b + 1]);
+        if (b < weight_wanted.size() && weight_wanted[b]) {
+            ReverseSlot s{};
+            s.record = (uint32_t) b; s.f0 = s.f1 = kWeightSlot; s.out = (uint32_t) (MTSAMD_BSDF_TANGENT_FLOATS * b);
+            merged.push_back(s);
+        }
+    }
+    if (!r.empty()) r.back() = (uint32_t) merged.size();
+    slots.swap(merged); range.swap(r);
+}
+
 // parameters_changed() of a (rough)plastic whose colours were set: the weight from the means the scene holds now.  The specular mean is
 // spec_mean[] in both variants, the one textured_lobe_weight reads: every setter of specular_reflectance keeps it current.
 static void constant_lobe_weight(SceneState &st, uint32_t bsdf) {

@@ -159,6 +159,18 @@ int build_tangent_records(const SceneState &st, const float *bsdf_tangents, floa
 // inv_2h are bit for bit what build_tangent_records gives for the tangent that is 1 on that scalar and 0 elsewhere, stored as a patch
 // of the record: the float offsets it moves and their plus / minus values.  Refusals are those of build_tangent_records, by name.
 int build_reverse_slots(const SceneState &st, const uint8_t *wanted, float h, std::vector<ReverseSlot> &slots, std::vector<uint32_t> &range);
+// blendbsdf / mask records in the forward and reverse renders (MTSAMD_FORWARD_NESTED / MTSAMD_REVERSE_NESTED, bit 4 of either descriptor).
+bool has_nested_records(const SceneState &st);
+// The flag rule of both descriptors and the refusals that depend on it: a bit is known only in a scene where it means something (bit 2:
+// textured BSDF parameters; bit 4: an RGB scene with a blend / mask record).  `nested`: the call runs the nested kernels.
+int check_derivative_flags(const SceneState &st, uint32_t flags, bool reverse, bool &nested);
+// Takes the rows of blend / mask records out of a tangent and / or a wanted list (either may be null): entry 18 * b + 0 of nested record b
+// is its weight / opacity -> weight_tangent[b] / weight_wanted[b]; everything else on such a row, and entry 0 of a textured weight, is
+// refused by name.  rest_*: the inputs with those rows zeroed (empty for a null input), for build_tangent_records / build_reverse_slots.
+int split_nested_rows(const SceneState &st, const float *bsdf_tangents, const uint8_t *bsdf_wanted, std::vector<float> &rest_tangents,
+                      std::vector<float> &weight_tangent, std::vector<uint8_t> &rest_wanted, std::vector<uint8_t> &weight_wanted);
+// One slot per wanted weight merged into the table of build_reverse_slots, in record order: f0 = f1 = kWeightSlot, out = 18 * record
+void add_weight_slots(const std::vector<uint8_t> &weight_wanted, std::vector<ReverseSlot> &slots, std::vector<uint32_t> &range);
 // these three change record `bsdf` / `emitter` only (valid indices) and the Jacobians behind jac_dirty / ejac_dirty
 int set_bsdf_reflectance(SceneState &st, uint32_t bsdf, const float *rgb);
 int set_bsdf_param(SceneState &st, uint32_t bsdf, int32_t kind, const float *value3);
